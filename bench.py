@@ -3,7 +3,7 @@
 src/alignments.rs:31-67) on synthetic MFCC-like sequences.  NO torch anywhere: device buffers, streams,
 the RCCL communicators and the timing fences all come from libapd_hip.so through its C ABI (include/apd.h).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 How N GPUs are driven:
   * WORLD_SIZE unset (how the driver starts it):  ONE process drives the N devices through the library's
@@ -22,15 +22,22 @@ the packed tile slabs, unpack into the N x N matrix on rank 0's device.  The pai
 (strong scaling).  Timed region: K steps between two fences (every device synchronised, all ranks at a barrier), wall
 clock of the slowest rank.
 
-Prints ONE JSON line (rank 0): metric DTW cell-updates/s (whole job), with
-  roofline      -- algorithmic bytes (4*D*(n+m)+4 per ordered pair) / measured kernel time vs 8 TB/s
-  cpu_baseline  -- the CPU oracle (a port of the reference's algorithm) timed on a bounded sample
-  parity_census -- default distance form vs the bit-exact strict mode over EVERY matrix entry (outside the timed region)
-  secondary     -- measured in the same run on the same context (N = 1, default workload only): cfg3_strict (the tolerance-
+Prints ONE JSON line (rank 0): metric DTW cell-updates/s (whole job), value, unit, ms_per_step, dtype, ... with
+  roofline      -- algorithmic bytes (4*D*(n+m)+4 per ordered pair) / kernel time of the timed steps vs 8 TB/s
+A plain run does nothing else: set up, warm up, time the K steps, write --dump-outputs if given, print the line.
+--full adds the checks and the other measurements, all outside the timed region:
+  max_rel_err_vs_oracle, parity_ok -- sampled entries of the matrix against the CPU oracle (--verify)
+  cpu_baseline  -- the CPU oracle (a port of the reference's algorithm) timed on a bounded sample (--cpu-seconds)
+  parity_census -- default distance form vs the bit-exact strict mode over EVERY matrix entry (--census)
+  pcie_inclusive -- the host-buffer entry point (H2D + align + D2H) on the same workload, one call
+  secondary     -- measured in the same run on the same context (N = 1, default workload only, --secondary): cfg3_strict (the tolerance-
                    compliant mode on the headline workload: kernel time, roofline fraction, bits against the oracle), cfg4 (through
                    apd_encode) and cfg5s (cfg 5's per-pair shape), each with its own census, and cfg2, cfg1
   clustering    -- percentile + UPGMA on the resident matrix (cfg3 at N = 1 by default, or --cluster): seconds, merges, us / merge,
                    algorithmic bytes / merge and the bandwidth they amount to
+
+--dump-outputs DIR: after the timed steps, the N x N matrix the last step left on rank 0's device, as float32 .npy files
+(see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared entry for entry.
 """
 import argparse
 import ctypes as C
@@ -65,7 +72,7 @@ WORKLOADS["cfg5e"] = dict(n_seq=256, length=2048, dim=13, pct=0.0625, audio=True
                                "cepstrum (spectrogram.rs:31-80, dft_win 256, step 128, ceps_filter 18 -> 13 bins) -> DTW band=128 (not a BASELINE config)")
 WORKLOADS["cfg5"] = dict(n_seq=16384, length=2048, dim=13, pct=0.0625, audio=True,
                          desc="cfg5: 16384 recordings x 262400 i16 samples -> on-device cepstrum (13 bins) -> DTW band=128 "
-                              "(add --cluster for the UPGMA leg); ~1 min per step on one GPU")
+                              "(add --full --cluster for the UPGMA leg); ~1 min per step on one GPU")
 WORKLOADS["ship"] = dict(n_seq=512, length=525, jitter=375, dim=10, pct=1.0, encode_from=26,
                          desc="the reference's shipped Discovery.toml shape: 512 ragged VAT slices of 150..900 frames, 26-bin cepstra -> "
                               "10-dim autoencoder embeddings on-device -> full DTW (warping_band_percentage = 1.0); not a BASELINE config")
@@ -123,11 +130,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=os.environ.get("APD_WORKLOAD", "cfg3"), choices=sorted(WORKLOADS))
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = auto)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget per leg (0 = skip)")
-    ap.add_argument("--verify", type=int, default=64, help="entries re-checked against the oracle after timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the checks and other measurements (oracle parity, census, CPU baseline, "
+                         "host-buffer path, secondary workloads, clustering); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the distance matrix of the last timed step to DIR/*.npy (float32; a fixed, seeded sample of rows when large)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget per leg (0 = skip)")
+    ap.add_argument("--verify", type=int, default=64, help="--full: entries re-checked against the oracle after timing")
     ap.add_argument("--distance", default="hybrid", choices=["hybrid", "exact", "strict"], help="local-distance form (apd_set_distance_mode); strict = the reference's arithmetic, bit-identical")
     ap.add_argument("--tau", type=float, default=0.0, help="hybrid recomputation threshold (0 = library default 1/64)")
-    ap.add_argument("--cluster", action="store_true", help="also time percentile + UPGMA (rank 0, outside the timed region)")
+    ap.add_argument("--cluster", action="store_true", help="--full: also time percentile + UPGMA (rank 0, outside the timed region)")
     ap.add_argument("--launcher", default="auto", choices=["auto", "inprocess", "spawn", "torchrun"],
                     help="auto: one process per GPU if RANK / WORLD_SIZE are set (torchrun), else ONE process driving --gpus devices "
                          "through apd_multi; spawn: start the --gpus ranks from here (before any GPU call)")
@@ -135,10 +147,15 @@ def parse():
                     help="process-per-GPU mode only.  apd = the library's own RCCL communicator (default); nccl = force the torch.distributed "
                          "fallback; gloo (staged through host memory) only to rehearse N>1 on a box with fewer GPUs")
     ap.add_argument("--census", default="auto", choices=["auto", "on", "off"],
-                    help="full-matrix parity census against the bit-exact strict mode after timing (auto: when it costs < ~10 s)")
+                    help="--full: full-matrix parity census against the bit-exact strict mode after timing (auto: when it costs < ~10 s)")
     ap.add_argument("--secondary", default="auto", choices=["auto", "on", "off"],
-                    help="also measure cfg2 and cfg1 in this run (auto: N = 1 and the default cfg3 workload)")
-    return ap.parse_args()
+                    help="--full: also measure cfg2 and cfg1 in this run (auto: N = 1 and the default cfg3 workload)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.cluster or args.census == "on" or args.secondary == "on"):
+        ap.error("--cluster, --census on and --secondary on are legs of a --full run")
+    return args
 
 
 def host_threads():
@@ -303,6 +320,22 @@ def census(default, strict):
         flat = int(np.flatnonzero(both)[int(np.argmax(rel))])
         out["worst_entry"] = [flat // default.shape[1], flat % default.shape[1]]
     return out
+
+
+DUMP_MATRIX_BYTES = 32 << 20      # --dump-outputs: whole rows of the matrix up to this size (the limit is 64 MB in all)
+DUMP_SEED = 0xD0A1
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: what a caller of the timed path receives, the N x N distance matrix, as
+      distances.npy      float32 [k][N]  -- the whole matrix (k = N) while it fits in DUMP_MATRIX_BYTES, else k whole rows
+      distance_rows.npy  float64 [k]     -- the row numbers, ascending; drawn with a fixed seed, so the same rows in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = result.shape[0]
+    k = max(1, min(n, DUMP_MATRIX_BYTES // (4 * n)))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    np.save(os.path.join(out_dir, "distances.npy"), np.ascontiguousarray(result[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, "distance_rows.npy"), rows.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------- control planes
@@ -708,11 +741,13 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = max(all_ranks(elapsed))
 
-    result = d_out.to_numpy(np.float32).reshape(n, n) if rank == 0 else None
-    # ---- parity census: the default distance form against strict mode (bit-identical to the CPU arithmetic) over EVERY entry,
-    # on the same resident batch, after the timed region; every rank takes part (the strict run is sharded like a step)
+    result = d_out.to_numpy(np.float32).reshape(n, n) if rank == 0 and (args.full or args.dump_outputs) else None
+    if result is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
+    # ---- --full from here on.  Parity census: the default distance form against strict mode (bit-identical to the CPU arithmetic)
+    # over EVERY entry, on the same resident batch, after the timed region; every rank takes part (the strict run is sharded like a step)
     strict, census_seconds, strict_kernel_ms = None, 0.0, None
-    want_census = args.census == "on" or (args.census == "auto" and args.distance != "strict" and cells_all <= 3e12)
+    want_census = args.full and (args.census == "on" or (args.census == "auto" and args.distance != "strict" and cells_all <= 3e12))
     if want_census and (multi_mode or comm is not None or world == 1):
         t0 = time.perf_counter()
         for c in ctxs:
@@ -731,7 +766,6 @@ def main():
         census_seconds = time.perf_counter() - t0
 
     if rank == 0:
-        verify = verify_sample(inp, result, args.verify) if args.verify > 0 else None
         traffic, valu_insts, counters_withheld = recorded_counters(args.workload, world) if args.distance == "hybrid" else (None, None, "recorded for the default distance form only")
         k_ms = float(np.mean(kernel_ms))
         achieved = bytes_r / (k_ms * 1e-3) / 1e9
@@ -748,7 +782,7 @@ def main():
                        "launch": mode, "collective": collective, "collective_fallback": collective_fallback,
                        "collective_error": collective_error, "ranks_seen": ranks_seen, "multi_selfcheck": multi_selfcheck,
                        "runtime": _lib.runtime_info(), "torch_imported": "torch" in sys.modules,
-                       "kernel_variant": args.variant, "distance_form": args.distance},
+                       "kernel_variant": args.variant, "distance_form": args.distance, "full": args.full},
             "wall_clock_matrix_s": elapsed / args.steps,
             "pairs_per_s": pairs_all * args.steps / elapsed,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -770,9 +804,12 @@ def main():
                 "peak_lane_instr_per_s": VALU_PEAK,
                 "frac": valu_insts * 64.0 / (k_ms * 1e-3) / VALU_PEAK,
                 "source": "profiles/hbm_traffic.json (rocprofv3 --pmc SQ_INSTS_VALU of this command, committed; not re-measured in this run)"},
-            "max_rel_err_vs_oracle": verify, "parity_ok": (verify is None) or bool(verify <= (1e-3 if inp["audio"] is not None else 1e-4)),
         }
-        if strict is not None:
+        if args.full:
+            verify = verify_sample(inp, result, args.verify) if args.verify > 0 else None
+            line["max_rel_err_vs_oracle"] = verify
+            line["parity_ok"] = (verify is None) or bool(verify <= (1e-3 if inp["audio"] is not None else 1e-4))
+        if strict is not None:                                       # --full only
             line["parity_census"] = census(result, strict)
             line["parity_census"]["seconds"] = census_seconds
             line["parity_census"]["strict_max_rel_err_vs_oracle"] = verify_sample(inp, strict, min(args.verify, 32), seed=11) if args.verify > 0 else None
@@ -782,7 +819,7 @@ def main():
                 line["parity_note"] = ("%d of %d entries beyond 1e-4 in the default distance form: the coincidental-tie deviation (DESIGN.md section 6, "
                                        "1-6 entries in 1e8 on the BASELINE shapes); --distance strict computes the reference's bits at 1.9x the time (secondary.cfg3_strict)"
                                        % (line["parity_census"]["over_1e-4"], line["parity_census"]["entries"]))
-        if inp["frames"] is not None and inp["enc_w"] is None and world == 1:
+        if args.full and inp["frames"] is not None and inp["enc_w"] is None and world == 1:
             # the host-buffer entry of the boundary (AlignmentWorkers::new + align_all on host Vec<f32>s): H2D of the frames,
             # repack, kernel, unpack, D2H of the matrix -- reported beside `value`, never as it
             host_out = np.empty(n * n, dtype=np.float32)
@@ -796,10 +833,10 @@ def main():
                                       "h2d_bytes": int(inp["frames"].nbytes), "d2h_bytes": int(host_out.nbytes),
                                       "bitwise_equal_to_resident_path": bool(np.array_equal(host_out.reshape(n, n), result)),
                                       "note": "apd_batch_create(host frames) + apd_align_all(host out), pageable host memory, one call"}
-        want_cluster = args.cluster or (world == 1 and args.workload == "cfg3" and args.secondary != "off")
+        want_cluster = args.full and (args.cluster or (world == 1 and args.workload == "cfg3" and args.secondary != "off"))
         if want_cluster:
             line["clustering"] = clustering_leg(ctx, d_out, n)
-        if world == 1 and (args.secondary == "on" or (args.secondary == "auto" and args.workload == "cfg3")):
+        if args.full and world == 1 and (args.secondary == "on" or (args.secondary == "auto" and args.workload == "cfg3")):
             sec = {}
             if strict is not None and args.workload == "cfg3":
                 # the tolerance-compliant mode on the headline workload: the census pass above IS a full strict-mode alignment
@@ -813,7 +850,7 @@ def main():
             sec["cfg2"] = measure_secondary(ctx, "cfg2")
             sec["cfg1"] = measure_secondary(ctx, "cfg1")
             line["secondary"] = sec
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             if inp["audio"] is None:
                 line["cpu_baseline"] = cpu_baseline(oracle_features(inp)[0], offsets, wl, args.cpu_seconds)
             else:
@@ -821,7 +858,7 @@ def main():
                 subset = list(range(0, n, max(n // 48, 1)))[:48]
                 fr, off, _ = oracle_features(inp, subset)
                 line["cpu_baseline"] = cpu_baseline(fr, off, wl, args.cpu_seconds, note=" among %d of the %d recordings (oracle cepstra)" % (len(subset), n))
-        else:
+        elif args.full:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if ranks_mode:

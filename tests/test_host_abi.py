@@ -235,6 +235,33 @@ def test_bench_gpus_n_starts_in_process():
     assert "torch.distributed.run" not in out.stderr and "no gfx950 HIP device" in out.stderr, out.stderr[-1500:]
 
 
+def test_bench_dump_outputs_and_plain_run_arguments(tmp_path):
+    """bench.py --dump-outputs: a small matrix whole, a large one as a fixed, seeded sample of whole rows under the size limit.
+    A plain run refuses the options that only mean something with --full, and a step count below one."""
+    import subprocess
+    import sys
+    import bench
+    small = np.arange(64 * 64, dtype=np.float32).reshape(64, 64)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "distances.npy"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "distance_rows.npy"), np.arange(64, dtype=np.float64))
+    big = np.random.default_rng(0).random((4096, 4096), dtype=np.float32)
+    got = []
+    for k in range(2):
+        d = tmp_path / ("big%d" % k)
+        bench.dump_outputs(str(d), big)
+        m, rows = np.load(d / "distances.npy"), np.load(d / "distance_rows.npy")
+        assert m.dtype == np.float32 and rows.dtype == np.float64 and m.shape == (len(rows), 4096) and 0 < len(rows) < 4096
+        assert np.all(np.diff(rows) > 0) and np.array_equal(m, big[rows.astype(np.int64)])
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64e6
+        got.append(rows)
+    assert np.array_equal(got[0], got[1])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra in (["--cluster"], ["--census", "on"], ["--secondary", "on"], ["--steps", "0"]):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra, capture_output=True, text=True, timeout=120, cwd=root)
+        assert out.returncode == 2 and "error:" in out.stderr, (extra, out.stderr[-800:])
+
+
 def test_formats_survive_the_sanitizer_fuzz(tmp_path):
     """csrc/formats.hip is host-only: built as plain C++ under AddressSanitizer + UBSan (CPU build: the pool has no GPU sanitizer)
     and fed random / mutated op lists (repeated ids, self references), Discovery.toml texts and bincode images."""
