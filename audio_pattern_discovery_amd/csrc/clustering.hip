@@ -1515,6 +1515,7 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
                          ccnt / m, csum / std::max(1.0, ccnt), rwsum / std::max(1.0, ccnt), cstart / m);
         }
         hipFree(st.dbg);
+        st.dbg = nullptr;                                                 // fail() below must not free it again
     }
     std::vector<uint32_t> ids(n), live(host_state[0]);
     e = hipMemcpyAsync(ops, st.ops, (size_t)cnt * sizeof(apd_cluster_op), hipMemcpyDeviceToHost, ctx->stream);

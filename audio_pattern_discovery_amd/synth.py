@@ -87,9 +87,19 @@ def make_distance_matrix(n, kind="points", seed=0):
     * "nan":    5 % NaN entries (percentile drops them, numerics.rs:127-130; a NaN linkage never wins),
     * "big":    three tight clusters -- late merges face clusters of hundreds of members (linkage chains of 10^5 terms),
     * "neg":    i.i.d. U(-1, 1): negative "distances" (what non-positive penalties can produce),
+    * "chain":  16 families in 64-d, member k of a family at noise radius ~ k / (n / 16) -- clusters grow one member at a time
+                (the cfg 5 proxy of tools/upgma_scale.py ... chain),
     * "uniform": i.i.d. U(0, 1)."""
     rng = np.random.default_rng(seed)
-    if kind == "points":
+    if kind == "chain":
+        families, dims = 16, 64
+        k = np.arange(n)
+        x = rng.standard_normal((n, dims)).astype(np.float32)
+        centres = rng.standard_normal((families, dims)).astype(np.float32) * 4
+        x = (x * (0.02 + 2.0 * (k // families).astype(np.float32)[:, None] / (n / families)) + centres[k % families]).astype(np.float32)
+        sq = (x * x).sum(1)
+        d = np.sqrt(np.maximum(sq[:, None] + sq[None, :] - 2.0 * (x @ x.T), 0.0))
+    elif kind == "points":
         centres = rng.standard_normal((max(n // 64, 4), 3)) * 4
         pts = centres[rng.integers(0, len(centres), n)] + rng.standard_normal((n, 3)) * 0.3
         d = np.zeros((n, n), dtype=np.float32)
