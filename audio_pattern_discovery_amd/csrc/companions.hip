@@ -120,9 +120,11 @@ __global__ __launch_bounds__(256) void encode_staged_kernel(const float *__restr
 // first N/2 bins, triangular filterbank with stride L/2, ln(. + 1e-6), DCT-I as a K x K table product, drop 4, subtract
 // the mean of what is left (spectrogram.rs:51-79).  The DFT is an autosort (Stockham) FFT in LDS, radix-4 passes, when N is a power of two and
 // the defining sum X_k = sum_s x_s e^(-2 pi i k s / N) otherwise (rustfft plans any length, spectrogram.rs:44-48; the
-// reference's shipped window is 256).  The tables live in LDS, loaded once per workgroup; the four wavefronts of a
-// workgroup never exchange data, so the stages are ordered by the wavefront's own in-order LDS queue, not by barriers.
+// reference's shipped window is 256).  The tables live in LDS, loaded once per workgroup; the wavefronts of a workgroup
+// never exchange data, so the stages are ordered by the wavefront's own in-order LDS queue, not by barriers.
 // Power-of-two windows: radix-4 passes, and each HALF of a wavefront (32 lanes) transforms a frame of its own.
+// A workgroup has 1 - 4 wavefronts, as many as the plan fits into 160 KiB of LDS; when the K x K DCT table does not fit
+// beside one frame slot (large K), it stays in global memory (L2) and only the other tables are copied.
 struct CepsParams {
     const int16_t *samples;
     const uint64_t *sample_off;   // [n_seq+1] first sample of every recording
@@ -131,6 +133,10 @@ struct CepsParams {
     uint64_t n_frames;
     uint32_t fft, step, L, fstep, K, log2n;   // log2n == 0: N is not a power of two, direct DFT
     uint32_t frames_per_wave;  // 2: each half of a wavefront transforms a frame of its own (power-of-two windows whose slots fit in LDS); else 1
+    uint32_t waves;            // wavefronts per workgroup, 1 .. 4 (blockDim.x / 64)
+    uint32_t dct_lds;          // 1: the DCT table is copied to LDS; 0: it is read from global memory
+    uint32_t tw_lds;           // float offset of the twiddle table in LDS (even: 8-byte aligned)
+    uint32_t slot_floats;      // floats per frame slot (even)
     const float *hamming;      // [fft]
     const float *triag;        // [L]
     const float2 *twiddle;     // power of two: [fft/2] exp(-2 pi i k / fft); else [fft] exp(-2 pi i t / fft)
@@ -177,26 +183,28 @@ __global__ __launch_bounds__(256) void cepstrum_kernel(const CepsParams P)
     extern __shared__ float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t N = P.fft, half = N / 2, K = P.K, n_tw = P.log2n ? half : N;
-    // tables, shared by the workgroup
+    // tables, shared by the workgroup: hamming[N], triag[L], dct[K][K] (when the plan keeps it in LDS), twiddles at P.tw_lds
     float *t_ham = lds, *t_tri = t_ham + N, *t_dct = t_tri + P.L;
-    float2 *t_tw = reinterpret_cast<float2 *>(lds + ((N + P.L + K * K + 1u) & ~1u));        // 8-byte aligned
+    float2 *t_tw = reinterpret_cast<float2 *>(lds + P.tw_lds);
     for (uint32_t e = threadIdx.x; e < N; e += blockDim.x) t_ham[e] = P.hamming[e];
     for (uint32_t e = threadIdx.x; e < P.L; e += blockDim.x) t_tri[e] = P.triag[e];
-    for (uint32_t e = threadIdx.x; e < K * K; e += blockDim.x) t_dct[e] = P.dct[e];
+    if (P.dct_lds)
+        for (uint32_t e = threadIdx.x; e < K * K; e += blockDim.x) t_dct[e] = P.dct[e];
     for (uint32_t e = threadIdx.x; e < n_tw; e += blockDim.x) t_tw[e] = P.twiddle[e];
     __syncthreads();
-    // per frame slot: two complex buffers of N/2 (ping-pong; the direct form uses the first as N real samples), mag[half], conv[K], ceps[K].
-    // Power-of-two windows: TWO slots per wavefront -- each half of the wave (32 lanes) transforms a frame of its own; else one.
-    const uint32_t slot_floats = (2 * N + half + 2 * K + 1u) & ~1u, slots = P.frames_per_wave;
+    // per frame slot: FFT -- two complex buffers of N/2 (ping-pong), mag[half], conv[K], ceps[K]; direct sum -- N real samples,
+    // mag[half], conv[K], ceps[K].  Power-of-two windows: TWO slots per wavefront when they fit -- each half of the wave (32 lanes)
+    // transforms a frame of its own; else one.
+    const uint32_t slot_floats = P.slot_floats, slots = P.frames_per_wave;
     float *wave_base = reinterpret_cast<float *>(t_tw + n_tw) + (size_t)wave * slots * slot_floats;
     // A wavefront takes a CONTIGUOUS run of frames: consecutive frames of a recording overlap (dft_step < dft_win: their samples
     // come from L2 the second time) and the recording index only ever steps forward (one binary search per run, not per frame).
-    const uint64_t n_waves = (uint64_t)gridDim.x * 4u, per_wave = (P.n_frames + n_waves - 1) / n_waves;
-    const uint64_t f_begin = ((uint64_t)blockIdx.x * 4u + wave) * per_wave, f_end = min(f_begin + per_wave, P.n_frames);
+    const uint64_t n_waves = (uint64_t)gridDim.x * P.waves, per_wave = (P.n_frames + n_waves - 1) / n_waves;
+    const uint64_t f_begin = ((uint64_t)blockIdx.x * P.waves + wave) * per_wave, f_end = min(f_begin + per_wave, P.n_frames);
     const uint32_t gsize = 64u / slots, gl = (uint32_t)lane % gsize, fs = (uint32_t)lane / gsize;   // lane group = frame slot
     float *base = wave_base + (size_t)fs * slot_floats;
     float2 *bufa = reinterpret_cast<float2 *>(base), *bufb = bufa + half;
-    float *mag = base + 2 * N, *conv = mag + half, *ceps = conv + K;
+    float *mag = base + (P.log2n ? 2 * N : N), *conv = mag + half, *ceps = conv + K;
     // recording holding this group's first frame: largest s with frame_off[s] <= frame
     uint32_t lo = 0;
     const uint64_t f_first = f_begin + fs;
@@ -282,7 +290,8 @@ __global__ __launch_bounds__(256) void cepstrum_kernel(const CepsParams P)
             }
         }
         APD_WAVE_LDS_FENCE();
-        finish_frame(P, t_tri, t_dct, mag, conv, ceps, gl, gsize, frame, live);
+        if (P.dct_lds) finish_frame(P, t_tri, t_dct, mag, conv, ceps, gl, gsize, frame, live);   // two copies, so that each reads
+        else finish_frame(P, t_tri, P.dct, mag, conv, ceps, gl, gsize, frame, live);           // its table through one address space
         APD_WAVE_LDS_FENCE();                                      // the buffers are reused by this lane group's next frame
     }
 }
@@ -480,6 +489,7 @@ static int cepstrum_geometry(const uint64_t *sample_off, uint32_t n_seq, uint32_
     uint32_t K = 0;
     for (uint32_t i = L; i < half; i += fstep) ++K;                                     // numerics.rs:105
     if (K < 5) return APD_ERR_INVALID_ARG;                                              // cepstrum[4..] of an empty tail
+    if (fft_size > 4096 || K > 512) return APD_ERR_UNSUPPORTED;                         // the limits of include/apd.h, apd_cepstrum
     frame_off[0] = 0;
     for (uint32_t s = 0; s < n_seq; ++s) {
         if (sample_off[s + 1] < sample_off[s]) return APD_ERR_INVALID_ARG;
@@ -505,7 +515,6 @@ extern "C" int apd_cepstrum_plan_create(apd_context *ctx, const uint64_t *sample
     uint32_t log2n = 0;
     while ((1u << log2n) < fft_size) ++log2n;
     if ((1u << log2n) != fft_size) log2n = 0;                                           // not a power of two: the defining sum
-    if (fft_size < 4 || fft_size > 4096 || K > 512) return APD_ERR_UNSUPPORTED;
     const uint32_t n_tw = log2n ? half : fft_size;
     HIP_TRY(ctx, apd::bind_device(ctx));
 
@@ -550,18 +559,31 @@ extern "C" int apd_cepstrum_plan_create(apd_context *ctx, const uint64_t *sample
     const float *d_tab = reinterpret_cast<const float *>(plan->pool);
     P.hamming = d_tab; P.triag = d_tab + fft_size; P.dct = d_tab + fft_size + L;
     P.twiddle = reinterpret_cast<const float2 *>(d_tab + tw_off);
-    const size_t table_floats = tw_off + 2 * (size_t)n_tw;                               // the kernel lays its LDS out the same way
-    const size_t slot_floats = (2 * (size_t)fft_size + half + 2 * K + 1) & ~(size_t)1;
+    // LDS of a workgroup, laid out as the kernel reads it: hamming | triag | dct (if kept in LDS) | twiddles, then waves x
+    // frames_per_wave frame slots.  The FFT slot holds two complex ping-pong buffers of N/2, the direct sum's N real samples.
+    const size_t lds_cap = 160 * 1024 / sizeof(float);
+    auto table_floats = [&](bool dct) { return (((size_t)fft_size + L + (dct ? (size_t)K * K : 0) + 1) & ~(size_t)1) + 2 * (size_t)n_tw; };
+    const size_t slot_floats = ((log2n ? 2 : 1) * (size_t)fft_size + half + 2 * K + 1) & ~(size_t)1;
     // two frames per wavefront for power-of-two windows, if eight slots fit beside the tables (windows up to 1024 do)
-    P.frames_per_wave = (log2n && (table_floats + 8 * slot_floats) * sizeof(float) <= 96 * 1024) ? 2u : 1u;
-    plan->lds_bytes = (table_floats + 4 * P.frames_per_wave * slot_floats) * sizeof(float);
+    P.frames_per_wave = (log2n && (table_floats(true) + 8 * slot_floats) * sizeof(float) <= 96 * 1024) ? 2u : 1u;
+    // the DCT table in LDS if it fits beside one wavefront's slots, else read from global memory; then as many wavefronts (up
+    // to 4) as fit.  fft_size <= 4096 and K <= 512 always fit one wavefront: under 77 KiB without the DCT table.
+    P.dct_lds = table_floats(true) + P.frames_per_wave * slot_floats <= lds_cap ? 1u : 0u;
+    const size_t tables = table_floats(P.dct_lds != 0);
+    P.waves = 4;
+    while (P.waves > 1 && tables + (size_t)P.waves * P.frames_per_wave * slot_floats > lds_cap) --P.waves;
+    P.tw_lds = (uint32_t)(tables - 2 * (size_t)n_tw);
+    P.slot_floats = (uint32_t)slot_floats;
+    plan->lds_bytes = (tables + (size_t)P.waves * P.frames_per_wave * slot_floats) * sizeof(float);
     // wavefronts loop over frames: enough workgroups to fill the GPU several times over, tables loaded once per workgroup
-    plan->blocks = (unsigned)std::min<uint64_t>((T + 4 * P.frames_per_wave - 1) / (4 * P.frames_per_wave), 256 * 16);
+    const uint32_t per_block = P.waves * P.frames_per_wave;
+    plan->blocks = (unsigned)std::min<uint64_t>((T + per_block - 1) / per_block, 256 * 16);
     int status = APD_OK;
     if (err != hipSuccess) { ctx->last_error = std::string("apd_cepstrum_plan_create: ") + hipGetErrorString(err); status = err == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP; }
     else if (plan->lds_bytes > 160 * 1024) status = APD_ERR_UNSUPPORTED;
+    // the attribute belongs to the kernel, not to the plan: raised to the most any plan asks for, so plans of any size may alternate
     else if (plan->lds_bytes > 64 * 1024 &&
-             hipFuncSetAttribute(reinterpret_cast<const void *>(cepstrum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan->lds_bytes) != hipSuccess) {
+             hipFuncSetAttribute(reinterpret_cast<const void *>(cepstrum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
         ctx->last_error = "apd_cepstrum_plan_create: the runtime refused the kernel its LDS";
         status = APD_ERR_HIP;
     }
@@ -593,7 +615,7 @@ extern "C" int apd_cepstrum_batch_async(apd_context *ctx, const apd_cepstrum_pla
     APD_AFFINITY(ctx, "cepstrum launch");
     CepsParams P = plan->P;
     P.samples = d_samples; P.out = d_out;
-    hipLaunchKernelGGL(cepstrum_kernel, dim3(plan->blocks), dim3(256), plan->lds_bytes, ctx->stream, P);
+    hipLaunchKernelGGL(cepstrum_kernel, dim3(plan->blocks), dim3(64 * P.waves), plan->lds_bytes, ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return APD_OK;
 }

@@ -338,7 +338,10 @@ int apd_cluster_sets(const apd_cluster_op *ops, uint32_t n_ops, const uint32_t *
 int apd_encode(apd_context *ctx, const float *x, uint64_t t, uint32_t d_in, const float *w_encode,
                const float *b_encode, uint32_t latent, int on_device, float *out);
 /* Cepstrum frames of NDSequence::new (src/spectrogram.rs:31-80).  Returns the frame count in
- * *n_frames and bins per frame in *n_bins; out may be NULL to query sizes. */
+ * *n_frames and bins per frame in *n_bins; out may be NULL to query sizes.
+ * Limits, the same for every cepstrum call (size queries and plans included): K = *n_bins + 4, the filterbank outputs, must be at
+ * least 5 (else APD_ERR_INVALID_ARG, as the reference's cepstrum[4..] would be empty); fft_size <= 4096 and K <= 512 run (any
+ * window length: powers of two by FFT, the others by the defining sum); fft_size > 4096 or K > 512 is APD_ERR_UNSUPPORTED. */
 int apd_cepstrum(apd_context *ctx, const int16_t *samples, uint64_t n_samples, uint32_t fft_size,
                  uint32_t fft_step, uint32_t filter_size, int on_device, float *out, uint64_t *n_frames,
                  uint32_t *n_bins);

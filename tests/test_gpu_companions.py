@@ -86,9 +86,13 @@ def test_cepstrum_random_audio(ctx, oracle, fft, step, filt):
 
 def test_cepstrum_window_limits(ctx, apd):
     """Any window length up to 4096 (rustfft plans any length, spectrogram.rs:44-48): powers of two by FFT, the others by the
-    defining sum.  Beyond the limit, and filter banks that leave fewer than 5 outputs, are refused."""
+    defining sum, with up to K = 512 filterbank outputs (include/apd.h, apd_cepstrum).  Windows beyond 4096 are refused with
+    APD_ERR_UNSUPPORTED, filter banks that leave fewer than 5 outputs with APD_ERR_INVALID_ARG.  Every window and K in between
+    is pinned against the oracle in tests/test_gpu_cepstrum.py."""
     from audio_pattern_discovery_amd.alignments import NDSequence
     assert NDSequence.new(300, 128, 18, synth.make_audio(2000, seed=1), ctx).n_bins > 0
+    s = NDSequence.new(4096, 2048, 18, synth.make_audio(4096 + 2048 * 2 + 1, seed=1), ctx)
+    assert (s.len(), s.n_bins) == (3, 13)
     with pytest.raises(apd.ApdError) as e:
         NDSequence.new(8192, 128, 18, synth.make_audio(20000, seed=1), ctx)
     assert e.value.status == apd.APD_ERR_UNSUPPORTED
