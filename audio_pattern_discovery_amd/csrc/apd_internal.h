@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <iterator>
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -60,20 +62,117 @@ constexpr int max_cells_per_lane(uint32_t d) { return d <= 13 ? 9 : (d <= 16 ? 7
 // Column strips of the full-matrix kernel hold CW frames per lane and one DP row: wider strips fit.
 constexpr int max_strip_columns(uint32_t d) { return d <= 10 ? 13 : (d <= 13 ? 11 : max_cells_per_lane(d)); }   // 13 x 14 floats do not fit at D = 13
 
-// geom_key = G * 100 + C of the systolic kernel, or 0 for the generic kernel (see pick_geometry_key)
-hipError_t launch_align(const AlignLaunch &L, int geom_key, hipStream_t stream, std::string &err, int *status);
+// ---- kernel geometry: which kernel family sweeps a tile class, and with which shape.
+struct KernelGeom {
+    enum Family : uint8_t { Generic, Systolic, Wide, Strip, BandedStrip };
+    Family family = Generic;
+    uint8_t lanes_or_waves = 0;   // systolic: lanes per pair G; wide: wavefronts per pair NW; strips: pairs per wavefront
+    uint8_t cells = 0;            // offsets per lane C (band form), columns per lane CW (strips)
+
+    // The integer form of apd_set_variant, the tile-plan cache key and the APD_DEBUG_PLAN line: 0 generic, G * 100 + C systolic,
+    // 10000 + NW * 100 + C wide, 20000 + ppw * 100 + CW column strips, 30000 + ppw * 100 + CW banded column strips.
+    constexpr int encode() const
+    {
+        constexpr int base[] = {0, 0, 10000, 20000, 30000};
+        return family == Generic ? 0 : base[family] + lanes_or_waves * 100 + cells;
+    }
+    // any other code (1 .. 99, negative, >= 40000) decodes to Generic
+    static constexpr KernelGeom decode(int key)
+    {
+        const Family f = key >= 100 && key < 10000 ? Systolic : key >= 10000 && key < 20000 ? Wide
+                       : key >= 20000 && key < 30000 ? Strip : key >= 30000 && key < 40000 ? BandedStrip : Generic;
+        if (f == Generic) return KernelGeom{};
+        return KernelGeom{f, (uint8_t)((key % 10000) / 100), (uint8_t)(key % 100)};
+    }
+    // work-items per pair (the launches are cut at 2^31 work-items): the generic and strip kernels use at most one wavefront
+    constexpr uint32_t lanes_per_pair() const
+    {
+        return family == Systolic ? lanes_or_waves : family == Wide ? 64u * lanes_or_waves : 64u;
+    }
+    // offsets (band form) or columns (strips) one pair covers per pass
+    constexpr uint32_t capacity() const { return (family == Wide ? 64u : 1u) * lanes_or_waves * cells; }
+    constexpr bool operator==(KernelGeom o) const { return family == o.family && lanes_or_waves == o.lanes_or_waves && cells == o.cells; }
+    constexpr bool operator<(KernelGeom o) const { return encode() < o.encode(); }   // tile classes run in this order
+};
+
+// The instantiated geometries, one list per family: the launchers (dtw_systolic.h, dtw_wide.h, dtw_full.h) expand them into
+// their compile-time cases, the dispatcher (dtw_generic.hip) walks them in this order for its automatic choices and tests a
+// forced variant against them.  max_cells_per_lane / max_strip_columns above drop the entries a frame dimension cannot hold
+// (geom_instantiated), in the launchers and the dispatcher alike.
+#define APD_SYSTOLIC_GEOMS(X) X(8, 5) X(8, 7) X(8, 9) X(16, 2) X(16, 3) X(16, 5) X(16, 7) X(16, 9) X(32, 5) X(32, 7) X(32, 9) \
+                              X(64, 3) X(64, 5) X(64, 7) X(64, 9)
+#define APD_WIDE_GEOMS(X) X(2, 5) X(2, 7) X(2, 9) X(4, 5) X(4, 7) X(4, 9) X(8, 5) X(8, 7) X(8, 9)   // ascending capacity
+#define APD_STRIP_GEOMS(X) X(1, 3) X(1, 5) X(1, 7) X(1, 9) X(1, 11) X(1, 13) X(2, 3) X(2, 5) X(2, 7) X(2, 9) X(2, 11) X(2, 13) \
+                           X(4, 3) X(4, 5) X(4, 7) X(4, 9) X(4, 11) X(4, 13)
+#define APD_BANDED_STRIP_GEOMS(X) X(1, 5) X(1, 9) X(4, 5) X(4, 9)
+
+#define APD_SYSTOLIC_ENTRY_(A, B) KernelGeom{KernelGeom::Systolic, A, B},
+#define APD_WIDE_ENTRY_(A, B) KernelGeom{KernelGeom::Wide, A, B},
+#define APD_STRIP_ENTRY_(A, B) KernelGeom{KernelGeom::Strip, A, B},
+#define APD_BANDED_STRIP_ENTRY_(A, B) KernelGeom{KernelGeom::BandedStrip, A, B},
+constexpr KernelGeom kSystolicGeoms[] = {APD_SYSTOLIC_GEOMS(APD_SYSTOLIC_ENTRY_)};
+constexpr KernelGeom kWideGeoms[] = {APD_WIDE_GEOMS(APD_WIDE_ENTRY_)};
+constexpr KernelGeom kStripGeoms[] = {APD_STRIP_GEOMS(APD_STRIP_ENTRY_)};
+constexpr KernelGeom kBandedStripGeoms[] = {APD_BANDED_STRIP_GEOMS(APD_BANDED_STRIP_ENTRY_)};
+#undef APD_SYSTOLIC_ENTRY_
+#undef APD_WIDE_ENTRY_
+#undef APD_STRIP_ENTRY_
+#undef APD_BANDED_STRIP_ENTRY_
+
+// Every frame dimension of the dispatch, as a compile-time constant: f(std::integral_constant<int, D>{}).  false: no kernels for `dim`.
+template <class F, size_t... I>
+bool with_kernel_dim_(uint32_t dim, F &&f, std::index_sequence<I...>)
+{
+    return ((dim == (uint32_t)kKernelDims[I] ? (f(std::integral_constant<int, kKernelDims[I]>{}), true) : false) || ...);
+}
+template <class F>
+bool with_kernel_dim(uint32_t dim, F &&f) { return with_kernel_dim_(dim, f, std::make_index_sequence<std::size(kKernelDims)>{}); }
+
+// The one test of "a kernel exists for g at frame dimension dim": on the family's list and within the dimension's clamp.
+constexpr bool geom_instantiated(KernelGeom g, uint32_t dim)
+{
+    if (g.family == KernelGeom::Generic) return true;
+    if (!is_kernel_dim(dim)) return false;
+    const bool strip = g.family == KernelGeom::Strip;
+    if (g.cells > (strip ? max_strip_columns(dim) : max_cells_per_lane(dim))) return false;
+    auto on = [g](const auto &list) { for (KernelGeom e : list) if (e == g) return true; return false; };
+    return g.family == KernelGeom::Systolic ? on(kSystolicGeoms) : g.family == KernelGeom::Wide ? on(kWideGeoms)
+         : strip ? on(kStripGeoms) : on(kBandedStripGeoms);
+}
+// the lists and their integer codes are one and the same: every entry decodes back to itself
+template <size_t N>
+constexpr bool geoms_round_trip(const KernelGeom (&list)[N])
+{
+    for (KernelGeom g : list) if (!(KernelGeom::decode(g.encode()) == g)) return false;
+    return true;
+}
+static_assert(geoms_round_trip(kSystolicGeoms) && geoms_round_trip(kWideGeoms) && geoms_round_trip(kStripGeoms) &&
+                  geoms_round_trip(kBandedStripGeoms), "a listed geometry has no integer code of its own");
+
+// LDS of the column-strip kernels (dtw_full.h): row frames of their lanes, one boundary column per pair and DP, and a few words
+constexpr uint64_t strip_lds_bytes(uint32_t dim, uint32_t ppw, bool banded, uint32_t rows)
+{
+    const uint64_t dp = (dim + 4) & ~3u;
+    return 4 * ((ppw == 1 ? 128 : 64) * dp + (uint64_t)ppw * (banded ? 2 : 1) * (rows + 4) + 16);
+}
+
+// One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
+hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);
 // The generic kernel over ALL tiles of L as a small persistent grid that does nothing unless *L.d_nonfinite is set.
 // *fits = false (and nothing launched) if the band of L.w_max needs more LDS than a workgroup can have.
 hipError_t launch_generic_fallback(const AlignLaunch &L, hipStream_t stream, bool *fits);
 // true if the literal kernel can hold a band of w_max in LDS AND the runtime grants it that much (the hipFuncSetAttribute is made
 // here, before anything is enqueued: a refusal sends the caller down the host-side choice instead of failing mid-call)
 bool generic_fallback_fits(uint32_t w_max);
-int pick_geometry_key(uint32_t need, uint32_t dim, int variant, bool uniform_pen, bool fast_shift);
-// >= 20000: full-matrix kernel, 20000 + (pairs per wavefront) * 100 + CW, for pairs of at most `rows` x `cols` frames (0 if it does not apply)
-int pick_full_key(uint32_t cols, uint32_t rows, uint32_t dim, int variant);   // (>= 10000: wide kernel, 10000 + NW * 100 + C)
-double full_key_cost(uint32_t cols, uint32_t rows, uint32_t dim, int key);    // modelled cost of one pair on that geometry (+inf: does not apply)
-// >= 30000: the same column strips with a binding band (two DPs): 30000 + (pairs per wavefront) * 100 + CW
-int pick_banded_strip_key(uint32_t cols, uint32_t rows, uint32_t dim, int variant);
+
+// One launch of the tile plan: the tiles [first, first + count) of its device tile list, all swept with geometry `geom`.
+struct TileClass { KernelGeom geom; uint32_t first, count, w_max, n_max; };
+// The policy of the tile plan (dtw_generic.hip): which kernel geometry sweeps which of `tiles` (tile-row pairs, see
+// rank_tile_list) of a batch whose resident sequence p spans offsets[p] .. offsets[p + 1].  `variant` is apd_set_variant's
+// code.  Fills `classes` in geometry order and `flat`, the tile list they index: (tile_a, tile_b, index in the slab, 0).
+void plan_tile_classes(const std::vector<uint64_t> &offsets, uint32_t n_seq, const std::vector<uint2> &tiles, const BandSpec &band,
+                       uint32_t dim, int variant, bool fast_ok, bool uniform_pen, bool fast_shift, std::vector<TileClass> &classes,
+                       std::vector<uint4> &flat);
 // d_flags[0] is raised when a frame holds a NaN or an infinity (the fast kernels' selects and sentinels assume finite features)
 // d_seq_nmax[p] (zeroed by the caller) receives the largest squared frame norm of resident sequence p
 hipError_t launch_pad(const float *d_src, float *d_dst, const uint32_t *d_seq_off, const uint32_t *d_src_off, uint32_t n_seq,
@@ -189,7 +288,6 @@ struct apd_batch {
     std::vector<uint64_t> offsets;    // frame offsets of the RESIDENT order (host)
     uint32_t min_len = 0, max_len = 0;
     // device-resident tile lists, grouped by the kernel geometry each tile needs
-    struct TileClass { int geom_key; uint32_t first, count, w_max, n_max; };
-    struct TilePlan { uint4 *d_tiles = nullptr; std::vector<TileClass> classes; };
+    struct TilePlan { uint4 *d_tiles = nullptr; std::vector<apd::TileClass> classes; };
     mutable std::map<std::string, TilePlan> tile_cache;   // keyed by rank/world/band/variant
 };

@@ -201,45 +201,19 @@ __device__ __forceinline__ void store_pair(const AlignLaunch &L, uint32_t, const
     slab[kSlotsPerTile + p.slot_a * kTile + p.slot_b] = s2;       // score(x=b, y=a)
 }
 
-// Host launchers of the templated systolic kernel, one translation unit per frame dimension.
-// Returns false when (G, C) is not instantiated.
+// Host launchers of the kernel families, defined in their headers and instantiated once per frame dimension by dtw_sys.hip,
+// dtw_sysx.hip and dtw_wf.hip.  Each launches geometry g if its family list (apd_internal.h) holds it for D, else returns
+// false.  L.hybrid selects the distance form; the dispatcher (launch_align) decides it.
 template <int D>
-bool launch_systolic(const AlignLaunch &L, int g, int c, bool uniform_pen, hipStream_t stream);   // L.hybrid selects the distance form
-extern template bool launch_systolic<8>(const AlignLaunch &, int, int, bool, hipStream_t);
-extern template bool launch_systolic<10>(const AlignLaunch &, int, int, bool, hipStream_t);
-extern template bool launch_systolic<13>(const AlignLaunch &, int, int, bool, hipStream_t);
-extern template bool launch_systolic<16>(const AlignLaunch &, int, int, bool, hipStream_t);
-extern template bool launch_systolic<20>(const AlignLaunch &, int, int, bool, hipStream_t);
-extern template bool launch_systolic<26>(const AlignLaunch &, int, int, bool, hipStream_t);
-
-// ... and of its strict-mode instantiations <D, C, G, unit penalties, difference form>, in units of their own (dtw_sysx_d<D>.hip).
+bool launch_systolic(const AlignLaunch &L, KernelGeom g, hipStream_t stream);
+// strict-mode instantiations <D, C, G, unit penalties, difference form>, in units of their own
 template <int D>
-bool launch_systolic_strict(const AlignLaunch &L, int g, int c, hipStream_t stream);
-extern template bool launch_systolic_strict<8>(const AlignLaunch &, int, int, hipStream_t);
-extern template bool launch_systolic_strict<10>(const AlignLaunch &, int, int, hipStream_t);
-extern template bool launch_systolic_strict<13>(const AlignLaunch &, int, int, hipStream_t);
-extern template bool launch_systolic_strict<16>(const AlignLaunch &, int, int, hipStream_t);
-extern template bool launch_systolic_strict<20>(const AlignLaunch &, int, int, hipStream_t);
-extern template bool launch_systolic_strict<26>(const AlignLaunch &, int, int, hipStream_t);
-
-// Wide-band kernel (dtw_wide.h): NW waves per pair; returns false when (NW, C) is not instantiated.
+bool launch_systolic_strict(const AlignLaunch &L, KernelGeom g, hipStream_t stream);
+// wide-band kernel (dtw_wide.h): NW waves per pair
 template <int D>
-bool launch_wide(const AlignLaunch &L, int nw, int c, hipStream_t stream, hipError_t *err);
-extern template bool launch_wide<8>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-extern template bool launch_wide<10>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-extern template bool launch_wide<13>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-extern template bool launch_wide<16>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-extern template bool launch_wide<20>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-extern template bool launch_wide<26>(const AlignLaunch &, int, int, hipStream_t, hipError_t *);
-
-// Full-matrix kernel (dtw_full.h): column strips, one DP for both ordered pairs.
+bool launch_wide(const AlignLaunch &L, KernelGeom g, hipStream_t stream, hipError_t *err);
+// column-strip kernels (dtw_full.h), unbanded and banded
 template <int D>
-bool launch_full(const AlignLaunch &L, bool banded, int ppw, int cw, hipStream_t stream, hipError_t *err);
-extern template bool launch_full<8>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
-extern template bool launch_full<10>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
-extern template bool launch_full<13>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
-extern template bool launch_full<16>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
-extern template bool launch_full<20>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
-extern template bool launch_full<26>(const AlignLaunch &, bool, int, int, hipStream_t, hipError_t *);
+bool launch_full(const AlignLaunch &L, KernelGeom g, hipStream_t stream, hipError_t *err);
 
 }  // namespace apd

@@ -243,8 +243,8 @@ __global__ __launch_bounds__(64) void dtw_full_matrix(const AlignLaunch L)
 template <int D, int CW, int G>
 static hipError_t launch_full_general(const AlignLaunch &L, hipStream_t stream)
 {
-    constexpr int DP = (D + 1 + 3) & ~3, R = (G == 64) ? 128 : 64, PPW = 64 / G;
-    const size_t lds_bytes = ((size_t)R * DP + (size_t)PPW * 2 * (L.n_max + 4) + 16) * sizeof(float);
+    constexpr int PPW = 64 / G;
+    const size_t lds_bytes = strip_lds_bytes(D, PPW, true, L.n_max);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid(L.n_tiles * (kSlotsPerTile / PPW)), block(64);
     if (lds_bytes > 64 * 1024) {
@@ -259,39 +259,34 @@ static hipError_t launch_full_general(const AlignLaunch &L, hipStream_t stream)
 template <int D, int CW, int G, bool BANDED>
 static hipError_t launch_full_c(const AlignLaunch &L, hipStream_t stream)
 {
-    constexpr int DP = (D + 1 + 3) & ~3, R = (G == 64) ? 128 : 64, PPW = 64 / G;
-    const size_t lds_bytes = ((size_t)R * DP + (size_t)PPW * (BANDED ? 2 : 1) * (L.n_max + 4) + 16) * sizeof(float);
+    constexpr int PPW = 64 / G;
+    const size_t lds_bytes = strip_lds_bytes(D, PPW, BANDED, L.n_max);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;      // the dispatcher keeps such tiles off this kernel
     const dim3 grid(L.n_tiles * (kSlotsPerTile / PPW)), block(64);
-    const bool hybrid = L.hybrid && D >= 10 && L.band.mat == 1.0f;   // (equal penalties here: all three are 1)
-    const void *fn = hybrid ? reinterpret_cast<const void *>(dtw_full_matrix<D, CW, G, true, BANDED>)
-                            : reinterpret_cast<const void *>(dtw_full_matrix<D, CW, G, false, BANDED>);
+    const void *fn = L.hybrid ? reinterpret_cast<const void *>(dtw_full_matrix<D, CW, G, true, BANDED>)
+                              : reinterpret_cast<const void *>(dtw_full_matrix<D, CW, G, false, BANDED>);
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    if (hybrid) hipLaunchKernelGGL((dtw_full_matrix<D, CW, G, true, BANDED>), grid, block, lds_bytes, stream, L);
+    if (L.hybrid) hipLaunchKernelGGL((dtw_full_matrix<D, CW, G, true, BANDED>), grid, block, lds_bytes, stream, L);
     else hipLaunchKernelGGL((dtw_full_matrix<D, CW, G, false, BANDED>), grid, block, lds_bytes, stream, L);
     return hipGetLastError();
 }
 
-// geometry key of the column-strip kernels: 20000 (band never binds, one DP) or 30000 (banded, two DPs)
-//                                          + (pairs per wavefront = 64 / G) * 100 + CW
 template <int D>
-bool launch_full(const AlignLaunch &L, bool banded, int ppw, int cw, hipStream_t stream, hipError_t *err)
+bool launch_full(const AlignLaunch &L, KernelGeom g, hipStream_t stream, hipError_t *err)
 {
-#define APD_FCASE(CC) if constexpr (CC <= max_strip_columns(D)) { if (cw == CC && !banded) { \
-        if (ppw == 1) { *err = launch_full_c<D, CC, 64, false>(L, stream); return true; } \
-        if (ppw == 2) { *err = launch_full_c<D, CC, 32, false>(L, stream); return true; } \
-        if (ppw == 4) { *err = launch_full_c<D, CC, 16, false>(L, stream); return true; } } }
-    APD_FCASE(3) APD_FCASE(5) APD_FCASE(7) APD_FCASE(9) APD_FCASE(11) APD_FCASE(13)
-#undef APD_FCASE
+#define APD_CASE(PP, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::Strip, PP, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::Strip, PP, CC}) { *err = launch_full_c<D, CC, 64 / PP, false>(L, stream); return true; } }
+    APD_STRIP_GEOMS(APD_CASE)
+#undef APD_CASE
     const bool general = !((L.band.ins == L.band.del) && (L.band.del == L.band.mat)) || L.strict;   // unequal penalties (or strict mode): literal select, strict distances
-#define APD_BCASE(CC) if constexpr (CC <= max_cells_per_lane(D)) { if (cw == CC && banded) { \
-        if (ppw == 1) { *err = general ? launch_full_general<D, CC, 64>(L, stream) : launch_full_c<D, CC, 64, true>(L, stream); return true; } \
-        if (ppw == 4) { *err = general ? launch_full_general<D, CC, 16>(L, stream) : launch_full_c<D, CC, 16, true>(L, stream); return true; } } }
-    APD_BCASE(5) APD_BCASE(9)
-#undef APD_BCASE
+#define APD_CASE(PP, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::BandedStrip, PP, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::BandedStrip, PP, CC}) { \
+            *err = general ? launch_full_general<D, CC, 64 / PP>(L, stream) : launch_full_c<D, CC, 64 / PP, true>(L, stream); return true; } }
+    APD_BANDED_STRIP_GEOMS(APD_CASE)
+#undef APD_CASE
     return false;
 }
 

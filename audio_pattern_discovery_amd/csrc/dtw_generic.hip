@@ -24,8 +24,8 @@
 // The kernel in this file is the slow, fully general one: any frame dimension, any band up to what 160 KB of LDS
 // holds (C chosen at run time, per-lane DP rows in LDS, every boundary tested per cell, any penalty values).
 // dtw_systolic.h holds the production kernel.
+#include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 #include "dtw_common.h"
 
@@ -317,63 +317,70 @@ hipError_t launch_unpack(const float *d_gathered, float *d_out, const uint32_t *
 }
 
 // ------------------------------------------------------------------------------------------------
-// dispatch
+// dispatch: which kernel sweeps which tile, with which geometry (the lists of what exists: apd_internal.h)
 // ------------------------------------------------------------------------------------------------
-struct Geometry { int g, c; };
 
-// Pick the (lanes per pair, offsets per lane) that wastes the fewest lanes for a band of `need` offsets; 0 = generic.
-int pick_geometry_key(uint32_t need, uint32_t dim, int variant, bool uniform_pen, bool fast_shift)
+// apd_set_variant, decoded once per tile plan: 0 lets every family be searched, 1 forces the generic kernel, a geometry's code
+// forces that geometry (tuning); any other code keeps the band-form search and turns the column strips off.
+struct VariantRequest {
+    bool automatic;   // variant 0: strips searched, small strip classes consolidated
+    bool generic;     // variant 1
+    KernelGeom geom;  // the forced geometry as decoded (it may name one that is not instantiated); Generic: none
+    explicit VariantRequest(int variant) : automatic(variant == 0), generic(variant == 1), geom(KernelGeom::decode(variant)) {}
+};
+
+// Band form: the (lanes per pair, offsets per lane) that wastes the fewest lanes for a band of `need` offsets; Generic if none.
+static KernelGeom pick_band_geom(uint32_t need, uint32_t dim, const VariantRequest &req, bool uniform_pen, bool fast_shift)
 {
-    if (variant == 1) return 0;                                        // forced generic kernel
-    if (variant >= 20000) variant = 0;                                 // a forced full-matrix geometry (pick_full_key) says nothing about band-form tiles
-    if (!is_kernel_dim(dim)) return 0;                                 // instantiated frame dimensions
-    if (variant >= 10000) {                                            // forced wide geometry (tuning)
-        const int nw = (variant - 10000) / 100, c = variant % 100;
-        return (uniform_pen && (uint32_t)(64 * nw * c) >= need) ? variant : 0;
-    }
-    if (variant >= 100) {                                              // forced geometry (tuning)
-        const int g = variant / 100, c = variant % 100;
-        return ((uint32_t)(g * c) >= need) ? variant : 0;
-    }
+    if (req.generic || !is_kernel_dim(dim)) return {};
+    const KernelGeom f = req.geom;
+    if (f.family == KernelGeom::Systolic || f.family == KernelGeom::Wide)   // forced; too narrow (or not instantiated): generic
+        return (f.family == KernelGeom::Systolic || uniform_pen) && f.capacity() >= need && geom_instantiated(f, dim) ? f : KernelGeom{};
     // score = lanes busy x how cheap a cell is at this C.  A macro-step costs about 116 SIMD cycles (window moves, exchanges,
     // threshold test) plus 76 per cell pair, so relative to C = 9 a cell costs 1.04 / 1.11 / 1.29 / 1.50
     // at C = 7 / 5 / 3 / 2.  G = 8 and G = 32 span half / two DPP rows: one-instruction moves only in the hybrid form with unit
     // penalties (`fast_shift`: masked column fetch), two instructions or a select per move otherwise.
-    static const Geometry all[] = {{8, 5}, {8, 7}, {8, 9}, {16, 2}, {16, 3}, {16, 5}, {16, 7}, {16, 9}, {32, 5}, {32, 7}, {32, 9}, {64, 3}, {64, 5}, {64, 7}, {64, 9}};
     auto cell_eff = [](int c) { return c >= 9 ? 1.0 : c >= 7 ? 0.96 : c >= 5 ? 0.90 : c >= 3 ? 0.78 : 0.67; };
-    Geometry best{0, 0};
+    KernelGeom best{};
     double best_util = 0.0;
-    for (const Geometry &q : all) {
-        if ((uint32_t)(q.g * q.c) < need || q.c > max_cells_per_lane(dim)) continue;
-        const bool split_rows = q.g == 8 || q.g == 32;
-        const double util = (double)need / (double)(q.g * q.c) * cell_eff(q.c) * (split_rows ? (fast_shift ? 0.99 : 0.90) : 1.0);
+    for (KernelGeom q : kSystolicGeoms) {
+        if (q.capacity() < need || !geom_instantiated(q, dim)) continue;
+        const bool split_rows = q.lanes_or_waves == 8 || q.lanes_or_waves == 32;
+        const double util = (double)need / (double)q.capacity() * cell_eff(q.cells) * (split_rows ? (fast_shift ? 0.99 : 0.90) : 1.0);
         if (util > best_util) { best_util = util; best = q; }
     }
-    if (best.g != 0) return best.g * 100 + best.c;
-    // beyond one wavefront: NW waves per pair (dtw_wide.h), uniform penalties only
-    if (uniform_pen) {
-        static const Geometry wide[] = {{2, 5}, {2, 7}, {2, 9}, {4, 5}, {4, 7}, {4, 9}, {8, 5}, {8, 7}, {8, 9}};   // (NW, C), ascending capacity
-        for (const Geometry &q : wide)
-            if ((uint32_t)(64 * q.g * q.c) >= need && q.c <= max_cells_per_lane(dim)) return 10000 + q.g * 100 + q.c;
-    }
-    return 0;
+    if (best.family != KernelGeom::Generic) return best;
+    // beyond one wavefront: NW waves per pair (dtw_wide.h), uniform penalties only; the smallest that holds the band
+    if (uniform_pen)
+        for (KernelGeom q : kWideGeoms)
+            if (q.capacity() >= need && geom_instantiated(q, dim)) return q;
+    return {};
 }
 
-// Full-matrix kernel: 20000 + (pairs per wavefront) * 100 + CW.  With G = 64 / ppw lanes per pair, a pair of `rows` x `cols`
-// takes ceil(cols / (G CW)) passes of rows + G macro-steps, each serving ppw pairs.  The cost of a macro-step was fitted on
-// MI355X (tools/debug/strip_grid.sh: every forced geometry on bench.py's short9 / full6 / ship / full8): proportional to
-// CW (+0.5 / +1.5 for the two-DPP moves and per-lane bookkeeping of 32- / 16-lane groups), 8 % more once CW frames of D + 1
-// floats push the kernel to two waves per SIMD, and inversely to the wavefronts per CU that the LDS boundary columns
-// (ppw * rows floats per wavefront) leave room for.  Returns +inf for a geometry that is not instantiated or does not fit.
-double full_key_cost(uint32_t cols, uint32_t rows, uint32_t dim, int key)
+struct GeomList {
+    const KernelGeom *first, *last;
+    const KernelGeom *begin() const { return first; }
+    const KernelGeom *end() const { return last; }
+};
+static GeomList strip_geoms(KernelGeom::Family family)
 {
-    const bool banded = key >= 30000;
-    const int ppw = (key % 10000) / 100, cw = key % 100;
-    if (key < 20000 || key >= 40000) return INFINITY;
-    if (!banded && (!(ppw == 1 || ppw == 2 || ppw == 4) || cw < 3 || cw > max_strip_columns(dim) || cw % 2 == 0)) return INFINITY;
-    if (banded && (!(ppw == 1 || ppw == 4) || !(cw == 5 || cw == 9) || cw > max_cells_per_lane(dim))) return INFINITY;   // instantiated: dtw_full.h
+    if (family == KernelGeom::Strip) return {std::begin(kStripGeoms), std::end(kStripGeoms)};
+    return {std::begin(kBandedStripGeoms), std::end(kBandedStripGeoms)};
+}
+
+// Column strips (dtw_full.h), one pair of `rows` x `cols`: with G = 64 / ppw lanes per pair it takes ceil(cols / (G CW))
+// passes of rows + G macro-steps, each serving ppw pairs.  The cost of a macro-step was fitted on MI355X
+// (tools/debug/strip_grid.sh: every forced geometry on bench.py's short9 / full6 / ship / full8): proportional to CW (+0.5 /
+// +1.5 for the two-DPP moves and per-lane bookkeeping of 32- / 16-lane groups), 8 % more once CW frames of D + 1 floats push
+// the kernel to two waves per SIMD, and inversely to the wavefronts per CU that the LDS boundary columns (ppw * rows floats
+// per wavefront) leave room for.  +inf for a geometry that is not instantiated or does not fit.
+static double strip_cost(uint32_t cols, uint32_t rows, uint32_t dim, KernelGeom key)
+{
+    const bool banded = key.family == KernelGeom::BandedStrip;
+    if ((key.family != KernelGeom::Strip && !banded) || !geom_instantiated(key, dim)) return INFINITY;
+    const int ppw = key.lanes_or_waves, cw = key.cells;
     const uint32_t g = 64u / ppw;
-    const double lds_bytes = 4.0 * ((g == 64 ? 128.0 : 64.0) * ((dim + 4) & ~3u) + (double)ppw * (banded ? 2 : 1) * (rows + 4) + 16);
+    const double lds_bytes = (double)strip_lds_bytes(dim, ppw, banded, rows);
     if (lds_bytes > 160.0 * 1024) return INFINITY;
     const double waves_per_cu = std::floor(160.0 * 1024 / lds_bytes);
     const double lds_factor = waves_per_cu >= 8.0 ? 1.0 : 8.0 / waves_per_cu;
@@ -383,119 +390,127 @@ double full_key_cost(uint32_t cols, uint32_t rows, uint32_t dim, int key)
     return passes * ((double)rows + g) * (cw + group_steps) * occupancy_factor * lds_factor / ppw;
 }
 
-int pick_full_key(uint32_t cols, uint32_t rows, uint32_t dim, int variant)
+// The cheapest strip geometry of `family` for pairs of at most `rows` x `cols` frames; Generic if none applies.
+static KernelGeom pick_strip_geom(uint32_t cols, uint32_t rows, uint32_t dim, const VariantRequest &req, KernelGeom::Family family)
 {
-    if (variant != 0 && (variant < 20000 || variant >= 30000)) return 0;   // another kernel was requested
-    if (!is_kernel_dim(dim)) return 0;
-    if (variant >= 20000) return std::isfinite(full_key_cost(cols, rows, dim, variant)) ? variant : 0;
-    int best = 0;
+    if (!is_kernel_dim(dim)) return {};
+    if (!req.automatic) return req.geom.family == family && std::isfinite(strip_cost(cols, rows, dim, req.geom)) ? req.geom : KernelGeom{};
+    KernelGeom best{};
     double best_cost = INFINITY;
-    for (int ppw = 1; ppw <= 4; ppw *= 2)
-        for (int cw = 5; cw <= max_strip_columns(dim); cw += 2) {          // 3-column strips only on request: measured slower than the model says
-            const double cost = full_key_cost(cols, rows, dim, 20000 + ppw * 100 + cw);
-            if (cost < best_cost) { best = 20000 + ppw * 100 + cw; best_cost = cost; }
-        }
-    return best;
-}
-
-int pick_banded_strip_key(uint32_t cols, uint32_t rows, uint32_t dim, int variant)
-{
-    if (variant != 0 && (variant < 30000 || variant >= 40000)) return 0;
-    if (!is_kernel_dim(dim)) return 0;
-    if (variant >= 30000) return std::isfinite(full_key_cost(cols, rows, dim, variant)) ? variant : 0;
-    int best = 0;
-    double best_cost = INFINITY;
-    for (int ppw = 1; ppw <= 4; ppw *= 4)
-        for (int cw = 5; cw <= 9; cw += 4) {
-            const double cost = full_key_cost(cols, rows, dim, 30000 + ppw * 100 + cw);
-            if (cost < best_cost) { best = 30000 + ppw * 100 + cw; best_cost = cost; }
-        }
-    return best;
-}
-
-static hipError_t launch_align_chunk(const AlignLaunch &L, int geom_key, hipStream_t stream, std::string &err, int *status);
-
-// A launch may not exceed 2^32 work-items (beyond, the grid is silently cut short on this runtime): launches are cut
-// into runs of tiles that stay below 2^31.  Work-items per tile: 256 pairs x lanes per pair.
-hipError_t launch_align(const AlignLaunch &L, int geom_key, hipStream_t stream, std::string &err, int *status)
-{
-    *status = APD_OK;
-    uint32_t lanes_per_pair = 64;                                         // generic kernel: one wavefront per pair
-    if (geom_key >= 20000) lanes_per_pair = 64;                                           // full-matrix: at most one wavefront per pair
-    else if (geom_key >= 10000) lanes_per_pair = 64u * (uint32_t)((geom_key % 10000) / 100);   // wide: NW waves per pair
-    else if (geom_key != 0) lanes_per_pair = (uint32_t)(geom_key / 100);                   // systolic: G lanes per pair
-    const uint32_t kTilesPerLaunch = (1u << 31) / (kSlotsPerTile * std::max(lanes_per_pair, 64u));
-    for (uint32_t first = 0; first < L.n_tiles; first += kTilesPerLaunch) {
-        AlignLaunch part = L;
-        part.d_tiles = L.d_tiles + first;
-        part.n_tiles = std::min(kTilesPerLaunch, L.n_tiles - first);
-        const hipError_t e = launch_align_chunk(part, geom_key, stream, err, status);
-        if (e != hipSuccess || *status != APD_OK) return e;
+    for (KernelGeom g : strip_geoms(family)) {
+        if (g.cells < 5) continue;                                     // 3-column strips only on request: measured slower than the model says
+        const double cost = strip_cost(cols, rows, dim, g);
+        if (cost < best_cost) { best = g; best_cost = cost; }
     }
-    return hipSuccess;
+    return best;
 }
 
-static hipError_t launch_align_chunk(const AlignLaunch &L, int geom_key, hipStream_t stream, std::string &err, int *status)
+// Which kernel sweeps which tile.  Tiles are grouped by the kernel geometry their widest pair needs (w is bounded per tile
+// from the lengths of its 32 sequences), one launch per group: a few long or unequal sequences do not force every pair
+// onto a wide kernel.
+void plan_tile_classes(const std::vector<uint64_t> &offsets, uint32_t n_seq, const std::vector<uint2> &tiles, const BandSpec &band,
+                       uint32_t dim, int variant, bool fast_ok, bool uniform_pen, bool fast_shift, std::vector<TileClass> &classes,
+                       std::vector<uint4> &flat)
 {
-    *status = APD_OK;
+    const VariantRequest req(variant);
+    // per tile-row (16 sequences) min / max length
+    const uint32_t side = (n_seq + kTile - 1) / kTile;
+    std::vector<uint32_t> lo(side, 0xFFFFFFFFu), hi(side, 0);
+    for (uint32_t s = 0; s < n_seq; ++s) {
+        const uint32_t len = (uint32_t)(offsets[s + 1] - offsets[s]);
+        lo[s / kTile] = std::min(lo[s / kTile], len);
+        hi[s / kTile] = std::max(hi[s / kTile], len);
+    }
+    struct Group { std::vector<uint4> tiles; uint32_t w_max = 0, n_max = 0; };
+    std::map<KernelGeom, Group> groups;
+    for (uint32_t t = 0; t < tiles.size(); ++t) {
+        const uint32_t mx = std::max(hi[tiles[t].x], hi[tiles[t].y]), mn = std::min(lo[tiles[t].x], lo[tiles[t].y]);
+        const uint32_t band_ub = band.use_explicit ? band.explicit_band : host_band_from_pct(band.pct, mx);
+        const uint32_t w = std::max(std::min(band_ub, mx), mx - mn) + 2;   // >= w of every pair of the tile
+        KernelGeom key = fast_ok ? pick_band_geom(2 * w + 1, dim, req, uniform_pen, fast_shift) : KernelGeom{};
+        // the band binds nowhere in this tile (band >= longest - 3 for its longest sequence, hence for all) and the penalties
+        // are equal: both ordered scores are one number, swept over column strips (dtw_full.h).  Not for very short columns,
+        // where four pairs per wavefront in band form keep more lanes busy.
+        const uint32_t cols = std::min(hi[tiles[t].x], hi[tiles[t].y]);
+        const bool never_binds = mx >= 3 && std::min(band_ub, mx) >= mx - 3;
+        if (fast_ok && uniform_pen && never_binds && (cols >= 49 || req.geom.family == KernelGeom::Strip)) {
+            const KernelGeom fk = pick_strip_geom(cols > 0 ? cols - 1 : 0, mx, dim, req, KernelGeom::Strip);
+            if (fk.family != KernelGeom::Generic) key = fk;
+        } else if (fast_ok && mx >= 3 && cols >= 49 &&                          // (any penalties: unequal ones take the literal select)
+                   (2ull * w + 1 >= cols ||                                   // band at least as wide as the short side
+                    key.family == KernelGeom::Generic ||                      // no band-form kernel fits: anything beats the generic one
+                    req.geom.family == KernelGeom::BandedStrip)) {
+            // the band binds, but is wider than the short side of the tile's pairs (w grows with |n - m|, alignments.rs:173):
+            // in band coordinates most offsets of such a pair lie outside it; column strips with masked band edges fit
+            const KernelGeom bk = pick_strip_geom(cols - 1, mx, dim, req, KernelGeom::BandedStrip);
+            if (bk.family != KernelGeom::Generic) key = bk;
+        }
+        Group &g = groups[key];
+        g.tiles.push_back(make_uint4(tiles[t].x, tiles[t].y, t, 0));
+        g.w_max = std::max(g.w_max, w);
+        g.n_max = std::max(g.n_max, mx);
+    }
+    // Every class is a launch of its own, and launches of one stream do not overlap: a full-matrix class of a few dozen
+    // tiles would run at a fraction of the machine.  Small classes (all of them, in a small batch) move to the geometry
+    // that is best for the full-matrix tiles as a whole.
+    if (req.automatic) {
+        for (KernelGeom::Family family : {KernelGeom::Strip, KernelGeom::BandedStrip}) {   // one DP (band never binds) / two DPs (banded)
+            size_t n_fam = 0;
+            for (auto &g : groups) if (g.first.family == family) n_fam += g.second.tiles.size();
+            if (n_fam == 0) continue;
+            const int max_ppw = n_fam * kSlotsPerTile < 8192 ? 1 : 4;    // too few pairs to fill the GPU: one wavefront each
+            KernelGeom global{};
+            double global_cost = INFINITY;
+            for (KernelGeom k : strip_geoms(family)) {
+                if (k.cells < 5 || k.lanes_or_waves > max_ppw) continue;
+                double total = 0.0;
+                for (auto &g : groups) {
+                    if (g.first.family != family) continue;
+                    for (const uint4 &t : g.second.tiles) {
+                        const uint32_t c = std::min(hi[t.x], hi[t.y]);
+                        total += strip_cost(c > 0 ? c - 1 : 0, std::max(hi[t.x], hi[t.y]), dim, k);
+                    }
+                }
+                if (total < global_cost) { global_cost = total; global = k; }
+            }
+            const size_t min_class = n_fam < 2048 ? n_fam + 1 : 256;
+            if (global.family == KernelGeom::Generic) continue;
+            std::vector<KernelGeom> small;
+            for (auto &g : groups) if (g.first.family == family && !(g.first == global) && g.second.tiles.size() < min_class) small.push_back(g.first);
+            for (KernelGeom k : small) {
+                Group &from = groups[k], &to = groups[global];
+                to.tiles.insert(to.tiles.end(), from.tiles.begin(), from.tiles.end());
+                to.w_max = std::max(to.w_max, from.w_max);
+                to.n_max = std::max(to.n_max, from.n_max);
+                groups.erase(k);
+            }
+            std::vector<uint4> &merged = groups[global].tiles;
+            std::sort(merged.begin(), merged.end(), [](const uint4 &a, const uint4 &b) { return a.z < b.z; });
+        }
+    }
+    classes.clear();
+    flat.clear();
+    for (auto &g : groups) {
+        classes.push_back(TileClass{g.first, (uint32_t)flat.size(), (uint32_t)g.second.tiles.size(), g.second.w_max, g.second.n_max});
+        flat.insert(flat.end(), g.second.tiles.begin(), g.second.tiles.end());
+    }
+}
+
+// the generic kernel's LDS: two DP rows of c_max cells per lane
+static size_t generic_lds_bytes(uint32_t w_max, int *c_max_out)
+{
+    int c_max = (int)((2 * (uint64_t)w_max + 1 + 63) / 64);
+    if (c_max < 2) c_max = 2;
+    if (c_max_out) *c_max_out = c_max;
+    return (size_t)c_max * 64 * 2 * sizeof(float);
+}
+
+static hipError_t launch_align_chunk(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status)
+{
     if (L.n_tiles == 0) return hipSuccess;
-    const BandSpec &b = L.band;
-    const bool unit_pens = (b.ins == 1.0f) && (b.del == 1.0f) && (b.mat == 1.0f);
-    // the systolic kernel's UNIFORM_PEN path (no weighting at all).  Strict mode keeps it: with unit penalties the fast select on
-    // the difference form -- which in the band kernels is the reference's arithmetic operation for operation -- gives the CPU
-    // code's bits (see dtw_systolic.h); only the hybrid distance form is switched off.
-    const bool unit = unit_pens;
-    bool done = false;
-    AlignLaunch LL = L;
-    // The norm expansion trades D - 1 vector ops per cell (systolic kernel, pre-scaled rows; D - 4 in the strip kernels) for a
-    // branch per macro-step: measured worth it from D = 8 in the systolic kernel (cfg 4: -2.6 %), from D = 10 elsewhere.
-    static const int hybrid_min_env = std::getenv("APD_HYBRID_MIN_DIM") ? std::atoi(std::getenv("APD_HYBRID_MIN_DIM")) : 0;   // tuning aid
-    const int hybrid_min_dim = hybrid_min_env ? hybrid_min_env : (geom_key >= 100 && geom_key < 10000 ? 8 : 10);
-    if ((int)LL.dim < hybrid_min_dim) LL.hybrid = 0;
-    if (L.strict && geom_key >= 100 && geom_key < 10000) LL.hybrid = 0;
-    if (geom_key >= 20000) {
-        const bool banded = geom_key >= 30000;
-        const int nw = (geom_key % 10000) / 100, cw = geom_key % 100;
-        hipError_t fe = hipSuccess;
-        switch (L.dim) {
-            case 8: done = launch_full<8>(LL, banded, nw, cw, stream, &fe); break;
-            case 10: done = launch_full<10>(LL, banded, nw, cw, stream, &fe); break;
-            case 13: done = launch_full<13>(LL, banded, nw, cw, stream, &fe); break;
-            case 16: done = launch_full<16>(LL, banded, nw, cw, stream, &fe); break;
-            case 20: done = launch_full<20>(LL, banded, nw, cw, stream, &fe); break;
-            case 26: done = launch_full<26>(LL, banded, nw, cw, stream, &fe); break;
-            default: break;
-        }
-        if (done && fe != hipSuccess) return fe;
-    } else if (geom_key >= 10000) {
-        const int nw = (geom_key - 10000) / 100, c = geom_key % 100;
-        hipError_t we = hipSuccess;
-        switch (L.dim) {
-            case 8: done = launch_wide<8>(LL, nw, c, stream, &we); break;
-            case 10: done = launch_wide<10>(LL, nw, c, stream, &we); break;
-            case 13: done = launch_wide<13>(LL, nw, c, stream, &we); break;
-            case 16: done = launch_wide<16>(LL, nw, c, stream, &we); break;
-            case 20: done = launch_wide<20>(LL, nw, c, stream, &we); break;
-            case 26: done = launch_wide<26>(LL, nw, c, stream, &we); break;
-            default: break;
-        }
-        if (done && we != hipSuccess) return we;
-    } else if (geom_key != 0) {
-        const int g = geom_key / 100, c = geom_key % 100;
-        switch (L.dim) {
-            case 8: done = launch_systolic<8>(LL, g, c, unit, stream); break;
-            case 10: done = launch_systolic<10>(LL, g, c, unit, stream); break;
-            case 13: done = launch_systolic<13>(LL, g, c, unit, stream); break;
-            case 16: done = launch_systolic<16>(LL, g, c, unit, stream); break;
-            case 20: done = launch_systolic<20>(LL, g, c, unit, stream); break;
-            case 26: done = launch_systolic<26>(LL, g, c, unit, stream); break;
-            default: break;
-        }
-    }
-    if (!done) {
-        int c_max = (int)((2 * (uint64_t)L.w_max + 1 + 63) / 64);
-        if (c_max < 2) c_max = 2;
-        const size_t lds_bytes = (size_t)c_max * 64 * 2 * sizeof(float);
+    if (g.family == KernelGeom::Generic) {
+        int c_max = 2;
+        const size_t lds_bytes = generic_lds_bytes(L.w_max, &c_max);
         if (lds_bytes > 160 * 1024) { *status = APD_ERR_BAND_TOO_WIDE; err = "band too wide for the generic kernel"; return hipSuccess; }
         if (lds_bytes > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_fused_generic),
@@ -504,16 +519,45 @@ static hipError_t launch_align_chunk(const AlignLaunch &L, int geom_key, hipStre
         }
         const uint64_t waves = (uint64_t)L.n_tiles * kSlotsPerTile;
         hipLaunchKernelGGL(dtw_fused_generic, dim3((uint32_t)waves), dim3(64), lds_bytes, stream, L, c_max);
+        return hipGetLastError();
     }
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    bool found = false;
+    with_kernel_dim(L.dim, [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        found = g.family == KernelGeom::Systolic ? launch_systolic<D>(L, g, stream)
+              : g.family == KernelGeom::Wide     ? launch_wide<D>(L, g, stream, &e)
+                                                 : launch_full<D>(L, g, stream, &e);
+    });
+    if (!found) {                                                      // the plan only names listed geometries
+        *status = APD_ERR_UNSUPPORTED;
+        err = "no kernel for geometry " + std::to_string(g.encode()) + " at dimension " + std::to_string(L.dim);
+        return hipSuccess;
+    }
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
-static size_t generic_lds_bytes(uint32_t w_max, int *c_max_out)
+// A launch may not exceed 2^32 work-items (beyond, the grid is silently cut short on this runtime): launches are cut
+// into runs of tiles that stay below 2^31.  Work-items per tile: 256 pairs x lanes per pair.
+hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status)
 {
-    int c_max = (int)((2 * (uint64_t)w_max + 1 + 63) / 64);
-    if (c_max < 2) c_max = 2;
-    if (c_max_out) *c_max_out = c_max;
-    return (size_t)c_max * 64 * 2 * sizeof(float);
+    *status = APD_OK;
+    const uint32_t kTilesPerLaunch = (1u << 31) / (kSlotsPerTile * std::max(g.lanes_per_pair(), 64u));
+    // The distance form (the kernels never read L.hybrid; their launchers pick the instantiation by it).  The norm expansion
+    // trades D - 1 vector ops per cell (systolic kernel, pre-scaled rows; D - 4 in the strip kernels) for a branch per
+    // macro-step: measured worth it from D = 8 in the systolic kernel (cfg 4: -2.6 %), from D = 10 in the wide and strip
+    // kernels, which have it with unit penalties only.  Strict mode keeps the systolic kernel's UNIFORM_PEN path with unit
+    // penalties (its fast select on the difference form is the reference's arithmetic operation for operation, see
+    // dtw_systolic.h) and switches only the hybrid form off.
+    AlignLaunch part = L;
+    part.hybrid = L.hybrid && (g.family == KernelGeom::Systolic ? L.dim >= 8 && !L.strict : L.dim >= 10 && L.band.mat == 1.0f);
+    for (uint32_t first = 0; first < L.n_tiles; first += kTilesPerLaunch) {
+        part.d_tiles = L.d_tiles + first;
+        part.n_tiles = std::min(kTilesPerLaunch, L.n_tiles - first);
+        const hipError_t e = launch_align_chunk(part, g, stream, err, status);
+        if (e != hipSuccess || *status != APD_OK) return e;
+    }
+    return hipSuccess;
 }
 
 bool generic_fallback_fits(uint32_t w_max)

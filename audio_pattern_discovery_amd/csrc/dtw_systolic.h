@@ -508,9 +508,9 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
     }
 }
 
-// The three instantiations of one (D, C, G) live in two translation units -- dtw_sys_d<D>.hip: hybrid form and the literal select
-// (non-unit penalties); dtw_sysx_d<D>.hip (APD_SYSTOLIC_STRICT_UNIT): strict mode's <.., true, false> -- so that each is
-// compiled once, in parallel, with the scheduler flags measured for its own instruction mix (csrc/Makefile).
+// The three instantiations of one (D, C, G) live in two translation units -- dtw_sys.hip: hybrid form and the literal select
+// (non-unit penalties); dtw_sysx.hip (APD_SYSTOLIC_STRICT_UNIT): strict mode's <.., true, false> -- so that each is compiled
+// once per D, in parallel, with the scheduler flags measured for its own instruction mix (csrc/Makefile).
 template <int D, int C, int G, bool UNIFORM_PEN, bool HYBRID>
 static void launch_systolic_kernel(const AlignLaunch &L, hipStream_t stream)
 {
@@ -520,29 +520,28 @@ static void launch_systolic_kernel(const AlignLaunch &L, hipStream_t stream)
     hipLaunchKernelGGL((dtw_fused_systolic<D, C, G, UNIFORM_PEN, HYBRID>), dim3(tiles8 * WPT), dim3(256), 0, stream, L);
 }
 
-// C = 9 keeps 10 column frames per lane in registers: only for D <= 13 (max_cells_per_lane)
-#define APD_SYSTOLIC_GEOMETRIES(X) \
-    X(8, 5) X(8, 7) X(8, 9) X(16, 2) X(16, 3) X(16, 5) X(16, 7) X(16, 9) X(32, 5) X(32, 7) X(32, 9) X(64, 3) X(64, 5) X(64, 7) X(64, 9)
-
 #ifdef APD_SYSTOLIC_STRICT_UNIT
 template <int D>
-bool launch_systolic_strict(const AlignLaunch &L, int g, int c, hipStream_t stream)
+bool launch_systolic_strict(const AlignLaunch &L, KernelGeom g, hipStream_t stream)
 {
-#define APD_CASE(GG, CC) if constexpr (CC <= max_cells_per_lane(D)) { if (g == GG && c == CC) { launch_systolic_kernel<D, CC, GG, true, false>(L, stream); return true; } }
-    APD_SYSTOLIC_GEOMETRIES(APD_CASE)
+#define APD_CASE(GG, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::Systolic, GG, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::Systolic, GG, CC}) { launch_systolic_kernel<D, CC, GG, true, false>(L, stream); return true; } }
+    APD_SYSTOLIC_GEOMS(APD_CASE)
 #undef APD_CASE
     return false;
 }
 #else
 template <int D>
-bool launch_systolic(const AlignLaunch &L, int g, int c, bool unit, hipStream_t stream)
+bool launch_systolic(const AlignLaunch &L, KernelGeom g, hipStream_t stream)
 {
     // unit penalties: the fast select, either distance form; anything else: literal select on strict (bit-faithful) distances
-    if (unit && !L.hybrid) return launch_systolic_strict<D>(L, g, c, stream);
-#define APD_CASE(GG, CC) if constexpr (CC <= max_cells_per_lane(D)) { if (g == GG && c == CC) { \
-        if (!unit) launch_systolic_kernel<D, CC, GG, false, false>(L, stream); else launch_systolic_kernel<D, CC, GG, true, true>(L, stream); \
-        return true; } }
-    APD_SYSTOLIC_GEOMETRIES(APD_CASE)
+    const bool unit = L.band.ins == 1.0f && L.band.del == 1.0f && L.band.mat == 1.0f;
+    if (unit && !L.hybrid) return launch_systolic_strict<D>(L, g, stream);
+#define APD_CASE(GG, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::Systolic, GG, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::Systolic, GG, CC}) { \
+            if (!unit) launch_systolic_kernel<D, CC, GG, false, false>(L, stream); else launch_systolic_kernel<D, CC, GG, true, true>(L, stream); \
+            return true; } }
+    APD_SYSTOLIC_GEOMS(APD_CASE)
 #undef APD_CASE
     return false;
 }

@@ -248,24 +248,23 @@ static hipError_t launch_wide_cn(const AlignLaunch &L, hipStream_t stream)
     constexpr int G = 64 * NW, DP = (D + 1 + 3) & ~3, R = (G <= 256) ? 512 : 1024;
     const size_t lds_bytes = ((size_t)R * DP + (NW + 1) * DP + 4 * (NW + 1)) * sizeof(float);
     const dim3 grid(L.n_tiles * kSlotsPerTile), block(G);
-    const bool hybrid = L.hybrid && D >= 10 && L.band.mat == 1.0f;   // (equal penalties here: all three are 1)
-    const void *fn = hybrid ? reinterpret_cast<const void *>(dtw_fused_wide<D, C, NW, true>) : reinterpret_cast<const void *>(dtw_fused_wide<D, C, NW, false>);
+    const void *fn = L.hybrid ? reinterpret_cast<const void *>(dtw_fused_wide<D, C, NW, true>) : reinterpret_cast<const void *>(dtw_fused_wide<D, C, NW, false>);
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    if (hybrid) hipLaunchKernelGGL((dtw_fused_wide<D, C, NW, true>), grid, block, lds_bytes, stream, L);
+    if (L.hybrid) hipLaunchKernelGGL((dtw_fused_wide<D, C, NW, true>), grid, block, lds_bytes, stream, L);
     else hipLaunchKernelGGL((dtw_fused_wide<D, C, NW, false>), grid, block, lds_bytes, stream, L);
     return hipGetLastError();
 }
 
-// geometry key for the wide kernel: 10000 + NW * 100 + C
 template <int D>
-bool launch_wide(const AlignLaunch &L, int nw, int c, hipStream_t stream, hipError_t *err)
+bool launch_wide(const AlignLaunch &L, KernelGeom g, hipStream_t stream, hipError_t *err)
 {
-#define APD_WCASE(NN, CC) if constexpr (CC <= max_cells_per_lane(D)) { if (nw == NN && c == CC) { *err = launch_wide_cn<D, CC, NN>(L, stream); return true; } }
-    APD_WCASE(2, 5) APD_WCASE(2, 7) APD_WCASE(2, 9) APD_WCASE(4, 5) APD_WCASE(4, 7) APD_WCASE(4, 9) APD_WCASE(8, 5) APD_WCASE(8, 7) APD_WCASE(8, 9)
-#undef APD_WCASE
+#define APD_CASE(NN, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::Wide, NN, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::Wide, NN, CC}) { *err = launch_wide_cn<D, CC, NN>(L, stream); return true; } }
+    APD_WIDE_GEOMS(APD_CASE)
+#undef APD_CASE
     return false;
 }
 

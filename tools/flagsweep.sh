@@ -12,7 +12,7 @@ OBJS=$(make -pn 2>/dev/null | sed -n 's/^OBJS := //p' | head -1)
 args=("$@")
 for ((i=0; i<${#args[@]}; i+=2)); do
   name=${args[i]}; flags=${args[i+1]}
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize $flags -Rpass-analysis=kernel-resource-usage -c $UNIT.hip -o /tmp/t/flag_$name.o 2> /tmp/t/flag_$name.log &
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize $flags -Rpass-analysis=kernel-resource-usage -DAPD_DIM=${UNIT##*_d} -c ${UNIT%_d*}.hip -o /tmp/t/flag_$name.o 2> /tmp/t/flag_$name.log &
 done
 wait
 for ((i=0; i<${#args[@]}; i+=2)); do
