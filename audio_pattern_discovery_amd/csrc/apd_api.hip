@@ -14,15 +14,6 @@ using namespace apd;
 
 namespace {
 
-#define HIP_TRY(ctx, call)                                                             \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);     \
-            return e_ == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;              \
-        }                                                                              \
-    } while (0)
-
 int ensure_ws(apd_context *ctx, void **p, size_t *have, size_t need)
 {
     APD_AFFINITY(ctx, "workspace allocation");

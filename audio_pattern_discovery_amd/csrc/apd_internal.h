@@ -229,6 +229,15 @@ bool affinity_ok(const apd_context *ctx, const char *where);
 #define APD_AFFINITY(ctx, where)                                                                   \
     do { if (apd::affinity_debug() && !apd::affinity_ok((ctx), (where))) return APD_ERR_HIP; } while (0)
 
+// A failed HIP call returns from the entry point: APD_ERR_OOM or APD_ERR_HIP, last_error naming the call and HIP's message.
+#define HIP_TRY(ctx, call)                                                             \
+    do {                                                                               \
+        if (hipError_t e_ = (call); e_ != hipSuccess) {                                \
+            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);     \
+            return e_ == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;              \
+        }                                                                              \
+    } while (0)
+
 struct apd_context {
     int device = 0;
     hipStream_t stream = nullptr;

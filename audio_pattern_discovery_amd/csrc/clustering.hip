@@ -36,14 +36,19 @@ using namespace apd;
 
 namespace {
 
-#define HIP_TRY(ctx, call)                                                             \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);     \
-            return e_ == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;              \
-        }                                                                              \
-    } while (0)
+// Everything an entry point of this file allocates or instantiates: whatever is set is released however the call ends.
+struct Owned {
+    void *ws = nullptr;                               // apd_clustering's workspace, apd_percentile's copy of its input, device_select's histogram
+    float *spare = nullptr;                           // two more n x n buffers: the defragmented copies rotate through d_T and these
+    unsigned long long *dbg = nullptr;                // APD_DEBUG_UPGMA_TIMING stamps
+    hipGraph_t graph[2] = {nullptr, nullptr};         // the two captured batches
+    hipGraphExec_t exec[2] = {nullptr, nullptr};
+    void drop_graphs()
+    {
+        for (int g = 0; g < 2; ++g) { if (exec[g]) hipGraphExecDestroy(exec[g]); if (graph[g]) hipGraphDestroy(graph[g]); exec[g] = nullptr; graph[g] = nullptr; }
+    }
+    ~Owned() { drop_graphs(); for (void *p : {(void *)dbg, (void *)spare, ws}) if (p) hipFree(p); }
+};
 
 // ---------------------------------------------------------------------------------- radix select
 
@@ -77,14 +82,14 @@ namespace apd {
 // numerics.rs:125-133 on a device array.  k = (len as f32 * perc) as usize is computed by the caller.
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value)
 {
-    int rc = APD_OK;
-    unsigned long long *d_hist = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_hist, 257 * sizeof(unsigned long long)));
+    Owned own;
+    HIP_TRY(ctx, hipMalloc(&own.ws, 257 * sizeof(unsigned long long)));
+    unsigned long long *d_hist = static_cast<unsigned long long *>(own.ws);
     uint32_t prefix = 0, mask = 0;
     uint64_t rank = k;
     unsigned long long h[257];
     const int blocks = (int)std::min<uint64_t>((len + 255) / 256, 4096);
-    for (int pass = 0; pass < 4 && rc == APD_OK; ++pass) {
+    for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
         hipError_t e = hipMemsetAsync(d_hist, 0, 257 * sizeof(unsigned long long), ctx->stream);
         if (e == hipSuccess) {
@@ -93,21 +98,19 @@ int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, 
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h, d_hist, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; break; }
+        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
         if (pass == 0) {
             const uint64_t non_nan = len - h[256];                // numbers.len() after the NaN filter (:127-130)
-            if (k >= non_nan) { rc = APD_ERR_INDEX; break; }      // numbers[n as usize] panics (:132)
+            if (k >= non_nan) return APD_ERR_INDEX;               // numbers[n as usize] panics (:132)
         }
         uint64_t acc = 0;
         int d = 0;
         for (; d < 256; ++d) { if (rank < acc + h[d]) break; acc += h[d]; }
-        if (d == 256) { rc = APD_ERR_INDEX; break; }
+        if (d == 256) return APD_ERR_INDEX;
         rank -= acc;
         prefix |= (uint32_t)d << shift;
         mask |= 0xFFu << shift;
     }
-    hipFree(d_hist);
-    if (rc != APD_OK) return rc;
     const uint32_t u = (prefix & 0x80000000u) ? (prefix & 0x7FFFFFFFu) : ~prefix;   // invert order_key
     std::memcpy(value, &u, sizeof(float));
     return APD_OK;
@@ -216,9 +219,31 @@ struct UpgmaState {
     SegRes *seg;              // [max_items] segment results of the current merge
     uint32_t *n_items;
     uint32_t *done;           // set once the loop condition of clustering.rs:104 fails
-    unsigned long long *dbg;  // APD_DEBUG_UPGMA_TIMING: [n][16] wall_clock64 stamps per merge (nullptr: off)
+    unsigned long long *dbg;  // APD_DEBUG_UPGMA_TIMING: [n][kStamps] per merge, see Stamp (nullptr: off)
     float threshold;
     uint32_t n;
+};
+
+// The words UpgmaState's counters, `rec` (read as two uint4) and `mat` point at, in one 256-byte slot of the workspace.  After every
+// batch the host reads back the first kWordsReadBack bytes (n_live .. whole_walks).
+struct alignas(256) UpgmaWords {
+    uint32_t n_live, n_ops, done, work, last_sp, last_sq, n_items, pack_used, n_stale, arrive, r_pending, n_big, pool_used,
+             items_total, whole_walks, unused[9];
+    MergeRec rec;
+    const float *mat[3];
+};
+constexpr size_t kWordsReadBack = 64;
+static_assert(offsetof(UpgmaWords, rec) % 32 == 0 && offsetof(UpgmaWords, mat) % 8 == 0 && offsetof(UpgmaWords, whole_walks) < kWordsReadBack);
+
+// APD_DEBUG_UPGMA_TIMING: the slots of a merge's row of UpgmaState::dbg (wall_clock64 stamps at 100 MHz, and counts).
+enum Stamp : uint32_t {
+    kStampEntry, kStampRows, kStampArrive, kStampArgmin, kStampLists,   // select: the phases of the workgroup that arrives last, in order
+    kStampStaleRows, kStampMerged,                                      //   stale rows; members of the new cluster
+    kStampChainEnd,                                                     // chain: its last wavefront with work finished
+    kStampCommitEnd, kStampLongestCommit, kStampSegments,               // segment: end of the last commit; the longest commit; segments
+    kStampLongestChain,                                                 //   the longest chain: segments << 32 | sub-blocks its commit walked
+    kStampLastCommitStart, kStampCommitTime, kStampCommits, kStampCommitRewalks,   // the last commit's start; all commits' time, count, walks
+    kStamps
 };
 
 // Launch 1 of a merge.  Every workgroup: (a) its share of R[x][sp'] += R[x][sq'] of the PREVIOUS merge (R only predicts
@@ -423,8 +448,9 @@ __global__ __launch_bounds__(1024) void upgma_select_kernel(UpgmaState st)
     __syncthreads();                                                      // every wavefront has read what thread 0 is about to overwrite
     if (threadIdx.x == 0) {
         if (st.dbg) {
-            unsigned long long *g = st.dbg + (uint64_t)t * 16;
-            g[0] = t_entry; g[1] = t_rows; g[2] = t_last; g[3] = t_argmin; g[4] = wall_clock64(); g[5] = ns; g[6] = cp + cq;
+            unsigned long long *g = st.dbg + (uint64_t)t * kStamps;
+            g[kStampEntry] = t_entry; g[kStampRows] = t_rows; g[kStampArrive] = t_last; g[kStampArgmin] = t_argmin; g[kStampLists] = wall_clock64();
+            g[kStampStaleRows] = ns; g[kStampMerged] = cp + cq;
         }
         uint32_t op;
         if (w.idp < n && w.idq < n) op = APD_SEQUENCE2SEQUENCE;           // clustering.rs:193-201
@@ -882,7 +908,7 @@ __global__ __launch_bounds__(256) void upgma_chain_kernel(UpgmaState st)
     const uint32_t sp = m.sp;
     if (sp == 0xFFFFFFFFu) return;
     auto stamp = [&]() __attribute__((always_inline)) {                  // tuning aid: when the last wavefront with work finished
-        if (st.dbg && lane == 0) atomicMax(st.dbg + (uint64_t)(m.t - 1u) * 16 + 7, (unsigned long long)wall_clock64());
+        if (st.dbg && lane == 0) atomicMax(st.dbg + (uint64_t)(m.t - 1u) * kStamps + kStampChainEnd, (unsigned long long)wall_clock64());
     };
     if (grp) {
         const uint32_t dir = wid & 1u, K = m.K;
@@ -1108,7 +1134,7 @@ __global__ __launch_bounds__(256) void upgma_segment_kernel(UpgmaState st)
             }
             maps = exact::segment_fn(src, lane, begin, end, es, pack_off != 0xFFFFFFFFu ? st.packed + pack_off : nullptr);
         }
-        if (st.dbg && lane == 0 && item == 0u) st.dbg[(uint64_t)(m.t - 1u) * 16 + 10] = n_items;
+        if (st.dbg && lane == 0 && item == 0u) st.dbg[(uint64_t)(m.t - 1u) * kStamps + kStampSegments] = n_items;
         uint32_t finished = 0;
         if (lane < 4) {                                                  // lane q publishes sub-block q's maps (uniform values: any lane holds them)
             uint32_t a0 = maps.f[0].a0, a1 = maps.f[0].a1, b0 = maps.g[0].a0, b1 = maps.g[0].a1;
@@ -1127,13 +1153,13 @@ __global__ __launch_bounds__(256) void upgma_segment_kernel(UpgmaState st)
             uint32_t rw = 0;
             commit_chain(st, c, m, lane, st.seg + first, &rw);          // reads the other wavefronts' results with agent-scope loads
             if (st.dbg && lane == 0) {                                   // tuning aid, stamped by the committing wavefronts only (a few dozen per merge)
-                unsigned long long *g = st.dbg + (uint64_t)(m.t - 1u) * 16;
+                unsigned long long *g = st.dbg + (uint64_t)(m.t - 1u) * kStamps;
                 const unsigned long long t1 = wall_clock64();
-                atomicMax(g + 8, t1);                                    // end of the merge's last commit
-                atomicMax(g + 9, t1 - t0);                               // the longest commit
-                atomicMax(g + 11, ((unsigned long long)c.nseg << 32) | rw);   // ... and the longest chain, in segments, with its re-walks
-                atomicMax(g + 12, t0);                                   // the start of the last commit to start
-                atomicAdd(g + 13, t1 - t0); atomicAdd(g + 14, 1ull); atomicAdd(g + 15, (unsigned long long)rw);
+                atomicMax(g + kStampCommitEnd, t1);
+                atomicMax(g + kStampLongestCommit, t1 - t0);
+                atomicMax(g + kStampLongestChain, ((unsigned long long)c.nseg << 32) | rw);
+                atomicMax(g + kStampLastCommitStart, t0);
+                atomicAdd(g + kStampCommitTime, t1 - t0); atomicAdd(g + kStampCommits, 1ull); atomicAdd(g + kStampCommitRewalks, (unsigned long long)rw);
             }
         }
     }
@@ -1251,6 +1277,52 @@ __global__ void upgma_init_kernel(UpgmaState st)
     }
 }
 
+int env_int(const char *name, int otherwise) { const char *v = std::getenv(name); return v ? std::atoi(v) : otherwise; }
+
+// The environment switches of apd_clustering (include/apd.h), read once per call.
+// Defragmentation (see upgma_permute_kernel) pays when the merges since the last one gathered many elements: the host asks for one
+// between two batches once the new clusters of `defrag_period` or more merges sum to 8 n members (a permutation moves 4 n^2 floats
+// at streaming speed; those merges gathered >= 16 n^2 of them one cache line apiece).  Measured at n = 16384 (round 4): a matrix whose
+// clusters grow to hundreds of members, 5.34 -> 4.00 s with anything from 128 to 512 merges between two; 64 blobs (18 members per
+// new cluster on average), 0.86 s without against 0.88 - 0.93 s on a fixed schedule -- hence the work criterion.
+struct UpgmaSwitches {
+    uint32_t n;
+    uint32_t defrag_period = (uint32_t)std::max(0, env_int("APD_UPGMA_DEFRAG", n >= 2048 ? 128 : 0));   // least merges between two (0: never)
+    bool defrag_forced = std::getenv("APD_UPGMA_DEFRAG_ALWAYS") != nullptr;   // tests: every `defrag_period` merges, whatever the work
+    // one wavefront per item up to 32768 items (one that commits a chain must not hold others back), grid-stride beyond; groups of 32 per XCD
+    uint32_t segment_blocks = (uint32_t)std::max(64, env_int("APD_UPGMA_SEGMENT_BLOCKS", (int)std::min((2 * n + 3) / 4, 8192u) + 63)) / 64u * 64u;
+    uint32_t short_chain = (uint32_t)std::max(64, env_int("APD_UPGMA_SHORT_CHAIN", (int)kShortChain));   // tuning: UpgmaState::short_chain
+    bool no_graph = std::getenv("APD_UPGMA_NO_GRAPH") != nullptr;             // plain launches instead of graph replay, for profilers that choke on graphs
+    int two_policy = env_int("APD_UPGMA_TWO_LAUNCH", 1);                      // 0: always three launches per merge, 2: always two (tests), else by batch
+    bool debug = std::getenv("APD_DEBUG_UPGMA") != nullptr;                   // progress of every batch on stderr
+    bool timing = std::getenv("APD_DEBUG_UPGMA_TIMING") != nullptr;           // report_timing
+};
+
+// APD_DEBUG_UPGMA_TIMING: where a merge's microseconds go, from the stamps of merges 1 .. n_ops - 2 (merge 0 scans every row).
+void report_timing(const unsigned long long *g, uint32_t n_ops)
+{
+    double ph[4] = {0, 0, 0, 0}, stale = 0, merged = 0, chain = 0, seg = 0, gap = 0, maps = 0, items = 0, longest = 0, rewalk = 0, cstart = 0, csum = 0, ccnt = 0, rwsum = 0;
+    for (uint32_t t = 1; t + 1 < n_ops; ++t) {
+        const unsigned long long *q = g + (size_t)t * kStamps;
+        for (int k = 0; k < 4; ++k) ph[k] += (double)(q[kStampRows + k] - q[kStampEntry + k]) * 0.01;
+        stale += (double)q[kStampStaleRows]; merged += (double)q[kStampMerged];
+        chain += (double)(q[kStampChainEnd] - q[kStampLists]) * 0.01;                 // end of select's bookkeeping -> last wavefront of the chain launch
+        const unsigned long long end = std::max(q[kStampCommitEnd], q[kStampChainEnd]);
+        seg += (double)(end - q[kStampChainEnd]) * 0.01;                              // -> last wavefront of the segment launch that had work
+        gap += (double)(q[kStamps + kStampEntry] - end) * 0.01;                       // -> the next merge's select launch
+        maps += (double)q[kStampLongestCommit] * 0.01; items += (double)q[kStampSegments];
+        longest += (double)(q[kStampLongestChain] >> 32); rewalk += (double)(q[kStampLongestChain] & 0xFFFFFFFFull);
+        if (q[kStampLastCommitStart] > q[kStampChainEnd]) cstart += (double)(q[kStampLastCommitStart] - q[kStampChainEnd]) * 0.01;
+        csum += (double)q[kStampCommitTime] * 0.01; ccnt += (double)q[kStampCommits]; rwsum += (double)q[kStampCommitRewalks];
+    }
+    const double m = std::max(1.0, (double)n_ops - 2.0);                 // merges stamped
+    std::fprintf(stderr, "[apd] upgma us per merge: select [rows %.2f | arrive %.2f | argmin %.2f | lists %.2f] chain launch %.2f, segment launch %.2f, "
+                         "(longest commit %.2f; %.1f segments per merge, longest chain %.1f, %.1f of its sub-blocks walked) to the next select's entry %.2f ; stale rows %.1f, merged list %.1f members\n",
+                 ph[0] / m, ph[1] / m, ph[2] / m, ph[3] / m, chain / m, seg / m, maps / m, items / m, longest / m, rewalk / m, gap / m, stale / m, merged / m);
+    std::fprintf(stderr, "[apd] upgma commits: %.1f per merge, mean %.2f us each, %.2f sub-block walks each; the last one starts %.2f us after the chain launch's end\n",
+                 ccnt / m, csum / std::max(1.0, ccnt), rwsum / std::max(1.0, ccnt), cstart / m);
+}
+
 }  // namespace
 
 extern "C" int apd_percentile(apd_context *ctx, const float *x, uint64_t len, float perc, int x_on_device, float *value)
@@ -1260,16 +1332,14 @@ extern "C" int apd_percentile(apd_context *ctx, const float *x, uint64_t len, fl
     const uint64_t k = percentile_index(len, perc);
     if (len == 0 || k >= len) return APD_ERR_INDEX;                       // numbers[n] out of range panics (numerics.rs:132)
     const float *d_x = x;
-    float *d_tmp = nullptr;
+    Owned own;
     if (!x_on_device) {
-        HIP_TRY(ctx, hipMalloc((void **)&d_tmp, len * sizeof(float)));
-        hipError_t e = hipMemcpyAsync(d_tmp, x, len * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { hipFree(d_tmp); ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
-        d_x = d_tmp;
+        HIP_TRY(ctx, hipMalloc(&own.ws, len * sizeof(float)));
+        hipError_t e = hipMemcpyAsync(own.ws, x, len * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
+        d_x = static_cast<const float *>(own.ws);
     }
-    const int rc = device_select(ctx, d_x, len, k, value);
-    if (d_tmp) hipFree(d_tmp);
-    return rc;
+    return device_select(ctx, d_x, len, k, value);
 }
 
 extern "C" int apd_clustering(apd_context *ctx, const float *distances, int distances_on_device, uint32_t n, float perc,
@@ -1281,108 +1351,72 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
     const uint64_t nn = (uint64_t)n * n;
     const uint64_t k = percentile_index(nn, perc);
     if (nn == 0 || k >= nn) return APD_ERR_INDEX;                         // percentile of an empty / too short vector panics
+    UpgmaSwitches sw{n};
+    auto hip_error = [ctx](hipError_t e) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; };
 
+    // The workspace: one allocation, every array on a 256-byte boundary (the row scans read S rows, sizes and ids with 16-byte loads).
+    // lay_out(0) measures it, lay_out(base) points the arrays into it.
+    Owned own;
     UpgmaState st{};
     st.n = n;
-    char *pool = nullptr;
-    const size_t bytes_S = nn * sizeof(float), bytes_f = (size_t)n * sizeof(float), bytes_u = (size_t)n * sizeof(uint32_t);
-    const size_t bytes_lists = ((size_t)n * (n + 1) / 2 + n) * sizeof(uint32_t);    // every merged list is appended once (twice: instance numbers, physical indices)
-    const size_t bytes_d = distances_on_device ? 0 : bytes_S;
     // segments of one merge: sum over chains of ceil(rows / rows-per-segment) <= 2 (sum of chain lengths) / kSegElems + chains,
     // and the chains of one merge hold 2 |Ck| (n - |Ck|) <= n^2 / 2 elements
     const size_t max_items = (size_t)(nn / kSegElems) + 2 * (size_t)n + 64;
-    const size_t bytes_items = (2 * (size_t)n + 2) * sizeof(uint32_t), bytes_seg = max_items * sizeof(SegRes), bytes_ichain = std::max<size_t>(max_items, 4 * 8192 + 256) * sizeof(uint32_t)   /* (every wavefront of the segment grid reads its entry) */;
     // packed copies of the segments the commit pass is likely to re-walk (a few per chain); when it is full, they are gathered again
-    const size_t bytes_packed = (size_t)std::min<uint64_t>(nn / 8 + 65536, 1ull << 30) * sizeof(float);
-    // one allocation, every array on a 256-byte boundary (the row scans read S rows, sizes and ids with 16-byte loads)
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { off = (off + 255) & ~(size_t)255; const size_t at = off; off += bytes; return at; };
-    const size_t o_S = carve(bytes_S), o_R = carve(bytes_S), o_d = carve(bytes_d), o_lists = carve(bytes_lists), o_plists = carve(bytes_lists), o_size = carve(bytes_f),
-                 o_id = carve(bytes_u), o_live = carve(bytes_u), o_mstart = carve(bytes_u), o_mcount = carve(bytes_u), o_rscan = carve(bytes_u),
-                 o_pos = carve(bytes_u), o_big = carve(bytes_u), o_bpos = carve(bytes_u), o_rbl = carve(bytes_f), o_stale = carve(bytes_u),
-                 o_rbest = carve((size_t)n * sizeof(Cand)), o_ops = carve((size_t)n * sizeof(apd_cluster_op)), o_seg = carve(bytes_seg),
-                 o_istart = carve(bytes_items), o_sdone = carve(bytes_items), o_ichain = carve(bytes_ichain), o_packed = carve(bytes_packed),
-                 o_T = carve(bytes_S), o_phys = carve(bytes_u), o_dsrc = carve(bytes_u), o_doff = carve(bytes_u), o_words = carve(256);
-    HIP_TRY(ctx, hipMalloc((void **)&pool, off));
-    st.S = (float *)(pool + o_S);
-    st.R = (float *)(pool + o_R);
-    float *d_copy = (float *)(pool + o_d);
-    st.pool = (uint32_t *)(pool + o_lists);
-    st.ppool = (uint32_t *)(pool + o_plists);
-    st.phys = (uint32_t *)(pool + o_phys); st.dsrc = (uint32_t *)(pool + o_dsrc); st.doff = (uint32_t *)(pool + o_doff);
-    st.size = (float *)(pool + o_size);
-    st.id = (uint32_t *)(pool + o_id);
-    st.live = (uint32_t *)(pool + o_live);
-    st.mstart = (uint32_t *)(pool + o_mstart);
-    st.mcount = (uint32_t *)(pool + o_mcount);
-    st.rscan = (uint32_t *)(pool + o_rscan);
-    st.pos = (uint32_t *)(pool + o_pos);
-    st.big = (uint32_t *)(pool + o_big);
-    st.bpos = (uint32_t *)(pool + o_bpos);
-    st.rb_l = (float *)(pool + o_rbl);
-    st.stale = (uint32_t *)(pool + o_stale);
-    st.rbest = (Cand *)(pool + o_rbest);
-    st.ops = (apd_cluster_op *)(pool + o_ops);
-    st.seg = (SegRes *)(pool + o_seg);
-    st.item_start = (uint32_t *)(pool + o_istart);
-    st.seg_done = (uint32_t *)(pool + o_sdone);
-    st.item_chain = (uint32_t *)(pool + o_ichain);
-    st.packed = (float *)(pool + o_packed);
-    st.pack_capacity = (uint32_t)(bytes_packed / sizeof(float));
-    float *d_T = (float *)(pool + o_T);
-    const float **d_mat = (const float **)(pool + o_words + 128);          // three device words behind the counters
-    st.mat = d_mat;
-    st.n_live = (uint32_t *)(pool + o_words); st.n_ops = st.n_live + 1; st.done = st.n_live + 2; st.work = st.n_live + 3;   // host_state reads these four
-    st.pool_used = st.n_live + 12; st.last_sp = st.n_live + 4; st.last_sq = st.n_live + 5; st.n_items = st.n_live + 6;
-    st.pack_used = st.n_live + 7; st.n_stale = st.n_live + 8; st.arrive = st.n_live + 9; st.r_pending = st.n_live + 10;
-    st.n_big = st.n_live + 11; st.rec = st.n_live + 24;   // (words 24..31: 32-byte aligned)
-    st.items_total = st.n_live + 13; st.whole_walks = st.n_live + 14;
-    float *spare = nullptr;                                               // two more n x n buffers: the defragmented copies rotate through d_T and these
-    auto fail = [&](int rc) { hipFree(pool); if (spare) hipFree(spare); if (st.dbg) hipFree(st.dbg); return rc; };
-    if (distances_on_device) st.d = distances;
-    else {
-        hipError_t e0 = hipMemcpyAsync(d_copy, distances, bytes_S, hipMemcpyHostToDevice, ctx->stream);
-        if (e0 != hipSuccess) { ctx->last_error = hipGetErrorString(e0); return fail(APD_ERR_HIP); }
-        st.d = d_copy;
-    }
-    hipError_t e = hipSuccess;
+    st.pack_capacity = (uint32_t)std::min<uint64_t>(nn / 8 + 65536, 1ull << 30);
+    float *d_copy = nullptr, *d_T = nullptr;
+    UpgmaWords *words = nullptr;
+    auto lay_out = [&](uintptr_t base) {
+        size_t off = 0;
+        auto carve = [&](auto *&p, size_t count) {
+            off = (off + 255) & ~(size_t)255;
+            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+            off += count * sizeof(*p);
+        };
+        const size_t lists = (size_t)n * (n + 1) / 2 + n;                 // every merged list is appended once (twice: instance numbers, physical indices)
+        carve(st.S, nn); carve(st.R, nn); carve(d_copy, distances_on_device ? 0 : nn); carve(st.pool, lists); carve(st.ppool, lists);
+        carve(st.size, n); carve(st.id, n); carve(st.live, n); carve(st.mstart, n); carve(st.mcount, n); carve(st.rscan, n);
+        carve(st.pos, n); carve(st.big, n); carve(st.bpos, n); carve(st.rb_l, n); carve(st.stale, n); carve(st.rbest, n); carve(st.ops, n);
+        carve(st.seg, max_items); carve(st.item_start, 2 * (size_t)n + 2); carve(st.seg_done, 2 * (size_t)n + 2);
+        carve(st.item_chain, std::max<size_t>(max_items, 4 * 8192 + 256));   // (every wavefront of the segment grid reads its entry)
+        carve(st.packed, st.pack_capacity); carve(d_T, nn); carve(st.phys, n); carve(st.dsrc, n); carve(st.doff, n); carve(words, 1);
+        return off;
+    };
+    HIP_TRY(ctx, hipMalloc(&own.ws, lay_out(0)));
+    lay_out((uintptr_t)own.ws);
+    st.n_live = &words->n_live; st.n_ops = &words->n_ops; st.done = &words->done; st.work = &words->work; st.last_sp = &words->last_sp;
+    st.last_sq = &words->last_sq; st.n_items = &words->n_items; st.pack_used = &words->pack_used; st.n_stale = &words->n_stale;
+    st.arrive = &words->arrive; st.r_pending = &words->r_pending; st.n_big = &words->n_big; st.pool_used = &words->pool_used;
+    st.items_total = &words->items_total; st.whole_walks = &words->whole_walks;
+    st.rec = reinterpret_cast<uint32_t *>(&words->rec); st.mat = words->mat;
+    st.d = distances_on_device ? distances : d_copy;
+    hipError_t e = distances_on_device ? hipSuccess : hipMemcpyAsync(d_copy, distances, nn * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_error(e);
 
-    float thr = 0.0f;
-    int rc = device_select(ctx, st.d, nn, k, &thr);                       // clustering.rs:101
-    if (rc != APD_OK) return fail(rc);
-    st.threshold = thr;
-    if (threshold) *threshold = thr;
+    if (const int rc = device_select(ctx, st.d, nn, k, &st.threshold); rc != APD_OK) return rc;   // clustering.rs:101
+    if (threshold) *threshold = st.threshold;
 
     hipLaunchKernelGGL(upgma_init_S_kernel, dim3((unsigned)std::min<uint64_t>((nn + 255) / 256, 8192)), dim3(256), 0, ctx->stream, st);
     hipLaunchKernelGGL(upgma_init_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, st);
     hipLaunchKernelGGL(upgma_transpose_kernel, dim3((unsigned)std::min<uint64_t>((uint64_t)((n + 31) / 32) * ((n + 31) / 32), 16384)), dim3(256), 0,
                        ctx->stream, st.d, d_T, n);
     // R[slot y][x] = d[x][y] while every cluster is a singleton (slot y holds instance y): the transpose
-    e = hipMemcpyAsync(st.R, d_T, bytes_S, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return fail(APD_ERR_HIP); }
+    e = hipMemcpyAsync(st.R, d_T, nn * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_error(e);
     // the working copies start out as the caller's matrix and its transpose
     const float *h_mat[3] = {st.d, d_T, nullptr};
-    e = hipMemcpyAsync((void *)d_mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return fail(APD_ERR_HIP); }
-    // Defragmentation (see upgma_permute_kernel) pays when the merges since the last one gathered many elements: the host asks for one
-    // between two batches once the new clusters of `defrag_period` or more merges sum to 8 n members (a permutation moves 4 n^2 floats
-    // at streaming speed; those merges gathered >= 16 n^2 of them one cache line apiece).  Measured at n = 16384 (round 4): a matrix whose
-    // clusters grow to hundreds of members, 5.34 -> 4.00 s with anything from 128 to 512 merges between two; 64 blobs (18 members per
-    // new cluster on average), 0.86 s without against 0.88 - 0.93 s on a fixed schedule -- hence the work criterion.
-    // APD_UPGMA_DEFRAG = least number of merges between two (0: never).  Without the two spare buffers the loop simply runs without.
-    uint32_t defrag_period = n >= 2048 ? 128u : 0u;
-    if (const char *v = std::getenv("APD_UPGMA_DEFRAG")) defrag_period = (uint32_t)std::max(0, std::atoi(v));
-    const bool defrag_forced = std::getenv("APD_UPGMA_DEFRAG_ALWAYS") != nullptr;   // tests: every `defrag_period` merges, whatever the work
-    if (defrag_period && hipMalloc((void **)&spare, 2 * bytes_S) != hipSuccess) { (void)hipGetLastError(); spare = nullptr; defrag_period = 0; }
+    e = hipMemcpyAsync((void *)words->mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_error(e);
+    // without the two spare buffers, or the LDS the staged permutation needs, the loop simply runs without defragmentation
+    if (sw.defrag_period && hipMalloc((void **)&own.spare, 2 * nn * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); own.spare = nullptr; sw.defrag_period = 0; }
     std::vector<float *> free_bufs;                                       // buffers not holding a working copy right now
-    if (spare) { free_bufs.push_back(spare + nn); free_bufs.push_back(spare); }
+    if (own.spare) { free_bufs.push_back(own.spare + nn); free_bufs.push_back(own.spare); }
     const bool permute_staged = (size_t)n * sizeof(float) <= 128 * 1024;
-    if (defrag_period && permute_staged &&
+    if (sw.defrag_period && permute_staged &&
         hipFuncSetAttribute((const void *)upgma_permute_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)n * sizeof(float))) != hipSuccess) {
         (void)hipGetLastError();
-        hipFree(spare); spare = nullptr; defrag_period = 0;
+        hipFree(own.spare); own.spare = nullptr; sw.defrag_period = 0;
     }
-    uint32_t defrag_at = 0, defrag_work = 0, n_defrag = 0;                // n_ops and work counter at the latest defragmentation
     auto defragment = [&]() {
         hipLaunchKernelGGL(upgma_defrag_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, st);
         hipLaunchKernelGGL(upgma_defrag_lists_kernel, dim3(std::min<uint32_t>((n + 3) / 4, 4096u)), dim3(256), 0, ctx->stream, st);
@@ -1395,9 +1429,13 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
             h_mat[m] = out;
         }
         h_mat[2] = h_mat[0];                                              // "defragmented": any non-null word
-        return hipMemcpyAsync((void *)d_mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
+        return hipMemcpyAsync((void *)words->mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
     };
-    uint32_t host_state[16] = {n, 0, 0, 0};                               // n_live, n_ops, done, work; [13] segments made, [14] long chains walked whole
+    if (sw.timing && hipMalloc((void **)&own.dbg, (size_t)n * kStamps * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemsetAsync(own.dbg, 0, (size_t)n * kStamps * sizeof(unsigned long long), ctx->stream);
+    st.dbg = own.dbg;
+    e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_error(e);
     // The merge loop is launch-bound (three short dependent launches per merge): a batch of merges is captured once into a
     // hipGraph and replayed until the device-side `done` flag rises; kernels launched after that return immediately.
     const uint32_t batch = 64;
@@ -1409,124 +1447,78 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
     // a wavefront that walks several chains or segments one after the other is what the critical path of a large merge is made of.
     const uint32_t chain_waves = 2 * ((n + 63) / 64) + 2 * n;             // singleton groups, then one wavefront per (other cluster, direction)
     const uint32_t chain_blocks = (chain_waves + 3) / 4;
-    // one wavefront per item up to 32768 items (a wavefront that commits a chain must not hold other items back), grid-stride beyond
-    uint32_t segment_blocks = (std::min((2 * n + 3) / 4, 8192u) + 63u) / 64u * 64u;   // groups of 32 wavefronts per XCD
-    if (const char *v = std::getenv("APD_UPGMA_SEGMENT_BLOCKS")) segment_blocks = (uint32_t)std::max(64, std::atoi(v)) / 64u * 64u;   // tuning
-    const bool debug_timing = std::getenv("APD_DEBUG_UPGMA_TIMING") != nullptr;   // tuning aid: phase stamps of every select launch
-    if (debug_timing && hipMalloc((void **)&st.dbg, (size_t)n * 16 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemsetAsync(st.dbg, 0, (size_t)n * 16 * sizeof(unsigned long long), ctx->stream);
+    st.short_chain = sw.short_chain;
     // Two captured batches: [select, chain, segment] x 64 and [select, chain] x 64.  The second one is replayed while the batch before
     // made no segment at all (most of a dendrogram at n = 4096: the segment launch then only costs its boundary, ~4.5 us per merge);
     // its chain launch walks a long chain whole if one turns up after all, and the host returns to three launches for the next batch.
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    hipGraphExec_t exec[2] = {nullptr, nullptr};
     auto enqueue_batch = [&](int two) {
         UpgmaState sb = st;
         sb.no_seg = two ? 1u : 0u;
         for (uint32_t b = 0; b < batch; ++b) {
             hipLaunchKernelGGL(upgma_select_kernel, dim3(select_blocks), dim3(1024), 0, ctx->stream, sb);
             hipLaunchKernelGGL(upgma_chain_kernel, dim3(chain_blocks), dim3(256), 0, ctx->stream, sb);
-            if (!two) hipLaunchKernelGGL(upgma_segment_kernel, dim3(segment_blocks), dim3(256), 0, ctx->stream, sb);
+            if (!two) hipLaunchKernelGGL(upgma_segment_kernel, dim3(sw.segment_blocks), dim3(256), 0, ctx->stream, sb);
         }
     };
-    auto drop_graph = [&]() {
-        for (int g = 0; g < 2; ++g) { if (exec[g]) hipGraphExecDestroy(exec[g]); if (graph[g]) hipGraphDestroy(graph[g]); exec[g] = nullptr; graph[g] = nullptr; }
-    };
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return fail(APD_ERR_HIP); }
     // the legacy default stream cannot be captured: then the batch is enqueued directly
-    st.short_chain = kShortChain;
-    if (const char *v = std::getenv("APD_UPGMA_SHORT_CHAIN")) st.short_chain = (uint32_t)std::max(64, std::atoi(v));   // tuning
-    bool use_graph = ctx->stream != nullptr && std::getenv("APD_UPGMA_NO_GRAPH") == nullptr &&   // (the env: plain launches, for profilers that choke on graphs)
-                     hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (use_graph) {
-        enqueue_batch(0);
-        use_graph = hipStreamEndCapture(ctx->stream, &graph[0]) == hipSuccess && hipGraphInstantiate(&exec[0], graph[0], nullptr, nullptr, 0) == hipSuccess;
-        if (use_graph && hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            enqueue_batch(1);
-            use_graph = hipStreamEndCapture(ctx->stream, &graph[1]) == hipSuccess && hipGraphInstantiate(&exec[1], graph[1], nullptr, nullptr, 0) == hipSuccess;
-        } else use_graph = false;
-        if (!use_graph) drop_graph();
+    bool use_graph = ctx->stream != nullptr && !sw.no_graph;
+    for (int two = 0; two < 2 && use_graph; ++two) {
+        use_graph = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (use_graph) enqueue_batch(two);
+        use_graph = use_graph && hipStreamEndCapture(ctx->stream, &own.graph[two]) == hipSuccess &&
+                    hipGraphInstantiate(&own.exec[two], own.graph[two], nullptr, nullptr, 0) == hipSuccess;
     }
+    if (!use_graph) own.drop_graphs();
     (void)hipGetLastError();
-    // APD_UPGMA_TWO_LAUNCH: 0 = always three launches per merge, 2 = always two (tests: every long chain walked whole), default = by batch
-    int two_policy = 1;
-    if (const char *v = std::getenv("APD_UPGMA_TWO_LAUNCH")) two_policy = std::atoi(v);
-    int two = two_policy == 2 ? 1 : 0;
-    uint32_t items_before = 0, whole_before = 0, n_two = 0, n_batches = 0;
-    const bool debug = std::getenv("APD_DEBUG_UPGMA") != nullptr;
 
-    uint32_t ops_before = 0;
+    UpgmaWords h{};                                                       // the counters as of the latest batch
+    int two = sw.two_policy == 2 ? 1 : 0;
+    uint32_t ops_before = 0, items_before = 0, whole_before = 0, n_two = 0, n_batches = 0;
+    uint32_t defrag_at = 0, defrag_work = 0, n_defrag = 0;                // n_ops and work counter at the latest defragmentation
     while (true) {
-        if (use_graph) e = hipGraphLaunch(exec[two], ctx->stream);
+        if (use_graph) e = hipGraphLaunch(own.exec[two], ctx->stream);
         else { enqueue_batch(two); e = hipGetLastError(); }
         ++n_batches; n_two += (uint32_t)two;
-        if (e == hipSuccess) e = hipMemcpyAsync(host_state, st.n_live, sizeof(host_state), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h, words, kWordsReadBack, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); drop_graph(); return fail(APD_ERR_HIP); }
-        if (debug) std::fprintf(stderr, "[apd] upgma: graph %d, live %u, ops %u, done %u\n", (int)use_graph, host_state[0], host_state[1], host_state[2]);
-        if (host_state[2] != 0) break;
+        if (e != hipSuccess) return hip_error(e);
+        if (sw.debug) std::fprintf(stderr, "[apd] upgma: graph %d, live %u, ops %u, done %u\n", (int)use_graph, h.n_live, h.n_ops, h.done);
+        if (h.done != 0) break;
         // every batch performs `batch` merges unless the loop condition failed: a batch without progress would spin forever
-        if (host_state[1] < ops_before + batch) {
-            ctx->last_error = "UPGMA made no progress in a batch of merges (n_ops " + std::to_string(host_state[1]) + " after " + std::to_string(ops_before) + ")";
-            drop_graph();
-            return fail(APD_ERR_HIP);
+        if (h.n_ops < ops_before + batch) {
+            ctx->last_error = "UPGMA made no progress in a batch of merges (n_ops " + std::to_string(h.n_ops) + " after " + std::to_string(ops_before) + ")";
+            return APD_ERR_HIP;
         }
-        ops_before = host_state[1];
-        if (two_policy == 1) {
-            if (!two) two = host_state[13] == items_before ? 1 : 0;      // a whole batch without a segment: leave the segment launches out
-            else if (host_state[14] != whole_before) two = 0;            // a long chain turned up: three launches again
-        }
-        items_before = host_state[13]; whole_before = host_state[14];
-        if (defrag_period && host_state[0] > 2 && host_state[1] - defrag_at >= defrag_period &&
-            (defrag_forced || (uint64_t)(host_state[3] - defrag_work) >= 8ull * n)) {
+        ops_before = h.n_ops;
+        // leave the segment launches out after a batch that made no segment; back to three launches once a long chain was walked whole
+        if (sw.two_policy == 1) two = two ? (h.whole_walks == whole_before) : (h.items_total == items_before);
+        items_before = h.items_total; whole_before = h.whole_walks;
+        const bool defrag_now = sw.defrag_period && h.n_live > 2 && h.n_ops - defrag_at >= sw.defrag_period &&
+                                (sw.defrag_forced || (uint64_t)(h.work - defrag_work) >= 8ull * n);
+        if (defrag_now) {
             e = defragment();
             if (e == hipSuccess) e = hipGetLastError();
-            if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); drop_graph(); return fail(APD_ERR_HIP); }
-            defrag_at = host_state[1]; defrag_work = host_state[3]; ++n_defrag;
+            if (e != hipSuccess) return hip_error(e);
+            defrag_at = h.n_ops; defrag_work = h.work; ++n_defrag;
         }
     }
-    drop_graph();
-    if (debug || debug_timing) std::fprintf(stderr, "[apd] upgma: %u defragmentations (period %u merges); %u of %u batches without segment launches, %u long chains walked whole\n",
-                                            n_defrag, defrag_period, n_two, n_batches, host_state[14]);
-    const uint32_t cnt = host_state[1];
-    if (st.dbg) {
-        std::vector<unsigned long long> g((size_t)n * 16);
-        if (hipMemcpy(g.data(), st.dbg, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess && cnt > 1) {
-            double ph[4] = {0, 0, 0, 0}, stale = 0, merged = 0, chain = 0, seg = 0, gap = 0, maps = 0, items = 0, longest = 0, rewalk = 0, cstart = 0, csum = 0, ccnt = 0, rwsum = 0;
-            double stamped = 0;
-            for (uint32_t t = 1; t + 1 < cnt; ++t) {                      // stamps: 100 MHz; merge 0 scans every row, the last merge ends the loop
-                const unsigned long long *q = &g[(size_t)t * 16];
-                stamped += 1;
-                for (int k = 0; k < 4; ++k) ph[k] += (double)(q[k + 1] - q[k]) * 0.01;
-                stale += (double)q[5]; merged += (double)q[6];
-                chain += (double)(q[7] - q[4]) * 0.01;                    // end of select's bookkeeping -> last wavefront of the chain launch
-                seg += (double)(std::max(q[8], q[7]) - q[7]) * 0.01;      // -> last wavefront of the segment launch that had work
-                gap += (double)(g[(size_t)(t + 1) * 16] - std::max(q[8], q[7])) * 0.01;
-                maps += (double)q[9] * 0.01; items += (double)q[10]; longest += (double)(q[11] >> 32); rewalk += (double)(q[11] & 0xFFFFFFFFull);
-                if (q[12] > q[7]) cstart += (double)(q[12] - q[7]) * 0.01;
-                csum += (double)q[13] * 0.01; ccnt += (double)q[14]; rwsum += (double)q[15];
-            }
-            const double m = std::max(1.0, stamped);
-            std::fprintf(stderr, "[apd] upgma us per merge: select [rows %.2f | arrive %.2f | argmin %.2f | lists %.2f] chain launch %.2f, segment launch %.2f, "
-                                 "(longest commit %.2f; %.1f segments per merge, longest chain %.1f, %.1f of its sub-blocks walked) to the next select's entry %.2f ; stale rows %.1f, merged list %.1f members\n",
-                         ph[0] / m, ph[1] / m, ph[2] / m, ph[3] / m, chain / m, seg / m, maps / m, items / m, longest / m, rewalk / m, gap / m, stale / m, merged / m);
-            std::fprintf(stderr, "[apd] upgma commits: %.1f per merge, mean %.2f us each, %.2f sub-block walks each; the last one starts %.2f us after the chain launch's end\n",
-                         ccnt / m, csum / std::max(1.0, ccnt), rwsum / std::max(1.0, ccnt), cstart / m);
-        }
-        hipFree(st.dbg);
-        st.dbg = nullptr;                                                 // fail() below must not free it again
+    if (sw.debug || sw.timing) std::fprintf(stderr, "[apd] upgma: %u defragmentations (period %u merges); %u of %u batches without segment launches, %u long chains walked whole\n",
+                                            n_defrag, sw.defrag_period, n_two, n_batches, h.whole_walks);
+    const uint32_t cnt = h.n_ops;
+    if (own.dbg) {
+        std::vector<unsigned long long> g((size_t)n * kStamps);
+        if (hipMemcpy(g.data(), own.dbg, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess && cnt > 1) report_timing(g.data(), cnt);
     }
-    std::vector<uint32_t> ids(n), live(host_state[0]);
+    std::vector<uint32_t> ids(n), live(h.n_live);
     e = hipMemcpyAsync(ops, st.ops, (size_t)cnt * sizeof(apd_cluster_op), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ids.data(), st.id, bytes_u, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ids.data(), st.id, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && !live.empty()) e = hipMemcpyAsync(live.data(), st.live, live.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return fail(APD_ERR_HIP); }
+    if (e != hipSuccess) return hip_error(e);
     // dendrogram.clusters() (clustering.rs:109,146-148): the root ids, ascending
     std::vector<uint32_t> r;
     for (uint32_t s : live) r.push_back(ids[s]);
-    if (host_state[2] == 2 && cnt > 0) {
+    if (h.done == 2 && cnt > 0) {
         // the degenerate (0, 0) merge re-parents INSTANCE 0 onto the new node (clustering.rs:136-138 with p = q = 0):
         // its old cluster keeps its other members, instance 0 alone now roots at `into`
         const uint32_t k_new = ops[cnt - 1].into;
@@ -1538,8 +1530,6 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
     for (size_t i = 0; i < r.size(); ++i) roots[i] = r[i];
     *n_roots = (uint32_t)r.size();
     *n_ops = cnt;
-    hipFree(pool);
-    if (spare) hipFree(spare);
     return APD_OK;
 }
 

@@ -31,15 +31,6 @@ struct apd_comm {
 
 namespace {
 
-#define HIP_TRY(ctx, call)                                                             \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);     \
-            return e_ == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;              \
-        }                                                                              \
-    } while (0)
-
 #define NCCL_TRY(ctx, call)                                                            \
     do {                                                                               \
         ncclResult_t r_ = (call);                                                      \

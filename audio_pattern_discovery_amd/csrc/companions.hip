@@ -13,15 +13,6 @@ using namespace apd;
 
 namespace {
 
-#define HIP_TRY(ctx, call)                                                             \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);     \
-            return e_ == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;              \
-        }                                                                              \
-    } while (0)
-
 // --------------------------------------------------------------------------------------- encoder
 // One thread per frame.  Arithmetic order follows the reference: Mat::mul accumulates k ascending with a separate
 // multiply and add (numerics.rs:310-316; this unit is built with -ffp-contract=off), add_col, sigmoid, scale(255),
