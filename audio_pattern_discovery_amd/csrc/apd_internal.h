@@ -64,30 +64,32 @@ constexpr int max_strip_columns(uint32_t d) { return d <= 10 ? 13 : (d <= 13 ? 1
 
 // ---- kernel geometry: which kernel family sweeps a tile class, and with which shape.
 struct KernelGeom {
-    enum Family : uint8_t { Generic, Systolic, Wide, Strip, BandedStrip };
+    enum Family : uint8_t { Generic, Systolic, Wide, Strip, BandedStrip, SharedColumns };
     Family family = Generic;
-    uint8_t lanes_or_waves = 0;   // systolic: lanes per pair G; wide: wavefronts per pair NW; strips: pairs per wavefront
+    uint8_t lanes_or_waves = 0;   // systolic, shared columns: lanes per pair G; wide: wavefronts per pair NW; strips: pairs per wavefront
     uint8_t cells = 0;            // offsets per lane C (band form), columns per lane CW (strips)
 
     // The integer form of apd_set_variant, the tile-plan cache key and the APD_DEBUG_PLAN line: 0 generic, G * 100 + C systolic,
-    // 10000 + NW * 100 + C wide, 20000 + ppw * 100 + CW column strips, 30000 + ppw * 100 + CW banded column strips.
+    // 10000 + NW * 100 + C wide, 20000 + ppw * 100 + CW column strips, 30000 + ppw * 100 + CW banded column strips,
+    // 40000 + G * 100 + C systolic with workgroup-shared column rings (the tiles that qualify; the others fall to G * 100 + C).
     constexpr int encode() const
     {
-        constexpr int base[] = {0, 0, 10000, 20000, 30000};
+        constexpr int base[] = {0, 0, 10000, 20000, 30000, 40000};
         return family == Generic ? 0 : base[family] + lanes_or_waves * 100 + cells;
     }
-    // any other code (1 .. 99, negative, >= 40000) decodes to Generic
+    // any other code (1 .. 99, negative, >= 50000) decodes to Generic
     static constexpr KernelGeom decode(int key)
     {
         const Family f = key >= 100 && key < 10000 ? Systolic : key >= 10000 && key < 20000 ? Wide
-                       : key >= 20000 && key < 30000 ? Strip : key >= 30000 && key < 40000 ? BandedStrip : Generic;
+                       : key >= 20000 && key < 30000 ? Strip : key >= 30000 && key < 40000 ? BandedStrip
+                       : key >= 40000 && key < 50000 ? SharedColumns : Generic;
         if (f == Generic) return KernelGeom{};
         return KernelGeom{f, (uint8_t)((key % 10000) / 100), (uint8_t)(key % 100)};
     }
     // work-items per pair (the launches are cut at 2^31 work-items): the generic and strip kernels use at most one wavefront
     constexpr uint32_t lanes_per_pair() const
     {
-        return family == Systolic ? lanes_or_waves : family == Wide ? 64u * lanes_or_waves : 64u;
+        return family == Systolic || family == SharedColumns ? lanes_or_waves : family == Wide ? 64u * lanes_or_waves : 64u;
     }
     // offsets (band form) or columns (strips) one pair covers per pass
     constexpr uint32_t capacity() const { return (family == Wide ? 64u : 1u) * lanes_or_waves * cells; }
@@ -105,19 +107,24 @@ struct KernelGeom {
 #define APD_STRIP_GEOMS(X) X(1, 3) X(1, 5) X(1, 7) X(1, 9) X(1, 11) X(1, 13) X(2, 3) X(2, 5) X(2, 7) X(2, 9) X(2, 11) X(2, 13) \
                            X(4, 3) X(4, 5) X(4, 7) X(4, 9) X(4, 11) X(4, 13)
 #define APD_BANDED_STRIP_GEOMS(X) X(1, 5) X(1, 9) X(4, 5) X(4, 9)
+// shared column rings: the hybrid form with unit penalties only, four pairs per wavefront (one ring per wavefront of the workgroup)
+#define APD_SHARED_COLUMN_GEOMS(X) X(16, 9)
 
 #define APD_SYSTOLIC_ENTRY_(A, B) KernelGeom{KernelGeom::Systolic, A, B},
 #define APD_WIDE_ENTRY_(A, B) KernelGeom{KernelGeom::Wide, A, B},
 #define APD_STRIP_ENTRY_(A, B) KernelGeom{KernelGeom::Strip, A, B},
 #define APD_BANDED_STRIP_ENTRY_(A, B) KernelGeom{KernelGeom::BandedStrip, A, B},
+#define APD_SHARED_COLUMN_ENTRY_(A, B) KernelGeom{KernelGeom::SharedColumns, A, B},
 constexpr KernelGeom kSystolicGeoms[] = {APD_SYSTOLIC_GEOMS(APD_SYSTOLIC_ENTRY_)};
 constexpr KernelGeom kWideGeoms[] = {APD_WIDE_GEOMS(APD_WIDE_ENTRY_)};
 constexpr KernelGeom kStripGeoms[] = {APD_STRIP_GEOMS(APD_STRIP_ENTRY_)};
 constexpr KernelGeom kBandedStripGeoms[] = {APD_BANDED_STRIP_GEOMS(APD_BANDED_STRIP_ENTRY_)};
+constexpr KernelGeom kSharedColumnGeoms[] = {APD_SHARED_COLUMN_GEOMS(APD_SHARED_COLUMN_ENTRY_)};
 #undef APD_SYSTOLIC_ENTRY_
 #undef APD_WIDE_ENTRY_
 #undef APD_STRIP_ENTRY_
 #undef APD_BANDED_STRIP_ENTRY_
+#undef APD_SHARED_COLUMN_ENTRY_
 
 // Every frame dimension of the dispatch, as a compile-time constant: f(std::integral_constant<int, D>{}).  false: no kernels for `dim`.
 template <class F, size_t... I>
@@ -137,7 +144,7 @@ constexpr bool geom_instantiated(KernelGeom g, uint32_t dim)
     if (g.cells > (strip ? max_strip_columns(dim) : max_cells_per_lane(dim))) return false;
     auto on = [g](const auto &list) { for (KernelGeom e : list) if (e == g) return true; return false; };
     return g.family == KernelGeom::Systolic ? on(kSystolicGeoms) : g.family == KernelGeom::Wide ? on(kWideGeoms)
-         : strip ? on(kStripGeoms) : on(kBandedStripGeoms);
+         : g.family == KernelGeom::SharedColumns ? on(kSharedColumnGeoms) : strip ? on(kStripGeoms) : on(kBandedStripGeoms);
 }
 // the lists and their integer codes are one and the same: every entry decodes back to itself
 template <size_t N>
@@ -147,7 +154,43 @@ constexpr bool geoms_round_trip(const KernelGeom (&list)[N])
     return true;
 }
 static_assert(geoms_round_trip(kSystolicGeoms) && geoms_round_trip(kWideGeoms) && geoms_round_trip(kStripGeoms) &&
-                  geoms_round_trip(kBandedStripGeoms), "a listed geometry has no integer code of its own");
+                  geoms_round_trip(kBandedStripGeoms) && geoms_round_trip(kSharedColumnGeoms), "a listed geometry has no integer code of its own");
+
+// ---- shared column rings (dtw_systolic.h, dtw_fused_systolic_shared).  A workgroup sweeps a 4 x 4 sub-block of a tile: wavefront k
+// row sequence a_k, its four lane groups the columns b_0 .. b_3, which the four wavefronts read from one LDS ring per b.
+// A macro-step block is U steps (the kernel's unroll); during one, the G lanes of the pairs of the workgroup read columns
+// spanning (G - 1)(C - 1) + U + (largest - smallest w of the workgroup's swept pairs), and the next block's U columns are
+// written meanwhile.  The ring holds what equal bands need (shared_column_ring_min) and at least 16 frames more, in whole
+// groups of 8 columns; what it holds beyond the minimum is the spread of w a workgroup may have (shared_column_slack).
+constexpr int shared_column_unroll(int c) { return (c + 1) % 2 == 0 ? c + 1 : 2 * (c + 1); }
+constexpr int shared_column_ring_min(int g, int c) { return (g - 1) * (c - 1) + 1 + 2 * shared_column_unroll(c); }
+constexpr int shared_column_ring_frames(int g, int c) { return (shared_column_ring_min(g, c) + 16 + 7) / 8 * 8; }
+// the spread of w one workgroup tolerates: what the ring holds beyond the window of equal bands
+constexpr uint32_t shared_column_slack(KernelGeom g)
+{
+    return (uint32_t)(shared_column_ring_frames(g.lanes_or_waves, g.cells) - shared_column_ring_min(g.lanes_or_waves, g.cells));
+}
+inline uint32_t host_w(const BandSpec &b, uint32_t n, uint32_t m);   // below
+// The qualification rule of the tile plan: in every 4 x 4 sub-block of tile (tile_a, tile_b) the swept pairs (a < b < n_seq, both
+// longer than one frame) have bands within `slack` of each other.  lens[s]: frames of resident sequence s.
+inline bool shared_columns_qualify(const std::vector<uint32_t> &lens, uint32_t tile_a, uint32_t tile_b, const BandSpec &band,
+                                   uint32_t slack)
+{
+    const uint32_t n_seq = (uint32_t)lens.size();
+    for (uint32_t sa = 0; sa < (uint32_t)kTile; sa += 4)
+        for (uint32_t sb = 0; sb < (uint32_t)kTile; sb += 4) {
+            uint32_t lo = 0xFFFFFFFFu, hi = 0;
+            for (uint32_t i = 0; i < 16; ++i) {
+                const uint32_t a = tile_a * kTile + sa + i / 4, b = tile_b * kTile + sb + i % 4;
+                if (!(a < b && b < n_seq) || lens[a] < 2 || lens[b] < 2) continue;
+                const uint32_t w = host_w(band, lens[a], lens[b]);
+                lo = w < lo ? w : lo;
+                hi = w > hi ? w : hi;
+            }
+            if (hi > lo && hi - lo > slack) return false;
+        }
+    return true;
+}
 
 // LDS of the column-strip kernels (dtw_full.h): row frames of their lanes, one boundary column per pair and DP, and a few words
 constexpr uint64_t strip_lds_bytes(uint32_t dim, uint32_t ppw, bool banded, uint32_t rows)

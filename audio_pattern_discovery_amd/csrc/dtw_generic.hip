@@ -333,7 +333,8 @@ struct VariantRequest {
 static KernelGeom pick_band_geom(uint32_t need, uint32_t dim, const VariantRequest &req, bool uniform_pen, bool fast_shift)
 {
     if (req.generic || !is_kernel_dim(dim)) return {};
-    const KernelGeom f = req.geom;
+    KernelGeom f = req.geom;
+    if (f.family == KernelGeom::SharedColumns) f.family = KernelGeom::Systolic;   // forced shared columns: its DPP twin here, promoted by the plan
     if (f.family == KernelGeom::Systolic || f.family == KernelGeom::Wide)   // forced; too narrow (or not instantiated): generic
         return (f.family == KernelGeom::Systolic || uniform_pen) && f.capacity() >= need && geom_instantiated(f, dim) ? f : KernelGeom{};
     // score = lanes busy x how cheap a cell is at this C.  A macro-step costs about 116 SIMD cycles (window moves, exchanges,
@@ -423,11 +424,31 @@ void plan_tile_classes(const std::vector<uint64_t> &offsets, uint32_t n_seq, con
     }
     struct Group { std::vector<uint4> tiles; uint32_t w_max = 0, n_max = 0; };
     std::map<KernelGeom, Group> groups;
+    // Shared column rings (dtw_systolic.h): the hybrid form with unit penalties (`fast_shift`), for the tiles whose workgroups
+    // sweep bands of nearly one width.  A forced systolic code keeps naming the DPP window; a forced shared-column code takes
+    // the tiles that qualify and leaves the others to its DPP twin.
+    const bool shared_ok = fast_shift && req.geom.family != KernelGeom::Systolic;
+    std::vector<uint32_t> lens;
+    if (shared_ok) {
+        lens.resize(n_seq);
+        for (uint32_t s = 0; s < n_seq; ++s) lens[s] = (uint32_t)(offsets[s + 1] - offsets[s]);
+    }
     for (uint32_t t = 0; t < tiles.size(); ++t) {
         const uint32_t mx = std::max(hi[tiles[t].x], hi[tiles[t].y]), mn = std::min(lo[tiles[t].x], lo[tiles[t].y]);
         const uint32_t band_ub = band.use_explicit ? band.explicit_band : host_band_from_pct(band.pct, mx);
         const uint32_t w = std::max(std::min(band_ub, mx), mx - mn) + 2;   // >= w of every pair of the tile
         KernelGeom key = fast_ok ? pick_band_geom(2 * w + 1, dim, req, uniform_pen, fast_shift) : KernelGeom{};
+        if (shared_ok && key.family == KernelGeom::Systolic) {
+            const KernelGeom shared{KernelGeom::SharedColumns, key.lanes_or_waves, key.cells};
+            // every pair of the tile has its w between these bounds: within the slack, no need to look at the pairs
+            const uint32_t lx = lo[tiles[t].x], ly = lo[tiles[t].y], hx = hi[tiles[t].x], hy = hi[tiles[t].y];
+            const uint32_t mx_lo = std::max(lx, ly), gap_lo = lx > hy ? lx - hy : ly > hx ? ly - hx : 0u;
+            const uint32_t band_lb = band.use_explicit ? band.explicit_band : host_band_from_pct(band.pct, mx_lo);
+            const uint32_t w_lb = std::max(std::min(band_lb, mx_lo), gap_lo) + 2;
+            const uint32_t slack = shared_column_slack(shared);
+            if (geom_instantiated(shared, dim) && (w - w_lb <= slack || shared_columns_qualify(lens, tiles[t].x, tiles[t].y, band, slack)))
+                key = shared;
+        }
         // the band binds nowhere in this tile (band >= longest - 3 for its longest sequence, hence for all) and the penalties
         // are equal: both ordered scores are one number, swept over column strips (dtw_full.h).  Not for very short columns,
         // where four pairs per wavefront in band form keep more lanes busy.
@@ -525,7 +546,7 @@ static hipError_t launch_align_chunk(const AlignLaunch &L, KernelGeom g, hipStre
     bool found = false;
     with_kernel_dim(L.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
-        found = g.family == KernelGeom::Systolic ? launch_systolic<D>(L, g, stream)
+        found = g.family == KernelGeom::Systolic || g.family == KernelGeom::SharedColumns ? launch_systolic<D>(L, g, stream)
               : g.family == KernelGeom::Wide     ? launch_wide<D>(L, g, stream, &e)
                                                  : launch_full<D>(L, g, stream, &e);
     });
@@ -550,7 +571,7 @@ hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, 
     // penalties (its fast select on the difference form is the reference's arithmetic operation for operation, see
     // dtw_systolic.h) and switches only the hybrid form off.
     AlignLaunch part = L;
-    part.hybrid = L.hybrid && (g.family == KernelGeom::Systolic ? L.dim >= 8 && !L.strict : L.dim >= 10 && L.band.mat == 1.0f);
+    part.hybrid = L.hybrid && (g.family == KernelGeom::Systolic || g.family == KernelGeom::SharedColumns ? L.dim >= 8 && !L.strict : L.dim >= 10 && L.band.mat == 1.0f);
     for (uint32_t first = 0; first < L.n_tiles; first += kTilesPerLaunch) {
         part.d_tiles = L.d_tiles + first;
         part.n_tiles = std::min(kTilesPerLaunch, L.n_tiles - first);

@@ -136,6 +136,51 @@ __device__ __forceinline__ float frame_sq_exact_pre(const float (&xm)[D + 1], co
     }
     return acc;
 }
+// The two DP rows of one macro-step, shared by the systolic kernels: DP1 = score(a, b) (left = DELETE), DP2 = score(b, a) (up = DELETE).
+// Exchanges across lanes wrap around the group (rotations: no +INF fill to materialise).  What the edge lanes
+// receive is either +INF already or never looked at: lane 0's DELETE/INSERT neighbour comes from offset
+// G*C - 1 >= 2w, outside DP1's band and therefore +INF (guarded nodes sit on their +INF MATCH predecessor), and
+// its DP2 node (u = 0) is guarded itself; lane G-1's last node is guarded in DP1, and in DP2 either guarded
+// (G*C - 1 > 2w) or handed lane 0's guarded u = 0 node, +INF.  (G = 8, 32: the rotation spans two groups / the wave; the nodes
+// that wrap in come from the neighbouring group's edges, which meet the same conditions -- G*C >= 2w + 1 holds
+// for every pair of the tile, and idle groups sweep a 1 x 1 dummy with w = 2.)
+template <int C, int G, bool UNIFORM_PEN>
+__device__ __forceinline__ void dp_rows_step(float (&prev1)[C], float (&prev2)[C], const float (&d)[C], const bool (&g1)[C],
+                                             const bool (&g2)[C], float del, float ins, float mat, int gl)
+{
+    float left1 = group_from_lower_wrap<G>(prev1[C - 1], APD_INF, gl);
+    float left2 = group_from_lower_wrap<G>(prev2[C - 1], APD_INF, gl);
+    float upr1 = APD_INF, upr2 = APD_INF;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (APD_ABLATE & 2) { prev1[c] += d[c]; prev2[c] -= d[c]; continue; }
+        const float up1 = (c < C - 1) ? prev1[(c + 1) % C] : upr1;
+        const float up2 = (c < C - 1) ? prev2[(c + 1) % C] : upr2;
+        // guards: outside a DP's band the node is forced onto its MATCH predecessor, which is +INF
+        const float r1 = select_node<UNIFORM_PEN>(left1, up1, prev1[c], d[c], del, ins, mat, (APD_ABLATE & 16) ? false : g1[c]);   // left = DELETE
+        const float r2 = select_node<UNIFORM_PEN>(up2, left2, prev2[c], d[c], del, ins, mat, (APD_ABLATE & 16) ? false : g2[c]);   // up   = DELETE
+        prev1[c] = r1; prev2[c] = r2;
+        left1 = r1; left2 = r2;
+        if (c == 0) {
+            upr1 = group_from_upper_wrap<G>(r1, APD_INF, gl);
+            upr2 = group_from_upper_wrap<G>(r2, APD_INF, gl);
+        }
+    }
+}
+// Slow-phase bookkeeping of one macro-step: D[0][0] = 0 once the lane has swept row 0, and the result cell (n-1, m-1) kept.
+template <int C>
+__device__ __forceinline__ void slow_phase_captures(float (&prev1)[C], float (&prev2)[C], float &res1, float &res2, int tau, int gl,
+                                                    int tau_cap, int cw, int cstar)
+{
+    if (tau == gl) {                              // this lane just swept row 0: D[0][0] = 0
+#pragma unroll
+        for (int c = 0; c < C; ++c) if (c == cw) { prev1[c] = 0.0f; prev2[c] = 0.0f; }
+    }
+    if (tau == tau_cap) {                         // row n-1 done: keep cell (n-1, m-1)
+#pragma unroll
+        for (int c = 0; c < C; ++c) if (c == cstar) { res1 = prev1[c]; res2 = prev2[c]; }
+    }
+}
 template <int D, int C, int G, bool UNIFORM_PEN, bool HYBRID>
 __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
 {
@@ -449,42 +494,8 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
                         for (int c = 0; c < C - 1; ++c) dn[c] = frame_dist_strict<D, DN>(xs[xb], yf[(r + 1 + c) % S]);
                     }
                 }
-                // the two DP rows
-                // Exchanges across lanes wrap around the group (rotations: no +INF fill to materialise).  What the edge lanes
-                // receive is either +INF already or never looked at: lane 0's DELETE/INSERT neighbour comes from offset
-                // G*C - 1 >= 2w, outside DP1's band and therefore +INF (guarded nodes sit on their +INF MATCH predecessor), and
-                // its DP2 node (u = 0) is guarded itself; lane G-1's last node is guarded in DP1, and in DP2 either guarded
-                // (G*C - 1 > 2w) or handed lane 0's guarded u = 0 node, +INF.  (G = 8, 32: the rotation spans two groups / the wave; the nodes
-                // that wrap in come from the neighbouring group's edges, which meet the same conditions -- G*C >= 2w + 1 holds
-                // for every pair of the tile, and idle groups sweep a 1 x 1 dummy with w = 2.)
-                float left1 = group_from_lower_wrap<G>(prev1[C - 1], APD_INF, gl);
-                float left2 = group_from_lower_wrap<G>(prev2[C - 1], APD_INF, gl);
-                float upr1 = APD_INF, upr2 = APD_INF;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (APD_ABLATE & 2) { prev1[c] += d[c]; prev2[c] -= d[c]; continue; }
-                    const float up1 = (c < C - 1) ? prev1[(c + 1) % C] : upr1;
-                    const float up2 = (c < C - 1) ? prev2[(c + 1) % C] : upr2;
-                    // guards: outside a DP's band the node is forced onto its MATCH predecessor, which is +INF
-                    const float r1 = select_node<UNIFORM_PEN>(left1, up1, prev1[c], d[c], del, ins, mat, (APD_ABLATE & 16) ? false : g1[c]);   // left = DELETE
-                    const float r2 = select_node<UNIFORM_PEN>(up2, left2, prev2[c], d[c], del, ins, mat, (APD_ABLATE & 16) ? false : g2[c]);   // up   = DELETE
-                    prev1[c] = r1; prev2[c] = r2;
-                    left1 = r1; left2 = r2;
-                    if (c == 0) {
-                        upr1 = group_from_upper_wrap<G>(r1, APD_INF, gl);
-                        upr2 = group_from_upper_wrap<G>(r2, APD_INF, gl);
-                    }
-                }
-                if (SLOW) {
-                    if (tau == gl) {                              // this lane just swept row 0: D[0][0] = 0
-#pragma unroll
-                        for (int c = 0; c < C; ++c) if (c == cw) { prev1[c] = 0.0f; prev2[c] = 0.0f; }
-                    }
-                    if (tau == tau_cap) {                         // row n-1 done: keep cell (n-1, m-1)
-#pragma unroll
-                        for (int c = 0; c < C; ++c) if (c == cstar) { res1 = prev1[c]; res2 = prev2[c]; }
-                    }
-                }
+                dp_rows_step<C, G, UNIFORM_PEN>(prev1, prev2, d, g1, g2, del, ins, mat, gl);
+                if (SLOW) slow_phase_captures<C>(prev1, prev2, res1, res2, tau, gl, tau_cap, cw, cstar);
                 if (!HYBRID) advance_window(q);
             }
             fill_store(tau0 + U + 1, fill_regs);
@@ -506,6 +517,324 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
             store_pair(L, tile, P, s, s);
         }
     }
+}
+
+// One resident frame (DN floats, 16-byte aligned) out of LDS: whole 16-byte pieces, and a last read of exactly the floats that are
+// left.  A fourth ds_read_b128 for a tail of two floats would need a register quad of its own (or one that overlaps the
+// neighbouring piece's, with a wait for the LDS in between): the shared-column kernel reads two frames per macro-step this way.
+typedef float apd_f32x2 __attribute__((ext_vector_type(2)));
+template <int DN>
+__device__ __forceinline__ void read_frame_lds(float (&dst)[DN], const float *p)
+{
+    constexpr int FULL = DN / 4, TAIL = DN % 4;
+#pragma unroll
+    for (int k = 0; k < FULL; ++k) {
+        const apd_f32x4 t = *reinterpret_cast<const apd_f32x4 *>(p + 4 * k);
+        dst[4 * k + 0] = t.x; dst[4 * k + 1] = t.y; dst[4 * k + 2] = t.z; dst[4 * k + 3] = t.w;
+    }
+    if (TAIL >= 2) {
+        const apd_f32x2 t = *reinterpret_cast<const apd_f32x2 *>(p + 4 * FULL);
+        dst[4 * FULL + 0] = t.x; dst[4 * FULL + 1] = t.y;
+    }
+    if (TAIL == 1) dst[4 * FULL] = p[4 * FULL];
+    if (TAIL == 3) dst[4 * FULL + 2] = p[4 * FULL + 2];
+}
+
+// Floats of one column ring: RC frames and a copy of the first U behind them (as the row ring has: the U consecutive slots a lane
+// reads during one unrolled block are contiguous), 16 bytes of padding per 8 frames, rounded to whole 256-byte bank rows so
+// that the four rings start on the same banks.
+constexpr int shared_column_ring_floats(int rc, int u, int dp) { return (((rc + u) * dp + ((rc + u + 7) / 8) * 4) * 4 + 255) / 256 * 64; }
+
+// ---- Shared column rings: the hybrid, unit-penalty kernel with the column window fed from LDS instead of moved by DPP.
+// A workgroup sweeps a 4 x 4 sub-block of its tile instead of a 1 x 16 row: wavefront k the row sequence a_k (one a per wavefront,
+// as above: the row ring and everything that rests on it stay), its four lane groups the columns b_0 .. b_3.  The four
+// wavefronts need the same four column sequences, so the workgroup keeps one ring of RC column frames per b in LDS:
+//  * wavefront k fills ring k, U columns per unrolled block, with coalesced 16-byte loads (sentinel frame for columns <= 0,
+//    clamped beyond m), stored at the block's end; one barrier per block orders the fills against the reads;
+//  * in each macro-step every lane reads the column entering its window, j = tau + 1 + (C-1)(gl+1) - w, into the dead register
+//    slot: LPF ds_read_b128 in place of the DN DPP moves and of the top lane's fetch.  The same frames reach the same fmac
+//    chains in the same order: results are bit-identical to dtw_fused_systolic<D, C, G, true, true>;
+//  * the 16 lanes of a group read columns C - 1 = 8 apart.  Ring slot p = j mod RC lives at p * FB + (p / 8) * 16 bytes: the
+//    16 bytes behind every eighth frame make the lane stride an odd number of 16-byte bank slots, conflict-free except where
+//    the ring wraps inside the group.  A copy of the first U frames sits behind the ring, so the U consecutive slots a lane
+//    reads during one unrolled block are contiguous: one base per block, the frame offsets are immediates of the ds_read and
+//    only the padding term is computed per macro-step (3 integer operations);
+//  * with the fill of block b + 1 written while other wavefronts still read block b, the ring spans the lanes' window,
+//    2 U columns and the spread of w inside the workgroup (apd_internal.h, shared_column_ring_frames); the tile plan sends
+//    only tiles within that spread here (shared_columns_qualify);
+//  * the block count is the workgroup's maximum, and a wavefront without a swept pair still walks the barriers and fills its ring.
+//    The phase boundaries (slow / steady / slow) stay per wavefront, so the four wavefronts may sit at DIFFERENT barrier
+//    instructions in the same block (the loop body is instantiated once per phase).  That is correct because s_barrier counts
+//    arrivals of the workgroup's wavefronts and does not match program locations, and every wavefront executes exactly
+//    total_r / U of them; it is a property of this hardware, beyond what the HIP model promises for __syncthreads().
+template <int D, int C, int G>
+__global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaunch L)
+{
+    static_assert(C >= 2 && G == 16, "one ring per wavefront: four lane groups");
+    if (L.d_nonfinite != nullptr && *L.d_nonfinite != 0u) return;   // a NaN / infinite feature in the batch: the literal kernel's job
+    constexpr int DN = D + 1;
+    constexpr int DP = (DN + 3) & ~3;
+    constexpr int PPW = 64 / G;                                // pairs per wave = wavefronts per workgroup = rings
+    constexpr int WPT = kSlotsPerTile / (4 * PPW);
+    constexpr int S = C + 1;
+    constexpr int U = shared_column_unroll(C);
+    constexpr int RC = shared_column_ring_frames(G, C);
+    constexpr int R = 64;                                      // row ring, as in dtw_fused_systolic
+    constexpr int LPF = DP / 4;
+    constexpr int FPF = 64 / LPF;
+    constexpr int RS = DP + 4;
+    constexpr uint32_t FB = DP * 4u;
+    constexpr int XRING = (R + U) * RS;                         // floats of one row ring
+    constexpr int CRING = shared_column_ring_floats(RC, U, DP);   // floats of one column ring
+    static_assert(FPF >= U && RC % 8 == 0, "one wave-wide load per fill");
+    // While some wavefront reads block tau0 (lowest column tau0 + C - w_hi) another may already store the fill of the next block
+    // (columns up to tau0 + 2U + (C-1)G - w_lo, which land on the slots of the columns RC below them): nothing still read is
+    // overwritten as long as RC >= (G-1)(C-1) + 2U + (w_hi - w_lo).  The plan's slack is what the host admits for w_hi - w_lo.
+    static_assert(RC >= (G - 1) * (C - 1) + 2 * U + (int)shared_column_slack(KernelGeom{KernelGeom::SharedColumns, G, C}),
+                  "ring too short for the spread of w the tile plan admits");
+    extern __shared__ __attribute__((aligned(16))) float apd_shared_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gl = lane % G;
+    float *const xring = apd_shared_lds + wave * XRING;
+    float *const crings = apd_shared_lds + 4 * XRING;
+    int *const wg_words = reinterpret_cast<int *>(crings + PPW * CRING);   // [wave][total, smallest w]
+    const uint32_t xcd = blockIdx.x & 7u, q = blockIdx.x >> 3;
+    const uint32_t tile = (q / WPT) * 8u + xcd;
+    const uint32_t sub = q % WPT;                                // 4 x 4 sub-block of the tile
+    const uint32_t slot = ((sub / 4u) * 4u + wave) * kTile + (sub % 4u) * 4u + lane / G;
+    const PairInfo P = decode_pair(L, tile, slot);
+    const bool special = P.valid && (P.n == 1 || P.m == 1);
+    const bool sweep = P.valid && !special;
+    const int n = sweep ? P.n : 1, m = sweep ? P.m : 1, w = sweep ? P.w : 2;
+    const int u0 = C * gl;
+    const int two_w = 2 * w;
+    const int g_act = (two_w + 1 + C - 1) / C;
+    int my_total = sweep ? (n - 1) + g_act : 0;
+    int my_min = sweep ? (n - 1) : 0x7fffffff;
+    int my_w = sweep ? w : 0x7fffffff;
+    int total = 0, min_rows = 0x7fffffff, w_lo = 0x7fffffff;
+#pragma unroll
+    for (int g = 0; g < PPW; ++g) {
+        total = max(total, __builtin_amdgcn_readlane(my_total, g * G));
+        min_rows = min(min_rows, __builtin_amdgcn_readlane(my_min, g * G));
+        w_lo = min(w_lo, __builtin_amdgcn_readlane(my_w, g * G));
+    }
+    if (lane == 0) { wg_words[2 * wave] = total; wg_words[2 * wave + 1] = w_lo; }
+    __syncthreads();
+    total = 0; w_lo = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { total = max(total, wg_words[2 * k]); w_lo = min(w_lo, wg_words[2 * k + 1]); }
+    if (total == 0) {                                            // workgroup-uniform: nothing to sweep (diagonal tiles, the batch's edge)
+        if (special && gl == 0) { const float s = (P.n == 1 && P.m == 1) ? 0.0f : APD_INF; store_pair(L, tile, P, s, s); }
+        return;
+    }
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)L.d_frames, 0, L.frames_bytes, 0x00020000);
+    const uint32_t a_off = (uint32_t)(P.A - L.d_frames) * 4u, b_off = (uint32_t)(P.B - L.d_frames) * 4u;
+    float ins = L.band.ins, del = L.band.del, mat = L.band.mat;
+    float tau_thr = L.tau, nmax_b = P.nmax_b;
+    asm volatile("" : "+v"(ins), "+v"(del), "+v"(mat), "+v"(tau_thr), "+v"(nmax_b));
+    // sequence a of this wavefront (none: a wavefront that only walks the barriers sweeps the first frame of the batch)
+    const unsigned long long sweeping = __ballot(sweep);
+    const int lead = sweeping ? __builtin_ctzll(sweeping) : 0;
+    const uint32_t a_off_w = sweeping ? __builtin_amdgcn_readlane(a_off, lead) : 0u;
+    const int n_w = sweeping ? __builtin_amdgcn_readlane(n, lead) : 1;
+    // the column sequence of this wavefront's ring: b_wave of the sub-block, whether or not this wavefront's own pair with it is valid
+    uint32_t cb_off = 0u;
+    int cm = 0;
+    bool cvalid = false;
+    {
+        const uint4 t = L.d_tiles[tile];                         // total > 0: the tile exists
+        const uint32_t b = t.y * kTile + (sub % 4u) * 4u + wave;
+        if (b < L.n_seq) {
+            const uint32_t ob = L.d_seq_off[b];
+            cm = (int)(L.d_seq_off[b + 1] - ob) - 2;
+            cb_off = ob * L.dpad * 4u;
+            cvalid = true;
+        }
+    }
+
+    bool g1[C], g2[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int u = u0 + c;
+        g1[c] = u >= two_w;
+        g2[c] = (u == 0) | (u > two_w);
+    }
+    const int cw = w - u0;
+    const int ustar = (m - 1) - (n - 1) + w;
+    const int cstar = ustar - u0;
+    const int tau_cap = (n - 1) + gl;
+    // block counts: the workgroup's (every block has one barrier); the phase boundaries stay this wavefront's own
+    const int total_r = ((total + U - 1) / U) * U;
+    const int a_end = min(((G + U - 1) / U) * U, total_r);
+    const int b_end = min(max((min_rows / U) * U, a_end), total_r);
+
+    float prev1[C], prev2[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) { prev1[c] = APD_INF; prev2[c] = APD_INF; }
+    float res1 = 0.0f, res2 = 0.0f;
+
+    // window at macro-step 0, from memory; the slot of the entering column is read from the ring in macro-step 0
+    float yf[S][DN];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int j = u0 - gl + c - w;
+        const int idx = (j >= 1) ? (min(j, m) - 1) : m;
+        load_frame<DN>(yf[c], rsrc, b_off + (uint32_t)idx * FB);
+    }
+#pragma unroll
+    for (int k = 0; k < DN; ++k) yf[C][k] = 0.0f;
+
+    // ---- row ring (as in dtw_fused_systolic)
+    constexpr int NFILL = (U + FPF - 1) / FPF;
+    const int fill_f = lane / LPF, fill_q = lane % LPF;
+    const bool fill_act = (fill_f < FPF) & (fill_f < U);
+    auto fill_load = [&](int first_row, apd_f32x4 (&regs)[NFILL]) __attribute__((always_inline)) {
+        const uint32_t off = a_off_w + (uint32_t)(min(first_row + fill_f, n_w) - 1) * FB + 16u * fill_q;
+        regs[0] = __builtin_bit_cast(apd_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, fill_act ? off : kNoFrame, 0, 0));
+    };
+    auto fill_store = [&](int first_row, const apd_f32x4 (&regs)[NFILL]) __attribute__((always_inline)) {
+        if (fill_act) {
+            apd_f32x4 v = regs[0];
+            prescale_row_piece<D>(v, fill_q);
+            const int rslot = (first_row + fill_f) & (R - 1);
+            *reinterpret_cast<apd_f32x4 *>(&xring[rslot * RS + 4 * fill_q]) = v;
+            if (rslot < U) *reinterpret_cast<apd_f32x4 *>(&xring[(rslot + R) * RS + 4 * fill_q]) = v;
+        }
+    };
+    for (int e = lane; e < G * DP; e += 64) {
+        const int rslot = (-(e / DP)) & (R - 1);
+        const float v = (e % DP) == D ? APD_INF : 0.0f;
+        xring[rslot * RS + (e % DP)] = v;
+        if (rslot < U) xring[(rslot + R) * RS + (e % DP)] = v;
+    }
+    {
+        apd_f32x4 regs[NFILL];
+        fill_load(1, regs);
+        fill_store(1, regs);
+    }
+    // ---- column rings.  Ring slot of column j: j mod RC (kept as running, wrapped counters: no division in the loop).
+    // During block tau0 the lanes read columns tau0 + C - w .. tau0 + U + (C-1) G - w; col_hi is the last of them for the
+    // smallest w of the workgroup.  The ring holds (col_hi - RC, col_hi] when the block starts.
+    float *const cring_fill = crings + wave * CRING;
+    const int col_hi0 = U + (C - 1) * G - w_lo;
+    auto ring_slot = [](int j) { return (j + 64 * RC) % RC; };   // prologue only: columns there are above -RC - G C / 2
+    auto ring_at = [](auto *ring, uint32_t p) { return ring + p * DP + ((p >> 3) << 2); };
+    auto col_load = [&](int j, bool act) __attribute__((always_inline)) {
+        const int idx = (j >= 1) ? (min(j, cm) - 1) : cm;        // sentinel H behind the sequence for columns <= 0
+        const uint32_t off = cb_off + (uint32_t)idx * FB + 16u * fill_q;
+        return __builtin_bit_cast(apd_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (act & cvalid) ? off : kNoFrame, 0, 0));
+    };
+    for (int j0 = col_hi0 - RC + 1; j0 <= col_hi0; j0 += FPF) {   // prologue: the whole ring
+        const int j = j0 + fill_f;
+        const bool act = (fill_f < FPF) & (j <= col_hi0);
+        const apd_f32x4 v = col_load(j, act);
+        const uint32_t ps = (uint32_t)ring_slot(j);
+        if (act) *reinterpret_cast<apd_f32x4 *>(ring_at(cring_fill, ps) + 4 * fill_q) = v;
+        if (act && ps < (uint32_t)U) *reinterpret_cast<apd_f32x4 *>(ring_at(cring_fill, ps + RC) + 4 * fill_q) = v;   // the copy behind the ring
+    }
+    uint32_t pf = (uint32_t)ring_slot(col_hi0 + 1 + fill_f);      // slot this lane fills at the end of the first block
+    // this lane's reads: the column entering at macro-step 1 first
+    const float *const cring_read = crings + (lane / G) * CRING;
+    uint32_t pr = (uint32_t)ring_slot(1 + (C - 1) * (gl + 1) - w);   // slot read in the first macro-step of the coming block
+    // step q of a block reads slot pr + q (< RC + U: the copy): the frame offset is an immediate, only the padding term moves
+    auto read_col = [&](float (&dst)[DN], const float *block_base, int q) __attribute__((always_inline)) {
+        read_frame_lds<DN>(dst, block_base + q * DP + (((pr + (uint32_t)q) >> 3) << 2));
+    };
+    __syncthreads();
+    auto read_row_at = [&](float (&dst)[DN], const float *p) __attribute__((always_inline)) { read_frame_lds<DN>(dst, p); };
+    float xs[DN];
+    read_row_at(xs, &xring[((0 - gl) & (R - 1)) * RS]);          // macro-step 0: row -gl
+
+    auto macro_steps = [&](int tau_begin, int tau_end, auto slow_tag) __attribute__((always_inline)) {
+        constexpr bool SLOW = decltype(slow_tag)::value;
+        for (int tau0 = tau_begin; tau0 < tau_end; tau0 += U) {
+            apd_f32x4 fill_regs[NFILL];
+            fill_load(tau0 + U + 1, fill_regs);                  // rows and columns of the NEXT block, stored at this block's end
+            const apd_f32x4 col_regs = col_load(tau0 + col_hi0 + 1 + fill_f, fill_act);
+            const float *const xrows = &xring[((tau0 + 1 - gl) & (R - 1)) * RS];
+            const float *const ycols = cring_read + pr * DP;
+#pragma unroll
+            for (int q = 0; q < U; ++q) {
+                const int tau = tau0 + q;
+                const int r = q % S;               // slot of this step's first column
+                const int e = (r + C) % S;         // slot of the column entering at tau + 1 (dead during this step)
+                float d[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) d[c] = frame_sq_expanded_pre<D>(xs, yf[(r + c) % S]);
+                float dmin = d[0];
+#pragma unroll
+                for (int c = 1; c + 1 < C; c += 2) dmin = __builtin_fminf(__builtin_fminf(dmin, d[c]), d[c + 1]);
+                if (C % 2 == 0) dmin = __builtin_fminf(dmin, d[C - 1]);
+                const bool any = dmin < (xs[D] + nmax_b) * tau_thr;
+                // the entering column, between the test and the branch on it (where the DPP kernel moves its window)
+                read_col(yf[e], ycols, q);
+                if (__builtin_expect(__ballot(any) != 0ull, 0)) {
+                    float nx = xs[D];
+                    asm volatile("" : "+v"(nx));
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const float sc = nx + yf[(r + c) % S][D];
+                        const float ex = frame_sq_exact_pre<D>(xs, yf[(r + c) % S]);
+                        d[c] = (d[c] < sc * tau_thr) ? ex : d[c];
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) d[c] = __builtin_amdgcn_sqrtf(d[c]);
+                read_row_at(xs, xrows + q * RS);
+                dp_rows_step<C, G, true>(prev1, prev2, d, g1, g2, del, ins, mat, gl);
+                if (SLOW) slow_phase_captures<C>(prev1, prev2, res1, res2, tau, gl, tau_cap, cw, cstar);
+            }
+            fill_store(tau0 + U + 1, fill_regs);
+            if (fill_act) *reinterpret_cast<apd_f32x4 *>(ring_at(cring_fill, pf) + 4 * fill_q) = col_regs;
+            if (fill_act && pf < (uint32_t)U) *reinterpret_cast<apd_f32x4 *>(ring_at(cring_fill, pf + RC) + 4 * fill_q) = col_regs;
+            pf = min(pf + (uint32_t)U, pf + (uint32_t)U - (uint32_t)RC);   // one wrap: pf + U - RC is huge (unsigned) until pf + U reaches RC
+            pr = min(pr + (uint32_t)U, pr + (uint32_t)U - (uint32_t)RC);
+            __syncthreads();                                     // the next block reads what the four wavefronts just stored
+        }
+    };
+    macro_steps(0, a_end, std::true_type{});
+    macro_steps(a_end, b_end, std::false_type{});
+    macro_steps(b_end, total_r, std::true_type{});
+
+    if (P.valid && gl == (sweep ? ustar / C : 0)) {
+        if (sweep) {
+            const float denom = (float)(n + m);
+            store_pair(L, tile, P, res1 / denom, res2 / denom);
+        } else {
+            const float s = (P.n == 1 && P.m == 1) ? 0.0f : APD_INF;
+            store_pair(L, tile, P, s, s);
+        }
+    }
+}
+
+// LDS of one workgroup of dtw_fused_systolic_shared<D, C, G>: four row rings, four column rings, the workgroup's words
+template <int D, int C, int G>
+constexpr size_t shared_columns_lds_bytes()
+{
+    constexpr int DP = (D + 1 + 3) & ~3, U = shared_column_unroll(C), RC = shared_column_ring_frames(G, C);
+    constexpr int XRING = (64 + U) * (DP + 4), CRING = shared_column_ring_floats(RC, U, DP);
+    return (size_t)(4 * XRING + (64 / G) * CRING + 8) * sizeof(float);
+}
+template <int D, int C, int G>
+static hipError_t launch_shared_columns_kernel(const AlignLaunch &L, hipStream_t stream)
+{
+    constexpr int WPT = kSlotsPerTile / (4 * (64 / G));
+    constexpr size_t lds = shared_columns_lds_bytes<D, C, G>();
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    // beyond the 64 KB default: asked for once per device (a race between two first launches asks twice, harmlessly)
+    static bool granted[64] = {};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !granted[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_fused_systolic_shared<D, C, G>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) granted[dev] = true;
+    }
+    const uint32_t tiles8 = (L.n_tiles + 7u) / 8u * 8u;
+    hipLaunchKernelGGL((dtw_fused_systolic_shared<D, C, G>), dim3(tiles8 * WPT), dim3(256), lds, stream, L);
+    return hipSuccess;
 }
 
 // The three instantiations of one (D, C, G) live in two translation units -- dtw_sys.hip: hybrid form and the literal select
@@ -536,6 +865,14 @@ bool launch_systolic(const AlignLaunch &L, KernelGeom g, hipStream_t stream)
 {
     // unit penalties: the fast select, either distance form; anything else: literal select on strict (bit-faithful) distances
     const bool unit = L.band.ins == 1.0f && L.band.del == 1.0f && L.band.mat == 1.0f;
+    if (g.family == KernelGeom::SharedColumns) {                 // hybrid form, unit penalties only: the plan names it for nothing else
+        if (!(unit && L.hybrid)) return false;
+#define APD_CASE(GG, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::SharedColumns, GG, CC}, D)) { \
+        if (g == KernelGeom{KernelGeom::SharedColumns, GG, CC}) return launch_shared_columns_kernel<D, CC, GG>(L, stream) == hipSuccess; }
+        APD_SHARED_COLUMN_GEOMS(APD_CASE)
+#undef APD_CASE
+        return false;
+    }
     if (unit && !L.hybrid) return launch_systolic_strict<D>(L, g, stream);
 #define APD_CASE(GG, CC) if constexpr (geom_instantiated(KernelGeom{KernelGeom::Systolic, GG, CC}, D)) { \
         if (g == KernelGeom{KernelGeom::Systolic, GG, CC}) { \

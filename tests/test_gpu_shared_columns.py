@@ -1,0 +1,201 @@
+"""The systolic kernel with workgroup-shared column rings (dtw_fused_systolic_shared, variant code 40000 + G * 100 + C).
+
+It feeds the same frames to the same arithmetic as the DPP-window kernel (code G * 100 + C), so every case asks for two things
+on one batch: parity with the CPU oracle at the suite's tolerance (1e-4 relative, identical zeros and +INF pattern), and
+the SAME BITS as the DPP kernel forced through apd_set_variant.  Which tiles took which kernel is read from the
+APD_DEBUG_PLAN lines of the tile plan (no ABI call reports it).
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from audio_pattern_discovery_amd import synth
+
+pytestmark = pytest.mark.gpu
+RTOL = 1e-4
+DPP, SHARED = 1609, 41609        # G = 16, C = 9: the one geometry with a shared-column twin
+SLACK = 19                       # spread of w one workgroup tolerates: ring of 160 frames, 141 needed by equal bands
+
+
+@pytest.fixture(scope="module")
+def ctx(apd):
+    c = apd.Context(0)
+    c.set_distance_mode("hybrid")
+    yield c
+    c.set_variant(0)
+    c.close()
+
+
+def assert_parity(got, want, rtol=RTOL):
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    assert got.shape == want.shape
+    fin = np.isfinite(want)
+    assert np.array_equal(fin, np.isfinite(got)), "INF/NaN pattern differs"
+    assert np.array_equal(np.isposinf(want), np.isposinf(got))
+    zero = fin & (want == 0)
+    assert np.all(got[zero] == 0), "exact zeros (diagonal, identical sequences) must stay 0"
+    nz = fin & ~zero
+    if nz.any():
+        rel = np.abs(got[nz] - want[nz]) / np.abs(want[nz])
+        print("max rel err %.3e" % rel.max())
+        assert rel.max() <= rtol, "max rel err %.3e" % rel.max()
+
+
+def assert_same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "%d entries differ" % int((a.view(np.uint32) != b.view(np.uint32)).sum())
+
+
+def align(ctx, seqs, pct, variant, capfd=None):
+    """The matrix of one forced variant; with capfd also {geometry code: tiles} of the plan it was computed with."""
+    from audio_pattern_discovery_amd.alignments import AlignmentWorkers, NDSequence
+    from audio_pattern_discovery_amd.discovery import Discovery
+    n = len(seqs)
+    ctx.set_variant(variant)
+    os.environ["APD_DEBUG_PLAN"] = "1"
+    try:
+        if capfd is not None:
+            capfd.readouterr()
+        out = AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx).align_all(
+            Discovery(warping_band_percentage=pct)).reshape(n, n).copy()
+        plan = None
+        if capfd is not None:
+            plan = {int(g): int(t) for g, t in re.findall(r"geometry (\d+): (\d+) tiles", capfd.readouterr().err)}
+    finally:
+        os.environ.pop("APD_DEBUG_PLAN", None)
+        ctx.set_variant(0)
+    return out, plan
+
+
+def oracle_matrix(oracle, seqs, pct):
+    frames = np.concatenate(seqs, axis=0).astype(np.float32)
+    offsets = np.zeros(len(seqs) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs])
+    return oracle.align_all(frames, offsets, pct, 1.0, 1.0, 1.0, workers=8)
+
+
+def check_both_paths(ctx, oracle, capfd, seqs, pct):
+    """Forced shared columns and forced DPP window on one batch: oracle parity, same bits.  Returns the two plans."""
+    want = oracle_matrix(oracle, seqs, pct)
+    shared, plan_s = align(ctx, seqs, pct, SHARED, capfd)
+    dpp, plan_d = align(ctx, seqs, pct, DPP, capfd)
+    assert SHARED not in plan_d                                  # the existing code keeps naming the DPP kernel
+    assert_parity(shared, want)
+    assert_same_bits(shared, dpp)
+    auto, _ = align(ctx, seqs, pct, 0)
+    assert_parity(auto, want)
+    return plan_s, plan_d
+
+
+def random_seqs(rng, lens, dim, integer=False):
+    out = []
+    for ln in lens:
+        s = np.cumsum(rng.standard_normal((int(ln), dim)), axis=0).astype(np.float32) * 0.3
+        out.append(np.rint(s).astype(np.float32) if integer else s)
+    return out
+
+
+@pytest.mark.parametrize("dim", [13, 8])
+def test_flagship_shape_takes_the_shared_path_and_keeps_its_bits(ctx, oracle, capfd, dim):
+    """cfg 3 / cfg 4 scaled down: 100 sequences (7 x 7 tile grid: diagonal, off-diagonal and a partly filled last tile), band 64."""
+    frames, offsets = synth.make_sequences(100, 384, dim, seed=31 + dim, jitter=12)
+    seqs = synth.split(frames, offsets)
+    plan_s, _ = check_both_paths(ctx, oracle, capfd, seqs, 1.0 / 6.0)
+    assert plan_s == {SHARED: 28}, plan_s                        # every tile qualifies: w within a few frames
+    _, plan_auto = align(ctx, seqs, 1.0 / 6.0, 0, capfd)
+    assert plan_auto == {SHARED: 28}, plan_auto                  # and the automatic choice is the new class
+
+
+def test_special_pairs_inside_sweeping_workgroups(ctx, oracle, capfd):
+    """Lengths 1 and 2 next to ordinary ones: absent result cells (+INF, or 0 for 1 x 1) in workgroups that also sweep."""
+    rng = np.random.default_rng(5)
+    lens = [1, 2, 1, 2, 2, 1] + list(rng.integers(3, 40, size=30))
+    rng.shuffle(lens)
+    seqs = random_seqs(rng, lens, 13)
+    plan_s, _ = check_both_paths(ctx, oracle, capfd, seqs, 0.5)
+    assert plan_s.get(SHARED, 0) > 0, plan_s
+
+
+def test_exact_copies_and_integer_features(ctx, oracle, capfd):
+    """Recompute branch (copies: distances at and near 0), structural ties (integer features), and the 0.375 known answer."""
+    frames, offsets = synth.make_sequences(40, 90, 13, seed=77, integer=True, jitter=6, copies=0.6)
+    seqs = synth.split(frames, offsets)
+    seqs += [seqs[3].copy(), seqs[17].copy(), seqs[3].copy()]    # exact copies: score exactly 0
+    plan_s, _ = check_both_paths(ctx, oracle, capfd, seqs, 0.25)
+    assert plan_s.get(SHARED, 0) > 0, plan_s
+    x, y = np.zeros((4, 13), np.float32), np.zeros((4, 13), np.float32)
+    x[:, 0], y[:, 0] = [0, 1, 0, 0], [1, 0, 1, 0]                # Dl == I < M takes MATCH: 3 / 8 (tests/test_oracle.py)
+    got, plan = align(ctx, [x, y] * 9, 0.0, SHARED, capfd)
+    assert plan == {SHARED: 3}, plan
+    for i in range(18):
+        for j in range(18):
+            assert got[i, j] == (0.0 if (i - j) % 2 == 0 else 0.375), (i, j, got[i, j])
+
+
+def test_ragged_batch_is_demoted_to_the_dpp_kernel(ctx, oracle, capfd):
+    """rag10's shape scaled down: D = 10, band 10 %, 18 lengths spread evenly over 32 .. 100.  w = max(band, |n - m|) + 2 follows
+    the length gap, and with lengths 4 apart the 4 x 4 pairs of a workgroup differ by up to 24 in w, beyond the ring's slack
+    (e.g. rows 100 .. 88 against columns 68 .. 56 of the first tile).  With the new class forced that tile must run on the DPP
+    kernel, and everything agrees bitwise."""
+    rng = np.random.default_rng(10)
+    lens = [100 - 4 * i for i in range(18)]
+    rng.shuffle(lens)
+    seqs = random_seqs(rng, lens, 10)
+    plan_s, plan_d = check_both_paths(ctx, oracle, capfd, seqs, 0.1)
+    assert plan_s.get(DPP, 0) >= 1, plan_s                       # the demoted tile(s)
+    assert sum(plan_s.values()) == 3 and plan_d == {DPP: 3}, (plan_s, plan_d)
+
+
+@pytest.mark.parametrize("longest,qualifies", [(41 + SLACK, True), (41 + SLACK + 1, False)])
+def test_band_spread_at_and_beyond_the_ring_slack(ctx, oracle, capfd, longest, qualifies):
+    """Band 0: w = |n - m| + 2.  Resident order is longest first, so the first workgroup row holds (longest, 41, 41, 41): its
+    pairs with the 40-frame sequences have w = longest - 38 and 3, its own pairs w = longest - 39 and 2 -- a spread of
+    longest - 41 in both sub-blocks."""
+    rng = np.random.default_rng(longest)
+    seqs = random_seqs(rng, [40, 41, 40, longest, 41, 40, 41, 40], 13)
+    plan_s, _ = check_both_paths(ctx, oracle, capfd, seqs, 0.0)
+    assert plan_s == ({SHARED: 1} if qualifies else {DPP: 1}), plan_s
+
+
+def test_bounded_sweep_with_the_shared_path_forced(ctx, oracle, capfd):
+    """tools/debug/fuzz.py's draw, restricted to what the new class serves (unit penalties, hybrid form, D <= 13; other frame
+    dimensions are padded up to 8 / 10 / 13), with the class forced: oracle parity and the DPP kernel's bits for every case.
+
+    A free draw is often ragged (demoted to the DPP kernel) or too wide (generic kernel), where "same bits" compares a kernel
+    with itself.  So every even case is drawn to qualify by construction: jitter <= 8 and band <= 10 % of at most 408 frames
+    give w = max(band, |n - m|) + 2 <= 42 (within the 144 offsets of G = 16, C = 9) and a spread of w over the whole batch of at
+    most 16 (gap) + 1 (band) <= the ring's slack.  Those cases must run EVERY tile on the shared class; the odd cases stay free."""
+    rng = np.random.default_rng(4141)
+    failures = []
+    shared_tiles = 0
+    for k in range(40):
+        dim = int(rng.choice([1, 3, 5, 8, 9, 10, 12, 13]))
+        n_seq = int(rng.integers(2, 40))
+        length = int(rng.choice([3, 8, 20, 60, 150, 400]))
+        jitter = int(rng.integers(0, max(length - 1, 1)))
+        pct = float(rng.choice([0.0, 0.01, 0.0625, 0.1, 0.25, 0.5, 1.0]))
+        if k % 2 == 0:
+            jitter = min(jitter, 8)
+            pct = float(rng.choice([0.0, 0.01, 0.0625, 0.1]))
+        if length >= 400:
+            n_seq = min(n_seq, 12)
+        case = dict(k=k, dim=dim, n_seq=n_seq, length=length, jitter=jitter, pct=pct)
+        frames, offsets = synth.make_sequences(n_seq, length, dim, seed=int(rng.integers(1 << 30)), integer=bool(rng.random() < 0.4),
+                                               jitter=jitter, copies=float(rng.choice([0.0, 0.25, 0.6])))
+        seqs = synth.split(frames, offsets)
+        want = oracle.align_all(frames, offsets, pct, 1.0, 1.0, 1.0, workers=8)
+        shared, plan = align(ctx, seqs, pct, SHARED, capfd)
+        dpp, _ = align(ctx, seqs, pct, DPP)
+        side = (n_seq + 15) // 16
+        try:
+            if k % 2 == 0:
+                assert plan == {SHARED: side * (side + 1) // 2}, plan
+            shared_tiles += plan.get(SHARED, 0)
+            assert_parity(shared, want)
+            assert_same_bits(shared, dpp)
+        except AssertionError as e:
+            failures.append((case, str(e)))
+    assert not failures, failures[:3]
+    assert shared_tiles >= 20                                    # 20 qualifying cases of at least one tile each

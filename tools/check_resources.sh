@@ -6,7 +6,7 @@ for fam in sys sysx wf; do for d in 8 10 13 16 20 26; do
   [ "$fam" = "sysx" ] && extra="-mllvm -amdgpu-sched-strategy=max-ilp"
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize $extra --cuda-device-only -Rpass-analysis=kernel-resource-usage -DAPD_DIM=$d -c dtw_${fam}.hip -o /dev/null 2>&1 \
    | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy" | sed -E 's/.*remark: +//; s/ \[-Rpass.*//' | paste - - - - \
-   | sed -E 's/Function Name: _ZN3apd18dtw_fused_systolicILi([0-9]+)ELi([0-9]+)ELi([0-9]+)ELb([01])ELb([01])EEEvNS_11AlignLaunchE/systolic D=\1 C=\2 G=\3 uniform=\4 hybrid=\5/' > /tmp/apd_res_${fam}_$d.txt &
+   | sed -E 's/Function Name: _ZN3apd18dtw_fused_systolicILi([0-9]+)ELi([0-9]+)ELi([0-9]+)ELb([01])ELb([01])EEEvNS_11AlignLaunchE/systolic D=\1 C=\2 G=\3 uniform=\4 hybrid=\5/; s/Function Name: _ZN3apd25dtw_fused_systolic_sharedILi([0-9]+)ELi([0-9]+)ELi([0-9]+)EEEvNS_11AlignLaunchE/systolic shared columns D=\1 C=\2 G=\3 (dynamic LDS: shared_columns_lds_bytes, <= 80 KB by static_assert)/' > /tmp/apd_res_${fam}_$d.txt &
 done; done
 # the UPGMA / companion kernels too: a launch that needs scratch pays for it every time, and the UPGMA loop is made of short launches
 # (round 4: two debug stamps in the commit pushed upgma_segment_kernel to 400 bytes of scratch per lane and doubled every dendrogram)
