@@ -1,0 +1,173 @@
+"""The DTW kernel table as the tests see it: parsed from the text of csrc/apd_internal.h, the single source of what is instantiated.
+
+The five APD_*_GEOMS(X) lists and kKernelDims are read from the header (continuation lines joined first); the two per-dimension
+clamps have a literal Python mirror here, which tests/test_kernel_table.py compares with the header's expressions.  A geometry
+added to a list becomes a new test case of tests/test_gpu_kernel_matrix.py without an edit to the tests.  Also here: the reader
+of the APD_DEBUG_PLAN lines (which geometry took how many tiles), the only report of which kernel ran.
+"""
+import os
+import re
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audio_pattern_discovery_amd", "csrc", "apd_internal.h")
+
+# family -> (macro of its list, base of its integer code): KernelGeom::encode, base + first * 100 + second
+FAMILIES = {
+    "systolic": ("APD_SYSTOLIC_GEOMS", 0),
+    "wide": ("APD_WIDE_GEOMS", 10000),
+    "strip": ("APD_STRIP_GEOMS", 20000),
+    "banded": ("APD_BANDED_STRIP_GEOMS", 30000),
+    "shared": ("APD_SHARED_COLUMN_GEOMS", 40000),
+}
+CLAMPS = ("max_cells_per_lane", "max_strip_columns")
+
+
+def header_text(path=HEADER):
+    """The header with its backslash-newline continuations joined, as the preprocessor sees the macro bodies."""
+    with open(path) as f:
+        return re.sub(r"\\[ \t]*\r?\n", " ", f.read())
+
+
+def parse_geoms(text, macro):
+    """[(first, second)] of one '#define MACRO(X) X(a, b) X(c, d) ...' line."""
+    m = re.search(r"^[ \t]*#[ \t]*define[ \t]+%s\(X\)[ \t]+(.*)$" % re.escape(macro), text, re.M)
+    if m is None:
+        raise ValueError("no '#define %s(X) ...' in %s" % (macro, HEADER))
+    body = m.group(1).split("//")[0]
+    geoms = [(int(a), int(b)) for a, b in re.findall(r"\bX\(\s*(\d+)\s*,\s*(\d+)\s*\)", body)]
+    left = re.sub(r"\bX\(\s*\d+\s*,\s*\d+\s*\)", "", body).strip()
+    if left:
+        raise ValueError("%s: not a list of X(a, b) entries: %r" % (macro, left))
+    return geoms
+
+
+def parse_dims(text):
+    m = re.search(r"\bkKernelDims\[\]\s*=\s*\{([^}]*)\}", text)
+    if m is None:
+        raise ValueError("no 'kKernelDims[] = {...}' in %s" % HEADER)
+    return [int(v) for v in m.group(1).split(",") if v.strip()]
+
+
+def parse_table(text=None):
+    """({family: [(first, second)]}, [kernel dims]) of the header."""
+    text = header_text() if text is None else text
+    return {fam: parse_geoms(text, macro) for fam, (macro, _) in FAMILIES.items()}, parse_dims(text)
+
+
+# ---- literal mirror of the header's per-dimension clamps (compared with the header text by tests/test_kernel_table.py)
+def max_cells_per_lane(d):
+    return 9 if d <= 13 else (7 if d <= 16 else 5)
+
+
+def max_strip_columns(d):
+    return 13 if d <= 10 else (11 if d <= 13 else max_cells_per_lane(d))
+
+
+def encode(family, first, second):
+    return FAMILIES[family][1] + first * 100 + second
+
+
+def decode(code):
+    """KernelGeom::decode: (family, first, second), or None for the codes that name the generic kernel."""
+    for fam, (_, base) in FAMILIES.items():
+        lo = 100 if fam == "systolic" else base
+        if lo <= code < base + 10000:
+            return fam, (code % 10000) // 100, code % 100
+    return None
+
+
+def instantiated(family, first, second, dim):
+    """geom_instantiated for a listed geometry at a kernel dimension: within the dimension's clamp."""
+    return second <= (max_strip_columns(dim) if family == "strip" else max_cells_per_lane(dim))
+
+
+def capacity(family, first, second):
+    """KernelGeom::capacity: band offsets one pair covers (band form); for the strips, columns per pass G * CW."""
+    if family in ("strip", "banded"):
+        return (64 // first) * second
+    return (64 if family == "wide" else 1) * first * second
+
+
+def pairs(table=None):
+    """([(family, first, second, dim)] that exist, [...] that the dimension's clamp drops), in header order."""
+    geoms, dims = parse_table() if table is None else table
+    have, dropped = [], []
+    for fam in FAMILIES:
+        for a, b in geoms[fam]:
+            for d in dims:
+                (have if instantiated(fam, a, b, d) else dropped).append((fam, a, b, d))
+    return have, dropped
+
+
+# ---- the header's own clamp expressions, evaluated: integers, the parameter, <=, <, ?:, parentheses, calls of the other clamp
+def clamp_source(text, name):
+    """(parameter name, expression text, 1-based line number) of 'constexpr int NAME(uint32_t d) { return EXPR; }'."""
+    m = re.search(r"constexpr\s+int\s+%s\s*\(\s*uint32_t\s+(\w+)\s*\)\s*\{\s*return\s+([^;]*);\s*\}" % re.escape(name), text)
+    if m is None:
+        raise ValueError("no 'constexpr int %s(uint32_t d) { return ...; }' in %s" % (name, HEADER))
+    return m.group(1), m.group(2).strip(), text.count("\n", 0, m.start()) + 1
+
+
+def eval_clamp(text, name, d):
+    """The value of the header's clamp `name` at dimension d."""
+    param, expr, line = clamp_source(text, name)
+    toks = re.findall(r"\d+|\w+|<=|<|[?:()]", expr)
+    if "".join(toks) != re.sub(r"\s+", "", expr):
+        raise ValueError("%s:%d: %s: cannot read %r" % (HEADER, line, name, expr))
+    pos = [0]
+
+    def peek():
+        return toks[pos[0]] if pos[0] < len(toks) else None
+
+    def take(want=None):
+        t = peek()
+        if t is None or (want is not None and t != want):
+            raise ValueError("%s:%d: %s: cannot read %r (at token %d)" % (HEADER, line, name, expr, pos[0]))
+        pos[0] += 1
+        return t
+
+    def primary():
+        t = take()
+        if t == "(":
+            v = ternary()
+            take(")")
+            return v
+        if t.isdigit():
+            return int(t)
+        if t == param:
+            return d
+        if t in CLAMPS and t != name and peek() == "(":
+            take("(")
+            arg = ternary()
+            take(")")
+            return eval_clamp(text, t, arg)
+        raise ValueError("%s:%d: %s: unknown name %r in %r" % (HEADER, line, name, t, expr))
+
+    def compare():
+        v = primary()
+        while peek() in ("<=", "<"):
+            op, rhs = take(), primary()
+            v = int(v <= rhs if op == "<=" else v < rhs)
+        return v
+
+    def ternary():
+        c = compare()
+        if peek() == "?":
+            take("?")
+            a = ternary()
+            take(":")
+            b = ternary()
+            return a if c else b
+        return c
+
+    v = ternary()
+    if peek() is not None:
+        raise ValueError("%s:%d: %s: trailing %r in %r" % (HEADER, line, name, peek(), expr))
+    return v
+
+
+def read_plan(stderr_text):
+    """{geometry code: tiles} of the '[apd] rank r/w: geometry <code>: <n> tiles, ...' lines APD_DEBUG_PLAN=1 prints per tile plan."""
+    plan = {}
+    for code, tiles in re.findall(r"geometry (\d+): (\d+) tiles", stderr_text):
+        plan[int(code)] = plan.get(int(code), 0) + int(tiles)
+    return plan

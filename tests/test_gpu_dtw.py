@@ -4,6 +4,7 @@ Tolerance (BASELINE.json north_star): every finite distance within 1e-4 relative
 identical 0.0 diagonal and identical +INF pattern.  The kernels use an fma chain for the frame
 distance and v_sqrt_f32 (<= 1 ulp), so results are not bitwise equal to the two-rounding CPU code.
 """
+import contextlib
 import ctypes as C
 import glob
 import os
@@ -11,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from _kernel_table import read_plan
 from audio_pattern_discovery_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +39,20 @@ def assert_parity(got, want, rtol=RTOL):
     if nz.any():
         rel = np.abs(got[nz] - want[nz]) / np.abs(want[nz])
         assert rel.max() <= rtol, "max rel err %.3e" % rel.max()
+
+
+@contextlib.contextmanager
+def debug_plan(capfd):
+    """{geometry code: tiles} of the tile plans built inside the block (the APD_DEBUG_PLAN lines on stderr), filled on exit: the
+    only report of which kernel a forced variant really ran -- a code the dimension cannot hold silently runs something else."""
+    plan = {}
+    os.environ["APD_DEBUG_PLAN"] = "1"
+    capfd.readouterr()
+    try:
+        yield plan
+    finally:
+        os.environ.pop("APD_DEBUG_PLAN", None)
+        plan.update(read_plan(capfd.readouterr().err))
 
 
 def gpu_align_all(ctx, frames, offsets, dim, pct, ins=1.0, dele=1.0, mat=1.0, variant=0):
@@ -329,7 +345,7 @@ def test_mixed_lengths_use_several_kernel_geometries(ctx, oracle, pct):
 
 @pytest.mark.parametrize("variant", [10205, 10207, 10209, 10405, 10407, 10409, 10805, 10807, 10809])
 @pytest.mark.parametrize("distance", ["hybrid", "exact"])
-def test_wide_kernel_geometries(ctx, oracle, variant, distance):
+def test_wide_kernel_geometries(ctx, oracle, capfd, variant, distance):
     """dtw_fused_wide (NW waves per pair, LDS mailboxes at the wave seams) in every instantiated geometry, full DTW and
     a binding band, on lengths that put the result cell, the D[0][0] injection and the band edges in different waves."""
     rng = np.random.default_rng(variant)
@@ -344,10 +360,12 @@ def test_wide_kernel_geometries(ctx, oracle, variant, distance):
         want = oracle.align_all(frames, offsets, pct, workers=8)
         ctx.set_distance_mode(distance)
         ctx.set_variant(variant)
-        w = AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx)
-        got = w.align_all(Discovery(warping_band_percentage=pct)).reshape(len(seqs), len(seqs)).copy()
+        with debug_plan(capfd) as plan:
+            w = AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx)
+            got = w.align_all(Discovery(warping_band_percentage=pct)).reshape(len(seqs), len(seqs)).copy()
         ctx.set_variant(0)
         ctx.set_distance_mode("hybrid")
+        assert plan.get(variant, 0) > 0, plan                            # the named kernel ran
         assert_parity(got, want)
         dup = len(seqs) - 1
     assert got[5, dup] == 0.0 and got[dup, 5] == 0.0
@@ -355,7 +373,7 @@ def test_wide_kernel_geometries(ctx, oracle, variant, distance):
 
 @pytest.mark.parametrize("variant", [0, 20103, 20105, 20107, 20109, 20111, 20113, 20203, 20207, 20213, 20403, 20405, 20409, 20413])
 @pytest.mark.parametrize("distance", ["hybrid", "exact"])
-def test_full_matrix_kernel(ctx, oracle, variant, distance):
+def test_full_matrix_kernel(ctx, oracle, capfd, variant, distance):
     """dtw_full_matrix (column strips in passes, ONE DP for both ordered pairs): valid when the band never binds and the penalties
     are equal -- then score(a,b) == score(b,a) in the reference itself, which the oracle confirms here bit for bit."""
     rng = np.random.default_rng(variant + 7)
@@ -364,7 +382,8 @@ def test_full_matrix_kernel(ctx, oracle, variant, distance):
     wcols = (64 // max((variant - 20000) // 100, 1)) * (variant % 100)   # columns per pass: G * CW
     lens = [2, 3, 50, 64, 65, 130, 190, 191] if variant == 0 else [2, 3, 70, 193, 194, 333, 520, 571, wcols + 1, wcols + 2, 2 * wcols + 1]
     lens = lens + [1, 17, 17, 18, 40, 40, 41, 75, 100]                   # 26 sequences: tiles whose waves hold several different pairs
-    seqs = [np.cumsum(rng.standard_normal((n, 13)), axis=0).astype(np.float32) * 0.4 for n in lens]
+    dim = 10 if variant % 100 == 13 else 13                              # 13 columns of 14 floats do not fit at D = 13 (max_strip_columns)
+    seqs = [np.cumsum(rng.standard_normal((n, dim)), axis=0).astype(np.float32) * 0.4 for n in lens]
     seqs.append(seqs[5].copy())
     frames = np.concatenate(seqs)
     offsets = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
@@ -374,11 +393,13 @@ def test_full_matrix_kernel(ctx, oracle, variant, distance):
     from audio_pattern_discovery_amd.discovery import Discovery
     ctx.set_distance_mode(distance)
     ctx.set_variant(variant)
-    w = AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx)
-    got = w.align_all(Discovery(warping_band_percentage=1.0, insertion_penalty=0.7, deletion_penalty=0.7,
-                                match_penalty=0.7)).reshape(len(seqs), len(seqs)).copy()
+    with debug_plan(capfd) as plan:
+        w = AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx)
+        got = w.align_all(Discovery(warping_band_percentage=1.0, insertion_penalty=0.7, deletion_penalty=0.7,
+                                    match_penalty=0.7)).reshape(len(seqs), len(seqs)).copy()
     ctx.set_variant(0)
     ctx.set_distance_mode("hybrid")
+    assert variant == 0 or plan == {variant: 3}, plan                    # a forced strip code takes every tile of a full band
     assert_parity(got, want)
     dup = len(seqs) - 1
     assert got[5, dup] == 0.0 and got[dup, 5] == 0.0
@@ -438,7 +459,7 @@ def test_launches_are_cut_below_the_work_item_limit(ctx, oracle):
 
 @pytest.mark.parametrize("dim", [13, 26])
 @pytest.mark.parametrize("key", [809, 1602, 1603, 1605, 1607, 1609, 3205, 3207, 3209, 6403, 6405, 6407, 6409])
-def test_every_systolic_geometry(ctx, oracle, key, dim):
+def test_every_systolic_geometry(ctx, oracle, capfd, key, dim):
     """Each (lanes per pair G, offsets per lane C) of dtw_fused_systolic, forced through the tuning variant, on a band that
     fills its lanes (2w+1 just below G*C) and on a narrow one (idle upper lanes); unit penalties in both distance forms,
     and unequal penalties (bit-identical to the oracle).  G = 32 moves data across lanes with two DPP writes per move."""
@@ -456,10 +477,12 @@ def test_every_systolic_geometry(ctx, oracle, key, dim):
             want = oracle.align_all(frames, offsets, pct, *pens, workers=8)
             ctx.set_distance_mode(mode)
             ctx.set_variant(key)
-            got = AlignmentWorkers.new(seqs, ctx).align_all(Discovery(warping_band_percentage=pct, insertion_penalty=pens[0],
-                                                                      deletion_penalty=pens[1], match_penalty=pens[2])).reshape(20, 20)
+            with debug_plan(capfd) as plan:
+                got = AlignmentWorkers.new(seqs, ctx).align_all(Discovery(warping_band_percentage=pct, insertion_penalty=pens[0],
+                                                                          deletion_penalty=pens[1], match_penalty=pens[2])).reshape(20, 20)
             ctx.set_variant(0)
             ctx.set_distance_mode("hybrid")
+            assert plan == {key: 3}, plan                                # the named kernel took every tile
             if pens == (1.0, 1.0, 1.0):
                 assert_parity(got, want)
             else:
@@ -468,7 +491,7 @@ def test_every_systolic_geometry(ctx, oracle, key, dim):
 
 @pytest.mark.parametrize("variant", [0, 30105, 30109, 30405, 30409])
 @pytest.mark.parametrize("distance", ["hybrid", "exact"])
-def test_banded_column_strips(ctx, oracle, variant, distance):
+def test_banded_column_strips(ctx, oracle, capfd, variant, distance):
     """Column strips with a binding band (dtw_full_matrix<..., BANDED>): two DPs, band edges masked by +INF distances.
     Ragged lengths make w = max(band, |n - m|) + 2 wide for unequal pairs and narrow for equal ones; forced variants put
     every tile on the strips, variant 0 lets the dispatcher mix them with the band-form kernels."""
@@ -484,11 +507,13 @@ def test_banded_column_strips(ctx, oracle, variant, distance):
         want = oracle.align_all(frames, offsets, pct, pen, pen, pen, workers=8)
         ctx.set_distance_mode(distance)
         ctx.set_variant(variant)
-        runs = [AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx).align_all(
-            Discovery(warping_band_percentage=pct, insertion_penalty=pen, deletion_penalty=pen, match_penalty=pen)
-        ).reshape(len(seqs), len(seqs)).copy() for _ in range(2)]
+        with debug_plan(capfd) as plan:
+            runs = [AlignmentWorkers.new([NDSequence(s) for s in seqs], ctx).align_all(
+                Discovery(warping_band_percentage=pct, insertion_penalty=pen, deletion_penalty=pen, match_penalty=pen)
+            ).reshape(len(seqs), len(seqs)).copy() for _ in range(2)]
         ctx.set_variant(0)
         ctx.set_distance_mode("hybrid")
+        assert variant == 0 or plan == {variant: 2 * 3}, plan            # two runs of three tiles, all on the forced strips
         assert np.array_equal(runs[0], runs[1])
         assert_parity(runs[0], want)
         assert runs[0][7, len(seqs) - 1] == 0.0

@@ -6,11 +6,11 @@ the SAME BITS as the DPP kernel forced through apd_set_variant.  Which tiles too
 APD_DEBUG_PLAN lines of the tile plan (no ABI call reports it).
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
+from _kernel_table import read_plan
 from audio_pattern_discovery_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +62,7 @@ def align(ctx, seqs, pct, variant, capfd=None):
             Discovery(warping_band_percentage=pct)).reshape(n, n).copy()
         plan = None
         if capfd is not None:
-            plan = {int(g): int(t) for g, t in re.findall(r"geometry (\d+): (\d+) tiles", capfd.readouterr().err)}
+            plan = read_plan(capfd.readouterr().err)
     finally:
         os.environ.pop("APD_DEBUG_PLAN", None)
         ctx.set_variant(0)
