@@ -561,8 +561,9 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     HIP_TRY(ctx, bind_device(ctx));
     const bool pens_ok = (band.ins > 0.0f) && (band.del > 0.0f) && (band.mat > 0.0f) && (band.ins < INFINITY) &&
                          (band.del < INFINITY) && (band.mat < INFINITY);   // the systolic kernel needs pen * INF = INF
-    // A NaN / infinite feature anywhere in the batch means: literal kernel only (the fast kernels' selects and sentinels assume
-    // finite features).  The repack kernel leaves that verdict in batch->d_flags[0]; it is consumed ON THE DEVICE: the fast
+    // A feature outside the fast range anywhere in the batch (NaN, infinite, |v| >= kFeatureBound, or non-zero below kFeatureFloor)
+    // means: literal kernel only (the fast kernels' selects and sentinels assume finite features, their distance forms normal
+    // squared distances).  The repack kernel leaves that verdict in batch->d_flags[0]; it is consumed ON THE DEVICE: the fast
     // kernels return at once when it is set, and a fallback launch of the generic kernel over the same tiles returns at once when
     // it is clear (`device_select`).  No host round trip, nothing blocks: the call only enqueues.  The one exception: a band so
     // wide that the generic kernel cannot hold it in LDS -- then the host reads the flag (a stream synchronisation), as the fast

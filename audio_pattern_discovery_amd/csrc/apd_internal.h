@@ -216,7 +216,8 @@ struct TileClass { KernelGeom geom; uint32_t first, count, w_max, n_max; };
 void plan_tile_classes(const std::vector<uint64_t> &offsets, uint32_t n_seq, const std::vector<uint2> &tiles, const BandSpec &band,
                        uint32_t dim, int variant, bool fast_ok, bool uniform_pen, bool fast_shift, std::vector<TileClass> &classes,
                        std::vector<uint4> &flat);
-// d_flags[0] is raised when a frame holds a NaN or an infinity (the fast kernels' selects and sentinels assume finite features)
+// d_flags[0] is raised when a frame holds a NaN, an infinity or a non-zero feature outside [kFeatureFloor, kFeatureBound) (the fast
+// kernels' selects, sentinels and distance forms assume finite features and normal squared distances)
 // d_seq_nmax[p] (zeroed by the caller) receives the largest squared frame norm of resident sequence p
 hipError_t launch_pad(const float *d_src, float *d_dst, const uint32_t *d_seq_off, const uint32_t *d_src_off, uint32_t n_seq,
                       uint64_t n_frames_padded, uint32_t src_dim, uint32_t dim, uint32_t dpad, uint32_t *d_flags, float *d_seq_nmax,
@@ -227,8 +228,16 @@ hipError_t launch_unpack(const float *d_gathered, float *d_out, const uint32_t *
                          uint64_t slab_floats, const uint32_t *d_flags, uint32_t *d_status, hipStream_t stream);
 hipError_t launch_selftest(int *d_result, hipStream_t stream);
 hipError_t launch_sqrt_sweep(uint32_t first, uint64_t count, unsigned long long *d_out, hipStream_t stream);
-// Features of magnitude >= 2^60 (or NaN / infinite) raise the batch's flag: below it every squared distance and every frame
-// norm is finite (26 * (2 * 2^60)^2 < 2^127), which the fast kernels' square roots and norm expansion rely on.
+// The feature range of the fast kernels: a batch is theirs when every feature is 0 or has kFeatureFloor <= |v| < kFeatureBound;
+// any other value (NaN and the infinities included) raises the batch's flag, and the literal kernel aligns every pair.
+// Bound: below 2^60 every squared distance and every frame norm is finite (26 * (2 * 2^60)^2 < 2^127), which the fast kernels'
+// square roots and norm expansion rely on.
+// Floor: the fast distance forms end in the bare v_sqrt_f32, which does not take subnormal inputs (the compiler's sqrtf rescales
+// them first), and the hybrid form compares against frame norms (an f64 sum cast to f32) that go subnormal from |v| ~ 2^-63 and
+// are 0 from ~ 2^-75.  With every non-zero |v| >= 2^-40 the ulp of a feature is at least 2^-63, so a non-zero component
+// difference is a multiple of 2^-63 and a non-zero squared distance at least 2^-126: normal; a non-zero frame norm is at least
+// 2^-80.  Exact zeros (silence, padding) contribute nothing to either and stay on the fast kernels.
+constexpr float kFeatureFloor = 0x1p-40f;
 constexpr float kFeatureBound = 0x1p60f;
 
 // comm.hip: called by apd_destroy for every communicator still alive on the context

@@ -160,7 +160,11 @@ __global__ __launch_bounds__(256) void pad_frames_kernel(const float *__restrict
                 const uint32_t k = 4 * q + i;
                 if (k < src_dim) {                                // components src_dim .. dim - 1 stay zero
                     v[i] = fr[k];
-                    nonfinite |= !(__builtin_fabsf(v[i]) < kFeatureBound);   // NaN, +-INF, or so large that a squared distance could overflow
+                    // outside [kFeatureFloor, kFeatureBound) and not 0: NaN, +-INF, so large that a squared distance could overflow, or
+                    // so small that one could be subnormal.  On the bits of |v| (they order like the magnitudes, NaN above +INF): a
+                    // subnormal feature is seen as what it is whatever the denormal mode of the float compare.
+                    const uint32_t mag = __builtin_bit_cast(uint32_t, v[i]) & 0x7FFFFFFFu;
+                    nonfinite |= mag != 0u && (mag < __builtin_bit_cast(uint32_t, kFeatureFloor) || mag >= __builtin_bit_cast(uint32_t, kFeatureBound));
                     part += (double)v[i] * (double)v[i];
                 }
             }
@@ -208,9 +212,10 @@ __global__ __launch_bounds__(256) void pad_frames_kernel(const float *__restrict
         }
         if (live) *reinterpret_cast<float4 *>(dst + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
-    // the fast kernels assume finite features (fminf-based select, +INF sentinels, norm expansion) and finite squared distances
-    // (sqrt_rn_finite): a batch with a NaN, an infinity or a feature of magnitude >= 2^60 anywhere is routed to the literal kernel,
-    // where NaN compares false and takes MATCH as in alignments.rs:153-159 and an overflowing distance is +INF as on the CPU
+    // the fast kernels assume finite features (fminf-based select, +INF sentinels, norm expansion) and finite, normal squared
+    // distances (sqrt_rn_finite, v_sqrt_f32): a batch with a NaN, an infinity, a feature of magnitude >= 2^60 or a non-zero one below
+    // 2^-40 anywhere is routed to the literal kernel, where NaN compares false and takes MATCH as in alignments.rs:153-159, an
+    // overflowing distance is +INF and an underflowing one is the subnormal or 0 that it is on the CPU
     if (__ballot(nonfinite) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flags, 1u);
 }
 

@@ -116,7 +116,11 @@ int apd_set_variant(apd_context *ctx, int variant);
  * differ by a few 1e-4 relative.  Counted over every entry of the BASELINE shapes (tests/test_gpu_census.py): none on cfg 2,
  * cfg 3 and cfg 5's shape, one pair of 8.4 million on cfg 4; over 60 corpora per shape 1-6 entries in 1e8, worst seen 2.2e-3
  * (tools/census_sweep.py).  Ties that are structural (identical frames, integer features,
- * +INF) are reproduced in every mode. */
+ * +INF) are reproduced in every mode.
+ * Feature range: all of the above holds for batches whose features are 0 or have 2^-40 <= |v| < 2^60 -- there every non-zero
+ * squared distance and frame norm is a normal, finite f32.  A batch with any other value (apd_batch_nonfinite) is aligned by the
+ * literal kernel whatever the mode: bit-identical to the CPU code, subnormal and overflowing distances included.  (Without that
+ * routing modes 0 and 1 lose the tolerance once squared distances go subnormal: DESIGN.md section 6 has the measured table.) */
 int apd_set_distance_mode(apd_context *ctx, int mode, float tau);
 /* Device self-test of the cross-lane primitives the kernels rely on (DPP wave shifts). */
 int apd_selftest(apd_context *ctx);
@@ -155,8 +159,12 @@ uint32_t apd_batch_len(const apd_batch *batch);
  * the repack kernel, asynchronously on the context's stream; the batch keeps its device buffers and its cached tile
  * plans.  For pipelines that call align_all repeatedly on features recomputed in HBM (bench.py's step). */
 int apd_batch_refill(apd_context *ctx, apd_batch *batch, const float *frames, int frames_on_device);
-/* 1 if the resident frames hold a NaN or an infinity (then every pair goes through the literal, NaN-faithful kernel:
- * NaN compares false and takes the MATCH branch, alignments.rs:153-159), 0 if all are finite.  Synchronises. */
+/* 1 if the resident frames hold a value outside the fast kernels' feature range: a NaN, an infinity, a magnitude of 2^60 or
+ * more, or a NON-ZERO magnitude below 2^-40 (exact zeros are inside the range).  Then every pair goes through the literal kernel,
+ * which computes operation for operation as the CPU code does: NaN compares false and takes the MATCH branch
+ * (alignments.rs:153-159), an overflowing distance is +INF, an underflowing one the subnormal or 0 it is on the CPU -- scores
+ * bit-identical to the CPU code in every distance mode, at the literal kernel's speed.  0 if every feature is 0 or has
+ * 2^-40 <= |v| < 2^60.  Follows apd_batch_refill.  Synchronises. */
 int apd_batch_nonfinite(apd_context *ctx, const apd_batch *batch, int *nonfinite);
 
 /* ---- AlignmentWorkers::align_all (src/alignments.rs:31-67) ---------------------------- */
@@ -182,7 +190,8 @@ uint64_t apd_slab_floats(uint32_t n_seq, uint32_t world);
 /* "_async" for the alignment entry points (this one, apd_align_all_device_async, apd_align_all_sharded_async,
  * apd_multi_align_all_async) means what it says: the kernels, the collective and the unpack are only ENQUEUED when the call
  * returns, also right after apd_batch_create / apd_batch_refill.  The choice between the fast kernels and the literal,
- * NaN-faithful one (a batch with a NaN / infinite feature must take the latter) is made ON THE DEVICE: the repack kernel
+ * CPU-faithful one (a batch with a NaN, an infinite feature or a non-zero one outside 2^-40 <= |v| < 2^60 must take the
+ * latter: apd_batch_nonfinite) is made ON THE DEVICE: the repack kernel
  * leaves its verdict in a flag word, the fast kernels return at once when it is raised, and a small persistent launch of the
  * literal kernel behind them returns at once when it is not.  One exception: a band so wide that the literal kernel cannot
  * hold it in LDS (2w+1 > 20 480 offsets) -- then the first alignment after a fill reads the flag back on the host (4 bytes,

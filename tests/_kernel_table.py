@@ -3,10 +3,13 @@
 The five APD_*_GEOMS(X) lists and kKernelDims are read from the header (continuation lines joined first); the two per-dimension
 clamps have a literal Python mirror here, which tests/test_kernel_table.py compares with the header's expressions.  A geometry
 added to a list becomes a new test case of tests/test_gpu_kernel_matrix.py without an edit to the tests.  Also here: the reader
-of the APD_DEBUG_PLAN lines (which geometry took how many tiles), the only report of which kernel ran.
+of the APD_DEBUG_PLAN lines (which geometry took how many tiles), the only report of which kernel ran, the header's fast-path
+feature range (kFeatureFloor, kFeatureBound) and the mixed-magnitude corpus that the CPU and the GPU range tests share.
 """
 import os
 import re
+
+import numpy as np
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audio_pattern_discovery_amd", "csrc", "apd_internal.h")
 
@@ -171,3 +174,42 @@ def read_plan(stderr_text):
     for code, tiles in re.findall(r"geometry (\d+): (\d+) tiles", stderr_text):
         plan[int(code)] = plan.get(int(code), 0) + int(tiles)
     return plan
+
+
+# ---- the fast kernels' feature range, and the corpus that leaves it at both ends
+def feature_range(text=None):
+    """(kFeatureFloor, kFeatureBound) of the header: a batch is flagged for the literal kernel when a non-zero feature has a
+    magnitude outside [floor, bound)."""
+    text = header_text() if text is None else text
+    out = []
+    for name in ("kFeatureFloor", "kFeatureBound"):
+        m = re.search(r"constexpr\s+float\s+%s\s*=\s*(0x1p[+-]?\d+)f\s*;" % name, text)
+        if m is None:
+            raise ValueError("no 'constexpr float %s = 0x1p<e>f;' in %s" % (name, HEADER))
+        out.append(float.fromhex(m.group(1)))
+    return tuple(out)
+
+
+def leaves_fast_range(frames, text=None):
+    """What pad_frames_kernel decides for these frames: True if one of them is NaN, infinite, non-zero below the floor or at /
+    beyond the bound."""
+    lo, hi = feature_range(text)
+    a = np.abs(np.asarray(frames, np.float32))
+    return bool(np.any(~(a < np.float32(hi)) | ((a != 0) & (a < np.float32(lo)))))
+
+
+def mixed_magnitude_corpus(n_seq=20, length=90, dim=13, seed=5):
+    """The corpus of tests/test_gpu_sqrt.py::test_strict_distance_bits_with_tiny_zero_and_huge_differences (the defaults give its
+    very values): O(1) Gaussian sequences, an identical pair, copies scaled by 1e-30 (squares underflow), that copy shifted by
+    1e-38, by 3e-20, 2e-15 and 1e17, and a sequence sharing every third frame with sequence 0.  [n_seq][length][dim] f32."""
+    assert n_seq >= 8
+    rng = np.random.default_rng(seed)
+    base = rng.standard_normal((n_seq, length, dim)).astype(np.float32)
+    base[1] = base[0]
+    base[2] = base[0] * np.float32(1e-30)
+    base[3] = base[2] + np.float32(1e-38)
+    base[4, ::3] = base[0, ::3]
+    base[5] = base[0] * np.float32(3e-20)
+    base[6] = base[0] * np.float32(2e-15)
+    base[7] = base[0] * np.float32(1e17)
+    return base

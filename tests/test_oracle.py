@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import _kernel_table as kt
 from audio_pattern_discovery_amd import synth
 from oracle import np_reference as npr
 
@@ -129,6 +130,69 @@ def test_oracle_matches_numpy_rederivation_bitwise(oracle, pct, pens, integer):
     c = npr.align_all(synth.split(frames, offsets), pct, *pens)
     assert np.array_equal(a, b)
     assert np.array_equal(a, c)
+
+
+def _ragged_walks(seed, dim, lens, copy_of):
+    """Random walks (x 0.4, the GPU suites' corpus) of the given lengths, an exact copy of sequence `copy_of` and, last, sequence
+    0 warped in time (its first third at half speed, the rest at double speed: the best path leaves a narrow band)."""
+    rng = np.random.default_rng(seed)
+    seqs = [np.cumsum(rng.standard_normal((n, dim)), axis=0).astype(np.float32) * np.float32(0.4) for n in lens]
+    seqs.append(seqs[copy_of].copy())
+    third = lens[0] // 3
+    seqs.append(seqs[0][np.concatenate([np.repeat(np.arange(third), 2), np.arange(third, lens[0], 2)])].copy())
+    offsets = np.zeros(len(seqs) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs])
+    return np.concatenate(seqs, axis=0), offsets
+
+
+@pytest.mark.parametrize("pens", [(1.0, 1.0, 1.0), (0.6, 1.3, 1.0)])
+@pytest.mark.parametrize("k", [-60, -40, -20, 20, 40, 55])
+def test_oracle_is_equivariant_under_power_of_two_scaling(oracle, k, pens):
+    """Scaling every feature by 2^k scales every difference, square (2^2k), sum, root and DP node exactly as long as nothing
+    leaves the normal range, and no comparison changes: align_all(2^k X) == 2^k align_all(X) bit for bit.  The premise of
+    tests/test_gpu_feature_range.py: over these exponents the GPU's fast forms face the SAME alignment problem, only the
+    binade moves.  The corpus has sequences of 1, 2 and 3 frames (+INF entries), an exact copy (0.0) and a band that binds
+    (10 % of 37 frames: 3, against length gaps up to 36 handled by the widening)."""
+    frames, offsets = _ragged_walks(20261017, 13, [37, 36, 33, 30, 30, 21, 3, 2, 1], copy_of=1)
+    base = oracle.align_all(frames, offsets, 0.1, *pens, workers=4)
+    assert base[1, 9] == 0.0 and base[9, 1] == 0.0 and np.isposinf(base[8, 0]) and np.isfinite(base[0, 1]) and base[0, 1] > 0
+    full = oracle.align_all(frames, offsets, 1.0, *pens, workers=4)
+    assert base[0, 10] > full[0, 10] and base[10, 0] > full[10, 0]               # the band binds
+    scaled = oracle.align_all(np.ldexp(frames, k), offsets, 0.1, *pens, workers=4)
+    want = np.ldexp(base, k)
+    assert np.all(np.isfinite(np.ldexp(frames, k))) and np.array_equal(np.isposinf(want), np.isposinf(base))
+    assert np.array_equal(scaled.view(np.uint32), want.view(np.uint32)), "%d entries differ" % int((scaled.view(np.uint32) != want.view(np.uint32)).sum())
+
+
+@pytest.mark.parametrize("k", [-62, -64, -66, -70, -75, -80])
+def test_oracle_matches_numpy_rederivation_bitwise_in_the_subnormal_range(oracle, k):
+    """Below 2^-61 the reference's own squares are subnormal or zero and the equivariance above ends; the oracle is still well
+    defined there (gradual underflow, IEEE square root), and it is what the literal GPU kernel is held to."""
+    frames, offsets = _ragged_walks(7, 5, [14, 13, 11, 9, 3, 2, 1], copy_of=0)
+    frames = np.ldexp(frames, k)
+    assert np.all(frames != 0) and np.abs(frames).max() < 2.0 ** (k + 5)
+    for pct, pens in ((0.25, (1.0, 1.0, 1.0)), (1.0, (0.6, 1.3, 1.0))):
+        a = oracle.align_all(frames, offsets, pct, *pens, workers=3)
+        b = oracle.align_all(frames, offsets, pct, *pens, workers=2, hashmap=True)
+        c = npr.align_all(synth.split(frames, offsets), pct, *pens)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        assert np.array_equal(a.view(np.uint32), c.view(np.uint32))
+        assert np.all(np.diag(a) == 0) and a[0, 7] == 0.0 and np.isposinf(a[6, 0])
+        if k >= -70:
+            assert np.count_nonzero(a[np.isfinite(a)]) > 20                     # not everything has underflowed to 0 yet
+
+
+@pytest.mark.parametrize("pct", [0.1, 1.0])
+def test_oracle_matches_numpy_rederivation_bitwise_on_mixed_magnitudes(oracle, pct):
+    """The corpus of tests/test_gpu_sqrt.py (rows scaled by 1e-30, 3e-20, 2e-15, 1e17, a shift by 1e-38, identical sequences and
+    frames) at a size the dict-based re-derivation can walk."""
+    base = kt.mixed_magnitude_corpus(n_seq=9, length=12, dim=13, seed=5)
+    frames = base.reshape(-1, 13)
+    offsets = np.arange(10, dtype=np.uint64) * 12
+    a = oracle.align_all(frames, offsets, pct, workers=3)
+    c = npr.align_all(list(base), pct)
+    assert np.array_equal(a.view(np.uint32), c.view(np.uint32))
+    assert a[0, 1] == 0.0 and a[2, 3] == 0.0 and 0 < a[2, 5] < 1e-18 and a[0, 7] > 1e15   # (2, 3): the squares of 1e-38 are 0
 
 
 def test_oracle_clustering_matches_numpy_rederivation(oracle):
