@@ -4,6 +4,8 @@
 // the alignment consumes are produced in HBM and never cross PCIe.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -434,6 +436,9 @@ extern "C" int apd_encode_async(apd_context *ctx, const apd_encoder *e, const fl
     // staged through LDS when the 4 x 64 staged rows fit next to the weights (they do for every shape the reference produces)
     const size_t staged_bytes = (((size_t)d_in * latent + latent + 3) & ~(size_t)3) * sizeof(float) +
                                 4 * 64 * (size_t)((d_in | 1u) + (latent | 1u)) * sizeof(float);
+    if (std::getenv("APD_DEBUG_PLAN"))                                  // as for the tile plans: the only report of which kernel ran
+        std::fprintf(stderr, "[apd] encoder %u -> %u: %s, %zu bytes of LDS\n", d_in, latent, staged_bytes <= 64 * 1024 ? "staged" : "direct",
+                     staged_bytes <= 64 * 1024 ? staged_bytes : ((size_t)d_in * latent + latent) * sizeof(float));
     if (staged_bytes <= 64 * 1024)
         hipLaunchKernelGGL(encode_staged_kernel, dim3(blocks), dim3(256), staged_bytes, ctx->stream, d_x, t, d_in, e->d_w,
                            e->d_w + (size_t)d_in * latent, latent, d_out);

@@ -4,6 +4,10 @@ A literal Python/numpy re-derivation of the reference recurrence that shares no 
 with oracle/apd_oracle.c: the DP table is a dict keyed (i, j) exactly like the
 reference's HashMap (alignments.rs:99-111), every scalar is an np.float32 so each
 operation rounds once as in the Rust build.  PARITY UNPINNED (see apd_oracle.h).
+
+The VAT pre-segmentation (variance, interesting_ranges) is re-derived the same way, as f32
+array operations that round once each; the encoder has a float64 evaluation of the same
+formula (encode64), the high-precision yardstick the f32 oracle and the kernels are measured with.
 """
 import numpy as np
 
@@ -127,3 +131,60 @@ def clustering(dist, n, perc):
         ops.append(dict(merge_i=p, merge_j=q, into=k, distance=float(best), operation=op))
         distance = best
     return ops, sorted(set(root(i) for i in range(n))), float(threshold)
+
+
+def variance(frames, k):
+    """spectrogram.rs:174-187 with mean / std of numerics.rs:12-29.  One f32 array operation per reference operation, the
+    frames side by side: every bin is added in order, `powf(v - mu, 2.0)` is the single rounded product (v - mu) * (v - mu)
+    (what the compiler makes of a constant exponent 2), the window is the k values BEFORE frame i, summed oldest first.
+    k = 0 takes the mean of an empty slice: 0 / 0 = NaN in every frame."""
+    f = np.asarray(frames, dtype=F)
+    t, n_bins = f.shape
+    k = int(k)
+    with np.errstate(all="ignore"):
+        mu = np.zeros(t, dtype=F)
+        for c in range(n_bins):
+            mu = mu + f[:, c]                                   # numerics.rs:14-16
+        mu = mu / F(n_bins)                                     # :17
+        sq = np.zeros(t, dtype=F)
+        for c in range(n_bins):
+            d = f[:, c] - mu
+            sq = sq + d * d                                     # :25-27
+        deltas = np.sqrt(sq / F(n_bins))                        # :28
+        out = np.zeros(t, dtype=F)                              # spectrogram.rs:183, i < k
+        if t > k:
+            acc = np.zeros(t - k, dtype=F)
+            for q in range(k):
+                acc = acc + deltas[q:q + t - k]                 # deltas[i - k + q] for i = k .. t-1
+            out[k:] = acc / F(k)
+    assert mu.dtype == F and deltas.dtype == F and out.dtype == F
+    return out
+
+
+def interesting_ranges(frames, k, perc, min_len):
+    """spectrogram.rs:192-216.  Raises IndexError where the reference panics (numerics.rs:132: the index, taken from the
+    unfiltered length, is past the NaN-filtered vector -- an empty sequence, perc = 1, k = 0, too many NaN frames)."""
+    var = variance(frames, k)
+    th = float(percentile(var, perc))                           # :198
+    ranges, start, recording = [], 0, True                      # :200-202
+    for i, v in enumerate(var.tolist()):                        # f32 -> Python float is exact: the comparisons are the f32 ones
+        if v >= th and not recording:                           # :204-207
+            start, recording = i, True
+        if v < th and recording:                                # :208-213
+            recording = False
+            if i - start > min_len:
+                ranges.append((start, i))
+    return ranges
+
+
+def encode64(x, w, b):
+    """neural.rs:55-71 evaluated in float64 on the f32 inputs: x.mul(w).add_col(b).sigmoid().scale(255), then every row
+    z-scored with its own population mean and std, the std floored at 1 (f32::max ignores a NaN operand, as fmax does)."""
+    x = np.asarray(x, dtype=F).astype(np.float64)
+    w = np.asarray(w, dtype=F).astype(np.float64)
+    b = np.asarray(b, dtype=F).astype(np.float64).reshape(1, -1)
+    with np.errstate(all="ignore"):
+        pred = 255.0 * (1.0 / (1.0 + np.exp(-(x @ w + b))))
+        mu = pred.mean(axis=1, keepdims=True)
+        sigma = np.fmax(np.sqrt(((pred - mu) ** 2).mean(axis=1, keepdims=True)), 1.0)
+        return (pred - mu) / sigma

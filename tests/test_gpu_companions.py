@@ -1,9 +1,13 @@
 """GPU parity tests of the feature companions against the CPU oracle.
 
-Encoder (neural.rs:55-71): same arithmetic order; expf differs from libm by <= 2 ulp -> 1e-5 relative.
+Encoder (neural.rs:55-71): same arithmetic order; expf differs from libm by <= 2 ulp -> 1e-5 at the Mat::seeded weight scale
+(the only regime drawn here).
 Cepstrum (spectrogram.rs:31-80): the reference's FFT/DCT come from un-vendored, un-pinned crates (rustfft 3.0.0,
 rustdct *), so this is PARITY UNPINNED against the reference; the oracle evaluates the mathematical definitions in
-f64, the kernel an f32 radix-2 FFT: agreement to 2e-4 absolute on values of magnitude ~1..10."""
+f64, the kernel an f32 packed-real FFT in radix-4 passes (power-of-two windows; the defining sum otherwise): agreement to 2e-4
+absolute on values of magnitude ~1..10.
+The encoder's other weight regimes, its switch edge and grid wraps are in tests/test_gpu_encoder.py, the VAT pre-segmentation's
+edges in tests/test_gpu_vat.py."""
 import os
 
 import numpy as np
