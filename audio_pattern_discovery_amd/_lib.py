@@ -42,6 +42,14 @@ class ClusterOp(C.Structure):
                 ("distance", C.c_float), ("operation", C.c_uint32)]
 
 
+class PathStep(C.Structure):
+    """apd_path_step: one cell of a warping path -- the reference's 1-based table indices, the bits of sparse[(i, j)], the branch."""
+    _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("cost", C.c_float), ("op", C.c_uint32)]
+
+
+APD_PATH_MATCH, APD_PATH_INSERT, APD_PATH_DELETE, APD_PATH_START = 0, 1, 2, 3
+
+
 class MatView(C.Structure):
     """apd_mat_view: where a Mat { flat, cols } (numerics.rs:171-174) lies in a bincode image."""
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64), ("cols", C.c_uint64)]
@@ -140,6 +148,11 @@ SYMBOLS = [
                                  _u64p, _u64p, _u64p]),
     ("apd_align_pair", C.c_int, [_vp, _f32p, C.c_uint64, _f32p, C.c_uint64, C.c_uint32,
                                  C.POINTER(AlignmentParamsC), _f32p]),
+    ("apd_path_bound", C.c_uint64, [C.c_uint64, C.c_uint64]),
+    ("apd_align_paths", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p,
+                                  _u32p, _f32p]),
+    ("apd_align_pair_path", C.c_int, [_vp, _f32p, C.c_uint64, _f32p, C.c_uint64, C.c_uint32, C.POINTER(AlignmentParamsC),
+                                      C.POINTER(PathStep), C.c_uint64, _u64p, _f32p]),
     ("apd_percentile", C.c_int, [_vp, _vp, C.c_uint64, C.c_float, C.c_int, _f32p]),
     ("apd_clustering", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_float, C.POINTER(ClusterOp), _u32p, _u32p,
                                  _u32p, _f32p]),

@@ -88,17 +88,23 @@ class AlignmentParams:
         return AlignmentParams(int(length), 1.0, 1.0, 1.0)
 
 
+# apd_path_step as a numpy record: what Alignment.path() and AlignmentWorkers.paths() return
+PATH_STEP = np.dtype([("i", np.uint32), ("j", np.uint32), ("cost", np.float32), ("op", np.uint32)])
+
+
 class Alignment:
-    """alignments.rs:99-181.  `sparse` (the DP table) is never read by any caller of the reference
-    (only score() is), so it is not materialised; construct_alignment runs the HIP kernel."""
+    """alignments.rs:99-181.  construct_alignment runs the HIP kernel.  The DP table `sparse` is not materialised as a whole; with
+    `path=True` the cells a reader of `sparse` walks back through from the score cell (n-1, m-1) are kept, with their table
+    values and branches: path() (include/apd.h, "warping paths")."""
 
     def __init__(self, ctx=None):           # Alignment::new, :107-111
         self.n = 0
         self.m = 0
         self._score = float("inf")
         self._ctx = ctx
+        self._path = None
 
-    def construct_alignment(self, x, y, params):     # :165-180
+    def construct_alignment(self, x, y, params, path=False):     # :165-180
         ctx = self._ctx or _lib.default_context()
         xs = np.ascontiguousarray(x.frames if isinstance(x, NDSequence) else x, dtype=np.float32)
         ys = np.ascontiguousarray(y.frames if isinstance(y, NDSequence) else y, dtype=np.float32)
@@ -107,15 +113,33 @@ class Alignment:
         p = _lib.AlignmentParamsC(int(params.warping_band), params.insertion_penalty,
                                   params.deletion_penalty, params.match_penalty)
         out = C.c_float(0)
-        _lib.check(_lib.lib().apd_align_pair(ctx.handle, xs.ctypes.data_as(C.POINTER(C.c_float)), self.n,
-                                             ys.ctypes.data_as(C.POINTER(C.c_float)), self.m, int(dim),
-                                             C.byref(p), C.byref(out)), ctx.handle)
+        self._path = None
+        if path:
+            L = _lib.lib()
+            steps = np.zeros(int(L.apd_path_bound(self.n, self.m)), dtype=PATH_STEP)
+            used = C.c_uint64(0)
+            _lib.check(L.apd_align_pair_path(ctx.handle, xs.ctypes.data_as(C.POINTER(C.c_float)), self.n,
+                                             ys.ctypes.data_as(C.POINTER(C.c_float)), self.m, int(dim), C.byref(p),
+                                             steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), C.byref(used),
+                                             C.byref(out)), ctx.handle)
+            self._path = steps[:used.value].copy()
+        else:
+            _lib.check(_lib.lib().apd_align_pair(ctx.handle, xs.ctypes.data_as(C.POINTER(C.c_float)), self.n,
+                                                 ys.ctypes.data_as(C.POINTER(C.c_float)), self.m, int(dim),
+                                                 C.byref(p), C.byref(out)), ctx.handle)
         self._score = float(out.value)
 
     def score(self):                        # :116-125
         if self.n == 0 and self.m == 0:
             return float("inf")
         return self._score
+
+    def path(self):
+        """The warping path of the last construct_alignment(..., path=True): a PATH_STEP array, origin first, end cell
+        (n-1, m-1) last; empty when the score cell is absent."""
+        if self._path is None:
+            raise ValueError("construct_alignment(..., path=True) has not run")
+        return self._path
 
 
 class Batch:
@@ -189,6 +213,27 @@ class AlignmentWorkers:
         _lib.check(_lib.lib().apd_align_all(self.ctx.handle, self._batch.handle, C.byref(cfg),
                                             self.result.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
         return self.result
+
+    def paths(self, pairs, params):
+        """Warping paths of the ordered pairs `pairs` ([(x, y), ...] in this object's sequence numbers; repeats and x == y
+        allowed), params: Discovery.  Returns (list of PATH_STEP arrays in input order, float32 scores): apd_align_paths."""
+        if self._multi is not None:
+            raise ValueError("paths() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_pairs = len(pr)
+        L = _lib.lib()
+        off = np.zeros(n_pairs + 1, dtype=np.uint64)
+        lens = np.zeros(n_pairs, dtype=np.uint32)
+        scores = np.zeros(n_pairs, dtype=np.float32)
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        _lib.check(L.apd_align_paths(self.ctx.handle, self._batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs, None, 0,
+                                     off.ctypes.data_as(u64p), None, None), self.ctx.handle)
+        steps = np.zeros(max(int(off[-1]), 1), dtype=PATH_STEP)
+        _lib.check(L.apd_align_paths(self.ctx.handle, self._batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs,
+                                     steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), off.ctypes.data_as(u64p),
+                                     lens.ctypes.data_as(u32p), scores.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
+        return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_pairs)], scores
 
     def close(self):
         """Releases the GPU side (the reference's Drop of the Arcs)."""

@@ -164,6 +164,8 @@ extern "C" int apd_destroy(apd_context *ctx)
     if (ctx->ws_slab) hipFree(ctx->ws_slab);
     if (ctx->ws_misc) hipFree(ctx->ws_misc);
     if (ctx->ws_gather) hipFree(ctx->ws_gather);
+    if (ctx->ws_path_dirs) hipFree(ctx->ws_path_dirs);
+    if (ctx->ws_path_steps) hipFree(ctx->ws_path_steps);
     if (ctx->d_status) hipFree(ctx->d_status);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -725,13 +727,9 @@ extern "C" int apd_align_all(apd_context *ctx, const apd_batch *batch, const apd
     return rc;
 }
 
-extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
-                              const apd_alignment_params *params, float *score)
+// The context's two-sequence batch holding (x, y): sequence 0 = x, sequence 1 = y.
+static int prepare_pair_batch(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim)
 {
-    if (!ctx || !params || !score || dim == 0) return APD_ERR_INVALID_ARG;
-    if (n == 0 && m == 0) { *score = INFINITY; return APD_OK; }           // alignments.rs:117-118
-    if (n == 0 || m == 0) return APD_ERR_EMPTY_SEQUENCE;                  // usize underflow at :120
-    if (!x || !y) return APD_ERR_INVALID_ARG;
     std::vector<float> frames((n + m) * (size_t)dim);
     std::memcpy(frames.data(), x, n * (size_t)dim * sizeof(float));
     std::memcpy(frames.data() + n * (size_t)dim, y, m * (size_t)dim * sizeof(float));
@@ -749,11 +747,29 @@ extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, cons
         rc = apd_batch_refill(ctx, ctx->pair_batch, frames.data(), 0);   // host frames: the refill has consumed them when it returns
         if (rc) return rc;
     }
-    apd_batch *b = ctx->pair_batch;
+    return APD_OK;
+}
+
+static BandSpec band_from_params(const apd_alignment_params *params)
+{
     BandSpec band{};
     band.use_explicit = 1;
     band.explicit_band = params->warping_band > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)params->warping_band;
     band.ins = params->insertion_penalty; band.del = params->deletion_penalty; band.mat = params->match_penalty;
+    return band;
+}
+
+extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
+                              const apd_alignment_params *params, float *score)
+{
+    if (!ctx || !params || !score || dim == 0) return APD_ERR_INVALID_ARG;
+    if (n == 0 && m == 0) { *score = INFINITY; return APD_OK; }           // alignments.rs:117-118
+    if (n == 0 || m == 0) return APD_ERR_EMPTY_SEQUENCE;                  // usize underflow at :120
+    if (!x || !y) return APD_ERR_INVALID_ARG;
+    int rc = prepare_pair_batch(ctx, x, n, y, m, dim);
+    if (rc) return rc;
+    apd_batch *b = ctx->pair_batch;
+    const BandSpec band = band_from_params(params);
     rc = ensure_ws(ctx, &ctx->ws_misc, &ctx->ws_misc_bytes, 256);
     if (rc) return rc;
     float *d_out = (float *)ctx->ws_misc;
@@ -765,6 +781,130 @@ extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, cons
         else rc = sync_and_report(ctx);
     }
     if (rc == APD_OK) *score = host[1];                                   // out[0*2+1] = score(x, y)
+    return rc;
+}
+
+// --------------------------------------------------------------------------------- warping paths
+
+extern "C" uint64_t apd_path_bound(uint64_t n, uint64_t m) { return (n == 0 || m == 0) ? 0 : n + m - 1; }
+
+// Cap of the direction workspace of one chunk of pairs (bytes); also bounds the chunk's step buffer.
+static uint64_t path_workspace_cap()
+{
+    if (const char *v = std::getenv("APD_PATH_WORKSPACE_BYTES")) {
+        const unsigned long long b = std::strtoull(v, nullptr, 10);
+        if (b > 0) return b;
+    }
+    return 1ull << 30;
+}
+
+// The sweep and the trace (dtw_path.hip) over `pairs`, in chunks whose direction words stay under the cap.
+static int align_paths_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, const uint32_t *pairs, uint64_t n_pairs,
+                            apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len, float *scores)
+{
+    if (!ctx || !batch || batch->ctx != ctx || !step_off || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
+    const uint32_t n_seq = batch->n_seq;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    step_off[0] = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) step_off[p + 1] = step_off[p] + apd_path_bound(len_of(pairs[2 * p]), len_of(pairs[2 * p + 1]));
+    if (!steps) return APD_OK;                                            // sizes only
+    if (capacity < step_off[n_pairs] || (n_pairs && !path_len)) return APD_ERR_INVALID_ARG;
+    if (n_pairs == 0) return APD_OK;
+    std::vector<PathPair> desc(n_pairs);
+    std::vector<uint64_t> dir_words(n_pairs);
+    std::vector<uint32_t> cells(n_pairs);
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint32_t n = len_of(pairs[2 * p]), m = len_of(pairs[2 * p + 1]);
+        const uint32_t w = host_w(band, n, m);
+        if (2ull * w + 1 > kPathMaxOffsets) { ctx->last_error = "band too wide for the path sweep"; return APD_ERR_BAND_TOO_WIDE; }
+        desc[p].px = pos[pairs[2 * p]];
+        desc[p].py = pos[pairs[2 * p + 1]];
+        dir_words[p] = path_dir_words(n, m, w);
+        cells[p] = path_cells_per_lane(w);
+    }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "path launch");
+    const uint64_t cap = path_workspace_cap();
+    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // 64 work-items per pair, launches stay below 2^31
+    std::vector<float> score_sink;
+    if (!scores) score_sink.resize(n_pairs);
+    float *h_scores = scores ? scores : score_sink.data();
+    bool first_chunk = true;
+    for (uint64_t first = 0; first < n_pairs;) {
+        // the chunk [first, last): at least one pair, then as many as keep the direction words and the steps under the cap
+        uint64_t last = first, words = 0, slots = 0;
+        uint32_t c_max = 2;
+        while (last < n_pairs && last - first < kMaxPairsPerLaunch) {
+            const uint64_t nw = words + dir_words[last], ns = slots + (step_off[last + 1] - step_off[last]);
+            if (last > first && (nw * sizeof(uint32_t) > cap || ns * sizeof(apd_path_step) > cap)) break;
+            desc[last].dir_off = words;
+            desc[last].step_off = slots;
+            words = nw; slots = ns;
+            c_max = std::max(c_max, cells[last]);
+            ++last;
+        }
+        const uint64_t np = last - first;
+        // steps workspace: [steps | pair descriptors | lengths | scores]
+        const size_t steps_bytes = (size_t)slots * sizeof(apd_path_step), desc_bytes = (size_t)np * sizeof(PathPair);
+        rc = ensure_ws(ctx, &ctx->ws_path_dirs, &ctx->ws_path_dirs_bytes, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
+        if (rc) return rc;
+        rc = ensure_ws(ctx, &ctx->ws_path_steps, &ctx->ws_path_steps_bytes, steps_bytes + desc_bytes + (size_t)np * 8 + 16);
+        if (rc) return rc;
+        char *base = (char *)ctx->ws_path_steps;
+        PathLaunch L{};
+        L.d_frames = batch->d_frames; L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
+        L.d_pairs = (const PathPair *)(base + steps_bytes);
+        L.n_pairs = (uint32_t)np;
+        L.d_dirs = (uint32_t *)ctx->ws_path_dirs;
+        L.d_steps = (apd_path_step *)base;
+        L.d_len = (uint32_t *)(base + steps_bytes + desc_bytes);
+        L.d_scores = (float *)(base + steps_bytes + desc_bytes + (size_t)np * 4);
+        HIP_TRY(ctx, hipMemcpyAsync((void *)L.d_pairs, desc.data() + first, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        HIP_TRY(ctx, launch_path_sweep(L, c_max, ctx->stream));
+        HIP_TRY(ctx, launch_path_trace(L, ctx->stream));
+        if (ctx->timing && last == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        if (slots) HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(path_len + first, L.d_len, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_scores + first, L.d_scores, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspaces
+        first = last;
+        first_chunk = false;
+    }
+    return APD_OK;
+}
+
+extern "C" int apd_align_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs,
+                               uint64_t n_pairs, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
+                               float *scores)
+{
+    if (!ctx || !batch || !cfg) return APD_ERR_INVALID_ARG;
+    return align_paths_impl(ctx, batch, band_from_cfg(cfg), pairs, n_pairs, steps, capacity, step_off, path_len, scores);
+}
+
+extern "C" int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
+                                   const apd_alignment_params *params, apd_path_step *steps, uint64_t capacity, uint64_t *n_steps,
+                                   float *score)
+{
+    if (!ctx || !params || !n_steps || !score || dim == 0) return APD_ERR_INVALID_ARG;
+    if (n == 0 && m == 0) { *n_steps = 0; *score = INFINITY; return APD_OK; }   // alignments.rs:117-118
+    if (n == 0 || m == 0) return APD_ERR_EMPTY_SEQUENCE;                  // usize underflow at :120
+    if (!x || !y) return APD_ERR_INVALID_ARG;
+    if (!steps) { *n_steps = apd_path_bound(n, m); return APD_OK; }
+    if (capacity < apd_path_bound(n, m)) return APD_ERR_INVALID_ARG;
+    int rc = prepare_pair_batch(ctx, x, n, y, m, dim);
+    if (rc) return rc;
+    const uint32_t pair[2] = {0, 1};
+    uint64_t off[2] = {0, 0};
+    uint32_t len = 0;
+    rc = align_paths_impl(ctx, ctx->pair_batch, band_from_params(params), pair, 1, steps, capacity, off, &len, score);
+    if (rc == APD_OK) *n_steps = len;
     return rc;
 }
 

@@ -199,6 +199,37 @@ constexpr uint64_t strip_lds_bytes(uint32_t dim, uint32_t ppw, bool banded, uint
     return 4 * ((ppw == 1 ? 128 : 64) * dp + (uint64_t)ppw * (banded ? 2 : 1) * (rows + 4) + 16);
 }
 
+// ---- warping paths (dtw_path.hip): one ordered pair per wavefront, a sweep that records every cell's branch and a trace.
+constexpr uint32_t kPathMaxOffsets = 20480;   // 2w + 1 beyond this: the sweep's DP row does not fit in LDS (the literal kernel's limit)
+// band offsets per lane of the sweep, as generic_pair chooses them
+__host__ __device__ constexpr uint32_t path_cells_per_lane(uint32_t w) { return (2 * w + 1 + 63) / 64 < 2 ? 2u : (2 * w + 1 + 63) / 64; }
+// direction words of a pair of n x m frames with half-width w: 2 bits per cell, ceil(C / 16) words per (macro-step, lane), n + 63
+// macro-steps (rows 1 .. n-1 on 64 lanes); none when either length is 1 (nothing is swept)
+inline uint64_t path_dir_words(uint32_t n, uint32_t m, uint32_t w)
+{
+    if (n < 2 || m < 2) return 0;
+    return ((uint64_t)n + 63) * ((path_cells_per_lane(w) + 15) / 16) * 64;
+}
+struct PathPair {
+    uint32_t px, py;       // resident positions of x and y
+    uint64_t dir_off;      // first direction word of the pair in d_dirs
+    uint64_t step_off;     // first step slot of the pair in d_steps
+};
+struct PathLaunch {
+    const float *d_frames;
+    const uint32_t *d_seq_off;
+    uint32_t dim, dpad;
+    BandSpec band;
+    const PathPair *d_pairs;
+    uint32_t n_pairs;
+    uint32_t *d_dirs;
+    apd_path_step *d_steps;
+    uint32_t *d_len;       // [n_pairs] steps used
+    float *d_scores;       // [n_pairs]
+};
+hipError_t launch_path_sweep(const PathLaunch &L, uint32_t c_max, hipStream_t stream);
+hipError_t launch_path_trace(const PathLaunch &L, hipStream_t stream);
+
 // One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
 hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);
 // The generic kernel over ALL tiles of L as a small persistent grid that does nothing unless *L.d_nonfinite is set.
@@ -323,6 +354,8 @@ struct apd_context {
     void *ws_slab = nullptr; size_t ws_slab_bytes = 0;
     void *ws_misc = nullptr; size_t ws_misc_bytes = 0;
     void *ws_gather = nullptr; size_t ws_gather_bytes = 0;   // gathered slabs of apd_align_all_sharded_async
+    void *ws_path_dirs = nullptr; size_t ws_path_dirs_bytes = 0;     // apd_align_paths: direction words of a chunk of pairs
+    void *ws_path_steps = nullptr; size_t ws_path_steps_bytes = 0;   // ... its steps, then [pairs | lengths | scores]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

@@ -102,25 +102,45 @@ thread_local! {
     };
 }
 
-/// alignments.rs:99-104.  `sparse` stays in the struct for source compatibility but is never filled: no caller of the
-/// reference reads it (only score() is used), and the DP table never leaves the GPU's registers.
+/// One cell of a warping path (apd_path_step): the reference's 1-based table indices, sparse[(i, j)], the branch taken.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct PathStep {
+    pub i: usize,
+    pub j: usize,
+    pub cost: f32,
+    pub op: PathOp,
+}
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum PathOp { Match, Insert, Delete, Start }
+
+/// alignments.rs:99-104.  `sparse` holds (0, 0) -> 0.0 from new() on, as in the reference, and after construct_alignment the
+/// cells of the warping path -- the cells a reader of the reference's table meets walking back from the score cell (n-1, m-1) --
+/// keyed as the reference keys them, with the table's values.  The cells off the path never leave the GPU.
 #[derive(Debug)]
 pub struct Alignment {
     pub n: usize,
     pub m: usize,
     pub sparse: HashMap<(usize, usize), f32>,
     score: f32,
+    path: Vec<PathStep>,
 }
 
 impl Alignment {
     /// alignments.rs:107-111
     pub fn new() -> Alignment {
-        Alignment { n: 0, m: 0, sparse: HashMap::new(), score: std::f32::INFINITY }
+        let mut sparse = HashMap::new();
+        sparse.insert((0, 0), 0.0);
+        Alignment { n: 0, m: 0, sparse, score: std::f32::INFINITY, path: Vec::new() }
     }
 
     /// alignments.rs:116-125: INF for two empty sequences, else D[n-1][m-1] / (n + m) (INF if that cell was never visited).
     pub fn score(&self) -> f32 {
         if self.n == 0 && self.m == 0 { std::f32::INFINITY } else { self.score }
+    }
+
+    /// The warping path of the last construct_alignment, origin first, end cell (n-1, m-1) last; empty if that cell is absent.
+    pub fn path(&self) -> &[PathStep] {
+        &self.path
     }
 
     /// alignments.rs:165-180
@@ -129,8 +149,18 @@ impl Alignment {
         self.m = y.len();
         let p = apd_alignment_params { warping_band: params.warping_band as u64, insertion_penalty: params.insertion_penalty,
                                        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty };
+        let bound = unsafe { apd_path_bound(self.n as u64, self.m as u64) } as usize;
+        let mut steps = vec![apd_path_step { i: 0, j: 0, cost: 0.0, op: 0 }; bound.max(1)];
+        let mut used: u64 = 0;
         PAIR_CTX.with(|ctx| unsafe {
-            check(apd_align_pair(*ctx, x.frames.as_ptr(), self.n as u64, y.frames.as_ptr(), self.m as u64, x.n_bins as u32, &p, &mut self.score));
+            check(apd_align_pair_path(*ctx, x.frames.as_ptr(), self.n as u64, y.frames.as_ptr(), self.m as u64, x.n_bins as u32, &p, steps.as_mut_ptr(), steps.len() as u64, &mut used, &mut self.score));
         });
+        self.path = steps[..used as usize].iter().map(|s| PathStep {
+            i: s.i as usize, j: s.j as usize, cost: s.cost,
+            op: match s.op { APD_PATH_INSERT => PathOp::Insert, APD_PATH_DELETE => PathOp::Delete, APD_PATH_START => PathOp::Start, _ => PathOp::Match },
+        }).collect();
+        self.sparse.clear();
+        self.sparse.insert((0, 0), 0.0);
+        for s in &self.path { self.sparse.insert((s.i, s.j), s.cost); }
     }
 }

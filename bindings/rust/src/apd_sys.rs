@@ -43,6 +43,19 @@ pub struct apd_alignment_params {
     pub match_penalty: f32,
 }
 
+/// One cell of a warping path: 1-based table indices, the bits of sparse[(i, j)], the branch (APD_PATH_*).
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct apd_path_step {
+    pub i: u32,
+    pub j: u32,
+    pub cost: f32,
+    pub op: u32,
+}
+pub const APD_PATH_MATCH: u32 = 0;
+pub const APD_PATH_INSERT: u32 = 1;
+pub const APD_PATH_DELETE: u32 = 2;
+pub const APD_PATH_START: u32 = 3;
+
 /// ClusteringOperation (clustering.rs:19-25); operation: 0 S2S, 1 S2C, 2 C2S, 3 C2C (clustering.rs:8-13).
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct apd_cluster_op {
@@ -154,6 +167,13 @@ extern "C" {
     // Alignment (alignments.rs:107-180)
     pub fn apd_align_pair(ctx: *mut apd_context, x: *const f32, n: u64, y: *const f32, m: u64, dim: u32,
                           params: *const apd_alignment_params, score: *mut f32) -> c_int;
+    pub fn apd_path_bound(n: u64, m: u64) -> u64;
+    pub fn apd_align_paths(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, pairs: *const u32,
+                           n_pairs: u64, steps: *mut apd_path_step, capacity: u64, step_off: *mut u64, path_len: *mut u32,
+                           scores: *mut f32) -> c_int;
+    pub fn apd_align_pair_path(ctx: *mut apd_context, x: *const f32, n: u64, y: *const f32, m: u64, dim: u32,
+                               params: *const apd_alignment_params, steps: *mut apd_path_step, capacity: u64, n_steps: *mut u64,
+                               score: *mut f32) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

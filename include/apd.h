@@ -319,6 +319,54 @@ int apd_align_work(const uint64_t *offsets, uint32_t n_seq, uint32_t dim, const 
 int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
                    const apd_alignment_params *params, float *score);
 
+/* ---- warping paths: the alignment information of Alignment.sparse (src/alignments.rs:99-111,165-180) ----------------
+ * The reference's one public result besides the score is its DP table; what a caller does with it is walk back from the score
+ * cell (n-1, m-1) (alignments.rs:120) to see which frames were matched to which.  These two calls return that walk for a
+ * caller-chosen list of ORDERED pairs of a resident batch, and for a single pair, backtracked on the GPU.
+ * Table: sparse[(0,0)] = 0; cells (i, j), 1 <= i <= n, max(i-w, 1) <= j < min(i+w, m+1), w = max(band, |n-m|) + 2; every other
+ * cell is absent and reads as +INF.  Each cell remembers the branch alignments.rs:153-159 took: DELETE (from (i, j-1)) if
+ * del < match && del < ins, INSERT (from (i-1, j)) if ins < match && ins < del, MATCH (from (i-1, j-1)) otherwise -- so an exact
+ * DELETE / INSERT tie takes MATCH even when MATCH is larger, and so does a NaN (compares false) and an all-INF node.
+ * Walk: from (n-1, m-1); if that cell is absent (exactly one of n, m is 1) the path is empty and the score +INF; at (0,0) emit
+ * START and stop; else emit the cell with its branch and move to that branch's predecessor, stopping if it is absent (row 0 /
+ * column 0 other than the origin, outside the band).  A finite end cell always leads back to (0,0); only NaN / INF tables end
+ * early.  The path is reported origin first, end cell last, at most n + m - 1 steps; n = m = 1 gives the single step
+ * (0, 0, 0.0, START) and score 0.  i, j are the reference's 1-based table indices (the cell compares x[i-1] with y[j-1]); cost
+ * holds the bits of sparse[(i,j)]; score = cost of the last step / (n + m) as f32 (alignments.rs:121).
+ * Arithmetic: ALWAYS the literal one (numerics.rs:114-120, alignments.rs:153-159 operation for operation: every difference,
+ * square and partial sum rounded on its own, correctly rounded square root, pen * d rounded, then added), whatever
+ * apd_set_distance_mode says -- a path that disagrees with its own costs by an ulp is useless.  The score is therefore
+ * bit-identical to the strict-mode (mode 2) matrix entry and to the CPU code; a default-mode (mode 1) matrix entry may differ
+ * from it within that mode's documented 1e-4.  A batch outside the fast feature range (apd_batch_nonfinite) needs no special
+ * routing here: NaN, infinite, overflowing and subnormal distances come out as on the CPU (NaN payloads aside). */
+enum { APD_PATH_MATCH = 0, APD_PATH_INSERT = 1, APD_PATH_DELETE = 2, APD_PATH_START = 3 };
+typedef struct apd_path_step {
+    uint32_t i, j;
+    float cost;
+    uint32_t op;
+} apd_path_step;   /* 16 bytes */
+/* Step slots a pair of n x m frames owns: n + m - 1, 0 if either is 0.  Host only. */
+uint64_t apd_path_bound(uint64_t n, uint64_t m);
+/* pairs: [n_pairs][2] = (x, y) in the CALLER's sequence numbers; any order, repeats and x == y allowed; results in input order.
+ * step_off (n_pairs + 1, always written, no GPU work needed for it): path p owns steps[step_off[p] .. step_off[p+1]),
+ *   step_off[p+1] - step_off[p] = apd_path_bound(len x, len y); path_len[p] of those slots are used, the others are zeroed.
+ * steps == NULL: sizes only.  capacity (in steps) < step_off[n_pairs]: APD_ERR_INVALID_ARG.  scores may be NULL.  A pair index
+ * >= the batch's sequence count is APD_ERR_INVALID_ARG, an empty sequence in the batch APD_ERR_EMPTY_SEQUENCE, a pair whose band
+ * needs 2w+1 > 20 480 offsets APD_ERR_BAND_TOO_WIDE (the literal kernel's limit), each before anything is launched.  Follows
+ * apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the two kernels of the call (all chunks).
+ * Workspace: 2 bits per swept cell in words of 16 cells per lane, (len x + 63) * ceil(C / 16) * 256 bytes per pair with
+ * C = max(ceil((2w+1) / 64), 2); a long list is cut into chunks that keep it under 1 GiB (APD_PATH_WORKSPACE_BYTES overrides
+ * the cap: tests only), results identical. */
+int apd_align_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs,
+                    uint64_t n_pairs, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
+                    float *scores);
+/* Alignment::construct_alignment with its alignment information: explicit band, host frames, as apd_align_pair (whose
+ * two-sequence batch it shares).  *n_steps = steps used (steps == NULL: apd_path_bound(n, m), nothing computed); capacity <
+ * apd_path_bound(n, m) is APD_ERR_INVALID_ARG.  n = m = 0: *n_steps = 0, *score = +INF; one of them 0: APD_ERR_EMPTY_SEQUENCE. */
+int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
+                        const apd_alignment_params *params, apd_path_step *steps, uint64_t capacity, uint64_t *n_steps,
+                        float *score);
+
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */
 int apd_percentile(apd_context *ctx, const float *x, uint64_t len, float perc, int x_on_device, float *value);

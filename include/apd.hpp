@@ -2,6 +2,7 @@
 // of apd.h.  Names and argument meaning follow the Rust items (file:line cited at each); the compute is libapd_hip.so.
 // Errors that are panics in the reference (zero-length sequence, percentile index out of range) throw apd::Error.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <fstream>
 #include <iterator>
@@ -154,22 +155,35 @@ struct Discovery {
     }
 };
 
-// alignments.rs:99-181.  `sparse` is never read outside the struct in the reference, so it is not materialised.
+// alignments.rs:99-181.  `sparse` is not materialised as a whole; path() returns the cells a reader of the table meets walking
+// back from the score cell (n-1, m-1), with their table values and branches (apd.h, "warping paths").
 class Alignment {
   public:
     explicit Alignment(Context &ctx) : ctx_(ctx) {}                                  // Alignment::new, :107-111
     std::size_t n = 0, m = 0;
-    void construct_alignment(const NDSequence &x, const NDSequence &y, const AlignmentParams &p)   // :165-180
+    void construct_alignment(const NDSequence &x, const NDSequence &y, const AlignmentParams &p, bool with_path = false)   // :165-180
     {
         n = x.len(); m = y.len();
         const apd_alignment_params cp{(uint64_t)p.warping_band, p.insertion_penalty, p.deletion_penalty, p.match_penalty};
         const uint32_t dim = (uint32_t)(x.n_bins ? x.n_bins : y.n_bins);
-        check(apd_align_pair(ctx_.get(), x.frames.data(), n, y.frames.data(), m, dim, &cp, &score_), ctx_.get());
+        path_.clear();
+        if (!with_path) {
+            check(apd_align_pair(ctx_.get(), x.frames.data(), n, y.frames.data(), m, dim, &cp, &score_), ctx_.get());
+            return;
+        }
+        path_.resize(std::max<uint64_t>(apd_path_bound(n, m), 1));
+        uint64_t used = 0;
+        check(apd_align_pair_path(ctx_.get(), x.frames.data(), n, y.frames.data(), m, dim, &cp, path_.data(), path_.size(), &used, &score_),
+              ctx_.get());
+        path_.resize(used);
     }
     float score() const { return (n == 0 && m == 0) ? std::numeric_limits<float>::infinity() : score_; }   // :116-125
+    // the warping path of the last construct_alignment(.., with_path = true): origin first, end cell last
+    const std::vector<apd_path_step> &path() const { return path_; }
   private:
     Context &ctx_;
     float score_ = std::numeric_limits<float>::infinity();
+    std::vector<apd_path_step> path_;
 };
 
 // alignments.rs:11-68
