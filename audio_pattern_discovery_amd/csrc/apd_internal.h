@@ -156,8 +156,26 @@ constexpr bool geoms_round_trip(const KernelGeom (&list)[N])
 static_assert(geoms_round_trip(kSystolicGeoms) && geoms_round_trip(kWideGeoms) && geoms_round_trip(kStripGeoms) &&
                   geoms_round_trip(kBandedStripGeoms) && geoms_round_trip(kSharedColumnGeoms), "a listed geometry has no integer code of its own");
 
+// ---- sweep bounds of the systolic kernels (dtw_systolic.h, both of them).  Lane gl of a pair owns the band offsets C gl .. C gl + C - 1
+// and sweeps row tau - gl in macro-step tau.  The result cell (rows - 1, cols - 1) has band offset u* = (cols - 1) - (rows - 1) + w
+// (2 <= u* <= 2w - 2: w >= |rows - cols| + 2), lives in lane u* / C and is final once that lane has swept row rows - 1: nothing a
+// later macro-step computes can reach it, so a pair needs sweep_steps_needed macro-steps, not the (rows - 1) + ceil((2w + 1) / C)
+// that run every lane of the band through the last row.
+__host__ __device__ constexpr int sweep_result_offset(int rows, int cols, int w) { return (cols - 1) - (rows - 1) + w; }
+__host__ __device__ constexpr int sweep_capture_step(int rows, int cols, int w, int c)
+{
+    return (rows - 1) + sweep_result_offset(rows, cols, w) / c;
+}
+__host__ __device__ constexpr int sweep_steps_needed(int rows, int cols, int w, int c) { return sweep_capture_step(rows, cols, w, c) + 1; }
+static_assert(sweep_result_offset(1000, 1024, 66) == 90 && sweep_capture_step(1000, 1024, 66, 9) == 1009 &&
+                  sweep_steps_needed(1000, 1024, 66, 9) == 1010, "cfg 3's shape, rows the shorter sequence: lane 10 ends the sweep");
+static_assert(sweep_steps_needed(1024, 1000, 66, 9) == 1028, "the same pair with the longer sequence as rows: u* = 42, lane 4");
+static_assert(sweep_capture_step(40, 72, 34, 9) == 39 + 7 && (2 * 34 + 1 + 8) / 9 == 8,
+              "|n - m| = w - 2: u* = 2w - 2 sits in the last active lane, nothing is cut at the end");
+static_assert(sweep_steps_needed(2, 2, 2, 2) == 3 && sweep_steps_needed(72, 40, 34, 9) == 72, "smallest pair; u* = 2: lane 0");
+
 // ---- shared column rings (dtw_systolic.h, dtw_fused_systolic_shared).  A workgroup sweeps a 4 x 4 sub-block of a tile: wavefront k
-// row sequence a_k, its four lane groups the columns b_0 .. b_3, which the four wavefronts read from one LDS ring per b.
+// row sequence b_k, its four lane groups the columns a_0 .. a_3, which the four wavefronts read from one LDS ring per a.
 // A macro-step block is U steps (the kernel's unroll); during one, the G lanes of the pairs of the workgroup read columns
 // spanning (G - 1)(C - 1) + U + (largest - smallest w of the workgroup's swept pairs), and the next block's U columns are
 // written meanwhile.  The ring holds what equal bands need (shared_column_ring_min) and at least 16 frames more, in whole
@@ -173,6 +191,9 @@ constexpr uint32_t shared_column_slack(KernelGeom g)
 inline uint32_t host_w(const BandSpec &b, uint32_t n, uint32_t m);   // below
 // The qualification rule of the tile plan: in every 4 x 4 sub-block of tile (tile_a, tile_b) the swept pairs (a < b < n_seq, both
 // longer than one frame) have bands within `slack` of each other.  lens[s]: frames of resident sequence s.
+// Which sequence of a pair is swept as rows does not enter: a lane's column in macro-step tau is tau - gl + u - w whatever the rows
+// are, so the span of columns a workgroup reads (and the ring span the kernel's static_assert bounds) depends on the pairs' w
+// alone, w is symmetric in (n, m), and a workgroup's pairs are the same 4 x 4 sub-block under either assignment.
 inline bool shared_columns_qualify(const std::vector<uint32_t> &lens, uint32_t tile_a, uint32_t tile_b, const BandSpec &band,
                                    uint32_t slack)
 {

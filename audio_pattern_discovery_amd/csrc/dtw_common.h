@@ -162,19 +162,19 @@ struct PairInfo {
     int n, m, w;
     int slot_a, slot_b;
     uint32_t slab_tile;     // position of the tile in the rank's slab
-    float nmax_b;           // largest squared frame norm of sequence b
+    float nmax_a, nmax_b;   // largest squared frame norm of the sequence at A, at B
     float nmax_ab;          // ... of either sequence (kernels that may take their columns from a or b)
     bool valid;
 };
 
-__device__ __forceinline__ PairInfo decode_pair(const AlignLaunch &L, uint32_t tile, uint32_t slot)
+__device__ __forceinline__ PairInfo decode_pair_at(const AlignLaunch &L, uint32_t tile, uint32_t slot_a, uint32_t slot_b)
 {
     PairInfo p;
-    p.slot_a = slot / kTile;
-    p.slot_b = slot % kTile;
+    p.slot_a = slot_a;
+    p.slot_b = slot_b;
     p.valid = false;
     p.slab_tile = 0;
-    p.nmax_b = 0.0f;
+    p.nmax_a = p.nmax_b = 0.0f;
     p.nmax_ab = 0.0f;
     p.A = p.B = L.d_frames; p.n = p.m = 2; p.w = 2;
     if (tile >= L.n_tiles) return p;
@@ -189,8 +189,32 @@ __device__ __forceinline__ PairInfo decode_pair(const AlignLaunch &L, uint32_t t
     p.A = L.d_frames + (uint64_t)oa * L.dpad;
     p.B = L.d_frames + (uint64_t)ob * L.dpad;
     p.w = pair_w(L.band, p.n, p.m);
+    p.nmax_a = L.d_seq_nmax[a];
     p.nmax_b = L.d_seq_nmax[b];
-    p.nmax_ab = fmaxf(L.d_seq_nmax[a], p.nmax_b);
+    p.nmax_ab = fmaxf(p.nmax_a, p.nmax_b);
+    return p;
+}
+__device__ __forceinline__ PairInfo decode_pair(const AlignLaunch &L, uint32_t tile, uint32_t slot)
+{
+    return decode_pair_at(L, tile, slot / kTile, slot % kTile);
+}
+
+// The systolic kernels sweep b as rows and a as columns: sequences are resident longest first, so b is the shorter of a pair, and
+// the number of macro-steps follows the rows.  `slot_t` is the transposed slot, slot_b * kTile + slot_a (consecutive slots share
+// their b); the pair comes back with A / n / nmax_a naming the ROW sequence b and B / m / nmax_b the COLUMN sequence a, while slot_a,
+// slot_b and the validity rule (a < b) stay the pair's own.  A kernel that computes s_rows = score(x = rows, y = cols) and
+// s_cols = score(x = cols, y = rows) hands them to store_pair_rows_b, which puts each into the plane store_pair would.
+// The scores keep their bits: w and the per-cell recompute test are symmetric, |x|^2 + |y|^2 commutes, (-2 x_k) y_k is the same
+// exact product with either factor scaled, and x_k - y_k becomes its exact negation under a square.
+__device__ __forceinline__ PairInfo decode_pair_rows_b(const AlignLaunch &L, uint32_t tile, uint32_t slot_t)
+{
+    PairInfo p = decode_pair_at(L, tile, slot_t % kTile, slot_t / kTile);
+    const float *const rows = p.B;
+    p.B = p.A; p.A = rows;
+    const int n_rows = p.m;
+    p.m = p.n; p.n = n_rows;
+    const float nmax_rows = p.nmax_b;
+    p.nmax_b = p.nmax_a; p.nmax_a = nmax_rows;
     return p;
 }
 
@@ -199,6 +223,10 @@ __device__ __forceinline__ void store_pair(const AlignLaunch &L, uint32_t, const
     float *slab = L.d_slab + (uint64_t)p.slab_tile * 2 * kSlotsPerTile;
     slab[p.slot_a * kTile + p.slot_b] = s1;                       // score(x=a, y=b)
     slab[kSlotsPerTile + p.slot_a * kTile + p.slot_b] = s2;       // score(x=b, y=a)
+}
+__device__ __forceinline__ void store_pair_rows_b(const AlignLaunch &L, uint32_t tile, const PairInfo &p, float s_rows, float s_cols)
+{
+    store_pair(L, tile, p, s_cols, s_rows);                       // rows are b: score(x=rows, y=cols) is plane 1's
 }
 
 // Host launchers of the kernel families, defined in their headers and instantiated once per frame dimension by dtw_sys.hip,

@@ -5,13 +5,21 @@
 //    band of 2w+1 offsets fills the wave instead of leaving lanes idle (w = 66 -> G = 16, C = 9: 133/144 busy);
 //  * column frames y[j] enter at lane G-1 of a group and move one lane down per macro-step (DPP row/wave shifts),
 //    each lane keeping its C-column window in registers; row frames x[i] (shared by every group of the wave: the
-//    pairs of a wave have the same a) are staged once per wave in a small LDS ring, filled by coalesced 16-byte
+//    pairs of a wave have the same b) are staged once per wave in a small LDS ring, filled by coalesced 16-byte
 //    loads U rows ahead, and read back by every lane (row tau + 1 - gl).  Each frame is fetched from memory once
 //    per wave: the algorithmic minimum 4*D*(n+m) bytes per ordered pair is an upper bound of what the kernel reads;
+//  * the rows are sequence b of the pair (a < b), the columns sequence a (decode_pair_rows_b): sequences are resident longest
+//    first, so b is the shorter one, and a sweep takes as many macro-steps as it has rows, plus the lane of the result cell.
+//    The kernel computes score(x = rows, y = cols) and score(x = cols, y = rows) whichever sequence the rows are, bit for bit
+//    (dtw_common.h), so this is a relabelling; store_pair_rows_b puts each score into its plane;
+//  * the sweep ends with the capture of the result cell, in lane u* / C at macro-step (rows - 1) + u* / C (sweep_steps_needed,
+//    apd_internal.h; the largest of the wave, of the workgroup in the shared-column kernel): the lanes above it would only run
+//    cells of the last rows through that nothing reads;
 //  * no per-cell boundary tests: rows <= 0 use an x frame of -INF, columns <= 0 the +INF sentinel frame stored
 //    behind every sequence, so those cells evaluate to +INF by arithmetic (penalties must be > 0; otherwise the
 //    dispatcher takes the generic kernel); D[0][0] = 0 (alignments.rs:109) is injected and the result cell
-//    (n-1, m-1) (alignments.rs:120) captured only in the first G and last G macro-steps ("slow" phases);
+//    (n-1, m-1) (alignments.rs:120) captured only in the first G and the last macro-steps, from the shortest pair's last row on
+//    ("slow" phases);
 //  * the static band edges (DP1 stops at u = 2w-1, DP2 spans u = 1..2w) are two per-lane scalar masks per offset
 //    OR-ed into the select (see select_node): no vector instruction;
 //  * hybrid distance form (unit penalties): |x|^2 + |y|^2 - 2 x.y with the row frames pre-scaled by -2 when they are staged
@@ -195,8 +203,8 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
     // XCD-aware placement: blocks b and b+8 share an XCD (and its L2); keep a tile's workgroups on one XCD.
     const uint32_t xcd = blockIdx.x & 7u, q = blockIdx.x >> 3;
     const uint32_t tile = (q / WPT) * 8u + xcd;
-    const uint32_t slot = ((q % WPT) * 4u + (threadIdx.x >> 6)) * PPW + lane / G;
-    const PairInfo P = decode_pair(L, tile, slot);
+    const uint32_t slot = ((q % WPT) * 4u + (threadIdx.x >> 6)) * PPW + lane / G;   // transposed: one b, consecutive a
+    const PairInfo P = decode_pair_rows_b(L, tile, slot);         // rows (A, n): sequence b, the shorter; columns (B, m): a
     const bool special = P.valid && (P.n == 1 || P.m == 1);   // absent result cell (alignments.rs:120-123)
     const bool sweep = P.valid && !special;
     if (__ballot(sweep) == 0ull) {
@@ -224,7 +232,7 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
     constexpr int U_ROWS = ((C + 1) % 2 == 0) ? (C + 1) : 2 * (C + 1);
     __shared__ float xring_all[4][(R + U_ROWS) * RS];
     float *const xring = xring_all[threadIdx.x >> 6];
-    // sequence a (and its length) is the same for every sweeping group of the wave
+    // the row sequence b (and its length) is the same for every sweeping group of the wave
     const int lead = __builtin_ctzll(__ballot(sweep));
     const uint32_t a_off_w = __builtin_amdgcn_readlane(a_off, lead);
     const int n_w = __builtin_amdgcn_readlane(n, lead);
@@ -240,13 +248,16 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
         g2[c] = (u == 0) | (u > two_w);           // DP2 spans u in [1, 2w]
     }
     const int cw = w - u0;                        // offset index holding u == w (cell (0,0)) if 0 <= cw < C
-    const int ustar = (m - 1) - (n - 1) + w;      // band offset of the result cell (n-1, m-1)
+    const int ustar = sweep_result_offset(n, m, w);   // band offset of the result cell (n-1, m-1)
     const int cstar = ustar - u0;
     const int tau_cap = (n - 1) + gl;             // macro-step in which this lane sweeps row n-1
 
-    // wave-uniform loop bounds
-    const int g_act = (two_w + 1 + C - 1) / C;
-    int my_total = sweep ? (n - 1) + g_act : 0;
+    // wave-uniform loop bounds: the sweep ends with the last capture of the wave (lane ustar / C at its tau_cap)
+    // (the bound goes through a copy of w the compiler cannot see through: it would otherwise keep this u* / C in a register for
+    // the store at the kernel's end instead of dividing again there, which costs some instantiations a wave per SIMD)
+    int w_bound = w;
+    asm volatile("" : "+v"(w_bound));
+    int my_total = sweep ? sweep_steps_needed(n, m, w_bound, C) : 0;
     int my_min = sweep ? (n - 1) : 0x7fffffff;
     int total = 0, min_rows = 0x7fffffff;
 #pragma unroll
@@ -511,7 +522,7 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
     if (P.valid && gl == (sweep ? ustar / C : 0)) {
         if (sweep) {
             const float denom = (float)(n + m);                  // alignments.rs:121
-            store_pair(L, tile, P, res1 / denom, res2 / denom);
+            store_pair_rows_b(L, tile, P, res1 / denom, res2 / denom);
         } else {
             const float s = (P.n == 1 && P.m == 1) ? 0.0f : APD_INF;
             store_pair(L, tile, P, s, s);
@@ -546,9 +557,9 @@ __device__ __forceinline__ void read_frame_lds(float (&dst)[DN], const float *p)
 constexpr int shared_column_ring_floats(int rc, int u, int dp) { return (((rc + u) * dp + ((rc + u + 7) / 8) * 4) * 4 + 255) / 256 * 64; }
 
 // ---- Shared column rings: the hybrid, unit-penalty kernel with the column window fed from LDS instead of moved by DPP.
-// A workgroup sweeps a 4 x 4 sub-block of its tile instead of a 1 x 16 row: wavefront k the row sequence a_k (one a per wavefront,
-// as above: the row ring and everything that rests on it stay), its four lane groups the columns b_0 .. b_3.  The four
-// wavefronts need the same four column sequences, so the workgroup keeps one ring of RC column frames per b in LDS:
+// A workgroup sweeps a 4 x 4 sub-block of its tile instead of a 16 x 1 column: wavefront k the row sequence b_k (one b per wavefront,
+// as above: the row ring and everything that rests on it stay), its four lane groups the columns a_0 .. a_3.  The four
+// wavefronts need the same four column sequences, so the workgroup keeps one ring of RC column frames per a in LDS:
 //  * wavefront k fills ring k, U columns per unrolled block, with coalesced 16-byte loads (sentinel frame for columns <= 0,
 //    clamped beyond m), stored at the block's end; one barrier per block orders the fills against the reads;
 //  * in each macro-step every lane reads the column entering its window, j = tau + 1 + (C-1)(gl+1) - w, into the dead register
@@ -601,15 +612,16 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaun
     const uint32_t xcd = blockIdx.x & 7u, q = blockIdx.x >> 3;
     const uint32_t tile = (q / WPT) * 8u + xcd;
     const uint32_t sub = q % WPT;                                // 4 x 4 sub-block of the tile
-    const uint32_t slot = ((sub / 4u) * 4u + wave) * kTile + (sub % 4u) * 4u + lane / G;
-    const PairInfo P = decode_pair(L, tile, slot);
+    const uint32_t slot = ((sub % 4u) * 4u + wave) * kTile + (sub / 4u) * 4u + lane / G;   // transposed: b of the wavefront, a of the group
+    const PairInfo P = decode_pair_rows_b(L, tile, slot);         // rows (A, n): sequence b, the shorter; columns (B, m): a
     const bool special = P.valid && (P.n == 1 || P.m == 1);
     const bool sweep = P.valid && !special;
     const int n = sweep ? P.n : 1, m = sweep ? P.m : 1, w = sweep ? P.w : 2;
     const int u0 = C * gl;
     const int two_w = 2 * w;
-    const int g_act = (two_w + 1 + C - 1) / C;
-    int my_total = sweep ? (n - 1) + g_act : 0;
+    int w_bound = w;                                             // opaque copy, as in dtw_fused_systolic
+    asm volatile("" : "+v"(w_bound));
+    int my_total = sweep ? sweep_steps_needed(n, m, w_bound, C) : 0;   // up to this pair's capture
     int my_min = sweep ? (n - 1) : 0x7fffffff;
     int my_w = sweep ? w : 0x7fffffff;
     int total = 0, min_rows = 0x7fffffff, w_lo = 0x7fffffff;
@@ -633,22 +645,22 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaun
     float ins = L.band.ins, del = L.band.del, mat = L.band.mat;
     float tau_thr = L.tau, nmax_b = P.nmax_b;
     asm volatile("" : "+v"(ins), "+v"(del), "+v"(mat), "+v"(tau_thr), "+v"(nmax_b));
-    // sequence a of this wavefront (none: a wavefront that only walks the barriers sweeps the first frame of the batch)
+    // row sequence b of this wavefront (none: a wavefront that only walks the barriers sweeps the first frame of the batch)
     const unsigned long long sweeping = __ballot(sweep);
     const int lead = sweeping ? __builtin_ctzll(sweeping) : 0;
     const uint32_t a_off_w = sweeping ? __builtin_amdgcn_readlane(a_off, lead) : 0u;
     const int n_w = sweeping ? __builtin_amdgcn_readlane(n, lead) : 1;
-    // the column sequence of this wavefront's ring: b_wave of the sub-block, whether or not this wavefront's own pair with it is valid
+    // the column sequence of this wavefront's ring: a_wave of the sub-block, whether or not this wavefront's own pair with it is valid
     uint32_t cb_off = 0u;
     int cm = 0;
     bool cvalid = false;
     {
         const uint4 t = L.d_tiles[tile];                         // total > 0: the tile exists
-        const uint32_t b = t.y * kTile + (sub % 4u) * 4u + wave;
-        if (b < L.n_seq) {
-            const uint32_t ob = L.d_seq_off[b];
-            cm = (int)(L.d_seq_off[b + 1] - ob) - 2;
-            cb_off = ob * L.dpad * 4u;
+        const uint32_t a = t.x * kTile + (sub / 4u) * 4u + wave;
+        if (a < L.n_seq) {
+            const uint32_t oa = L.d_seq_off[a];
+            cm = (int)(L.d_seq_off[a + 1] - oa) - 2;
+            cb_off = oa * L.dpad * 4u;
             cvalid = true;
         }
     }
@@ -661,7 +673,7 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaun
         g2[c] = (u == 0) | (u > two_w);
     }
     const int cw = w - u0;
-    const int ustar = (m - 1) - (n - 1) + w;
+    const int ustar = sweep_result_offset(n, m, w);
     const int cstar = ustar - u0;
     const int tau_cap = (n - 1) + gl;
     // block counts: the workgroup's (every block has one barrier); the phase boundaries stay this wavefront's own
@@ -800,7 +812,7 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaun
     if (P.valid && gl == (sweep ? ustar / C : 0)) {
         if (sweep) {
             const float denom = (float)(n + m);
-            store_pair(L, tile, P, res1 / denom, res2 / denom);
+            store_pair_rows_b(L, tile, P, res1 / denom, res2 / denom);
         } else {
             const float s = (P.n == 1 && P.m == 1) ? 0.0f : APD_INF;
             store_pair(L, tile, P, s, s);

@@ -60,8 +60,8 @@ def fused_pair(A, B, band, ins, dele, mat, G, C):
     prev2 = np.full((G, C), INF, F)
     res1 = np.full(G, np.nan, F)
     res2 = np.full(G, np.nan, F)
-    g_act = (2 * w + 1 + C - 1) // C
-    for tau in range(0, (n - 1) + g_act):
+    ustar = (m - 1) - (n - 1) + w                            # band offset of the result cell, in lane ustar // C
+    for tau in range(0, (n - 1) + ustar // C + 1):           # sweep_steps_needed (csrc/apd_internal.h): up to the capture
         i = tau - lane                                       # row per lane
         left1 = shift_up(prev1[:, C - 1], INF)               # (i, u-1) from lane l-1, previous macro-step
         left2 = shift_up(prev2[:, C - 1], INF)
@@ -95,7 +95,6 @@ def fused_pair(A, B, band, ins, dele, mat, G, C):
                 upr1 = shift_down(r1, INF)                   # (i-1, u+1) of the last offset: lane l+1's fresh c=0
                 upr2 = shift_down(r2, INF)
         prev1, prev2 = cur1, cur2
-    ustar = (m - 1) - (n - 1) + w
     ls = ustar // C
     return F(res1[ls] / F(n + m)), F(res2[ls] / F(n + m))
 
