@@ -160,6 +160,25 @@ class Batch:
                                                self.n_seq, self.dim, int(bool(on_device)), C.byref(self.handle)),
                    ctx.handle)
 
+    @staticmethod
+    def join(first, second):
+        """apd_batch_join: a resident batch holding `first`'s sequences followed by `second`'s (numbers n_first + c), made from the
+        two batches' resident frames on the device.  An ordinary batch for align_all / paths, and what cross() aligns."""
+        if first.ctx is not second.ctx:
+            raise ValueError("join() needs two batches of one context")
+        b = Batch.__new__(Batch)
+        b.ctx, b.dim = first.ctx, first.dim
+        b.handle = C.c_void_p()
+        _lib.check(_lib.lib().apd_batch_join(first.ctx.handle, first.handle, second.handle, C.byref(b.handle)), first.ctx.handle)
+        b.n_seq = first.n_seq + second.n_seq
+        b.n_first = first.n_seq
+        b.offsets = np.concatenate([first.offsets, second.offsets[1:] + first.offsets[-1]]).astype(np.uint64)
+        return b
+
+    def first_len(self):
+        """apd_batch_first_len: sequences of the first set of a joined batch; all of them for a plain one."""
+        return int(_lib.lib().apd_batch_first_len(self.handle))
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.lib().apd_batch_destroy(self.handle)
@@ -234,6 +253,23 @@ class AlignmentWorkers:
                                      steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), off.ctypes.data_as(u64p),
                                      lens.ctypes.data_as(u32p), scores.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_pairs)], scores
+
+    def cross(self, other, params):
+        """Aligns this object's sequences against `other`'s (an AlignmentWorkers of the same context), params: Discovery.  Returns
+        (fs [n1][n2], sf [n2][n1]): fs[q][c] = score(x = self q, y = other c), sf[c][q] = score(x = other c, y = self q):
+        apd_batch_join + apd_align_cross."""
+        if self._multi is not None or other._multi is not None:
+            raise ValueError("cross() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        n1, n2 = len(self.data), len(other.data)
+        fs, sf = np.zeros((n1, n2), dtype=np.float32), np.zeros((n2, n1), dtype=np.float32)
+        joined = Batch.join(self._batch, other._batch)
+        try:
+            _lib.check(_lib.lib().apd_align_cross(self.ctx.handle, joined.handle, C.byref(cfg), fs.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  sf.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
+        finally:
+            joined.close()
+        return fs, sf
 
     def close(self):
         """Releases the GPU side (the reference's Drop of the Arcs)."""

@@ -63,6 +63,29 @@ class AgglomerativeClustering:
         return [members[set_off[s]:set_off[s + 1]].tolist() for s in range(n_sets.value)]
 
 
+def cross_linkage(fs, sf, sets, ctx=None):
+    """apd_cross_linkage: the reference's average linkage (clustering.rs:153-170) between every first-set sequence q and every
+    set of second-set sequence numbers in `sets` (as cluster_sets returns them; any order inside a set), from the cross matrices
+    fs [n1][n2] and sf [n2][n1] of AlignmentWorkers.cross.  Returns (link_fs [n1][len(sets)], link_sf, nearest, nearest_linkage):
+    nearest[q] is the set merge() would pick for q (0xFFFFFFFF if none has a linkage below +INF)."""
+    ctx = ctx or _lib.default_context()
+    fs = np.ascontiguousarray(fs, dtype=np.float32)
+    sf = np.ascontiguousarray(sf, dtype=np.float32)
+    if fs.ndim != 2 or sf.shape != fs.shape[::-1]:
+        raise ValueError("fs must be [n1][n2] and sf [n2][n1]")
+    n1, n2 = fs.shape
+    members = np.array([m for s in sets for m in s], dtype=np.uint32)
+    set_off = np.zeros(len(sets) + 1, dtype=np.uint32)
+    set_off[1:] = np.cumsum([len(s) for s in sets])
+    link_fs, link_sf = np.zeros((n1, len(sets)), np.float32), np.zeros((n1, len(sets)), np.float32)
+    nearest, nearest_linkage = np.zeros(n1, np.uint32), np.zeros(n1, np.float32)
+    u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+    _lib.check(_lib.lib().apd_cross_linkage(ctx.handle, vp(fs.ctypes.data), vp(sf.ctypes.data), 0, n1, n2, members.ctypes.data_as(u32p),
+                                            set_off.ctypes.data_as(u32p), len(sets), vp(link_fs.ctypes.data), vp(link_sf.ctypes.data),
+                                            vp(nearest.ctypes.data), vp(nearest_linkage.ctypes.data)), ctx.handle)
+    return link_fs, link_sf, nearest, nearest_linkage
+
+
 def percentile(x, perc, ctx=None):
     """numerics.rs:125-133 on the GPU (apd_percentile)."""
     ctx = ctx or _lib.default_context()

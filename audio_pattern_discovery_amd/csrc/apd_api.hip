@@ -36,6 +36,23 @@ void rank_tile_list(uint32_t n_seq, uint32_t rank, uint32_t world, std::vector<u
             if (g % world == rank) out.push_back(make_uint2(ta, tb));
 }
 
+// apd_align_cross: the tiles of the pair matrix that hold a pair of the first resident segment (positions below seg0) with one of
+// the second: the full rectangle ta in [0, ceil(seg0 / kTile)) x tb in [seg0 / kTile, ceil(n_seq / kTile)), row-major -- a tile's
+// place in this list is its place in the slab.  ta <= tb throughout, so the kernels' a < b rule holds for every cross pair.
+void cross_tile_list(uint32_t n_seq, uint32_t seg0, std::vector<uint2> &out)
+{
+    out.clear();
+    if (seg0 == 0 || seg0 >= n_seq) return;
+    const uint32_t side = tiles_side(n_seq), rows = tiles_side(seg0), tb0 = seg0 / kTile;
+    for (uint32_t ta = 0; ta < rows; ++ta)
+        for (uint32_t tb = tb0; tb < side; ++tb) out.push_back(make_uint2(ta, tb));
+}
+uint64_t cross_num_tiles(uint32_t n_seq, uint32_t seg0)
+{
+    if (seg0 == 0 || seg0 >= n_seq) return 0;
+    return (uint64_t)tiles_side(seg0) * (tiles_side(n_seq) - seg0 / kTile);
+}
+
 // Resident / tiling order: position p holds sequence order[p]; longest first, equal lengths by ascending index.  Pure
 // function of the lengths, so every rank derives the same order.
 void length_order(const uint64_t *offsets, uint32_t n_seq, std::vector<uint32_t> &order)
@@ -376,7 +393,7 @@ extern "C" int apd_batch_create(apd_context *ctx, const float *frames, const uin
 
 extern "C" int apd_batch_refill(apd_context *ctx, apd_batch *b, const float *frames, int frames_on_device)
 {
-    if (!ctx || !b || b->ctx != ctx) return APD_ERR_INVALID_ARG;
+    if (!ctx || !b || b->ctx != ctx || b->joined) return APD_ERR_INVALID_ARG;   // a joined batch is a snapshot of two others
     const uint64_t total = b->total_frames, padded_frames = total + 2ull * b->n_seq;
     if (total > 0 && !frames) return APD_ERR_INVALID_ARG;
     HIP_TRY(ctx, bind_device(ctx));
@@ -447,6 +464,69 @@ extern "C" int apd_batch_destroy(apd_batch *b)
 }
 
 extern "C" uint32_t apd_batch_len(const apd_batch *b) { return b ? b->n_seq : 0; }
+extern "C" uint32_t apd_batch_first_len(const apd_batch *b) { return !b ? 0 : b->joined ? b->first_len : b->n_seq; }
+
+extern "C" int apd_batch_join(apd_context *ctx, const apd_batch *first, const apd_batch *second, apd_batch **out)
+{
+    if (!ctx || !first || !second || !out) return APD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (first->ctx != ctx || second->ctx != ctx || first->src_dim != second->src_dim) return APD_ERR_INVALID_ARG;
+    const uint64_t n_seq64 = (uint64_t)first->n_seq + second->n_seq, total = first->total_frames + second->total_frames;
+    if (n_seq64 > 0xFFFFFFFFull || total + 2ull * n_seq64 >= (1ull << 32)) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    apd_batch *b = new (std::nothrow) apd_batch();
+    if (!b) return APD_ERR_OOM;
+    // The first resident segment: the set with the larger mean length (the first set on a tie), so that -- as in a plain batch -- the
+    // column sequence a of most pairs is the longer one.  mean(first) < mean(second) without a division:
+    const bool swapped = first->n_seq && second->n_seq &&
+                         first->total_frames * second->n_seq < second->total_frames * first->n_seq;   // both factors below 2^32
+    const apd_batch *seg[2] = {swapped ? second : first, swapped ? first : second};
+    const uint32_t n_seq = (uint32_t)n_seq64, n0 = seg[0]->n_seq;
+    b->ctx = ctx; b->n_seq = n_seq; b->src_dim = first->src_dim; b->dim = first->dim; b->dpad = first->dpad; b->total_frames = total;
+    b->joined = true; b->swapped = swapped; b->first_len = first->n_seq; b->seg0 = n0;
+    b->min_len = n_seq ? 0xFFFFFFFFu : 0u; b->max_len = 0;
+    for (const apd_batch *s : seg)
+        if (s->n_seq) { b->min_len = std::min(b->min_len, s->min_len); b->max_len = std::max(b->max_len, s->max_len); }
+    // host metadata: each segment keeps its own resident (length) order; the second one is rebased behind the first
+    const size_t m1 = (size_t)n_seq + 1;
+    b->order.resize(n_seq);
+    b->offsets.assign(m1, 0);
+    b->h_meta.assign(4 * m1 + 4, 0u);
+    uint32_t *off32 = b->h_meta.data(), *ord32 = off32 + 2 * m1;          // src_off stays zero: there is no caller array to refill from
+    const uint64_t padded0 = seg[0]->total_frames + 2ull * n0;            // padded frames of the first segment
+    for (uint32_t p = 0; p < n_seq; ++p) {
+        const int k = p < n0 ? 0 : 1;
+        const uint32_t q = p - (k ? n0 : 0u);                             // position inside its segment
+        const bool is_second = (k == 1) != swapped;                       // does this segment hold the caller's second set?
+        b->order[p] = seg[k]->order[q] + (is_second ? first->n_seq : 0u);
+        ord32[p] = b->order[p];
+        b->offsets[p + 1] = b->offsets[p] + (seg[k]->offsets[q + 1] - seg[k]->offsets[q]);
+    }
+    for (uint32_t p = 0; p <= n_seq; ++p) off32[p] = (uint32_t)b->offsets[p] + 2 * p;
+    auto fail = [&](int rc) { apd_batch_destroy(b); return rc; };
+    const uint64_t padded_frames = total + 2ull * n_seq;
+    const size_t frame_bytes = (size_t)b->dpad * sizeof(float);
+    const size_t padded_bytes = std::max<size_t>((size_t)padded_frames * frame_bytes, 16);
+    b->frames_bytes = padded_bytes < 0xFFFFFE00ull ? (uint32_t)padded_bytes : 0u;
+    ctx->batches.insert(b);                                               // from here on apd_batch_destroy undoes everything
+    if (hipMalloc((void **)&b->d_frames, padded_bytes) != hipSuccess) return fail(APD_ERR_OOM);
+    if (hipMalloc((void **)&b->d_meta, b->h_meta.size() * sizeof(uint32_t)) != hipSuccess) return fail(APD_ERR_OOM);
+    b->d_seq_off = b->d_meta; b->d_src_off = b->d_meta + m1; b->d_order = b->d_meta + 2 * m1; b->d_flags = b->d_meta + 3 * m1;
+    b->d_seq_nmax = reinterpret_cast<float *>(b->d_meta + 3 * m1 + 4);
+    hipError_t e = hipMemcpyAsync(b->d_meta, b->h_meta.data(), b->h_meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+    // frames (sentinels included) and per-sequence norm maxima: device to device, segment by segment, behind the metadata copy
+    const size_t bytes0 = (size_t)padded0 * frame_bytes, bytes1 = (size_t)(padded_frames - padded0) * frame_bytes;
+    if (e == hipSuccess && bytes0) e = hipMemcpyAsync(b->d_frames, seg[0]->d_frames, bytes0, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && bytes1) e = hipMemcpyAsync((char *)b->d_frames + bytes0, seg[1]->d_frames, bytes1, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && n0) e = hipMemcpyAsync(b->d_seq_nmax, seg[0]->d_seq_nmax, (size_t)n0 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && n_seq > n0)
+        e = hipMemcpyAsync(b->d_seq_nmax + n0, seg[1]->d_seq_nmax, (size_t)(n_seq - n0) * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = launch_join_flags(b->d_flags, first->d_flags, second->d_flags, ctx->stream);   // no host synchronisation
+    if (e != hipSuccess) { ctx->last_error = std::string("apd_batch_join: ") + hipGetErrorString(e); return fail(APD_ERR_HIP); }
+    if (first->nonfinite >= 0 && second->nonfinite >= 0) b->nonfinite = (first->nonfinite | second->nonfinite) ? 1 : 0;   // both already read back
+    *out = b;
+    return APD_OK;
+}
 
 // ------------------------------------------------------------------------------------- tiles
 
@@ -527,12 +607,13 @@ static int check_lengths(const apd_batch *b)
 }
 
 // The tile plan (device tile list + classes, plan_tile_classes) of one rank, cached in the batch.
-static int build_tile_plan(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint32_t rank, uint32_t world,
+static int build_tile_plan(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint32_t rank, uint32_t world, bool cross,
                            bool fast_ok, bool uniform_pen, bool fast_shift, apd_batch::TilePlan &plan_out)
 {
     apd_batch::TilePlan plan;                                             // built locally, published only when complete
     std::vector<uint2> tiles;
-    rank_tile_list(batch->n_seq, rank, world, tiles);
+    if (cross) cross_tile_list(batch->n_seq, batch->seg0, tiles);
+    else rank_tile_list(batch->n_seq, rank, world, tiles);
     std::vector<uint4> flat;
     plan_tile_classes(batch->offsets, batch->n_seq, tiles, band, batch->dim, ctx->variant, fast_ok, uniform_pen, fast_shift,
                       plan.classes, flat);
@@ -554,10 +635,15 @@ static int build_tile_plan(apd_context *ctx, const apd_batch *batch, const BandS
     return APD_OK;
 }
 
+// `cross`: the tile rectangle of apd_align_cross (cross_tile_list, rank 0 of 1) instead of rank's share of the upper triangle; the
+// slab then holds cross_num_tiles tiles.  Everything else -- kernel choice, poison, fan-out, fallback, timing -- is one code path.
 static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint32_t rank,
-                            uint32_t world, float *d_slab)
+                            uint32_t world, float *d_slab, bool cross = false)
 {
     if (!ctx || !batch || !d_slab || world == 0 || rank >= world || batch->ctx != ctx) return APD_ERR_INVALID_ARG;
+    if (cross && (!batch->joined || world != 1)) return APD_ERR_INVALID_ARG;
+    const uint64_t n_tiles_all = cross ? cross_num_tiles(batch->n_seq, batch->seg0) : apd_num_tiles(batch->n_seq);
+    const uint64_t slab_floats = cross ? n_tiles_all * 2 * kSlotsPerTile : apd_slab_floats(batch->n_seq, world);
     int rc = check_lengths(batch);
     if (rc) return rc;
     HIP_TRY(ctx, bind_device(ctx));
@@ -575,7 +661,7 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     if (static_fast) {
         const uint32_t band_ub = band.use_explicit ? band.explicit_band : host_band_from_pct(band.pct, batch->max_len);
         const uint32_t w_all = std::max(std::min(band_ub, batch->max_len), batch->max_len - batch->min_len) + 2;   // >= w of every pair
-        device_select = generic_fallback_fits(w_all) && apd_num_tiles(batch->n_seq) * kSlotsPerTile <= 0xFFFFFFFFull;
+        device_select = generic_fallback_fits(w_all) && n_tiles_all * kSlotsPerTile <= 0xFFFFFFFFull;
         if (!device_select) {
             rc = batch_nonfinite(ctx, batch, &nonfinite);
             if (rc) return rc;
@@ -594,12 +680,12 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     // the band kernel's hybrid form with unit penalties moves its column window with one DPP instruction per register at any
     // group size (dtw_systolic.h, MASKED_FETCH): 8- and 32-lane groups cost no more than 16- and 64-lane ones there
     const bool fast_shift = band.ins == 1.0f && band.del == 1.0f && band.mat == 1.0f && ctx->distance_mode == 1 && batch->dim >= 8;
-    std::snprintf(keybuf, sizeof(keybuf), "%u/%u/%08x/%u/%d/%d/%d/%d/%d", rank, world, pct_bits, band.explicit_band, band.use_explicit,
+    std::snprintf(keybuf, sizeof(keybuf), "%s%u/%u/%08x/%u/%d/%d/%d/%d/%d", cross ? "cross/" : "", rank, world, pct_bits, band.explicit_band, band.use_explicit,
                   ctx->variant, (int)fast_ok, (int)uniform_pen, (int)fast_shift);   // everything the choice of kernels depends on
     auto cached = batch->tile_cache.find(keybuf);
     if (cached == batch->tile_cache.end()) {
         apd_batch::TilePlan fresh;
-        rc = build_tile_plan(ctx, batch, band, rank, world, fast_ok, uniform_pen, fast_shift, fresh);
+        rc = build_tile_plan(ctx, batch, band, rank, world, cross, fast_ok, uniform_pen, fast_shift, fresh);
         if (rc) return rc;
         cached = batch->tile_cache.emplace(keybuf, std::move(fresh)).first;
     }
@@ -607,7 +693,7 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     // Poison: every score slot of the rank's slab starts as NaN, so a pair that no kernel writes (a launch cut short, a
     // skipped class) reaches the matrix as NaN and raises APD_ERR_INCOMPLETE in the unpack -- never a stale or zero distance.
     APD_AFFINITY(ctx, "alignment launches");
-    HIP_TRY(ctx, hipMemsetAsync(d_slab, 0xFF, apd_slab_floats(batch->n_seq, world) * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_slab, 0xFF, slab_floats * sizeof(float), ctx->stream));
     AlignLaunch L{};
     L.d_frames = batch->d_frames; L.frames_bytes = batch->frames_bytes; L.d_seq_off = batch->d_seq_off; L.d_seq_nmax = batch->d_seq_nmax;
     L.n_seq = batch->n_seq; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band; L.d_slab = d_slab;
@@ -725,6 +811,115 @@ extern "C" int apd_align_all(apd_context *ctx, const apd_batch *batch, const apd
     }
     hipFree(d_out);
     return rc;
+}
+
+// ------------------------------------------------------------------------------ cross alignment
+
+static int align_cross_device_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, float *d_fs, float *d_sf)
+{
+    const uint32_t n_first = batch->first_len, n_second = batch->n_seq - n_first;
+    const size_t slab_bytes = std::max<size_t>(cross_num_tiles(batch->n_seq, batch->seg0) * 2 * kSlotsPerTile * sizeof(float), 16);
+    int rc = ensure_ws(ctx, &ctx->ws_slab, &ctx->ws_slab_bytes, slab_bytes);
+    if (rc) return rc;
+    rc = align_tiles_impl(ctx, batch, band, 0, 1, (float *)ctx->ws_slab, true);
+    if (rc) return rc;
+    APD_AFFINITY(ctx, "unpack launch");
+    // the unpack writes every entry; anything it fails to write stays NaN
+    const size_t out_bytes = (size_t)n_first * n_second * sizeof(float);
+    if (d_fs) HIP_TRY(ctx, hipMemsetAsync(d_fs, 0xFF, out_bytes, ctx->stream));
+    if (d_sf) HIP_TRY(ctx, hipMemsetAsync(d_sf, 0xFF, out_bytes, ctx->stream));
+    HIP_TRY(ctx, launch_unpack_cross((const float *)ctx->ws_slab, d_fs, d_sf, batch->d_order, batch->n_seq, batch->seg0, n_first,
+                                     batch->swapped, batch->d_flags, ctx->d_status, ctx->stream));
+    return APD_OK;
+}
+
+extern "C" int apd_align_cross_device_async(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, float *d_out_fs,
+                                            float *d_out_sf)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || !batch->joined) return APD_ERR_INVALID_ARG;
+    if (batch->first_len == 0 || batch->first_len == batch->n_seq) return APD_OK;   // an empty set: nothing to write
+    if (!d_out_fs && !d_out_sf) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    return align_cross_device_impl(ctx, batch, band_from_cfg(cfg), d_out_fs, d_out_sf);
+}
+
+extern "C" int apd_align_cross(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, float *out_fs, float *out_sf)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || !batch->joined) return APD_ERR_INVALID_ARG;
+    if (batch->first_len == 0 || batch->first_len == batch->n_seq) return APD_OK;
+    if (!out_fs && !out_sf) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    const size_t bytes = (size_t)batch->first_len * (batch->n_seq - batch->first_len) * sizeof(float);
+    float *d_out = nullptr;                                               // [fs | sf]
+    HIP_TRY(ctx, hipMalloc((void **)&d_out, 2 * bytes));
+    float *d_fs = out_fs ? d_out : nullptr, *d_sf = out_sf ? d_out + bytes / sizeof(float) : nullptr;
+    int rc = align_cross_device_impl(ctx, batch, band_from_cfg(cfg), d_fs, d_sf);
+    if (rc == APD_OK) {
+        hipError_t e = hipSuccess;
+        if (out_fs) e = hipMemcpyAsync(out_fs, d_fs, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out_sf) e = hipMemcpyAsync(out_sf, d_sf, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; }
+        else rc = sync_and_report(ctx);                                   // APD_ERR_INCOMPLETE: the outputs hold NaN where no score was written
+    }
+    hipFree(d_out);
+    return rc;
+}
+
+// Linkage of the first set to clusters of the second (kernels: clustering.hip).  Workspace (ws_tiles, owned by the context so that
+// the device form only enqueues): [members | set_off | link fs, sf].
+extern "C" int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on_device, uint32_t n_first, uint32_t n_second,
+                                 const uint32_t *members, const uint32_t *set_off, uint32_t n_sets, float *link_fs, float *link_sf,
+                                 uint32_t *nearest, float *nearest_linkage)
+{
+    if (!ctx || (n_sets && !set_off)) return APD_ERR_INVALID_ARG;
+    const uint32_t n_members = n_sets ? set_off[n_sets] : 0u;
+    if (n_sets && set_off[0] != 0) return APD_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < n_sets; ++k) if (set_off[k + 1] < set_off[k]) return APD_ERR_INVALID_ARG;
+    if (n_members && !members) return APD_ERR_INVALID_ARG;
+    for (uint32_t t = 0; t < n_members; ++t) if (members[t] >= n_second) return APD_ERR_INVALID_ARG;
+    if (n_first && (!nearest || !nearest_linkage || (n_members && (!fs || !sf)))) return APD_ERR_INVALID_ARG;
+    if (n_first == 0) return APD_OK;
+    HIP_TRY(ctx, bind_device(ctx));
+    // ascending sequence number inside every set: the order the reference's loops over 0..n visit the members in
+    std::vector<uint32_t> stage(members, members + n_members);
+    for (uint32_t k = 0; k < n_sets; ++k) std::sort(stage.begin() + set_off[k], stage.begin() + set_off[k + 1]);
+    stage.insert(stage.end(), set_off, set_off + (n_sets ? n_sets + 1 : 0));
+    if (n_sets == 0) stage.push_back(0u);
+    const size_t meta_bytes = (stage.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t link_floats = (size_t)n_first * n_sets, mat_bytes = (size_t)n_first * n_second * sizeof(float);
+    const size_t res_bytes = (size_t)n_first * 8;                          // host form: [nearest | nearest_linkage]
+    size_t need = meta_bytes + 2 * link_floats * sizeof(float);
+    const size_t in_off = (need + 255) & ~(size_t)255;
+    if (!on_device) need = in_off + 2 * mat_bytes + res_bytes;
+    int rc = ensure_ws(ctx, &ctx->ws_tiles, &ctx->ws_tiles_bytes, std::max<size_t>(need, 256));
+    if (rc) return rc;
+    char *base = (char *)ctx->ws_tiles;
+    uint32_t *d_members = (uint32_t *)base, *d_set_off = d_members + n_members;
+    float *d_link = (float *)(base + meta_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(d_members, stage.data(), stage.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    const float *d_fs = fs, *d_sf = sf;
+    uint32_t *d_nearest = nearest;
+    float *d_nl = nearest_linkage;
+    if (!on_device) {
+        float *in = (float *)(base + in_off);
+        if (mat_bytes && fs) HIP_TRY(ctx, hipMemcpyAsync(in, fs, mat_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (mat_bytes && sf) HIP_TRY(ctx, hipMemcpyAsync(in + mat_bytes / sizeof(float), sf, mat_bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_fs = in; d_sf = in + mat_bytes / sizeof(float);
+        d_nearest = (uint32_t *)(base + in_off + 2 * mat_bytes);
+        d_nl = (float *)(d_nearest + n_first);
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // `stage` is a local: its upload must have left the host
+    APD_AFFINITY(ctx, "linkage launch");
+    HIP_TRY(ctx, launch_cross_linkage(d_fs, d_sf, n_first, n_second, d_members, d_set_off, n_sets, d_link, d_nearest, d_nl, ctx->stream));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (link_fs && link_floats) HIP_TRY(ctx, hipMemcpyAsync(link_fs, d_link, link_floats * sizeof(float), kind, ctx->stream));
+    if (link_sf && link_floats) HIP_TRY(ctx, hipMemcpyAsync(link_sf, d_link + link_floats, link_floats * sizeof(float), kind, ctx->stream));
+    if (!on_device) {
+        HIP_TRY(ctx, hipMemcpyAsync(nearest, d_nearest, (size_t)n_first * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(nearest_linkage, d_nl, (size_t)n_first * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return APD_OK;
 }
 
 // The context's two-sequence batch holding (x, y): sequence 0 = x, sequence 1 = y.

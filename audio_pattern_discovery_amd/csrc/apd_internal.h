@@ -279,6 +279,20 @@ hipError_t launch_pad(const float *d_src, float *d_dst, const uint32_t *d_seq_of
 hipError_t launch_unpack(const float *d_gathered, float *d_out, const uint32_t *d_order, uint32_t n_seq, uint32_t world,
                          uint64_t slab_floats, const uint32_t *d_flags, uint32_t *d_status, hipStream_t stream);
 hipError_t launch_selftest(int *d_result, hipStream_t stream);
+// Joined batches (apd_batch_join): flags_out[0] = flags_a[0] | flags_b[0], on the device.
+hipError_t launch_join_flags(uint32_t *d_flags_out, const uint32_t *d_flags_a, const uint32_t *d_flags_b, hipStream_t stream);
+// The rectangular unpack of apd_align_cross.  d_slab: [tiles][2][kTile][kTile] over the tile rectangle ta in [0, ceil(n0 / kTile)) x
+// tb in [n0 / kTile, ceil(n_seq / kTile)), row-major; n0: sequences of the first RESIDENT segment; n_first: sequences of the caller's
+// first set; `swapped`: the resident first segment holds the caller's SECOND set.  One work-item per (position < n0, position >= n0);
+// same-set pairs of straddling tiles are dropped.  d_fs / d_sf (either may be null) are NaN-filled by the caller; *d_status |= 1
+// as in launch_unpack.
+hipError_t launch_unpack_cross(const float *d_slab, float *d_fs, float *d_sf, const uint32_t *d_order, uint32_t n_seq, uint32_t n0,
+                               uint32_t n_first, bool swapped, const uint32_t *d_flags, uint32_t *d_status, hipStream_t stream);
+// clustering.hip: the two kernels of apd_cross_linkage.  d_members: member lists sorted ascending per set; d_link: [2][n_first][n_sets]
+// workspace (plane 0 fs, plane 1 sf).
+hipError_t launch_cross_linkage(const float *d_fs, const float *d_sf, uint32_t n_first, uint32_t n_second, const uint32_t *d_members,
+                                const uint32_t *d_set_off, uint32_t n_sets, float *d_link, uint32_t *d_nearest, float *d_nearest_linkage,
+                                hipStream_t stream);
 hipError_t launch_sqrt_sweep(uint32_t first, uint64_t count, unsigned long long *d_out, hipStream_t stream);
 // The feature range of the fast kernels: a batch is theirs when every feature is 0 or has kFeatureFloor <= |v| < kFeatureBound;
 // any other value (NaN and the infinities included) raises the batch's flag, and the literal kernel aligns every pair.
@@ -402,6 +416,10 @@ struct apd_batch {
     std::vector<uint32_t> order;      // host copy of d_order
     std::vector<uint64_t> offsets;    // frame offsets of the RESIDENT order (host)
     uint32_t min_len = 0, max_len = 0;
+    // apd_batch_join: two resident segments, each in its own length order.  first_len: sequences of the caller's first set (n_seq for
+    // a plain batch); seg0: sequences of the first resident segment; swapped: that segment holds the caller's SECOND set
+    bool joined = false, swapped = false;
+    uint32_t first_len = 0, seg0 = 0;
     // device-resident tile lists, grouped by the kernel geometry each tile needs
     struct TilePlan { uint4 *d_tiles = nullptr; std::vector<apd::TileClass> classes; };
     mutable std::map<std::string, TilePlan> tile_cache;   // keyed by rank/world/band/variant

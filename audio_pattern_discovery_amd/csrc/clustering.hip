@@ -1325,6 +1325,73 @@ void report_timing(const unsigned long long *g, uint32_t n_ops)
 
 }  // namespace
 
+// ------------------------------------------------------------------------- linkage of one set to clusters of another
+namespace {
+
+// clustering.rs:153-170 for (cluster {q} of the first set, set k of the second) in both directions: one serial f32 chain per
+// (q, k, direction), members ascending.  Lanes run over consecutive q: in the sf direction a member's row sf[x][q .. q + 63] is one
+// coalesced load; the fs direction gathers fs[q][x] through the member list.  blockIdx.z: direction (0 fs, 1 sf).
+__global__ __launch_bounds__(64) void cross_linkage_kernel(const float *__restrict__ fs, const float *__restrict__ sf, uint32_t n_first,
+                                                           uint32_t n_second, const uint32_t *__restrict__ members,
+                                                           const uint32_t *__restrict__ set_off, uint32_t n_sets, float *__restrict__ link)
+{
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t dir = blockIdx.z;
+    if (q >= n_first) return;
+    float *const out = link + (size_t)dir * n_first * n_sets + (size_t)q * n_sets;
+    for (uint32_t k = blockIdx.y; k < n_sets; k += gridDim.y) {
+        const uint32_t t0 = set_off[k], t1 = set_off[k + 1];
+        const float size = (float)(t1 - t0);
+        float distance = 0.0f;
+        if (dir == 0) {
+            const float *row = fs + (size_t)q * n_second;
+            for (uint32_t t = t0; t < t1; ++t) distance += row[members[t]];
+        } else {
+            for (uint32_t t = t0; t < t1; ++t) distance += sf[(size_t)members[t] * n_first + q];
+        }
+        // size_x * size_y as the reference multiplies them: {q} is the x cluster in the fs direction, the y cluster in the other
+        out[k] = distance / (dir == 0 ? 1.0f * size : size * 1.0f);
+    }
+}
+
+// merge()'s scan (clustering.rs:178-187) over the ordered pairs that involve q: k ascending, ({q}, S_k) then (S_k, {q}); a value
+// replaces the best only if strictly below it (NaN never is)
+__global__ __launch_bounds__(64) void cross_nearest_kernel(const float *__restrict__ link, uint32_t n_first, uint32_t n_sets,
+                                                           uint32_t *__restrict__ nearest, float *__restrict__ nearest_linkage)
+{
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    if (q >= n_first) return;
+    const float *lf = link + (size_t)q * n_sets, *ls = link + (size_t)n_first * n_sets + (size_t)q * n_sets;
+    float best = __builtin_inff();
+    uint32_t arg = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < n_sets; ++k) {
+        const float a = lf[k], b = ls[k];
+        if (a < best) { best = a; arg = k; }
+        if (b < best) { best = b; arg = k; }
+    }
+    nearest[q] = arg;
+    nearest_linkage[q] = best;
+}
+
+}  // namespace
+
+namespace apd {
+hipError_t launch_cross_linkage(const float *d_fs, const float *d_sf, uint32_t n_first, uint32_t n_second, const uint32_t *d_members,
+                                const uint32_t *d_set_off, uint32_t n_sets, float *d_link, uint32_t *d_nearest, float *d_nearest_linkage,
+                                hipStream_t stream)
+{
+    if (n_first == 0) return hipSuccess;
+    const uint32_t q_blocks = (n_first + 63) / 64;
+    if (n_sets) {
+        hipLaunchKernelGGL(cross_linkage_kernel, dim3(q_blocks, std::min<uint32_t>(n_sets, 16384u), 2), dim3(64), 0, stream, d_fs, d_sf, n_first,
+                           n_second, d_members, d_set_off, n_sets, d_link);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(cross_nearest_kernel, dim3(q_blocks), dim3(64), 0, stream, d_link, n_first, n_sets, d_nearest, d_nearest_linkage);
+    return hipGetLastError();
+}
+}  // namespace apd
+
 extern "C" int apd_percentile(apd_context *ctx, const float *x, uint64_t len, float perc, int x_on_device, float *value)
 {
     if (!ctx || !value || (len && !x)) return APD_ERR_INVALID_ARG;

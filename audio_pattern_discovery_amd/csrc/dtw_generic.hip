@@ -248,6 +248,43 @@ __global__ void unpack_tiles_kernel(const float *__restrict__ gathered, float *_
     if (__ballot(poisoned) != 0ull && (threadIdx.x & 63) == 0 && flags[0] == 0u) atomicOr(status, 1u);
 }
 
+// The rectangular unpack of apd_align_cross: one work-item per (position pa of the first resident segment, position pb of the
+// second).  slab: [tiles][2][kTile][kTile] over the tile rectangle ta in [0, ceil(n0 / kTile)) x tb in [tb0, tb0 + tiles_b), row-major.
+// order[] holds joined caller numbers (first set below n_first, second set from n_first on); `swapped`: the first resident segment
+// is the caller's second set.  Same-set pairs that the straddling tiles swept are never read.
+__global__ __launch_bounds__(256) void unpack_cross_kernel(const float *__restrict__ slab, float *__restrict__ out_fs, float *__restrict__ out_sf,
+                                                           const uint32_t *__restrict__ order, uint32_t n_seq, uint32_t n0, uint32_t n_first,
+                                                           uint32_t swapped, uint32_t tb0, uint32_t tiles_b,
+                                                           const uint32_t *__restrict__ flags, uint32_t *__restrict__ status)
+{
+    const uint32_t n1 = n_seq - n0, n_second = n_seq - n_first;
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool poisoned = false;
+    if (e < (uint64_t)n0 * n1) {
+        const uint32_t pa = (uint32_t)(e / n1), pb = n0 + (uint32_t)(e % n1);   // consecutive lanes: consecutive pb
+        const uint32_t ta = pa / kTile, tb = pb / kTile, sa = pa % kTile, sb = pb % kTile;
+        const float *t = slab + ((uint64_t)ta * tiles_b + (tb - tb0)) * 2 * kSlotsPerTile;
+        const float s1 = t[sa * kTile + sb], s2 = t[kSlotsPerTile + sa * kTile + sb];   // score(x = pa, y = pb), score(x = pb, y = pa)
+        const uint32_t a = order[pa], b = order[pb];
+        if (!swapped) {                                            // a: first set, b: second set
+            if (out_fs) out_fs[(uint64_t)a * n_second + (b - n_first)] = s1;
+            if (out_sf) out_sf[(uint64_t)(b - n_first) * n_first + a] = s2;
+        } else {                                                   // a: second set, b: first set
+            if (out_sf) out_sf[(uint64_t)(a - n_first) * n_first + b] = s1;
+            if (out_fs) out_fs[(uint64_t)b * n_second + (a - n_first)] = s2;
+        }
+        poisoned = (s1 != s1) | (s2 != s2);
+    }
+    // as in unpack_tiles_kernel: with frames in range no score is NaN, so a NaN is the poison of a pair no kernel wrote
+    if (__ballot(poisoned) != 0ull && (threadIdx.x & 63) == 0 && flags[0] == 0u) atomicOr(status, 1u);
+}
+
+// apd_batch_join: the joined batch is out of the fast kernels' feature range if either input is
+__global__ void join_flags_kernel(uint32_t *__restrict__ out, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = a[0] | b[0];
+}
+
 __global__ void selftest_kernel(int *result)
 {
     const int lane = threadIdx.x;
@@ -318,6 +355,23 @@ hipError_t launch_unpack(const float *d_gathered, float *d_out, const uint32_t *
     if (n_tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(unpack_tiles_kernel, dim3((uint32_t)n_tiles), dim3(kSlotsPerTile), 0, stream, d_gathered, d_out,
                        d_order, n_seq, world, slab_floats, side, d_flags, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_flags(uint32_t *d_flags_out, const uint32_t *d_flags_a, const uint32_t *d_flags_b, hipStream_t stream)
+{
+    hipLaunchKernelGGL(join_flags_kernel, dim3(1), dim3(64), 0, stream, d_flags_out, d_flags_a, d_flags_b);
+    return hipGetLastError();
+}
+
+hipError_t launch_unpack_cross(const float *d_slab, float *d_fs, float *d_sf, const uint32_t *d_order, uint32_t n_seq, uint32_t n0,
+                               uint32_t n_first, bool swapped, const uint32_t *d_flags, uint32_t *d_status, hipStream_t stream)
+{
+    const uint64_t pairs = (uint64_t)n0 * (n_seq - n0);
+    if (pairs == 0) return hipSuccess;
+    const uint32_t tb0 = n0 / kTile, tiles_b = (n_seq + kTile - 1) / kTile - tb0;
+    hipLaunchKernelGGL(unpack_cross_kernel, dim3((uint32_t)((pairs + 255) / 256)), dim3(256), 0, stream, d_slab, d_fs, d_sf, d_order, n_seq,
+                       n0, n_first, swapped ? 1u : 0u, tb0, tiles_b, d_flags, d_status);
     return hipGetLastError();
 }
 

@@ -73,6 +73,44 @@ impl AlignmentWorkers {
     }
 }
 
+/// Not in the reference: its align_all only knows one set.  Aligns every sequence of `queries` against every sequence of `corpus`
+/// on the first device of APD_DEVICES (apd_batch_join + apd_align_cross) and returns (fs, sf), row-major:
+/// fs[q * n2 + c] = score(x = queries[q], y = corpus[c]), sf[c * n1 + q] = score(x = corpus[c], y = queries[q]).
+pub fn align_cross(queries: &[NDSequence], corpus: &[NDSequence], params: &Discovery) -> (Vec<f32>, Vec<f32>) {
+    let (n1, n2) = (queries.len(), corpus.len());
+    let (mut fs, mut sf) = (vec![0.0f32; n1 * n2], vec![0.0f32; n1 * n2]);
+    if n1 == 0 || n2 == 0 { return (fs, sf); }
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let pack = |set: &[NDSequence]| {
+        let mut offsets = vec![0u64; set.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in set.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        (frames, offsets)
+    };
+    let dim = queries[0].n_bins as u32;
+    let ((fa, oa), (fb, ob)) = (pack(queries), pack(corpus));
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let (mut a, mut b, mut j) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        check(apd_batch_create(ctx, fa.as_ptr(), oa.as_ptr(), n1 as u32, dim, 0, &mut a));
+        check(apd_batch_create(ctx, fb.as_ptr(), ob.as_ptr(), n2 as u32, dim, 0, &mut b));
+        check(apd_batch_join(ctx, a, b, &mut j));
+        debug_assert_eq!(apd_batch_first_len(j) as usize, n1);
+        let rc = apd_align_cross(ctx, j, &cfg, fs.as_mut_ptr(), sf.as_mut_ptr());
+        apd_destroy(ctx);                                                 // releases the device side of the three batches
+        for h in [j, b, a] { apd_batch_destroy(h); }
+        check(rc);
+    }
+    (fs, sf)
+}
+
 fn last_error(multi: *mut apd_multi) -> String {
     unsafe { std::ffi::CStr::from_ptr(apd_multi_last_error(multi)) }.to_string_lossy().into_owned()
 }

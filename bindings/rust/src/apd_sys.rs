@@ -112,6 +112,11 @@ extern "C" {
     pub fn apd_batch_refill(ctx: *mut apd_context, batch: *mut apd_batch, frames: *const f32, frames_on_device: c_int) -> c_int;
     pub fn apd_batch_nonfinite(ctx: *mut apd_context, batch: *const apd_batch, nonfinite: *mut c_int) -> c_int;
     // AlignmentWorkers::align_all (alignments.rs:31-67)
+    pub fn apd_batch_join(ctx: *mut apd_context, first: *const apd_batch, second: *const apd_batch, joined: *mut *mut apd_batch) -> c_int;
+    pub fn apd_batch_first_len(batch: *const apd_batch) -> u32;
+    pub fn apd_align_cross(ctx: *mut apd_context, joined: *const apd_batch, cfg: *const apd_align_config, out_fs: *mut f32, out_sf: *mut f32) -> c_int;
+    pub fn apd_align_cross_device_async(ctx: *mut apd_context, joined: *const apd_batch, cfg: *const apd_align_config, d_out_fs: *mut f32,
+                                        d_out_sf: *mut f32) -> c_int;
     pub fn apd_align_all(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, out: *mut f32) -> c_int;
     pub fn apd_align_all_device_async(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, d_out: *mut f32) -> c_int;
     pub fn apd_tile_size() -> u32;
@@ -180,6 +185,9 @@ extern "C" {
                           ops: *mut apd_cluster_op, n_ops: *mut u32, roots: *mut u32, n_roots: *mut u32, threshold: *mut f32) -> c_int;
     pub fn apd_cluster_sets(ops: *const apd_cluster_op, n_ops: u32, roots: *const u32, n_roots: u32, n: u32,
                             members: *mut u32, set_off: *mut u32, n_sets: *mut u32) -> c_int;
+    pub fn apd_cross_linkage(ctx: *mut apd_context, fs: *const f32, sf: *const f32, on_device: c_int, n_first: u32, n_second: u32,
+                             members: *const u32, set_off: *const u32, n_sets: u32, link_fs: *mut f32, link_sf: *mut f32,
+                             nearest: *mut u32, nearest_linkage: *mut f32) -> c_int;
     // companions
     pub fn apd_encode(ctx: *mut apd_context, x: *const f32, t: u64, d_in: u32, w_encode: *const f32, b_encode: *const f32,
                       latent: u32, on_device: c_int, out: *mut f32) -> c_int;

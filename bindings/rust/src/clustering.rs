@@ -71,6 +71,22 @@ impl AgglomerativeClustering {
         (ops, roots[..n_roots as usize].iter().map(|r| *r as usize).collect())
     }
 
+    /// Not in the reference: the linkage of clustering.rs:153-170 between every query (a cluster of its own) and every set of corpus
+    /// sequence numbers in `sets` (as cluster_sets returns them), from the cross matrices of alignments::align_cross.  Returns, per
+    /// query, the set merge() would pick (None if no linkage is below +INF) and that linkage.
+    pub fn cross_linkage(fs: &[f32], sf: &[f32], n_queries: usize, n_corpus: usize, sets: &[Vec<usize>]) -> Vec<(Option<usize>, f32)> {
+        let members: Vec<u32> = sets.iter().flat_map(|s| s.iter().map(|v| *v as u32)).collect();
+        let mut set_off = vec![0u32; sets.len() + 1];
+        for (k, s) in sets.iter().enumerate() { set_off[k + 1] = set_off[k] + s.len() as u32; }
+        let mut nearest = vec![0u32; n_queries.max(1)];
+        let mut linkage = vec![0f32; n_queries.max(1)];
+        with_context(|ctx| unsafe {
+            check(apd_cross_linkage(ctx, fs.as_ptr(), sf.as_ptr(), 0, n_queries as u32, n_corpus as u32, members.as_ptr(), set_off.as_ptr(),
+                                    sets.len() as u32, std::ptr::null_mut(), std::ptr::null_mut(), nearest.as_mut_ptr(), linkage.as_mut_ptr()));
+        });
+        (0..n_queries).map(|q| (if nearest[q] == u32::MAX { None } else { Some(nearest[q] as usize) }, linkage[q])).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

@@ -167,6 +167,32 @@ int apd_batch_refill(apd_context *ctx, apd_batch *batch, const float *frames, in
  * 2^-40 <= |v| < 2^60.  Follows apd_batch_refill.  Synchronises. */
 int apd_batch_nonfinite(apd_context *ctx, const apd_batch *batch, int *nonfinite);
 
+/* ---- two sets in one batch: the cross alignment (the `cdist` next to align_all's `pdist`) ------------------------------
+ * A resident batch holding the sequences of `first` followed by those of `second` (same context, same caller frame dimension,
+ * else APD_ERR_INVALID_ARG).  Caller's sequence numbers: s < apd_batch_len(first) is first's sequence s, the others second's
+ * s - apd_batch_len(first).  A snapshot: made from the two batches' resident frames by device-to-device copies on the context's
+ * stream (no host round trip of frames, no synchronisation: the out-of-range flag of apd_batch_nonfinite is the OR of the two
+ * inputs' flags, formed on the device); later refills of first / second are not followed.  Both inputs stay usable.
+ * Resident order: two segments, each in its own length order; which set lies first is the library's choice (the one with the
+ * larger mean length) and no result depends on it.  total frames + 2 * sequences >= 2^32 is APD_ERR_INVALID_ARG.
+ * A joined batch is an ordinary batch for apd_batch_len / apd_batch_destroy / apd_destroy, apd_batch_nonfinite, apd_align_all*,
+ * apd_align_tiles_async / apd_unpack_tiles_async (which use the batch's own order) and apd_align_paths (the warping path between
+ * a sequence of one set and one of the other).  apd_batch_refill on it is APD_ERR_INVALID_ARG.  The host-only views that take
+ * raw offsets (apd_length_order, apd_rank_tile_list, apd_unpack_tiles_host, apd_align_work) describe LENGTH-ORDERED batches
+ * only, not joined ones.  The multi-GPU entry points (apd_multi_*, apd_comm_*, apd_align_all_sharded_async) do not take the
+ * cross alignment: out of scope. */
+int apd_batch_join(apd_context *ctx, const apd_batch *first, const apd_batch *second, apd_batch **joined);
+uint32_t apd_batch_first_len(const apd_batch *batch);   /* sequences of the first set; apd_batch_len for a plain batch */
+/* out_fs: [n_first][n_second], out_fs[q][c] = Alignment::score(x = first q, y = second c);
+ * out_sf: [n_second][n_first], out_sf[c][q] = score(x = second c, y = first q).  Either may be NULL.  Blocking / asynchronous
+ * exactly as apd_align_all / apd_align_all_device_async; band per pair from max(len) as everywhere; distance modes, feature-range
+ * routing to the literal kernel, poison + APD_ERR_INCOMPLETE, apd_set_variant, apd_set_timing / apd_last_kernel_ms and
+ * apd_set_fault_injection all as for apd_align_all.  An empty set: APD_OK, nothing written.  A plain (not joined) batch:
+ * APD_ERR_INVALID_ARG.  Only the tiles of the pair matrix that hold a first-second pair are swept. */
+int apd_align_cross(apd_context *ctx, const apd_batch *joined, const apd_align_config *cfg, float *out_fs, float *out_sf);
+int apd_align_cross_device_async(apd_context *ctx, const apd_batch *joined, const apd_align_config *cfg, float *d_out_fs,
+                                 float *d_out_sf);
+
 /* ---- AlignmentWorkers::align_all (src/alignments.rs:31-67) ---------------------------- */
 /* out: n_seq*n_seq f32 row-major, out[i*n+j] = Alignment::score of (x = seq i, y = seq j),
  * diagonal 0.0 (alignments.rs:21-23,51,57).  Blocking. */
@@ -390,6 +416,23 @@ int apd_clustering(apd_context *ctx, const float *distances, int distances_on_de
  * members capacity >= n + n_ops + 2, set_off capacity >= n_roots+1. */
 int apd_cluster_sets(const apd_cluster_op *ops, uint32_t n_ops, const uint32_t *roots, uint32_t n_roots,
                      uint32_t n, uint32_t *members, uint32_t *set_off, uint32_t *n_sets);
+
+/* Average linkage of every first-set sequence to clusters of the second set, from the two cross matrices of apd_align_cross:
+ * clustering.rs:153-170 with each first-set sequence q as a cluster of its own and set k of the second set as the other:
+ *   link_fs[q][k] = (((0 + fs[q][y1]) + fs[q][y2]) + ...) / (1.0f * (float)|S_k|)     y ascending over S_k
+ *   link_sf[q][k] = (((0 + sf[x1][q]) + sf[x2][q]) + ...) / ((float)|S_k| * 1.0f)     x ascending over S_k
+ * f32, one rounded add per member in ASCENDING sequence number whatever order `members` lists them (the reference loops x, y
+ * over 0..n); an empty set gives 0/0 = NaN as the reference would.  members / set_off / n_sets: as apd_cluster_sets returns them
+ * (sequence numbers of the second set; >= n_second is APD_ERR_INVALID_ARG); singletons the caller wants considered are sets of one.
+ * nearest[q]: merge()'s choice (clustering.rs:178-187) among the ordered pairs that involve q: scan k ascending, link_fs[q][k]
+ * then link_sf[q][k], keep a value only if it is strictly below the best so far, starting from +INF; nearest_linkage[q] that
+ * value; none kept (all +INF / NaN, or n_sets = 0): 0xFFFFFFFF and +INF.
+ * fs: [n_first][n_second], sf: [n_second][n_first]; fs / sf / outputs: host, or all device pointers if on_device (matrices and
+ * results stay in HBM; the call waits once for the upload of the member lists, the kernels are only enqueued on the context's
+ * stream).  link_fs, link_sf: [n_first][n_sets], may be NULL.  members / set_off: always host. */
+int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on_device, uint32_t n_first, uint32_t n_second,
+                      const uint32_t *members, const uint32_t *set_off, uint32_t n_sets,
+                      float *link_fs, float *link_sf, uint32_t *nearest, float *nearest_linkage);
 
 /* ---- companions ---------------------------------------------------------------------- */
 /* AutoEncoder::predict over every frame = NDSequence::encoded (src/neural.rs:55-71,

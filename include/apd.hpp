@@ -186,6 +186,28 @@ class Alignment {
     std::vector<apd_path_step> path_;
 };
 
+// An apd_batch owned by the caller; Batch::join: the sequences of `first` followed by those of `second` in one resident batch
+// (apd_batch_join), an ordinary batch for every call that takes one and what apd_align_cross aligns.
+class Batch {
+  public:
+    explicit Batch(apd_batch *handle) : handle_(handle) {}
+    static Batch join(Context &ctx, const apd_batch *first, const apd_batch *second)
+    {
+        apd_batch *j = nullptr;
+        check(apd_batch_join(ctx.get(), first, second, &j), ctx.get());
+        return Batch(j);
+    }
+    ~Batch() { if (handle_) apd_batch_destroy(handle_); }
+    Batch(Batch &&o) noexcept : handle_(o.handle_) { o.handle_ = nullptr; }
+    Batch(const Batch &) = delete;
+    Batch &operator=(const Batch &) = delete;
+    apd_batch *get() const { return handle_; }
+    uint32_t len() const { return apd_batch_len(handle_); }
+    uint32_t first_len() const { return apd_batch_first_len(handle_); }
+  private:
+    apd_batch *handle_ = nullptr;
+};
+
 // alignments.rs:11-68
 class AlignmentWorkers {
   public:
@@ -235,6 +257,17 @@ class AlignmentWorkers {
         check(apd_multi_ranks_seen(multi_, &seen));
         return seen;
     }
+    // Not in the reference: this object's sequences against `other`'s (same context): apd_batch_join + apd_align_cross.
+    // fs[q * n2 + c] = score(x = data[q], y = other.data[c]); sf[c * n1 + q] = score(x = other.data[c], y = data[q]).
+    std::pair<std::vector<float>, std::vector<float>> cross(const AlignmentWorkers &other, const Discovery &params)
+    {
+        const apd_align_config c = params.config();
+        const std::size_t n1 = data.size(), n2 = other.data.size();
+        std::pair<std::vector<float>, std::vector<float>> out{std::vector<float>(n1 * n2), std::vector<float>(n1 * n2)};
+        Batch joined = Batch::join(ctx_, batch_, other.batch_);
+        check(apd_align_cross(ctx_.get(), joined.get(), &c, out.first.data(), out.second.data()), ctx_.get());
+        return out;
+    }
     const char *collective() const { return multi_ ? apd_multi_collective(multi_) : "none (one device)"; }
     std::vector<NDSequence> data;
     std::vector<float> result;                                                       // n*n row-major, diagonal 0.0
@@ -281,6 +314,20 @@ struct AgglomerativeClustering {
         std::vector<std::vector<std::size_t>> out;
         for (uint32_t s = 0; s < n_sets; ++s) out.emplace_back(members.begin() + off[s], members.begin() + off[s + 1]);
         return out;
+    }
+    // Not in the reference: clustering.rs:153-170 between every first-set sequence (a cluster of its own) and every set of second-set
+    // sequence numbers in `sets`, from the cross matrices of AlignmentWorkers::cross (apd_cross_linkage).
+    struct CrossLinkage { std::vector<float> link_fs, link_sf; std::vector<uint32_t> nearest; std::vector<float> nearest_linkage; };
+    static CrossLinkage cross_linkage(Context &ctx, const std::vector<float> &fs, const std::vector<float> &sf, std::size_t n_first,
+                                      std::size_t n_second, const std::vector<std::vector<std::size_t>> &sets)
+    {
+        std::vector<uint32_t> members, off(1, 0u);
+        for (const auto &s : sets) { members.insert(members.end(), s.begin(), s.end()); off.push_back((uint32_t)members.size()); }
+        CrossLinkage r{std::vector<float>(n_first * sets.size()), std::vector<float>(n_first * sets.size()), std::vector<uint32_t>(n_first),
+                       std::vector<float>(n_first)};
+        check(apd_cross_linkage(ctx.get(), fs.data(), sf.data(), 0, (uint32_t)n_first, (uint32_t)n_second, members.data(), off.data(),
+                                (uint32_t)sets.size(), r.link_fs.data(), r.link_sf.data(), r.nearest.data(), r.nearest_linkage.data()), ctx.get());
+        return r;
     }
 };
 
