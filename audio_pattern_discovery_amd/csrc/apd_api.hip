@@ -14,16 +14,6 @@ using namespace apd;
 
 namespace {
 
-int ensure_ws(apd_context *ctx, void **p, size_t *have, size_t need)
-{
-    APD_AFFINITY(ctx, "workspace allocation");
-    if (*have >= need && *p) return APD_OK;
-    if (*p) { HIP_TRY(ctx, hipFree(*p)); *p = nullptr; *have = 0; }
-    HIP_TRY(ctx, hipMalloc(p, need));
-    *have = need;
-    return APD_OK;
-}
-
 uint32_t tiles_side(uint32_t n_seq) { return (n_seq + kTile - 1) / kTile; }
 
 void rank_tile_list(uint32_t n_seq, uint32_t rank, uint32_t world, std::vector<uint2> &out)
@@ -46,11 +36,6 @@ void cross_tile_list(uint32_t n_seq, uint32_t seg0, std::vector<uint2> &out)
     const uint32_t side = tiles_side(n_seq), rows = tiles_side(seg0), tb0 = seg0 / kTile;
     for (uint32_t ta = 0; ta < rows; ++ta)
         for (uint32_t tb = tb0; tb < side; ++tb) out.push_back(make_uint2(ta, tb));
-}
-uint64_t cross_num_tiles(uint32_t n_seq, uint32_t seg0)
-{
-    if (seg0 == 0 || seg0 >= n_seq) return 0;
-    return (uint64_t)tiles_side(seg0) * (tiles_side(n_seq) - seg0 / kTile);
 }
 
 // Resident / tiling order: position p holds sequence order[p]; longest first, equal lengths by ascending index.  Pure
@@ -159,30 +144,16 @@ extern "C" int apd_create(int device, apd_context **out)
     return APD_OK;
 }
 
-static void release_batch_device_memory(apd_batch *b);
-
 extern "C" int apd_destroy(apd_context *ctx)
 {
     if (!ctx) return APD_ERR_INVALID_ARG;
     bind_device(ctx);
     hipStreamSynchronize(ctx->stream);
     if (ctx->pair_batch) { apd_batch_destroy(ctx->pair_batch); ctx->pair_batch = nullptr; }   // apd_align_pair's own (nobody else holds it)
-    for (apd_batch *b : ctx->batches) { release_batch_device_memory(b); b->ctx = nullptr; }   // orphans: see apd_batch_destroy
-    ctx->batches.clear();
-    for (apd_comm *c : ctx->comms) apd::orphan_comm(c);
-    ctx->comms.clear();
-    for (apd_encoder *e : ctx->encoders) apd::orphan_encoder(e);
-    ctx->encoders.clear();
-    for (apd_cepstrum_plan *cp : ctx->cepstrum_plans) apd::orphan_cepstrum_plan(cp);
-    ctx->cepstrum_plans.clear();
+    for (ContextChild *c : ctx->children) { c->release_device(); c->ctx = nullptr; }   // orphans: see destroy_child
+    ctx->children.clear();
     for (void *p : ctx->buffers) hipFree(p);                              // apd_device_alloc'ed and never freed
     ctx->buffers.clear();
-    if (ctx->ws_tiles) hipFree(ctx->ws_tiles);
-    if (ctx->ws_slab) hipFree(ctx->ws_slab);
-    if (ctx->ws_misc) hipFree(ctx->ws_misc);
-    if (ctx->ws_gather) hipFree(ctx->ws_gather);
-    if (ctx->ws_path_dirs) hipFree(ctx->ws_path_dirs);
-    if (ctx->ws_path_steps) hipFree(ctx->ws_path_steps);
     if (ctx->d_status) hipFree(ctx->d_status);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -192,7 +163,21 @@ extern "C" int apd_destroy(apd_context *ctx)
         if (ctx->side_done[k]) hipEventDestroy(ctx->side_done[k]);
     }
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                                                          // frees the workspaces: the device is still bound
+    return APD_OK;
+}
+
+// The shared body of the children's destroy entry points (apd::ContextChild).
+int apd::destroy_child(ContextChild *child)
+{
+    if (!child) return APD_ERR_INVALID_ARG;
+    if (apd_context *ctx = child->ctx) {                                 // else: orphaned by apd_destroy, device side already released
+        bind_device(ctx);
+        hipStreamSynchronize(ctx->stream);
+        child->release_device();
+        ctx->children.erase(child);
+    }
+    delete child;
     return APD_OK;
 }
 
@@ -290,12 +275,13 @@ extern "C" int apd_selftest(apd_context *ctx)
 {
     if (!ctx) return APD_ERR_INVALID_ARG;
     HIP_TRY(ctx, bind_device(ctx));
-    int rc = ensure_ws(ctx, &ctx->ws_misc, &ctx->ws_misc_bytes, 256);
+    int rc = reserve_ws(ctx, ctx->ws_misc, 256);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ws_misc, 0, sizeof(int), ctx->stream));
-    HIP_TRY(ctx, launch_selftest((int *)ctx->ws_misc, ctx->stream));
+    int *d_ok = ctx->ws_misc.as<int>();
+    HIP_TRY(ctx, hipMemsetAsync(d_ok, 0, sizeof(int), ctx->stream));
+    HIP_TRY(ctx, launch_selftest(d_ok, ctx->stream));
     int ok = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&ok, ctx->ws_misc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ok, d_ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (!ok) { ctx->last_error = "DPP wave_shr/wave_shl self-test failed"; return APD_ERR_HIP; }
     return APD_OK;
@@ -306,13 +292,13 @@ extern "C" int apd_selftest_sqrt(apd_context *ctx, uint32_t first_bits, uint64_t
 {
     if (!ctx || !mismatches || count > (1ull << 32)) return APD_ERR_INVALID_ARG;
     HIP_TRY(ctx, bind_device(ctx));
-    int rc = ensure_ws(ctx, &ctx->ws_misc, &ctx->ws_misc_bytes, 256);
+    int rc = reserve_ws(ctx, ctx->ws_misc, 256);
     if (rc) return rc;
-    unsigned long long h[7] = {0, ~0ull, 0, 0, 0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_misc, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long h[7] = {0, ~0ull, 0, 0, 0, 0, 0}, *d_h = ctx->ws_misc.as<unsigned long long>();
+    HIP_TRY(ctx, hipMemcpyAsync(d_h, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // h is a stack buffer
-    if (count) HIP_TRY(ctx, launch_sqrt_sweep(first_bits, count, (unsigned long long *)ctx->ws_misc, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->ws_misc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    if (count) HIP_TRY(ctx, launch_sqrt_sweep(first_bits, count, d_h, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h, d_h, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *mismatches = h[0];
     if (first_mismatch) *first_mismatch = h[0] ? (uint32_t)(h[1] - 1ull) : 0u;
@@ -339,6 +325,42 @@ extern "C" int apd_discovery_alignment_params(const apd_align_config *cfg, uint6
 
 // ------------------------------------------------------------------------------------- batch
 
+// The resident form of a batch, described HERE and nowhere else.  Expects n_seq, dim, dpad, total_frames, order and offsets (of the
+// resident order) filled in.
+//   d_frames: total_frames + 2 n_seq frames of dpad floats, two sentinel frames behind every sequence (dtw_generic.hip);
+//   d_meta:   one allocation filled by one copy of h_meta, [seq_off m1 | src_off m1 | order m1 | flags 4 | nmax m1] with m1 = n_seq + 1:
+//             padded frame offsets; first frame of every resident sequence in the caller's frame array (`caller_offsets`; zeros without
+//             one: a joined batch is never refilled); resident position -> caller's index; then what the device writes (repack
+//             kernel, join): the flag words and the per-sequence norm maxima, meta_tail_words from d_flags to the end.
+// The batch is registered with the context before anything is allocated: on any failure apd_batch_destroy undoes everything.
+static constexpr size_t meta_tail_words(uint32_t n_seq) { return 4 + (size_t)n_seq + 1; }
+
+static int batch_make_resident(apd_context *ctx, apd_batch *b, const uint64_t *caller_offsets)
+{
+    const uint32_t n_seq = b->n_seq;
+    const size_t m1 = (size_t)n_seq + 1;
+    b->h_meta.assign(3 * m1 + meta_tail_words(n_seq), 0u);
+    uint32_t *off32 = b->h_meta.data(), *src32 = off32 + m1, *ord32 = src32 + m1;
+    for (uint32_t p = 0; p < n_seq; ++p) {
+        if (caller_offsets) src32[p] = (uint32_t)caller_offsets[b->order[p]];
+        ord32[p] = b->order[p];
+    }
+    for (uint32_t p = 0; p <= n_seq; ++p) off32[p] = (uint32_t)b->offsets[p] + 2 * p;   // two sentinel frames behind every sequence
+    const uint64_t padded_frames = b->total_frames + 2ull * n_seq;
+    const size_t padded_bytes = std::max<size_t>((size_t)padded_frames * b->dpad * sizeof(float), 16);
+    b->frames_bytes = padded_bytes < 0xFFFFFE00ull ? (uint32_t)padded_bytes : 0u;   // 4 GiB and beyond: no buffer addressing
+    b->ctx = ctx;
+    ctx->children.insert(b);
+    const size_t meta_bytes = b->h_meta.size() * sizeof(uint32_t);
+    if (b->d_frames.alloc(padded_bytes) != hipSuccess || b->d_meta.alloc(meta_bytes) != hipSuccess) return APD_ERR_OOM;
+    uint32_t *d_meta = b->d_meta.as<uint32_t>();
+    b->d_seq_off = d_meta; b->d_src_off = d_meta + m1; b->d_order = d_meta + 2 * m1; b->d_flags = d_meta + 3 * m1;
+    b->d_seq_nmax = reinterpret_cast<float *>(b->d_flags + 4);
+    if (hipMemcpyAsync(d_meta, b->h_meta.data(), meta_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        return APD_ERR_HIP;                                               // h_meta lives as long as the batch: no sync needed
+    return APD_OK;
+}
+
 extern "C" int apd_batch_create(apd_context *ctx, const float *frames, const uint64_t *offsets, uint32_t n_seq,
                                 uint32_t dim, int frames_on_device, apd_batch **out)
 {
@@ -351,7 +373,7 @@ extern "C" int apd_batch_create(apd_context *ctx, const float *frames, const uin
     apd_batch *b = new (std::nothrow) apd_batch();
     if (!b) return APD_ERR_OOM;
     // resident frames carry kernel_dim(dim) >= dim components (zero fill: distances unchanged, dtw_common.h), then the squared norm
-    b->ctx = ctx; b->n_seq = n_seq; b->src_dim = dim; b->dim = kernel_dim(dim); b->dpad = (b->dim + 4) & ~3u; b->total_frames = total;
+    b->n_seq = n_seq; b->src_dim = dim; b->dim = kernel_dim(dim); b->dpad = (b->dim + 4) & ~3u; b->total_frames = total;
     b->min_len = 0xFFFFFFFFu; b->max_len = 0;
     for (uint32_t s = 0; s < n_seq; ++s) {
         if (offsets[s + 1] < offsets[s]) { delete b; return APD_ERR_INVALID_ARG; }
@@ -364,29 +386,10 @@ extern "C" int apd_batch_create(apd_context *ctx, const float *frames, const uin
     // one kernel geometry fits the whole tile -- and the most expensive tiles of a launch start first.
     length_order(offsets, n_seq, b->order);
     b->offsets.assign(n_seq + 1, 0);                                     // offsets of the RESIDENT order
-    // device metadata, one allocation and one copy: [seq_off | src_off | order | flags]
-    const size_t m1 = (size_t)n_seq + 1;
-    b->h_meta.assign(4 * m1 + 4, 0u);
-    uint32_t *off32 = b->h_meta.data(), *src32 = off32 + m1, *ord32 = src32 + m1;
-    for (uint32_t p = 0; p < n_seq; ++p) {
-        b->offsets[p + 1] = b->offsets[p] + (offsets[b->order[p] + 1] - offsets[b->order[p]]);
-        src32[p] = (uint32_t)offsets[b->order[p]];
-        ord32[p] = b->order[p];
-    }
-    for (uint32_t p = 0; p <= n_seq; ++p) off32[p] = (uint32_t)b->offsets[p] + 2 * p;   // two sentinel frames behind every sequence
-    auto fail = [&](int rc) { apd_batch_destroy(b); return rc; };
-    const uint64_t padded_frames = total + 2ull * n_seq;
-    const size_t padded_bytes = std::max<size_t>((size_t)padded_frames * b->dpad * sizeof(float), 16);
-    b->frames_bytes = padded_bytes < 0xFFFFFE00ull ? (uint32_t)padded_bytes : 0u;
-    if (hipMalloc((void **)&b->d_frames, padded_bytes) != hipSuccess) return fail(APD_ERR_OOM);
-    if (hipMalloc((void **)&b->d_meta, b->h_meta.size() * sizeof(uint32_t)) != hipSuccess) return fail(APD_ERR_OOM);
-    b->d_seq_off = b->d_meta; b->d_src_off = b->d_meta + m1; b->d_order = b->d_meta + 2 * m1; b->d_flags = b->d_meta + 3 * m1;
-    b->d_seq_nmax = reinterpret_cast<float *>(b->d_meta + 3 * m1 + 4);
-    if (hipMemcpyAsync(b->d_meta, b->h_meta.data(), b->h_meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(APD_ERR_HIP);                                         // h_meta lives as long as the batch: no sync needed
-    ctx->batches.insert(b);
-    const int rc_fill = apd_batch_refill(ctx, b, frames, frames_on_device);
-    if (rc_fill != APD_OK) return fail(rc_fill);
+    for (uint32_t p = 0; p < n_seq; ++p) b->offsets[p + 1] = b->offsets[p] + (offsets[b->order[p] + 1] - offsets[b->order[p]]);
+    int rc = batch_make_resident(ctx, b, offsets);
+    if (rc == APD_OK) rc = apd_batch_refill(ctx, b, frames, frames_on_device);
+    if (rc != APD_OK) { apd_batch_destroy(b); return rc; }
     *out = b;
     return APD_OK;
 }
@@ -398,21 +401,19 @@ extern "C" int apd_batch_refill(apd_context *ctx, apd_batch *b, const float *fra
     if (total > 0 && !frames) return APD_ERR_INVALID_ARG;
     HIP_TRY(ctx, bind_device(ctx));
     b->nonfinite = -1;
-    HIP_TRY(ctx, hipMemsetAsync(b->d_flags, 0, (4 + (size_t)b->n_seq + 1) * sizeof(uint32_t), ctx->stream));   // flags and the per-sequence norm maxima
+    HIP_TRY(ctx, hipMemsetAsync(b->d_flags, 0, meta_tail_words(b->n_seq) * sizeof(uint32_t), ctx->stream));   // flags and the per-sequence norm maxima
     if (padded_frames > 0) {
         const float *d_src = frames;
-        float *d_tmp = nullptr;
+        DeviceBuf tmp;                                                    // the caller's host frames on their way to the repack kernel
         const uint32_t dim = b->src_dim;
         if (!frames_on_device && total > 0) {
-            if (hipMalloc((void **)&d_tmp, (size_t)total * dim * sizeof(float)) != hipSuccess) return APD_ERR_OOM;
-            if (hipMemcpyAsync(d_tmp, frames, (size_t)total * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-                hipFree(d_tmp);
-                return APD_ERR_HIP;
-            }
-            d_src = d_tmp;
+            const size_t bytes = (size_t)total * dim * sizeof(float);
+            if (tmp.alloc(bytes) != hipSuccess) return APD_ERR_OOM;
+            if (hipMemcpyAsync(tmp.ptr, frames, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return APD_ERR_HIP;
+            d_src = tmp.as<float>();
         }
-        hipError_t e = launch_pad(d_src, b->d_frames, b->d_seq_off, b->d_src_off, b->n_seq, padded_frames, dim, b->dim, b->dpad, b->d_flags, b->d_seq_nmax, ctx->stream);
-        if (d_tmp) { hipStreamSynchronize(ctx->stream); hipFree(d_tmp); }
+        hipError_t e = launch_pad(d_src, b->d_frames.as<float>(), b->d_seq_off, b->d_src_off, b->n_seq, padded_frames, dim, b->dim, b->dpad, b->d_flags, b->d_seq_nmax, ctx->stream);
+        if (tmp) hipStreamSynchronize(ctx->stream);                       // the host frames and `tmp` are read until the repack is done
         if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
     }
     return APD_OK;
@@ -441,27 +442,15 @@ extern "C" int apd_batch_nonfinite(apd_context *ctx, const apd_batch *b, int *no
     return rc;
 }
 
-static void release_batch_device_memory(apd_batch *b)
+void apd_batch::release_device()
 {
-    for (auto &kv : b->tile_cache) if (kv.second.d_tiles) hipFree(kv.second.d_tiles);
-    b->tile_cache.clear();
-    if (b->d_frames) hipFree(b->d_frames);
-    if (b->d_meta) hipFree(b->d_meta);
-    b->d_frames = nullptr; b->d_meta = nullptr; b->d_seq_off = nullptr; b->d_src_off = nullptr; b->d_order = nullptr; b->d_flags = nullptr; b->d_seq_nmax = nullptr;
+    tile_cache.clear();
+    d_frames.reset();
+    d_meta.reset();
+    d_seq_off = nullptr; d_src_off = nullptr; d_order = nullptr; d_flags = nullptr; d_seq_nmax = nullptr;
 }
 
-extern "C" int apd_batch_destroy(apd_batch *b)
-{
-    if (!b) return APD_ERR_INVALID_ARG;
-    if (b->ctx) {                                                        // else: orphaned by apd_destroy, device memory already released
-        bind_device(b->ctx);
-        hipStreamSynchronize(b->ctx->stream);
-        release_batch_device_memory(b);
-        b->ctx->batches.erase(b);
-    }
-    delete b;
-    return APD_OK;
-}
+extern "C" int apd_batch_destroy(apd_batch *b) { return destroy_child(b); }
 
 extern "C" uint32_t apd_batch_len(const apd_batch *b) { return b ? b->n_seq : 0; }
 extern "C" uint32_t apd_batch_first_len(const apd_batch *b) { return !b ? 0 : b->joined ? b->first_len : b->n_seq; }
@@ -482,42 +471,31 @@ extern "C" int apd_batch_join(apd_context *ctx, const apd_batch *first, const ap
                          first->total_frames * second->n_seq < second->total_frames * first->n_seq;   // both factors below 2^32
     const apd_batch *seg[2] = {swapped ? second : first, swapped ? first : second};
     const uint32_t n_seq = (uint32_t)n_seq64, n0 = seg[0]->n_seq;
-    b->ctx = ctx; b->n_seq = n_seq; b->src_dim = first->src_dim; b->dim = first->dim; b->dpad = first->dpad; b->total_frames = total;
+    b->n_seq = n_seq; b->src_dim = first->src_dim; b->dim = first->dim; b->dpad = first->dpad; b->total_frames = total;
     b->joined = true; b->swapped = swapped; b->first_len = first->n_seq; b->seg0 = n0;
     b->min_len = n_seq ? 0xFFFFFFFFu : 0u; b->max_len = 0;
     for (const apd_batch *s : seg)
         if (s->n_seq) { b->min_len = std::min(b->min_len, s->min_len); b->max_len = std::max(b->max_len, s->max_len); }
-    // host metadata: each segment keeps its own resident (length) order; the second one is rebased behind the first
-    const size_t m1 = (size_t)n_seq + 1;
+    // each segment keeps its own resident (length) order; the second one is rebased behind the first
     b->order.resize(n_seq);
-    b->offsets.assign(m1, 0);
-    b->h_meta.assign(4 * m1 + 4, 0u);
-    uint32_t *off32 = b->h_meta.data(), *ord32 = off32 + 2 * m1;          // src_off stays zero: there is no caller array to refill from
-    const uint64_t padded0 = seg[0]->total_frames + 2ull * n0;            // padded frames of the first segment
+    b->offsets.assign((size_t)n_seq + 1, 0);
     for (uint32_t p = 0; p < n_seq; ++p) {
         const int k = p < n0 ? 0 : 1;
         const uint32_t q = p - (k ? n0 : 0u);                             // position inside its segment
         const bool is_second = (k == 1) != swapped;                       // does this segment hold the caller's second set?
         b->order[p] = seg[k]->order[q] + (is_second ? first->n_seq : 0u);
-        ord32[p] = b->order[p];
         b->offsets[p + 1] = b->offsets[p] + (seg[k]->offsets[q + 1] - seg[k]->offsets[q]);
     }
-    for (uint32_t p = 0; p <= n_seq; ++p) off32[p] = (uint32_t)b->offsets[p] + 2 * p;
     auto fail = [&](int rc) { apd_batch_destroy(b); return rc; };
-    const uint64_t padded_frames = total + 2ull * n_seq;
-    const size_t frame_bytes = (size_t)b->dpad * sizeof(float);
-    const size_t padded_bytes = std::max<size_t>((size_t)padded_frames * frame_bytes, 16);
-    b->frames_bytes = padded_bytes < 0xFFFFFE00ull ? (uint32_t)padded_bytes : 0u;
-    ctx->batches.insert(b);                                               // from here on apd_batch_destroy undoes everything
-    if (hipMalloc((void **)&b->d_frames, padded_bytes) != hipSuccess) return fail(APD_ERR_OOM);
-    if (hipMalloc((void **)&b->d_meta, b->h_meta.size() * sizeof(uint32_t)) != hipSuccess) return fail(APD_ERR_OOM);
-    b->d_seq_off = b->d_meta; b->d_src_off = b->d_meta + m1; b->d_order = b->d_meta + 2 * m1; b->d_flags = b->d_meta + 3 * m1;
-    b->d_seq_nmax = reinterpret_cast<float *>(b->d_meta + 3 * m1 + 4);
-    hipError_t e = hipMemcpyAsync(b->d_meta, b->h_meta.data(), b->h_meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (const int rc = batch_make_resident(ctx, b, nullptr); rc != APD_OK) return fail(rc);   // no caller array to refill from
     // frames (sentinels included) and per-sequence norm maxima: device to device, segment by segment, behind the metadata copy
+    const size_t frame_bytes = (size_t)b->dpad * sizeof(float);
+    const uint64_t padded0 = seg[0]->total_frames + 2ull * n0, padded_frames = total + 2ull * n_seq;
     const size_t bytes0 = (size_t)padded0 * frame_bytes, bytes1 = (size_t)(padded_frames - padded0) * frame_bytes;
-    if (e == hipSuccess && bytes0) e = hipMemcpyAsync(b->d_frames, seg[0]->d_frames, bytes0, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess && bytes1) e = hipMemcpyAsync((char *)b->d_frames + bytes0, seg[1]->d_frames, bytes1, hipMemcpyDeviceToDevice, ctx->stream);
+    char *d_dst = b->d_frames.as<char>();
+    hipError_t e = hipSuccess;
+    if (bytes0) e = hipMemcpyAsync(d_dst, seg[0]->d_frames.ptr, bytes0, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && bytes1) e = hipMemcpyAsync(d_dst + bytes0, seg[1]->d_frames.ptr, bytes1, hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess && n0) e = hipMemcpyAsync(b->d_seq_nmax, seg[0]->d_seq_nmax, (size_t)n0 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess && n_seq > n0)
         e = hipMemcpyAsync(b->d_seq_nmax + n0, seg[1]->d_seq_nmax, (size_t)(n_seq - n0) * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
@@ -606,47 +584,57 @@ static int check_lengths(const apd_batch *b)
     return APD_OK;
 }
 
-// The tile plan (device tile list + classes, plan_tile_classes) of one rank, cached in the batch.
-static int build_tile_plan(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint32_t rank, uint32_t world, bool cross,
-                           bool fast_ok, bool uniform_pen, bool fast_shift, apd_batch::TilePlan &plan_out)
+// Which tiles of a batch's pair matrix a call aligns, and what follows from that choice: the slab they fill and the prefix of the
+// tile plan's cache key.  Kernel choice, poison, fan-out, fallback and timing are one code path for both cases.
+struct TileSource {
+    bool cross;             // false: rank's share (every world-th tile) of the upper triangle; true: apd_align_cross's rectangle
+    uint32_t rank, world;   // cross: 0 of 1
+    static TileSource triangle(uint32_t rank, uint32_t world) { return {false, rank, world}; }
+    static TileSource cross_rectangle() { return {true, 0, 1}; }
+    void tiles(const apd_batch &b, std::vector<uint2> &out) const
+    {
+        if (cross) cross_tile_list(b.n_seq, b.seg0, out);
+        else rank_tile_list(b.n_seq, rank, world, out);
+    }
+    uint64_t num_tiles(const apd_batch &b) const                          // over all ranks
+    {
+        if (!cross) return apd_num_tiles(b.n_seq);
+        if (b.seg0 == 0 || b.seg0 >= b.n_seq) return 0;
+        return (uint64_t)tiles_side(b.seg0) * (tiles_side(b.n_seq) - b.seg0 / kTile);
+    }
+    uint64_t slab_floats(const apd_batch &b) const { return cross ? num_tiles(b) * 2 * kSlotsPerTile : apd_slab_floats(b.n_seq, world); }
+    std::string key_prefix() const { return (cross ? "cross/" : "") + std::to_string(rank) + "/" + std::to_string(world); }
+};
+
+// The tile plan (device tile list + classes, plan_tile_classes) of one tile source.
+static int build_tile_plan(apd_context *ctx, const apd_batch *batch, const BandSpec &band, const TileSource &src, bool fast_ok,
+                           bool uniform_pen, bool fast_shift, apd_batch::TilePlan &plan_out)
 {
     apd_batch::TilePlan plan;                                             // built locally, published only when complete
     std::vector<uint2> tiles;
-    if (cross) cross_tile_list(batch->n_seq, batch->seg0, tiles);
-    else rank_tile_list(batch->n_seq, rank, world, tiles);
+    src.tiles(*batch, tiles);
     std::vector<uint4> flat;
     plan_tile_classes(batch->offsets, batch->n_seq, tiles, band, batch->dim, ctx->variant, fast_ok, uniform_pen, fast_shift,
                       plan.classes, flat);
     if (std::getenv("APD_DEBUG_PLAN"))                                  // tuning aid: which kernel geometry got how many tiles
         for (const TileClass &tc : plan.classes)
-            std::fprintf(stderr, "[apd] rank %u/%u: geometry %d: %u tiles, w_max %u, n_max %u\n", rank, world, tc.geom.encode(), tc.count,
-                         tc.w_max, tc.n_max);
-    HIP_TRY(ctx, hipMalloc((void **)&plan.d_tiles, std::max<size_t>(flat.size(), 1) * sizeof(uint4)));
+            std::fprintf(stderr, "[apd] rank %u/%u: geometry %d: %u tiles, w_max %u, n_max %u\n", src.rank, src.world, tc.geom.encode(),
+                         tc.count, tc.w_max, tc.n_max);
+    HIP_TRY(ctx, plan.d_tiles.alloc(std::max<size_t>(flat.size(), 1) * sizeof(uint4)));
     if (!flat.empty()) {
-        hipError_t e = hipMemcpyAsync(plan.d_tiles, flat.data(), flat.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream);
+        hipError_t e = hipMemcpyAsync(plan.d_tiles.ptr, flat.data(), flat.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {                                            // never leave a half-made plan in the cache
-            hipFree(plan.d_tiles);
-            ctx->last_error = std::string("tile plan upload: ") + hipGetErrorString(e);
-            return APD_ERR_HIP;
-        }
+        if (e != hipSuccess) { ctx->last_error = std::string("tile plan upload: ") + hipGetErrorString(e); return APD_ERR_HIP; }
     }
     plan_out = std::move(plan);
     return APD_OK;
 }
 
-// `cross`: the tile rectangle of apd_align_cross (cross_tile_list, rank 0 of 1) instead of rank's share of the upper triangle; the
-// slab then holds cross_num_tiles tiles.  Everything else -- kernel choice, poison, fan-out, fallback, timing -- is one code path.
-static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint32_t rank,
-                            uint32_t world, float *d_slab, bool cross = false)
+// How one call chooses between the fast kernels and the literal one.  fast_ok: the plan may use the fast kernels; device_select:
+// ... and the batch's flag decides ON THE DEVICE whether they or the literal fallback behind them run.
+static int choose_align_mode(apd_context *ctx, const apd_batch *batch, const BandSpec &band, uint64_t n_tiles_all, bool &fast_ok,
+                             bool &device_select)
 {
-    if (!ctx || !batch || !d_slab || world == 0 || rank >= world || batch->ctx != ctx) return APD_ERR_INVALID_ARG;
-    if (cross && (!batch->joined || world != 1)) return APD_ERR_INVALID_ARG;
-    const uint64_t n_tiles_all = cross ? cross_num_tiles(batch->n_seq, batch->seg0) : apd_num_tiles(batch->n_seq);
-    const uint64_t slab_floats = cross ? n_tiles_all * 2 * kSlotsPerTile : apd_slab_floats(batch->n_seq, world);
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    HIP_TRY(ctx, bind_device(ctx));
     const bool pens_ok = (band.ins > 0.0f) && (band.del > 0.0f) && (band.mat > 0.0f) && (band.ins < INFINITY) &&
                          (band.del < INFINITY) && (band.mat < INFINITY);   // the systolic kernel needs pen * INF = INF
     // A feature outside the fast range anywhere in the batch (NaN, infinite, |v| >= kFeatureBound, or non-zero below kFeatureFloor)
@@ -657,53 +645,52 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     // wide that the generic kernel cannot hold it in LDS -- then the host reads the flag (a stream synchronisation), as the fast
     // kernels are the only ones that can run.
     const bool static_fast = pens_ok && batch->frames_bytes != 0;
-    bool nonfinite = false, device_select = false;
+    bool nonfinite = false;
+    device_select = false;
     if (static_fast) {
         const uint32_t band_ub = band.use_explicit ? band.explicit_band : host_band_from_pct(band.pct, batch->max_len);
         const uint32_t w_all = std::max(std::min(band_ub, batch->max_len), batch->max_len - batch->min_len) + 2;   // >= w of every pair
         device_select = generic_fallback_fits(w_all) && n_tiles_all * kSlotsPerTile <= 0xFFFFFFFFull;
-        if (!device_select) {
-            rc = batch_nonfinite(ctx, batch, &nonfinite);
-            if (rc) return rc;
-        }
+        if (!device_select)
+            if (const int rc = batch_nonfinite(ctx, batch, &nonfinite)) return rc;
     }
-    const bool fast_ok = static_fast && !nonfinite;
+    fast_ok = static_fast && !nonfinite;
+    return APD_OK;
+}
+
+// The cached plan of (tile source, band, everything the choice of kernels depends on); built on first use.
+static int tile_plan(apd_context *ctx, const apd_batch *batch, const BandSpec &band, const TileSource &src, bool fast_ok,
+                     const apd_batch::TilePlan **plan)
+{
     // strict mode: distances computed operation for operation as numerics.rs:114-120 in every kernel family.  The band kernels
     // keep the fast select with unit penalties (it picks the reference's predecessor for every non-NaN input: dtw_systolic.h, <.., true,
     // false>) and take the literal comparison chain with any others; the strip kernels go through their literal-select path, which
     // is why `uniform_pen` is cleared here -- it steers the strip / wide families only (plan_tile_classes, dtw_generic.hip).
     const bool strict = ctx->distance_mode == 2;
     const bool uniform_pen = (band.ins == band.del) && (band.del == band.mat) && !strict;
-    char keybuf[160];
-    uint32_t pct_bits;
-    std::memcpy(&pct_bits, &band.pct, sizeof(pct_bits));
     // the band kernel's hybrid form with unit penalties moves its column window with one DPP instruction per register at any
     // group size (dtw_systolic.h, MASKED_FETCH): 8- and 32-lane groups cost no more than 16- and 64-lane ones there
     const bool fast_shift = band.ins == 1.0f && band.del == 1.0f && band.mat == 1.0f && ctx->distance_mode == 1 && batch->dim >= 8;
-    std::snprintf(keybuf, sizeof(keybuf), "%s%u/%u/%08x/%u/%d/%d/%d/%d/%d", cross ? "cross/" : "", rank, world, pct_bits, band.explicit_band, band.use_explicit,
+    char keybuf[160];
+    uint32_t pct_bits;
+    std::memcpy(&pct_bits, &band.pct, sizeof(pct_bits));
+    std::snprintf(keybuf, sizeof(keybuf), "%s/%08x/%u/%d/%d/%d/%d/%d", src.key_prefix().c_str(), pct_bits, band.explicit_band, band.use_explicit,
                   ctx->variant, (int)fast_ok, (int)uniform_pen, (int)fast_shift);   // everything the choice of kernels depends on
     auto cached = batch->tile_cache.find(keybuf);
     if (cached == batch->tile_cache.end()) {
         apd_batch::TilePlan fresh;
-        rc = build_tile_plan(ctx, batch, band, rank, world, cross, fast_ok, uniform_pen, fast_shift, fresh);
-        if (rc) return rc;
+        if (const int rc = build_tile_plan(ctx, batch, band, src, fast_ok, uniform_pen, fast_shift, fresh)) return rc;
         cached = batch->tile_cache.emplace(keybuf, std::move(fresh)).first;
     }
-    const apd_batch::TilePlan &plan = cached->second;
-    // Poison: every score slot of the rank's slab starts as NaN, so a pair that no kernel writes (a launch cut short, a
-    // skipped class) reaches the matrix as NaN and raises APD_ERR_INCOMPLETE in the unpack -- never a stale or zero distance.
-    APD_AFFINITY(ctx, "alignment launches");
-    HIP_TRY(ctx, hipMemsetAsync(d_slab, 0xFF, slab_floats * sizeof(float), ctx->stream));
-    AlignLaunch L{};
-    L.d_frames = batch->d_frames; L.frames_bytes = batch->frames_bytes; L.d_seq_off = batch->d_seq_off; L.d_seq_nmax = batch->d_seq_nmax;
-    L.n_seq = batch->n_seq; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band; L.d_slab = d_slab;
-    L.variant = ctx->variant;
-    L.hybrid = ctx->distance_mode == 1; L.strict = strict; L.tau = ctx->tau;
-    L.d_nonfinite = device_select ? batch->d_flags : nullptr;
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    // Classes are independent (disjoint tiles, disjoint slab regions): with more than one, their launches are spread over
-    // side streams forked from and joined back into the context's stream, so that a class of a few tiles does not hold the
-    // GPU alone (a ragged banded corpus splits into a dozen geometries).
+    *plan = &cached->second;
+    return APD_OK;
+}
+
+// One launch per class of the plan.  Classes are independent (disjoint tiles, disjoint slab regions): with more than one, their
+// launches are spread over side streams forked from and joined back into the context's stream, so that a class of a few tiles
+// does not hold the GPU alone (a ragged banded corpus splits into a dozen geometries).
+static int launch_classes(apd_context *ctx, const apd_batch::TilePlan &plan, AlignLaunch L)
+{
     const bool fan_out = plan.classes.size() > 1 && ctx->side[0] != nullptr;
     if (fan_out) {
         HIP_TRY(ctx, hipEventRecord(ctx->fork, ctx->stream));
@@ -712,7 +699,7 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     int rc_launch = APD_OK;
     size_t ci = 0;
     for (const TileClass &tc : plan.classes) {
-        L.d_tiles = plan.d_tiles + tc.first; L.n_tiles = tc.count; L.w_max = tc.w_max; L.n_max = tc.n_max;
+        L.d_tiles = plan.d_tiles.as<uint4>() + tc.first; L.n_tiles = tc.count; L.w_max = tc.w_max; L.n_max = tc.n_max;
         if (ctx->drop_tiles) L.n_tiles -= std::min(L.n_tiles, ctx->drop_tiles);   // fault injection (apd_set_fault_injection)
         int status = APD_OK;
         hipStream_t s = fan_out ? ctx->side[ci++ % apd_context::kSideStreams] : ctx->stream;
@@ -725,25 +712,57 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
             HIP_TRY(ctx, hipEventRecord(ctx->side_done[k], ctx->side[k]));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done[k], 0));
         }
-    if (rc_launch != APD_OK) return rc_launch;
-    if (device_select) {
-        // the literal kernel behind the fast ones, idle unless the flag is raised -- over the classes a FAST kernel took (a class
-        // that already runs the literal kernel, geometry 0, ignores the flag and must not be aligned twice); neighbouring classes
-        // are contiguous in the tile list and share a launch
-        size_t k = 0;
-        while (k < plan.classes.size()) {
-            if (plan.classes[k].geom.family == KernelGeom::Generic) { ++k; continue; }
-            uint32_t first = plan.classes[k].first, total = 0, w_max = 0, n_max = 0;
-            for (; k < plan.classes.size() && plan.classes[k].geom.family != KernelGeom::Generic && plan.classes[k].first == first + total; ++k) {
-                total += plan.classes[k].count; w_max = std::max(w_max, plan.classes[k].w_max); n_max = std::max(n_max, plan.classes[k].n_max);
-            }
-            L.d_tiles = plan.d_tiles + first; L.n_tiles = total; L.w_max = w_max; L.n_max = n_max;
-            if (ctx->drop_tiles) L.n_tiles -= std::min(L.n_tiles, ctx->drop_tiles);
-            bool fits = true;
-            const hipError_t e = launch_generic_fallback(L, ctx->stream, &fits);
-            if (e != hipSuccess || !fits) { ctx->last_error = std::string("launch_generic_fallback: ") + (fits ? hipGetErrorString(e) : "band too wide"); return APD_ERR_HIP; }
+    return rc_launch;
+}
+
+// The literal kernel behind the fast ones (device_select), idle unless the flag is raised -- over the classes a FAST kernel took (a
+// class that already runs the literal kernel, geometry 0, ignores the flag and must not be aligned twice); neighbouring classes
+// are contiguous in the tile list and share a launch.
+static int launch_literal_fallback(apd_context *ctx, const apd_batch::TilePlan &plan, AlignLaunch L)
+{
+    size_t k = 0;
+    while (k < plan.classes.size()) {
+        if (plan.classes[k].geom.family == KernelGeom::Generic) { ++k; continue; }
+        uint32_t first = plan.classes[k].first, total = 0, w_max = 0, n_max = 0;
+        for (; k < plan.classes.size() && plan.classes[k].geom.family != KernelGeom::Generic && plan.classes[k].first == first + total; ++k) {
+            total += plan.classes[k].count; w_max = std::max(w_max, plan.classes[k].w_max); n_max = std::max(n_max, plan.classes[k].n_max);
         }
+        L.d_tiles = plan.d_tiles.as<uint4>() + first; L.n_tiles = total; L.w_max = w_max; L.n_max = n_max;
+        if (ctx->drop_tiles) L.n_tiles -= std::min(L.n_tiles, ctx->drop_tiles);
+        bool fits = true;
+        const hipError_t e = launch_generic_fallback(L, ctx->stream, &fits);
+        if (e != hipSuccess || !fits) { ctx->last_error = std::string("launch_generic_fallback: ") + (fits ? hipGetErrorString(e) : "band too wide"); return APD_ERR_HIP; }
     }
+    return APD_OK;
+}
+
+static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, const TileSource &src, float *d_slab)
+{
+    if (!ctx || !batch || !d_slab || src.world == 0 || src.rank >= src.world || batch->ctx != ctx) return APD_ERR_INVALID_ARG;
+    if (src.cross && !batch->joined) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    HIP_TRY(ctx, bind_device(ctx));
+    bool fast_ok = false, device_select = false;
+    rc = choose_align_mode(ctx, batch, band, src.num_tiles(*batch), fast_ok, device_select);
+    if (rc) return rc;
+    const apd_batch::TilePlan *plan = nullptr;
+    rc = tile_plan(ctx, batch, band, src, fast_ok, &plan);
+    if (rc) return rc;
+    // Poison: every score slot of the rank's slab starts as NaN, so a pair that no kernel writes (a launch cut short, a
+    // skipped class) reaches the matrix as NaN and raises APD_ERR_INCOMPLETE in the unpack -- never a stale or zero distance.
+    APD_AFFINITY(ctx, "alignment launches");
+    HIP_TRY(ctx, hipMemsetAsync(d_slab, 0xFF, src.slab_floats(*batch) * sizeof(float), ctx->stream));
+    AlignLaunch L{};
+    L.d_frames = batch->d_frames.as<float>(); L.frames_bytes = batch->frames_bytes; L.d_seq_off = batch->d_seq_off; L.d_seq_nmax = batch->d_seq_nmax;
+    L.n_seq = batch->n_seq; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band; L.d_slab = d_slab;
+    L.variant = ctx->variant;
+    L.hybrid = ctx->distance_mode == 1; L.strict = ctx->distance_mode == 2; L.tau = ctx->tau;
+    L.d_nonfinite = device_select ? batch->d_flags : nullptr;
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    rc = launch_classes(ctx, *plan, L);
+    if (rc == APD_OK && device_select) rc = launch_literal_fallback(ctx, *plan, L);
+    if (rc) return rc;
     if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
     return APD_OK;
 }
@@ -760,7 +779,7 @@ extern "C" int apd_align_tiles_async(apd_context *ctx, const apd_batch *batch, c
                                      uint32_t rank, uint32_t world, float *d_slab)
 {
     if (!cfg) return APD_ERR_INVALID_ARG;
-    return align_tiles_impl(ctx, batch, band_from_cfg(cfg), rank, world, d_slab);
+    return align_tiles_impl(ctx, batch, band_from_cfg(cfg), TileSource::triangle(rank, world), d_slab);
 }
 
 extern "C" int apd_unpack_tiles_async(apd_context *ctx, const apd_batch *batch, uint32_t world, const float *d_gathered,
@@ -781,11 +800,25 @@ static int align_all_device_impl(apd_context *ctx, const apd_batch *batch, const
 {
     if (!ctx || !batch || !d_out) return APD_ERR_INVALID_ARG;
     const size_t slab_bytes = std::max<size_t>(apd_slab_floats(batch->n_seq, 1) * sizeof(float), 16);
-    int rc = ensure_ws(ctx, &ctx->ws_slab, &ctx->ws_slab_bytes, slab_bytes);
+    int rc = reserve_ws(ctx, ctx->ws_slab, slab_bytes);
     if (rc) return rc;
-    rc = align_tiles_impl(ctx, batch, band, 0, 1, (float *)ctx->ws_slab);
+    rc = align_tiles_impl(ctx, batch, band, TileSource::triangle(0, 1), ctx->ws_slab.as<float>());
     if (rc) return rc;
-    return apd_unpack_tiles_async(ctx, batch, 1, (const float *)ctx->ws_slab, d_out);
+    return apd_unpack_tiles_async(ctx, batch, 1, ctx->ws_slab.as<float>(), d_out);
+}
+
+// The end of a blocking entry point: given the status of what was enqueued so far, the copies of the results to the host (entries
+// without a destination are skipped), then the wait and the device's verdict (sync_and_report).
+struct ReadBack { void *dst; const void *d_src; size_t bytes; };
+static int read_back(apd_context *ctx, int rc, std::initializer_list<ReadBack> copies)
+{
+    if (rc != APD_OK) return rc;
+    for (const ReadBack &c : copies) {
+        if (!c.dst) continue;
+        const hipError_t e = hipMemcpyAsync(c.dst, c.d_src, c.bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
+    }
+    return sync_and_report(ctx);                                          // APD_ERR_INCOMPLETE: the outputs hold NaN where no score was written
 }
 
 extern "C" int apd_align_all_device_async(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg,
@@ -801,16 +834,10 @@ extern "C" int apd_align_all(apd_context *ctx, const apd_batch *batch, const apd
     if (batch->n_seq == 0) return APD_OK;
     HIP_TRY(ctx, bind_device(ctx));
     const size_t bytes = (size_t)batch->n_seq * batch->n_seq * sizeof(float);
-    float *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_out, bytes));
-    int rc = align_all_device_impl(ctx, batch, band_from_cfg(cfg), d_out);
-    if (rc == APD_OK) {
-        hipError_t e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; }
-        else rc = sync_and_report(ctx);                                   // APD_ERR_INCOMPLETE: `out` holds NaN where no score was written
-    }
-    hipFree(d_out);
-    return rc;
+    DeviceBuf d_out;
+    HIP_TRY(ctx, d_out.alloc(bytes));
+    const int rc = align_all_device_impl(ctx, batch, band_from_cfg(cfg), d_out.as<float>());
+    return read_back(ctx, rc, {{out, d_out.ptr, bytes}});
 }
 
 // ------------------------------------------------------------------------------ cross alignment
@@ -818,17 +845,17 @@ extern "C" int apd_align_all(apd_context *ctx, const apd_batch *batch, const apd
 static int align_cross_device_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, float *d_fs, float *d_sf)
 {
     const uint32_t n_first = batch->first_len, n_second = batch->n_seq - n_first;
-    const size_t slab_bytes = std::max<size_t>(cross_num_tiles(batch->n_seq, batch->seg0) * 2 * kSlotsPerTile * sizeof(float), 16);
-    int rc = ensure_ws(ctx, &ctx->ws_slab, &ctx->ws_slab_bytes, slab_bytes);
+    const TileSource src = TileSource::cross_rectangle();
+    int rc = reserve_ws(ctx, ctx->ws_slab, std::max<size_t>(src.slab_floats(*batch) * sizeof(float), 16));
     if (rc) return rc;
-    rc = align_tiles_impl(ctx, batch, band, 0, 1, (float *)ctx->ws_slab, true);
+    rc = align_tiles_impl(ctx, batch, band, src, ctx->ws_slab.as<float>());
     if (rc) return rc;
     APD_AFFINITY(ctx, "unpack launch");
     // the unpack writes every entry; anything it fails to write stays NaN
     const size_t out_bytes = (size_t)n_first * n_second * sizeof(float);
     if (d_fs) HIP_TRY(ctx, hipMemsetAsync(d_fs, 0xFF, out_bytes, ctx->stream));
     if (d_sf) HIP_TRY(ctx, hipMemsetAsync(d_sf, 0xFF, out_bytes, ctx->stream));
-    HIP_TRY(ctx, launch_unpack_cross((const float *)ctx->ws_slab, d_fs, d_sf, batch->d_order, batch->n_seq, batch->seg0, n_first,
+    HIP_TRY(ctx, launch_unpack_cross(ctx->ws_slab.as<float>(), d_fs, d_sf, batch->d_order, batch->n_seq, batch->seg0, n_first,
                                      batch->swapped, batch->d_flags, ctx->d_status, ctx->stream));
     return APD_OK;
 }
@@ -850,22 +877,14 @@ extern "C" int apd_align_cross(apd_context *ctx, const apd_batch *batch, const a
     if (!out_fs && !out_sf) return APD_ERR_INVALID_ARG;
     HIP_TRY(ctx, bind_device(ctx));
     const size_t bytes = (size_t)batch->first_len * (batch->n_seq - batch->first_len) * sizeof(float);
-    float *d_out = nullptr;                                               // [fs | sf]
-    HIP_TRY(ctx, hipMalloc((void **)&d_out, 2 * bytes));
-    float *d_fs = out_fs ? d_out : nullptr, *d_sf = out_sf ? d_out + bytes / sizeof(float) : nullptr;
-    int rc = align_cross_device_impl(ctx, batch, band_from_cfg(cfg), d_fs, d_sf);
-    if (rc == APD_OK) {
-        hipError_t e = hipSuccess;
-        if (out_fs) e = hipMemcpyAsync(out_fs, d_fs, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && out_sf) e = hipMemcpyAsync(out_sf, d_sf, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; }
-        else rc = sync_and_report(ctx);                                   // APD_ERR_INCOMPLETE: the outputs hold NaN where no score was written
-    }
-    hipFree(d_out);
-    return rc;
+    DeviceBuf d_out;                                                      // [fs | sf]
+    HIP_TRY(ctx, d_out.alloc(2 * bytes));
+    float *d_fs = out_fs ? d_out.as<float>() : nullptr, *d_sf = out_sf ? d_out.as<float>() + bytes / sizeof(float) : nullptr;
+    const int rc = align_cross_device_impl(ctx, batch, band_from_cfg(cfg), d_fs, d_sf);
+    return read_back(ctx, rc, {{out_fs, d_fs, bytes}, {out_sf, d_sf, bytes}});
 }
 
-// Linkage of the first set to clusters of the second (kernels: clustering.hip).  Workspace (ws_tiles, owned by the context so that
+// Linkage of the first set to clusters of the second (kernels: clustering.hip).  Workspace (ws_linkage, owned by the context so that
 // the device form only enqueues): [members | set_off | link fs, sf].
 extern "C" int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on_device, uint32_t n_first, uint32_t n_second,
                                  const uint32_t *members, const uint32_t *set_off, uint32_t n_sets, float *link_fs, float *link_sf,
@@ -891,9 +910,9 @@ extern "C" int apd_cross_linkage(apd_context *ctx, const float *fs, const float 
     size_t need = meta_bytes + 2 * link_floats * sizeof(float);
     const size_t in_off = (need + 255) & ~(size_t)255;
     if (!on_device) need = in_off + 2 * mat_bytes + res_bytes;
-    int rc = ensure_ws(ctx, &ctx->ws_tiles, &ctx->ws_tiles_bytes, std::max<size_t>(need, 256));
+    int rc = reserve_ws(ctx, ctx->ws_linkage, std::max<size_t>(need, 256));
     if (rc) return rc;
-    char *base = (char *)ctx->ws_tiles;
+    char *base = ctx->ws_linkage.as<char>();
     uint32_t *d_members = (uint32_t *)base, *d_set_off = d_members + n_members;
     float *d_link = (float *)(base + meta_bytes);
     HIP_TRY(ctx, hipMemcpyAsync(d_members, stage.data(), stage.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -965,16 +984,11 @@ extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, cons
     if (rc) return rc;
     apd_batch *b = ctx->pair_batch;
     const BandSpec band = band_from_params(params);
-    rc = ensure_ws(ctx, &ctx->ws_misc, &ctx->ws_misc_bytes, 256);
+    rc = reserve_ws(ctx, ctx->ws_misc, 256);
     if (rc) return rc;
-    float *d_out = (float *)ctx->ws_misc;
-    rc = align_all_device_impl(ctx, b, band, d_out);
+    float *d_out = ctx->ws_misc.as<float>();
     float host[4] = {0, 0, 0, 0};
-    if (rc == APD_OK) {
-        hipError_t e = hipMemcpyAsync(host, d_out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; }
-        else rc = sync_and_report(ctx);
-    }
+    rc = read_back(ctx, align_all_device_impl(ctx, b, band, d_out), {{host, d_out, sizeof(host)}});
     if (rc == APD_OK) *score = host[1];                                   // out[0*2+1] = score(x, y)
     return rc;
 }
@@ -1047,16 +1061,16 @@ static int align_paths_impl(apd_context *ctx, const apd_batch *batch, const Band
         const uint64_t np = last - first;
         // steps workspace: [steps | pair descriptors | lengths | scores]
         const size_t steps_bytes = (size_t)slots * sizeof(apd_path_step), desc_bytes = (size_t)np * sizeof(PathPair);
-        rc = ensure_ws(ctx, &ctx->ws_path_dirs, &ctx->ws_path_dirs_bytes, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
+        rc = reserve_ws(ctx, ctx->ws_path_dirs, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
         if (rc) return rc;
-        rc = ensure_ws(ctx, &ctx->ws_path_steps, &ctx->ws_path_steps_bytes, steps_bytes + desc_bytes + (size_t)np * 8 + 16);
+        rc = reserve_ws(ctx, ctx->ws_path_steps, steps_bytes + desc_bytes + (size_t)np * 8 + 16);
         if (rc) return rc;
-        char *base = (char *)ctx->ws_path_steps;
+        char *base = ctx->ws_path_steps.as<char>();
         PathLaunch L{};
-        L.d_frames = batch->d_frames; L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
+        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
         L.d_pairs = (const PathPair *)(base + steps_bytes);
         L.n_pairs = (uint32_t)np;
-        L.d_dirs = (uint32_t *)ctx->ws_path_dirs;
+        L.d_dirs = ctx->ws_path_dirs.as<uint32_t>();
         L.d_steps = (apd_path_step *)base;
         L.d_len = (uint32_t *)(base + steps_bytes + desc_bytes);
         L.d_scores = (float *)(base + steps_bytes + desc_bytes + (size_t)np * 4);

@@ -306,11 +306,42 @@ hipError_t launch_sqrt_sweep(uint32_t first, uint64_t count, unsigned long long 
 constexpr float kFeatureFloor = 0x1p-40f;
 constexpr float kFeatureBound = 0x1p60f;
 
-// comm.hip: called by apd_destroy for every communicator still alive on the context
-void orphan_comm(apd_comm *comm);
-// companions.hip: likewise for the resident feature objects
-void orphan_encoder(apd_encoder *enc);
-void orphan_cepstrum_plan(apd_cepstrum_plan *plan);
+// ---- ownership of device memory.  Whatever the library allocates for itself lives in a DeviceBuf: a move-only owner of ONE hipMalloc
+// allocation, released by reset() or the destructor -- so an early return (HIP_TRY) between an allocation and its release leaks
+// nothing.  Frees are plain hipFree (which waits for the device); the device of the owning context must be bound when one runs.
+// Buffers handed to the caller (apd_device_alloc) are not DeviceBufs: they are the caller's to free.
+struct DeviceBuf {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }   // (no copies: the moves suppress them)
+    DeviceBuf &operator=(DeviceBuf &&o) noexcept { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); return *this; }   // o's destructor frees the old one
+    ~DeviceBuf() { reset(); }
+    hipError_t reset() { const hipError_t e = ptr ? hipFree(ptr) : hipSuccess; ptr = nullptr; bytes = 0; return e; }
+    // a fresh allocation of n bytes (whatever was held is released first)
+    hipError_t alloc(size_t n)
+    {
+        if (hipError_t e = reset(); e != hipSuccess) return e;
+        if (hipError_t e = hipMalloc(&ptr, n); e != hipSuccess) { ptr = nullptr; return e; }
+        bytes = n;
+        return hipSuccess;
+    }
+    // at least n bytes; grows only, and growth discards the contents
+    hipError_t reserve(size_t n) { return ptr && bytes >= n ? hipSuccess : alloc(n); }
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+    explicit operator bool() const { return ptr != nullptr; }
+};
+
+// ---- objects made on a context that may outlive it (destruction order is the caller's, e.g. a garbage collector's): batches,
+// communicators, encoders, cepstrum plans.  While the context lives, it lists them in apd_context::children and the object's
+// destroy entry point (destroy_child) releases the device side and takes it off the list.  apd_destroy calls release_device() on
+// every child still listed and clears its `ctx`: the later destroy call then only deletes the host part.
+struct ContextChild {
+    apd_context *ctx = nullptr;
+    virtual void release_device() = 0;   // frees device memory / tears the RCCL handle down; host fields stay
+    virtual ~ContextChild() = default;
+};
+int destroy_child(ContextChild *child);   // the shared body of apd_batch_destroy, apd_comm_destroy, ... (apd_api.hip)
 
 // numerics.rs:125-133 on a device array (clustering.hip): radix select of the k-th smallest non-NaN value.
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value);
@@ -367,14 +398,8 @@ struct apd_context {
     hipStream_t side[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t side_done[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fork = nullptr;
-    // batches created on this context and not yet destroyed: apd_destroy releases their device memory and orphans them, so
-    // that a later apd_batch_destroy (destruction order is the caller's, e.g. a garbage collector's) only frees the host part
-    std::set<apd_batch *> batches;
-    // communicators made on this context and not yet destroyed: apd_destroy tears their RCCL side down and orphans them, so
-    // that a later apd_comm_destroy only frees the host part (same contract as for batches)
-    std::set<apd_comm *> comms;
-    std::set<apd_encoder *> encoders;                 // resident feature objects (companions.hip), same contract
-    std::set<apd_cepstrum_plan *> cepstrum_plans;
+    // batches, communicators, encoders and cepstrum plans made on this context and not yet destroyed (see apd::ContextChild)
+    std::set<apd::ContextChild *> children;
     // buffers handed out by apd_device_alloc and not yet freed: apd_destroy releases them (a host whose destructors run in any
     // order -- a garbage collector's -- may free a buffer after its context: apd_device_free on a destroyed context is never
     // called by the mirrors, and nothing leaks)
@@ -384,13 +409,13 @@ struct apd_context {
     int distance_mode = 1;            // 0 exact differences, 1 hybrid, 2 strict (bit-identical to the CPU arithmetic)
     float tau = 1.0f / 64.0f;
     std::string last_error;
-    // reusable device workspaces
-    void *ws_tiles = nullptr; size_t ws_tiles_bytes = 0;
-    void *ws_slab = nullptr; size_t ws_slab_bytes = 0;
-    void *ws_misc = nullptr; size_t ws_misc_bytes = 0;
-    void *ws_gather = nullptr; size_t ws_gather_bytes = 0;   // gathered slabs of apd_align_all_sharded_async
-    void *ws_path_dirs = nullptr; size_t ws_path_dirs_bytes = 0;     // apd_align_paths: direction words of a chunk of pairs
-    void *ws_path_steps = nullptr; size_t ws_path_steps_bytes = 0;   // ... its steps, then [pairs | lengths | scores]
+    // reusable device workspaces, grown through reserve_ws
+    apd::DeviceBuf ws_linkage;        // apd_cross_linkage: [members | set_off | link fs, sf], then the host form's staging
+    apd::DeviceBuf ws_slab;
+    apd::DeviceBuf ws_misc;
+    apd::DeviceBuf ws_gather;         // gathered slabs of apd_align_all_sharded_async
+    apd::DeviceBuf ws_path_dirs;      // apd_align_paths: direction words of a chunk of pairs
+    apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat
@@ -398,14 +423,21 @@ struct apd_context {
     uint32_t pair_dim = 0;
 };
 
-struct apd_batch {
-    apd_context *ctx = nullptr;
+// Grows a workspace of the context to `need` bytes (contents are lost when it grows; the hipFree of the old one waits for the device).
+inline int reserve_ws(apd_context *ctx, apd::DeviceBuf &ws, size_t need)
+{
+    APD_AFFINITY(ctx, "workspace allocation");
+    HIP_TRY(ctx, ws.reserve(need));
+    return APD_OK;
+}
+
+struct apd_batch : apd::ContextChild {
     uint32_t n_seq = 0, dim = 0, dpad = 0;   // dim: resident (kernel) frame dimension, >= src_dim
     uint32_t src_dim = 0;                    // the caller's frame dimension
     uint64_t total_frames = 0;
-    float *d_frames = nullptr;        // padded layout with sentinels (see dtw_generic.hip)
+    apd::DeviceBuf d_frames;          // floats: padded layout with sentinels (see dtw_generic.hip)
     uint32_t frames_bytes = 0;
-    uint32_t *d_meta = nullptr;       // ONE allocation: [seq_off n+1 | src_off n+1 | order n+1 | flags 4 | nmax n+1], filled by one copy of h_meta
+    apd::DeviceBuf d_meta;            // ONE allocation, filled by one copy of h_meta; layout: batch_make_resident (apd_api.hip)
     std::vector<uint32_t> h_meta;     // host image of d_meta, alive as long as the batch (the H2D copy is asynchronous)
     uint32_t *d_seq_off = nullptr;
     uint32_t *d_src_off = nullptr;    // first frame of resident sequence p in the caller's frame array
@@ -421,6 +453,7 @@ struct apd_batch {
     bool joined = false, swapped = false;
     uint32_t first_len = 0, seg0 = 0;
     // device-resident tile lists, grouped by the kernel geometry each tile needs
-    struct TilePlan { uint4 *d_tiles = nullptr; std::vector<apd::TileClass> classes; };
-    mutable std::map<std::string, TilePlan> tile_cache;   // keyed by rank/world/band/variant
+    struct TilePlan { apd::DeviceBuf d_tiles; std::vector<apd::TileClass> classes; };   // d_tiles: uint4 per tile
+    mutable std::map<std::string, TilePlan> tile_cache;   // keyed by tile source/band/variant (tile_plan, apd_api.hip)
+    void release_device() override;
 };

@@ -38,16 +38,16 @@ namespace {
 
 // Everything an entry point of this file allocates or instantiates: whatever is set is released however the call ends.
 struct Owned {
-    void *ws = nullptr;                               // apd_clustering's workspace, apd_percentile's copy of its input, device_select's histogram
-    float *spare = nullptr;                           // two more n x n buffers: the defragmented copies rotate through d_T and these
-    unsigned long long *dbg = nullptr;                // APD_DEBUG_UPGMA_TIMING stamps
+    DeviceBuf ws;                                     // apd_clustering's workspace, apd_percentile's copy of its input, device_select's histogram
+    DeviceBuf spare;                                  // two more n x n float buffers: the defragmented copies rotate through d_T and these
+    DeviceBuf dbg;                                    // APD_DEBUG_UPGMA_TIMING stamps
     hipGraph_t graph[2] = {nullptr, nullptr};         // the two captured batches
     hipGraphExec_t exec[2] = {nullptr, nullptr};
     void drop_graphs()
     {
         for (int g = 0; g < 2; ++g) { if (exec[g]) hipGraphExecDestroy(exec[g]); if (graph[g]) hipGraphDestroy(graph[g]); exec[g] = nullptr; graph[g] = nullptr; }
     }
-    ~Owned() { drop_graphs(); for (void *p : {(void *)dbg, (void *)spare, ws}) if (p) hipFree(p); }
+    ~Owned() { drop_graphs(); }                       // then the buffers, last declared first
 };
 
 // ---------------------------------------------------------------------------------- radix select
@@ -83,8 +83,8 @@ namespace apd {
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value)
 {
     Owned own;
-    HIP_TRY(ctx, hipMalloc(&own.ws, 257 * sizeof(unsigned long long)));
-    unsigned long long *d_hist = static_cast<unsigned long long *>(own.ws);
+    HIP_TRY(ctx, own.ws.alloc(257 * sizeof(unsigned long long)));
+    unsigned long long *d_hist = own.ws.as<unsigned long long>();
     uint32_t prefix = 0, mask = 0;
     uint64_t rank = k;
     unsigned long long h[257];
@@ -1401,10 +1401,10 @@ extern "C" int apd_percentile(apd_context *ctx, const float *x, uint64_t len, fl
     const float *d_x = x;
     Owned own;
     if (!x_on_device) {
-        HIP_TRY(ctx, hipMalloc(&own.ws, len * sizeof(float)));
-        hipError_t e = hipMemcpyAsync(own.ws, x, len * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+        HIP_TRY(ctx, own.ws.alloc(len * sizeof(float)));
+        hipError_t e = hipMemcpyAsync(own.ws.ptr, x, len * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return APD_ERR_HIP; }
-        d_x = static_cast<const float *>(own.ws);
+        d_x = own.ws.as<float>();
     }
     return device_select(ctx, d_x, len, k, value);
 }
@@ -1449,8 +1449,8 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
         carve(st.packed, st.pack_capacity); carve(d_T, nn); carve(st.phys, n); carve(st.dsrc, n); carve(st.doff, n); carve(words, 1);
         return off;
     };
-    HIP_TRY(ctx, hipMalloc(&own.ws, lay_out(0)));
-    lay_out((uintptr_t)own.ws);
+    HIP_TRY(ctx, own.ws.alloc(lay_out(0)));
+    lay_out((uintptr_t)own.ws.ptr);
     st.n_live = &words->n_live; st.n_ops = &words->n_ops; st.done = &words->done; st.work = &words->work; st.last_sp = &words->last_sp;
     st.last_sq = &words->last_sq; st.n_items = &words->n_items; st.pack_used = &words->pack_used; st.n_stale = &words->n_stale;
     st.arrive = &words->arrive; st.r_pending = &words->r_pending; st.n_big = &words->n_big; st.pool_used = &words->pool_used;
@@ -1475,14 +1475,14 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
     e = hipMemcpyAsync((void *)words->mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return hip_error(e);
     // without the two spare buffers, or the LDS the staged permutation needs, the loop simply runs without defragmentation
-    if (sw.defrag_period && hipMalloc((void **)&own.spare, 2 * nn * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); own.spare = nullptr; sw.defrag_period = 0; }
+    if (sw.defrag_period && own.spare.alloc(2 * nn * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); sw.defrag_period = 0; }
     std::vector<float *> free_bufs;                                       // buffers not holding a working copy right now
-    if (own.spare) { free_bufs.push_back(own.spare + nn); free_bufs.push_back(own.spare); }
+    if (own.spare) { free_bufs.push_back(own.spare.as<float>() + nn); free_bufs.push_back(own.spare.as<float>()); }
     const bool permute_staged = (size_t)n * sizeof(float) <= 128 * 1024;
     if (sw.defrag_period && permute_staged &&
         hipFuncSetAttribute((const void *)upgma_permute_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)n * sizeof(float))) != hipSuccess) {
         (void)hipGetLastError();
-        hipFree(own.spare); own.spare = nullptr; sw.defrag_period = 0;
+        own.spare.reset(); sw.defrag_period = 0;
     }
     auto defragment = [&]() {
         hipLaunchKernelGGL(upgma_defrag_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, st);
@@ -1498,9 +1498,9 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
         h_mat[2] = h_mat[0];                                              // "defragmented": any non-null word
         return hipMemcpyAsync((void *)words->mat, h_mat, sizeof(h_mat), hipMemcpyHostToDevice, ctx->stream);
     };
-    if (sw.timing && hipMalloc((void **)&own.dbg, (size_t)n * kStamps * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemsetAsync(own.dbg, 0, (size_t)n * kStamps * sizeof(unsigned long long), ctx->stream);
-    st.dbg = own.dbg;
+    if (sw.timing && own.dbg.alloc((size_t)n * kStamps * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemsetAsync(own.dbg.ptr, 0, own.dbg.bytes, ctx->stream);
+    st.dbg = own.dbg.as<unsigned long long>();
     e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_error(e);
     // The merge loop is launch-bound (three short dependent launches per merge): a batch of merges is captured once into a
@@ -1574,7 +1574,7 @@ extern "C" int apd_clustering(apd_context *ctx, const float *distances, int dist
     const uint32_t cnt = h.n_ops;
     if (own.dbg) {
         std::vector<unsigned long long> g((size_t)n * kStamps);
-        if (hipMemcpy(g.data(), own.dbg, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess && cnt > 1) report_timing(g.data(), cnt);
+        if (hipMemcpy(g.data(), own.dbg.ptr, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess && cnt > 1) report_timing(g.data(), cnt);
     }
     std::vector<uint32_t> ids(n), live(h.n_live);
     e = hipMemcpyAsync(ops, st.ops, (size_t)cnt * sizeof(apd_cluster_op), hipMemcpyDeviceToHost, ctx->stream);

@@ -23,10 +23,10 @@
 
 static_assert(sizeof(ncclUniqueId) == APD_COMM_ID_BYTES, "apd.h promises 128-byte communicator ids");
 
-struct apd_comm {
+struct apd_comm : apd::ContextChild {   // ctx: the context (device, stream) this end of the communicator belongs to
     ncclComm_t comm = nullptr;
-    apd_context *ctx = nullptr;       // the context (device, stream) this end of the communicator belongs to
     uint32_t rank = 0, world = 1;
+    void release_device() override { if (comm) ncclCommDestroy(comm); comm = nullptr; }
 };
 
 namespace {
@@ -39,16 +39,6 @@ namespace {
             return APD_ERR_COMM;                                                       \
         }                                                                              \
     } while (0)
-
-int ensure_gather(apd_context *ctx, size_t need)
-{
-    APD_AFFINITY(ctx, "gather workspace allocation");
-    if (ctx->ws_gather && ctx->ws_gather_bytes >= need) return APD_OK;
-    if (ctx->ws_gather) { HIP_TRY(ctx, hipFree(ctx->ws_gather)); ctx->ws_gather = nullptr; ctx->ws_gather_bytes = 0; }
-    HIP_TRY(ctx, hipMalloc(&ctx->ws_gather, need));
-    ctx->ws_gather_bytes = need;
-    return APD_OK;
-}
 
 }  // namespace
 
@@ -77,32 +67,12 @@ extern "C" int apd_comm_create(apd_context *ctx, const void *id_bytes, uint32_t 
         delete c;
         return APD_ERR_COMM;
     }
-    ctx->comms.insert(c);
+    ctx->children.insert(c);
     *out = c;
     return APD_OK;
 }
 
-namespace apd {
-void orphan_comm(apd_comm *c)                                            // the context is going away (apd_destroy)
-{
-    if (c->comm) ncclCommDestroy(c->comm);
-    c->comm = nullptr;
-    c->ctx = nullptr;
-}
-}  // namespace apd
-
-extern "C" int apd_comm_destroy(apd_comm *c)
-{
-    if (!c) return APD_ERR_INVALID_ARG;
-    if (c->ctx) {                                                        // else: orphaned by apd_destroy, RCCL side already gone
-        apd::bind_device(c->ctx);
-        hipStreamSynchronize(c->ctx->stream);
-        if (c->comm) ncclCommDestroy(c->comm);
-        c->ctx->comms.erase(c);
-    }
-    delete c;
-    return APD_OK;
-}
+extern "C" int apd_comm_destroy(apd_comm *c) { return apd::destroy_child(c); }
 
 extern "C" int apd_comm_count(const apd_comm *c, uint32_t *world)
 {
@@ -141,9 +111,9 @@ extern "C" int apd_align_all_sharded_async(apd_context *ctx, apd_comm *c, const 
     if (c->ctx != ctx) return APD_ERR_INVALID_ARG;
     if (batch->n_seq == 0) return APD_OK;
     const uint64_t slab = apd_slab_floats(batch->n_seq, c->world);
-    int rc = ensure_gather(ctx, std::max<size_t>((size_t)slab * c->world * sizeof(float), 16));
+    int rc = reserve_ws(ctx, ctx->ws_gather, std::max<size_t>((size_t)slab * c->world * sizeof(float), 16));
     if (rc) return rc;
-    float *gathered = (float *)ctx->ws_gather, *mine = gathered + (size_t)slab * c->rank;
+    float *gathered = ctx->ws_gather.as<float>(), *mine = gathered + (size_t)slab * c->rank;
     rc = apd_align_tiles_async(ctx, batch, cfg, c->rank, c->world, mine);
     if (rc) return rc;
     NCCL_TRY(ctx, ncclAllGather(mine, gathered, (size_t)slab, ncclFloat, c->comm, ctx->stream));
@@ -241,8 +211,7 @@ struct apd_multi {
     bool gathered_valid = false;
     std::string collective, last_error;
     std::set<apd_multi_batch *> batches;
-    float *d_result = nullptr;                     // matrix owned by the handle (apd_multi_align_all_async with d_out == NULL)
-    size_t result_bytes = 0;
+    apd::DeviceBuf d_result;                       // matrix owned by the handle (apd_multi_align_all_async with d_out == NULL), on devices[0]
     const float *last_result = nullptr;
     WorkerPool *pool = nullptr;
 };
@@ -345,7 +314,7 @@ extern "C" int apd_multi_destroy(apd_multi *m)
     for (ncclComm_t c : m->comms) if (c) ncclCommDestroy(c);
     for (uint32_t i = 0; i < m->slab_ready.size(); ++i) if (m->slab_ready[i] && m->ctx[i]) { apd::bind_device(m->ctx[i]); hipEventDestroy(m->slab_ready[i]); }
     if (m->gathered && m->ctx[0]) { apd::bind_device(m->ctx[0]); hipEventDestroy(m->gathered); }
-    if (m->d_result && m->ctx[0]) { apd::bind_device(m->ctx[0]); hipFree(m->d_result); }
+    if (m->ctx[0]) { apd::bind_device(m->ctx[0]); m->d_result.reset(); }
     for (apd_context *c : m->ctx) if (c) apd_destroy(c);
     delete m;
     return APD_OK;
@@ -420,21 +389,20 @@ static int apd_multi_align_all_async_impl(apd_multi *m, const apd_multi_batch *m
     const size_t gather_bytes = std::max<size_t>((size_t)slab * n * sizeof(float), 16);
     if (!d_out) {                                                          // the handle's own result matrix on devices[0]
         const size_t need = (size_t)n_seq * n_seq * sizeof(float);
-        if (m->result_bytes < need) {
+        if (m->d_result.bytes < need) {
             apd::bind_device(m->ctx[0]);
-            if (m->d_result) { hipStreamSynchronize(m->ctx[0]->stream); hipFree(m->d_result); m->d_result = nullptr; m->result_bytes = 0; }
-            if (hipMalloc((void **)&m->d_result, need) != hipSuccess) return multi_fail(m, APD_ERR_OOM, "device " + std::to_string(m->devices[0]) + ": result matrix");
-            m->result_bytes = need;
+            if (m->d_result) hipStreamSynchronize(m->ctx[0]->stream);
+            if (m->d_result.reserve(need) != hipSuccess) return multi_fail(m, APD_ERR_OOM, "device " + std::to_string(m->devices[0]) + ": result matrix");
         }
-        d_out = m->d_result;
+        d_out = m->d_result.as<float>();
     }
     const bool peer = m->comms.empty();
     if (peer && m->gathered_valid) {
-        // A larger batch than the last one makes ensure_gather free and re-allocate a device's gather buffer -- while devices[0]'s
+        // A larger batch than the last one makes reserve_ws free and re-allocate a device's gather buffer -- while devices[0]'s
         // stream may still be copying the previous slab out of it (hipFree drains only the owning device's streams).  Wait for that
         // gather on the host first; the common case (same size again) never gets here.
         bool grows = false;
-        for (uint32_t i = 0; i < n; ++i) grows |= m->ctx[i]->ws_gather_bytes < gather_bytes;
+        for (uint32_t i = 0; i < n; ++i) grows |= m->ctx[i]->ws_gather.bytes < gather_bytes;
         if (grows) {
             apd::bind_device(m->ctx[0]);
             if (hipEventSynchronize(m->gathered) != hipSuccess) return multi_fail(m, APD_ERR_HIP, "hipEventSynchronize(gathered)");
@@ -445,11 +413,11 @@ static int apd_multi_align_all_async_impl(apd_multi *m, const apd_multi_batch *m
     m->pool->run(n, [&](uint32_t i) -> int {
         apd_context *c = m->ctx[i];
         if (apd::bind_device(c) != hipSuccess) return (int)APD_ERR_HIP;      // worker threads have their own current device
-        int r = ensure_gather(c, gather_bytes);
+        int r = reserve_ws(c, c->ws_gather, gather_bytes);
         if (r != APD_OK) return r;
         // peer fallback: devices[0] must have copied this device's previous slab before it is poisoned again
         if (peer && i != 0 && m->gathered_valid && hipStreamWaitEvent(c->stream, m->gathered, 0) != hipSuccess) return (int)APD_ERR_HIP;
-        r = apd_align_tiles_async(c, mb->per_device[i], cfg, i, n, (float *)c->ws_gather + (size_t)slab * i);
+        r = apd_align_tiles_async(c, mb->per_device[i], cfg, i, n, c->ws_gather.as<float>() + (size_t)slab * i);
         if (r == APD_OK && peer) {
             APD_AFFINITY(c, "slab_ready event record");
             if (hipEventRecord(m->slab_ready[i], c->stream) != hipSuccess) r = APD_ERR_HIP;
@@ -462,7 +430,7 @@ static int apd_multi_align_all_async_impl(apd_multi *m, const apd_multi_batch *m
     if (!peer) {
         ncclResult_t r = ncclGroupStart();
         for (uint32_t i = 0; i < n && r == ncclSuccess; ++i) {
-            float *g = (float *)m->ctx[i]->ws_gather;
+            float *g = m->ctx[i]->ws_gather.as<float>();
             apd::bind_device(m->ctx[i]);
             r = ncclAllGather(g + (size_t)slab * i, g, (size_t)slab, ncclFloat, m->comms[i], m->ctx[i]->stream);
         }
@@ -472,9 +440,9 @@ static int apd_multi_align_all_async_impl(apd_multi *m, const apd_multi_batch *m
     } else {
         apd_context *c0 = m->ctx[0];
         apd::bind_device(c0);
-        float *g0 = (float *)c0->ws_gather;
+        float *g0 = c0->ws_gather.as<float>();
         for (uint32_t i = 1; i < n; ++i) {
-            const float *gi = (const float *)m->ctx[i]->ws_gather + (size_t)slab * i;
+            const float *gi = m->ctx[i]->ws_gather.as<float>() + (size_t)slab * i;
             if (hipStreamWaitEvent(c0->stream, m->slab_ready[i], 0) != hipSuccess ||
                 hipMemcpyPeerAsync(g0 + (size_t)slab * i, c0->device, gi, m->ctx[i]->device, (size_t)slab * sizeof(float), c0->stream) != hipSuccess)
                 return multi_fail(m, APD_ERR_HIP, "device " + std::to_string(m->devices[i]) + ": peer copy of the slab failed");
@@ -483,7 +451,7 @@ static int apd_multi_align_all_async_impl(apd_multi *m, const apd_multi_batch *m
         m->gathered_valid = true;
     }
     // 3. unpack on devices[0] (rank 0 is the consumer: UPGMA runs there)
-    st = apd_unpack_tiles_async(m->ctx[0], mb->per_device[0], n, (const float *)m->ctx[0]->ws_gather, d_out);
+    st = apd_unpack_tiles_async(m->ctx[0], mb->per_device[0], n, m->ctx[0]->ws_gather.as<float>(), d_out);
     if (st != APD_OK) { rc.assign(n, APD_OK); rc[0] = st; return merge_status(m, rc); }
     m->last_result = d_out;
     return APD_OK;

@@ -325,27 +325,21 @@ extern "C" int apd_interesting_ranges(apd_context *ctx, const float *frames, uin
     const uint64_t kidx = apd::percentile_index(t, perc);
     if (t == 0 || kidx >= t) return APD_ERR_INDEX;                      // percentile of an empty / too short vector panics (numerics.rs:132)
     HIP_TRY(ctx, apd::bind_device(ctx));
-    char *pool = nullptr;
+    apd::DeviceBuf pool;                                                                      // [deltas | variance | host frames]
     const size_t in_bytes = on_device ? 0 : (size_t)t * n_bins * sizeof(float), v_bytes = ((size_t)t * sizeof(float) + 255) & ~(size_t)255;
-    HIP_TRY(ctx, hipMalloc((void **)&pool, 2 * v_bytes + in_bytes + 256));
-    float *d_deltas = (float *)pool, *d_var = (float *)(pool + v_bytes);
-    const float *d_frames = on_device ? frames : (const float *)(pool + 2 * v_bytes);
-    int rc = APD_OK;
-    auto guard = [&](hipError_t e) { if (e != hipSuccess && rc == APD_OK) { ctx->last_error = hipGetErrorString(e); rc = APD_ERR_HIP; } };
-    if (!on_device) guard(hipMemcpyAsync(pool + 2 * v_bytes, frames, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, pool.alloc(2 * v_bytes + in_bytes + 256));
+    float *d_deltas = pool.as<float>(), *d_var = (float *)(pool.as<char>() + v_bytes);
+    const float *d_frames = on_device ? frames : (const float *)(pool.as<char>() + 2 * v_bytes);
+    if (!on_device) HIP_TRY(ctx, hipMemcpyAsync(pool.as<char>() + 2 * v_bytes, frames, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const unsigned blocks = (unsigned)std::min<uint64_t>((t + 255) / 256, 8192);
-    if (rc == APD_OK) {
-        hipLaunchKernelGGL(frame_std_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_frames, t, n_bins, d_deltas);
-        hipLaunchKernelGGL(moving_mean_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_deltas, t, moving_average, d_var);
-        guard(hipGetLastError());
-    }
+    hipLaunchKernelGGL(frame_std_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_frames, t, n_bins, d_deltas);
+    hipLaunchKernelGGL(moving_mean_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_deltas, t, moving_average, d_var);
+    HIP_TRY(ctx, hipGetLastError());
     float th = 0.0f;
-    if (rc == APD_OK) rc = apd::device_select(ctx, d_var, t, kidx, &th);                    // :198
+    if (const int rc = apd::device_select(ctx, d_var, t, kidx, &th)) return rc;               // :198
     std::vector<float> var(t);
-    if (rc == APD_OK) guard(hipMemcpyAsync(var.data(), d_var, (size_t)t * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    guard(hipStreamSynchronize(ctx->stream));
-    hipFree(pool);
-    if (rc != APD_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(var.data(), d_var, (size_t)t * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t start = 0, cnt = 0;
     bool recording = true;                                                                    // :202 (the scan starts "recording")
     for (uint64_t i = 0; i < t; ++i) {
@@ -367,25 +361,20 @@ extern "C" int apd_interesting_ranges(apd_context *ctx, const float *frames, uin
 // device runs the whole corpus' feature kernel concurrently (replicated, not sharded: the kernels take 0.15 ms (cfg 4) and 19 ms
 // (cfg 5) for the WHOLE corpus, less than an all-gather of their 134 MB / 1.74 GB output over xGMI would).
 
-struct apd_encoder {
-    apd_context *ctx = nullptr;
-    float *d_w = nullptr;             // [d_in][latent] weights, then [latent] bias
+struct apd_encoder : apd::ContextChild {
+    apd::DeviceBuf d_w;               // floats: [d_in][latent] weights, then [latent] bias
     uint32_t d_in = 0, latent = 0;
+    void release_device() override { d_w.reset(); }
 };
 
-struct apd_cepstrum_plan {
-    apd_context *ctx = nullptr;
-    char *pool = nullptr;             // tables | sample offsets | frame offsets
+struct apd_cepstrum_plan : apd::ContextChild {
+    apd::DeviceBuf pool;              // tables | sample offsets | frame offsets
     CepsParams P{};                   // samples / out filled per call
     size_t lds_bytes = 0;
     unsigned blocks = 0;
     uint64_t n_samples = 0;
+    void release_device() override { pool.reset(); }
 };
-
-namespace apd {
-void orphan_encoder(apd_encoder *e) { if (e->d_w) hipFree(e->d_w); e->d_w = nullptr; e->ctx = nullptr; }
-void orphan_cepstrum_plan(apd_cepstrum_plan *p) { if (p->pool) hipFree(p->pool); p->pool = nullptr; p->ctx = nullptr; }
-}  // namespace apd
 
 extern "C" int apd_encoder_create(apd_context *ctx, const float *w_encode, const float *b_encode, uint32_t d_in, uint32_t latent, apd_encoder **out)
 {
@@ -397,33 +386,22 @@ extern "C" int apd_encoder_create(apd_context *ctx, const float *w_encode, const
     apd_encoder *e = new (std::nothrow) apd_encoder();
     if (!e) return APD_ERR_OOM;
     e->ctx = ctx; e->d_in = d_in; e->latent = latent;
-    hipError_t err = hipMalloc((void **)&e->d_w, wb_bytes);
-    if (err == hipSuccess) err = hipMemcpyAsync(e->d_w, w_encode, (size_t)d_in * latent * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(e->d_w + (size_t)d_in * latent, b_encode, latent * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    hipError_t err = e->d_w.alloc(wb_bytes);
+    float *d_w = e->d_w.as<float>();
+    if (err == hipSuccess) err = hipMemcpyAsync(d_w, w_encode, (size_t)d_in * latent * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_w + (size_t)d_in * latent, b_encode, latent * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);      // the host arrays are the caller's: done with them on return
     if (err != hipSuccess) {
         ctx->last_error = std::string("apd_encoder_create: ") + hipGetErrorString(err);
-        if (e->d_w) hipFree(e->d_w);
         delete e;
         return err == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;
     }
-    ctx->encoders.insert(e);
+    ctx->children.insert(e);
     *out = e;
     return APD_OK;
 }
 
-extern "C" int apd_encoder_destroy(apd_encoder *e)
-{
-    if (!e) return APD_ERR_INVALID_ARG;
-    if (e->ctx) {                                                         // else: orphaned by apd_destroy, device side already gone
-        apd::bind_device(e->ctx);
-        hipStreamSynchronize(e->ctx->stream);
-        if (e->d_w) hipFree(e->d_w);
-        e->ctx->encoders.erase(e);
-    }
-    delete e;
-    return APD_OK;
-}
+extern "C" int apd_encoder_destroy(apd_encoder *e) { return apd::destroy_child(e); }
 
 extern "C" int apd_encode_async(apd_context *ctx, const apd_encoder *e, const float *d_x, uint64_t t, float *d_out)
 {
@@ -432,6 +410,7 @@ extern "C" int apd_encode_async(apd_context *ctx, const apd_encoder *e, const fl
     HIP_TRY(ctx, apd::bind_device(ctx));
     APD_AFFINITY(ctx, "encoder launch");
     const uint32_t d_in = e->d_in, latent = e->latent;
+    const float *d_w = e->d_w.as<float>();
     const unsigned blocks = (unsigned)std::min<uint64_t>((t + 255) / 256, 8192);
     // staged through LDS when the 4 x 64 staged rows fit next to the weights (they do for every shape the reference produces)
     const size_t staged_bytes = (((size_t)d_in * latent + latent + 3) & ~(size_t)3) * sizeof(float) +
@@ -440,12 +419,28 @@ extern "C" int apd_encode_async(apd_context *ctx, const apd_encoder *e, const fl
         std::fprintf(stderr, "[apd] encoder %u -> %u: %s, %zu bytes of LDS\n", d_in, latent, staged_bytes <= 64 * 1024 ? "staged" : "direct",
                      staged_bytes <= 64 * 1024 ? staged_bytes : ((size_t)d_in * latent + latent) * sizeof(float));
     if (staged_bytes <= 64 * 1024)
-        hipLaunchKernelGGL(encode_staged_kernel, dim3(blocks), dim3(256), staged_bytes, ctx->stream, d_x, t, d_in, e->d_w,
-                           e->d_w + (size_t)d_in * latent, latent, d_out);
+        hipLaunchKernelGGL(encode_staged_kernel, dim3(blocks), dim3(256), staged_bytes, ctx->stream, d_x, t, d_in, d_w,
+                           d_w + (size_t)d_in * latent, latent, d_out);
     else
-        hipLaunchKernelGGL(encode_kernel, dim3(blocks), dim3(256), ((size_t)d_in * latent + latent) * sizeof(float), ctx->stream, d_x, t, d_in, e->d_w,
-                           e->d_w + (size_t)d_in * latent, latent, d_out);
+        hipLaunchKernelGGL(encode_kernel, dim3(blocks), dim3(256), ((size_t)d_in * latent + latent) * sizeof(float), ctx->stream, d_x, t, d_in, d_w,
+                           d_w + (size_t)d_in * latent, latent, d_out);
     HIP_TRY(ctx, hipGetLastError());
+    return APD_OK;
+}
+
+// The encoder over host arrays (through temporary device buffers) or device arrays (as they are); blocking either way.
+static int encode_blocking(apd_context *ctx, const apd_encoder *e, const float *x, uint64_t t, int on_device, float *out)
+{
+    apd::DeviceBuf d_x, d_out;
+    const size_t in_bytes = t * e->d_in * sizeof(float), out_bytes = t * e->latent * sizeof(float);
+    if (!on_device) {
+        HIP_TRY(ctx, d_x.alloc(in_bytes));
+        HIP_TRY(ctx, d_out.alloc(out_bytes));
+        HIP_TRY(ctx, hipMemcpyAsync(d_x.ptr, x, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (const int rc = apd_encode_async(ctx, e, on_device ? x : d_x.as<float>(), t, on_device ? out : d_out.as<float>())) return rc;
+    if (!on_device) HIP_TRY(ctx, hipMemcpyAsync(out, d_out.ptr, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 
@@ -459,19 +454,8 @@ extern "C" int apd_encode(apd_context *ctx, const float *x, uint64_t t, uint32_t
     apd_encoder *e = nullptr;
     int rc = apd_encoder_create(ctx, w_encode, b_encode, d_in, latent, &e);
     if (rc != APD_OK) return rc;
-    float *d_x = nullptr, *d_out = nullptr;
-    auto guard = [&](hipError_t err) { if (err != hipSuccess && rc == APD_OK) { ctx->last_error = hipGetErrorString(err); rc = err == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP; } };
-    if (!on_device) {
-        guard(hipMalloc((void **)&d_x, t * d_in * sizeof(float)));
-        if (rc == APD_OK) guard(hipMalloc((void **)&d_out, t * latent * sizeof(float)));
-        if (rc == APD_OK) guard(hipMemcpyAsync(d_x, x, t * d_in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (rc == APD_OK) rc = apd_encode_async(ctx, e, on_device ? x : d_x, t, on_device ? out : d_out);
-    if (!on_device && rc == APD_OK) guard(hipMemcpyAsync(out, d_out, t * latent * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    guard(hipStreamSynchronize(ctx->stream));
-    if (d_x) hipFree(d_x);
-    if (d_out) hipFree(d_out);
-    apd_encoder_destroy(e);
+    rc = encode_blocking(ctx, e, x, t, on_device, out);
+    apd_encoder_destroy(e);                                               // waits for the stream, also after a failure
     return rc;
 }
 
@@ -543,16 +527,17 @@ extern "C" int apd_cepstrum_plan_create(apd_context *ctx, const uint64_t *sample
     plan->n_samples = sample_off[n_seq];
     const size_t tab_bytes = tab.size() * sizeof(float), off_bytes = 2 * ((size_t)n_seq + 1) * sizeof(uint64_t);
     const size_t offs_off = (tab_bytes + 255) & ~(size_t)255;
-    hipError_t err = hipMalloc((void **)&plan->pool, offs_off + off_bytes + 256);
-    if (err == hipSuccess) err = hipMemcpyAsync(plan->pool, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(plan->pool + offs_off, sample_off, off_bytes / 2, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(plan->pool + offs_off + off_bytes / 2, frame_off, off_bytes / 2, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t err = plan->pool.alloc(offs_off + off_bytes + 256);
+    char *pool = plan->pool.as<char>();
+    if (err == hipSuccess) err = hipMemcpyAsync(pool, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(pool + offs_off, sample_off, off_bytes / 2, hipMemcpyHostToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(pool + offs_off + off_bytes / 2, frame_off, off_bytes / 2, hipMemcpyHostToDevice, ctx->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);                     // `tab` and the caller's offsets are free after this
     CepsParams &P = plan->P;
-    P.sample_off = reinterpret_cast<const uint64_t *>(plan->pool + offs_off);
+    P.sample_off = reinterpret_cast<const uint64_t *>(pool + offs_off);
     P.frame_off = P.sample_off + n_seq + 1;
     P.n_seq = n_seq; P.n_frames = T; P.fft = fft_size; P.step = fft_step; P.L = L; P.fstep = fstep; P.K = K; P.log2n = log2n;
-    const float *d_tab = reinterpret_cast<const float *>(plan->pool);
+    const float *d_tab = reinterpret_cast<const float *>(pool);
     P.hamming = d_tab; P.triag = d_tab + fft_size; P.dct = d_tab + fft_size + L;
     P.twiddle = reinterpret_cast<const float2 *>(d_tab + tw_off);
     // LDS of a workgroup, laid out as the kernel reads it: hamming | triag | dct (if kept in LDS) | twiddles, then waves x
@@ -583,24 +568,13 @@ extern "C" int apd_cepstrum_plan_create(apd_context *ctx, const uint64_t *sample
         ctx->last_error = "apd_cepstrum_plan_create: the runtime refused the kernel its LDS";
         status = APD_ERR_HIP;
     }
-    if (status != APD_OK) { if (plan->pool) hipFree(plan->pool); delete plan; return status; }
-    ctx->cepstrum_plans.insert(plan);
+    if (status != APD_OK) { delete plan; return status; }
+    ctx->children.insert(plan);
     *out = plan;
     return APD_OK;
 }
 
-extern "C" int apd_cepstrum_plan_destroy(apd_cepstrum_plan *plan)
-{
-    if (!plan) return APD_ERR_INVALID_ARG;
-    if (plan->ctx) {
-        apd::bind_device(plan->ctx);
-        hipStreamSynchronize(plan->ctx->stream);
-        if (plan->pool) hipFree(plan->pool);
-        plan->ctx->cepstrum_plans.erase(plan);
-    }
-    delete plan;
-    return APD_OK;
-}
+extern "C" int apd_cepstrum_plan_destroy(apd_cepstrum_plan *plan) { return apd::destroy_child(plan); }
 
 extern "C" int apd_cepstrum_batch_async(apd_context *ctx, const apd_cepstrum_plan *plan, const int16_t *d_samples, float *d_out)
 {
@@ -613,6 +587,22 @@ extern "C" int apd_cepstrum_batch_async(apd_context *ctx, const apd_cepstrum_pla
     P.samples = d_samples; P.out = d_out;
     hipLaunchKernelGGL(cepstrum_kernel, dim3(plan->blocks), dim3(64 * P.waves), plan->lds_bytes, ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
+    return APD_OK;
+}
+
+// The plan over host arrays (through temporary device buffers) or device arrays (as they are); blocking either way.
+static int cepstrum_blocking(apd_context *ctx, const apd_cepstrum_plan *plan, const int16_t *samples, size_t in_bytes, int on_device,
+                             float *out, size_t out_bytes)
+{
+    apd::DeviceBuf d_in, d_o;
+    if (!on_device) {
+        HIP_TRY(ctx, d_in.alloc(in_bytes));
+        HIP_TRY(ctx, d_o.alloc(out_bytes));
+        HIP_TRY(ctx, hipMemcpyAsync(d_in.ptr, samples, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (const int rc = apd_cepstrum_batch_async(ctx, plan, on_device ? samples : d_in.as<int16_t>(), on_device ? out : d_o.as<float>())) return rc;
+    if (!on_device) HIP_TRY(ctx, hipMemcpyAsync(out, d_o.ptr, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 
@@ -630,20 +620,8 @@ static int cepstrum_impl(apd_context *ctx, const int16_t *samples, const uint64_
     apd_cepstrum_plan *plan = nullptr;
     rc = apd_cepstrum_plan_create(ctx, sample_off, n_seq, fft_size, fft_step, filter_size, frame_off, n_bins, &plan);
     if (rc != APD_OK) return rc;
-    int16_t *d_in = nullptr;
-    float *d_o = nullptr;
-    auto guard = [&](hipError_t e) { if (e != hipSuccess && rc == APD_OK) { ctx->last_error = hipGetErrorString(e); rc = e == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP; } };
-    if (!on_device) {
-        guard(hipMalloc((void **)&d_in, n_samples * sizeof(int16_t)));
-        if (rc == APD_OK) guard(hipMalloc((void **)&d_o, T * (K - 4) * sizeof(float)));
-        if (rc == APD_OK) guard(hipMemcpyAsync(d_in, samples, n_samples * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (rc == APD_OK) rc = apd_cepstrum_batch_async(ctx, plan, on_device ? samples : d_in, on_device ? out : d_o);
-    if (!on_device && rc == APD_OK) guard(hipMemcpyAsync(out, d_o, T * (K - 4) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    guard(hipStreamSynchronize(ctx->stream));
-    if (d_in) hipFree(d_in);
-    if (d_o) hipFree(d_o);
-    apd_cepstrum_plan_destroy(plan);
+    rc = cepstrum_blocking(ctx, plan, samples, n_samples * sizeof(int16_t), on_device, out, T * (K - 4) * sizeof(float));
+    apd_cepstrum_plan_destroy(plan);                                      // waits for the stream, also after a failure
     return rc;
 }
 
