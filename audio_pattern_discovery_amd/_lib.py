@@ -50,6 +50,11 @@ class PathStep(C.Structure):
 APD_PATH_MATCH, APD_PATH_INSERT, APD_PATH_DELETE, APD_PATH_START = 0, 1, 2, 3
 
 
+class SpotBest(C.Structure):
+    """apd_spot_best: a matched window of a stream -- 1-based columns of its last and first frame, the bits of T[n][end], the score."""
+    _fields_ = [("end", C.c_uint32), ("start", C.c_uint32), ("cost", C.c_float), ("score", C.c_float)]
+
+
 class MatView(C.Structure):
     """apd_mat_view: where a Mat { flat, cols } (numerics.rs:171-174) lies in a bincode image."""
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64), ("cols", C.c_uint64)]
@@ -158,6 +163,8 @@ SYMBOLS = [
                                   _u32p, _f32p]),
     ("apd_align_pair_path", C.c_int, [_vp, _f32p, C.c_uint64, _f32p, C.c_uint64, C.c_uint32, C.POINTER(AlignmentParamsC),
                                       C.POINTER(PathStep), C.c_uint64, _u64p, _f32p]),
+    ("apd_spot", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, _f32p, _u32p, C.c_uint64, _u64p, C.POINTER(SpotBest)]),
+    ("apd_spot_hits", C.c_int, [_f32p, _u32p, C.c_uint64, C.c_uint64, C.c_float, C.POINTER(SpotBest), C.c_uint64, _u64p]),
     ("apd_percentile", C.c_int, [_vp, _vp, C.c_uint64, C.c_float, C.c_int, _f32p]),
     ("apd_clustering", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_float, C.POINTER(ClusterOp), _u32p, _u32p,
                                  _u32p, _f32p]),

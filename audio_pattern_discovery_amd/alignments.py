@@ -90,6 +90,8 @@ class AlignmentParams:
 
 # apd_path_step as a numpy record: what Alignment.path() and AlignmentWorkers.paths() return
 PATH_STEP = np.dtype([("i", np.uint32), ("j", np.uint32), ("cost", np.float32), ("op", np.uint32)])
+# apd_spot_best as a numpy record: what AlignmentWorkers.spot() and spot_hits() return
+SPOT_BEST = np.dtype([("end", np.uint32), ("start", np.uint32), ("cost", np.float32), ("score", np.float32)])
 
 
 class Alignment:
@@ -254,6 +256,36 @@ class AlignmentWorkers:
                                      lens.ctypes.data_as(u32p), scores.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_pairs)], scores
 
+    def spot(self, pairs, params, curves=True, streams=None):
+        """Subsequence alignment (include/apd.h, "subsequence alignment"): every (query, stream) pair of `pairs` -- this object's
+        sequence numbers, or, with `streams` (an AlignmentWorkers of the same context), numbers of the two joined: below len(self.data)
+        this object's, the others `streams`' -- params: Discovery (penalties only: there is no band).  Returns (list of (cost, start)
+        arrays in input order, `best` as a SPOT_BEST array); the list is empty with curves=False: apd_spot."""
+        if self._multi is not None or (streams is not None and streams._multi is not None):
+            raise ValueError("spot() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_pairs = len(pr)
+        L = _lib.lib()
+        off = np.zeros(n_pairs + 1, dtype=np.uint64)
+        best = np.zeros(n_pairs, dtype=SPOT_BEST)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
+        try:
+            head = (self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs)
+            tail = (off.ctypes.data_as(u64p), best.ctypes.data_as(C.POINTER(_lib.SpotBest)))
+            if not curves:
+                _lib.check(L.apd_spot(*head, None, None, 0, *tail), self.ctx.handle)
+                return [], best
+            _lib.check(L.apd_spot(*head, None, None, 0, tail[0], None), self.ctx.handle)          # sizes
+            cost = np.zeros(max(int(off[-1]), 1), dtype=np.float32)
+            start = np.zeros(len(cost), dtype=np.uint32)
+            _lib.check(L.apd_spot(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
+        finally:
+            if streams is not None:
+                batch.close()
+        return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(n_pairs)], best
+
     def cross(self, other, params):
         """Aligns this object's sequences against `other`'s (an AlignmentWorkers of the same context), params: Discovery.  Returns
         (fs [n1][n2], sf [n2][n1]): fs[q][c] = score(x = self q, y = other c), sf[c][q] = score(x = other c, y = self q):
@@ -279,6 +311,22 @@ class AlignmentWorkers:
         if self._multi is not None:
             self._multi.close()
             self._multi = None
+
+
+def spot_hits(cost, start, n, threshold):
+    """apd_spot_hits: greedy non-overlapping peak picking on one pair's curves (query of n frames): the windows whose score is
+    strictly below `threshold`, best first, as a SPOT_BEST array.  Host only."""
+    cost = np.ascontiguousarray(cost, dtype=np.float32)
+    start = np.ascontiguousarray(start, dtype=np.uint32)
+    if cost.shape != start.shape or cost.ndim != 1:
+        raise ValueError("cost and start are the two curves of one pair")
+    L = _lib.lib()
+    args = (cost.ctypes.data_as(C.POINTER(C.c_float)), start.ctypes.data_as(C.POINTER(C.c_uint32)), len(cost), int(n), float(threshold))
+    count = C.c_uint64(0)
+    _lib.check(L.apd_spot_hits(*args, None, 0, C.byref(count)))
+    hits = np.zeros(count.value, dtype=SPOT_BEST)
+    _lib.check(L.apd_spot_hits(*args, hits.ctypes.data_as(C.POINTER(_lib.SpotBest)), len(hits), C.byref(count)))
+    return hits
 
 
 def align_work(offsets, dim, cfg, rank=0, world=1):

@@ -1117,6 +1117,154 @@ extern "C" int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n,
     return rc;
 }
 
+// ------------------------------------------------------------------------- subsequence alignment
+
+// Cap of the device curves of one chunk of pairs (bytes).
+static uint64_t spot_workspace_cap()
+{
+    if (const char *v = std::getenv("APD_SPOT_WORKSPACE_BYTES")) {
+        const unsigned long long b = std::strtoull(v, nullptr, 10);
+        if (b > 0) return b;
+    }
+    return 1ull << 30;
+}
+
+extern "C" int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+                        float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off, apd_spot_best *best)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || !curve_off || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
+    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
+    const uint32_t n_seq = batch->n_seq;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    curve_off[0] = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) curve_off[p + 1] = curve_off[p] + len_of(pairs[2 * p + 1]);
+    const bool curves = cost != nullptr;
+    if (!curves && !best) return APD_OK;                                  // sizes only
+    if (curves && capacity < curve_off[n_pairs]) return APD_ERR_INVALID_ARG;
+    if (n_pairs == 0) return APD_OK;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (len_of(pairs[2 * p]) > kSpotMaxQuery || len_of(pairs[2 * p + 1]) >= kSpotMaxStream) {
+            ctx->last_error = "apd_spot: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
+            return APD_ERR_UNSUPPORTED;
+        }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot launch");
+    const uint64_t cap = spot_workspace_cap();
+    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // 64 work-items per pair, launches stay below 2^31
+    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
+    std::vector<apd_spot_best> best_sink;
+    if (!best) best_sink.resize(n_pairs);
+    apd_spot_best *h_best = best ? best : best_sink.data();
+    std::vector<SpotPair> desc;
+    bool first_chunk = true;
+    for (uint64_t first = 0; first < n_pairs;) {
+        // the chunk [first, last): at least one pair, then as many as keep the curves under the cap
+        uint64_t last = first, entries = 0;
+        while (last < n_pairs && last - first < kMaxPairsPerLaunch) {
+            const uint64_t ne = entries + (curve_off[last + 1] - curve_off[last]);
+            if (curves && last > first && ne * (sizeof(float) + sizeof(uint32_t)) > cap) break;
+            entries = ne;
+            ++last;
+        }
+        const uint64_t np = last - first;
+        // the chunk's descriptors, grouped by kernel class (one launch each); `out` keeps the input order
+        uint64_t class_count[kClasses] = {}, class_first[kClasses] = {};
+        uint32_t r_max = 1;
+        for (uint64_t p = first; p < last; ++p) {
+            const uint32_t n = len_of(pairs[2 * p]);
+            const uint32_t c = spot_row_class(batch->dim, n);
+            ++class_count[c];
+            if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(n));
+        }
+        for (uint32_t c = 1; c < kClasses; ++c) class_first[c] = class_first[c - 1] + class_count[c - 1];
+        desc.resize(np);
+        uint64_t fill[kClasses];
+        std::copy(class_first, class_first + kClasses, fill);
+        for (uint64_t p = first; p < last; ++p) {
+            SpotPair &d = desc[fill[spot_row_class(batch->dim, len_of(pairs[2 * p]))]++];
+            d.px = pos[pairs[2 * p]];
+            d.py = pos[pairs[2 * p + 1]];
+            d.out = (uint32_t)(p - first);
+            d.pad = 0;
+            d.curve_off = curve_off[p] - curve_off[first];
+        }
+        // workspace: [cost | start | pair descriptors | best]
+        const size_t curve_floats = curves ? (size_t)entries : 0;
+        const size_t curve_bytes = (curve_floats * 4 + 15) / 16 * 16;
+        const size_t desc_bytes = (size_t)np * sizeof(SpotPair), best_bytes = (size_t)np * sizeof(apd_spot_best);
+        rc = reserve_ws(ctx, ctx->ws_spot, 2 * curve_bytes + desc_bytes + best_bytes + 16);
+        if (rc) return rc;
+        char *base = ctx->ws_spot.as<char>();
+        SpotLaunch L{};
+        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
+        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
+        L.d_cost = curves ? (float *)base : nullptr;
+        L.d_start = curves ? (uint32_t *)(base + curve_bytes) : nullptr;
+        const SpotPair *d_desc = (const SpotPair *)(base + 2 * curve_bytes);
+        L.d_best = (apd_spot_best *)(base + 2 * curve_bytes + desc_bytes);
+        HIP_TRY(ctx, hipMemcpyAsync((void *)d_desc, desc.data(), desc_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        for (uint32_t c = 0; c < kClasses; ++c) {
+            L.d_pairs = d_desc + class_first[c];
+            L.n_pairs = (uint32_t)class_count[c];
+            HIP_TRY(ctx, launch_spot(L, c, r_max, ctx->stream));
+        }
+        if (ctx->timing && last == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        if (curve_floats) {
+            HIP_TRY(ctx, hipMemcpyAsync(cost + curve_off[first], L.d_cost, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(start + curve_off[first], L.d_start, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(h_best + first, L.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `desc`)
+        first = last;
+        first_chunk = false;
+    }
+    return APD_OK;
+}
+
+// score(j) of the spotting contract: one f32 division, the window's length in place of m (alignments.rs:121)
+static float spot_score(float cost, uint64_t j, uint32_t start, uint64_t n)
+{
+    return cost / (float)(n + (j - start + 1));
+}
+
+extern "C" int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t m, uint64_t n, float threshold, apd_spot_best *hits,
+                             uint64_t capacity, uint64_t *n_hits)
+{
+    if (!n_hits || n == 0 || (m && (!cost || !start)) || (capacity && !hits)) return APD_ERR_INVALID_ARG;
+    *n_hits = 0;
+    try {
+        std::vector<std::pair<float, uint64_t>> cand;                     // (score, end), ends ascending
+        for (uint64_t j = 1; j <= m; ++j) {
+            if (start[j - 1] > j) return APD_ERR_INVALID_ARG;             // not a curve of apd_spot
+            const float s = spot_score(cost[j - 1], j, start[j - 1], n);
+            if (s < threshold) cand.emplace_back(s, j);                   // strict; NaN compares false
+        }
+        std::stable_sort(cand.begin(), cand.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+        std::map<uint64_t, uint64_t> taken;                               // accepted windows, first column -> last column (disjoint)
+        for (const auto &c : cand) {
+            const uint64_t hi = c.second, lo = start[hi - 1];
+            auto next = taken.upper_bound(hi);                            // the first accepted window that begins after `hi`
+            if (next != taken.begin() && std::prev(next)->second >= lo) continue;   // the one before it reaches into [lo, hi]
+            taken.emplace(lo, hi);
+            if (*n_hits < capacity) {
+                apd_spot_best &h = hits[*n_hits];
+                h.end = (uint32_t)hi; h.start = (uint32_t)lo; h.cost = cost[hi - 1]; h.score = c.first;
+            }
+            ++*n_hits;
+        }
+    } catch (const std::bad_alloc &) {
+        return APD_ERR_OOM;
+    }
+    return APD_OK;
+}
+
 // ------------------------------------------------------------------------------- work accounting
 
 extern "C" int apd_align_work(const uint64_t *offsets, uint32_t n_seq, uint32_t dim, const apd_align_config *cfg,

@@ -251,6 +251,38 @@ struct PathLaunch {
 hipError_t launch_path_sweep(const PathLaunch &L, uint32_t c_max, hipStream_t stream);
 hipError_t launch_path_trace(const PathLaunch &L, hipStream_t stream);
 
+// ---- subsequence alignment (dtw_spot.hip): one (query, stream) pair per wavefront, lane l owns ceil(n / 64) consecutive query rows.
+constexpr uint32_t kSpotMaxQuery = 16384;     // frames of a query: 256 rows per lane, 128 KB of LDS for the lane columns
+constexpr uint32_t kSpotMaxStream = 0xFFFF0000u;   // frames of a stream: query + window + 1 stays below 2^32
+constexpr uint32_t kSpotRegisterRows = 4;     // rows per lane the kernels hold in registers
+constexpr uint32_t spot_rows_per_lane(uint32_t n) { return (n + 63) / 64; }
+// The kernel class of a query of n frames at resident dimension dim: R = 1 .. kSpotRegisterRows rows per lane in registers (frame
+// dimensions with instantiated kernels only), 0: the lane columns in LDS.
+constexpr uint32_t spot_row_class(uint32_t dim, uint32_t n)
+{
+    return is_kernel_dim(dim) && spot_rows_per_lane(n) <= kSpotRegisterRows ? spot_rows_per_lane(n) : 0u;
+}
+struct SpotPair {
+    uint32_t px, py;       // resident positions of the query x and the stream y
+    uint32_t out;          // the pair's record in d_best
+    uint32_t pad;
+    uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
+};
+struct SpotLaunch {
+    const float *d_frames;
+    const uint32_t *d_seq_off;
+    uint32_t dim, dpad;
+    float ins, del, mat;
+    const SpotPair *d_pairs;
+    uint32_t n_pairs;
+    float *d_cost;         // both null: best only
+    uint32_t *d_start;
+    apd_spot_best *d_best;
+};
+size_t spot_lds_bytes(uint32_t rows_per_lane);
+// The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
+hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
+
 // One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
 hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);
 // The generic kernel over ALL tiles of L as a small persistent grid that does nothing unless *L.d_nonfinite is set.
@@ -416,6 +448,7 @@ struct apd_context {
     apd::DeviceBuf ws_gather;         // gathered slabs of apd_align_all_sharded_async
     apd::DeviceBuf ws_path_dirs;      // apd_align_paths: direction words of a chunk of pairs
     apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
+    apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

@@ -111,6 +111,56 @@ pub fn align_cross(queries: &[NDSequence], corpus: &[NDSequence], params: &Disco
     (fs, sf)
 }
 
+/// Not in the reference: subsequence alignment.  Every template against every stream on the first device of APD_DEVICES
+/// (apd_batch_join + apd_spot, best only): out[t * streams.len() + r] = the best window of templates[t] in streams[r]; end and
+/// start are 1-based stream columns, (0, 0) with an infinite score when nothing was kept.  Penalties from `params`; no band.
+pub fn spot(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery) -> Vec<apd_spot_best> {
+    let (n1, n2) = (templates.len(), streams.len());
+    let mut best = vec![apd_spot_best::default(); n1 * n2];
+    if n1 == 0 || n2 == 0 { return best; }
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let pack = |set: &[NDSequence]| {
+        let mut offsets = vec![0u64; set.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in set.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        (frames, offsets)
+    };
+    let dim = templates[0].n_bins as u32;
+    let ((fa, oa), (fb, ob)) = (pack(templates), pack(streams));
+    let mut pairs: Vec<u32> = Vec::with_capacity(2 * n1 * n2);
+    for t in 0..n1 { for r in 0..n2 { pairs.push(t as u32); pairs.push((n1 + r) as u32); } }
+    let mut curve_off = vec![0u64; n1 * n2 + 1];
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let (mut a, mut b, mut j) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        check(apd_batch_create(ctx, fa.as_ptr(), oa.as_ptr(), n1 as u32, dim, 0, &mut a));
+        check(apd_batch_create(ctx, fb.as_ptr(), ob.as_ptr(), n2 as u32, dim, 0, &mut b));
+        check(apd_batch_join(ctx, a, b, &mut j));
+        let rc = apd_spot(ctx, j, &cfg, pairs.as_ptr(), (n1 * n2) as u64, std::ptr::null_mut(), std::ptr::null_mut(), 0, curve_off.as_mut_ptr(), best.as_mut_ptr());
+        apd_destroy(ctx);                                                 // releases the device side of the three batches
+        for h in [j, b, a] { apd_batch_destroy(h); }
+        check(rc);
+    }
+    best
+}
+
+/// apd_spot_hits: the non-overlapping windows of one pair's curves whose score is strictly below `threshold`, best first.
+pub fn spot_hits(cost: &[f32], start: &[u32], n: usize, threshold: f32) -> Vec<apd_spot_best> {
+    assert_eq!(cost.len(), start.len());
+    let mut count: u64 = 0;
+    unsafe { check(apd_spot_hits(cost.as_ptr(), start.as_ptr(), cost.len() as u64, n as u64, threshold, std::ptr::null_mut(), 0, &mut count)); }
+    let mut hits = vec![apd_spot_best::default(); count as usize];
+    unsafe { check(apd_spot_hits(cost.as_ptr(), start.as_ptr(), cost.len() as u64, n as u64, threshold, hits.as_mut_ptr(), count, &mut count)); }
+    hits
+}
+
 fn last_error(multi: *mut apd_multi) -> String {
     unsafe { std::ffi::CStr::from_ptr(apd_multi_last_error(multi)) }.to_string_lossy().into_owned()
 }

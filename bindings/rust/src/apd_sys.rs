@@ -56,6 +56,15 @@ pub const APD_PATH_INSERT: u32 = 1;
 pub const APD_PATH_DELETE: u32 = 2;
 pub const APD_PATH_START: u32 = 3;
 
+/// A matched window of a stream (apd_spot): 1-based columns of its last and first frame, the bits of T[n][end], the score.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct apd_spot_best {
+    pub end: u32,
+    pub start: u32,
+    pub cost: f32,
+    pub score: f32,
+}
+
 /// ClusteringOperation (clustering.rs:19-25); operation: 0 S2S, 1 S2C, 2 C2S, 3 C2C (clustering.rs:8-13).
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct apd_cluster_op {
@@ -179,6 +188,11 @@ extern "C" {
     pub fn apd_align_pair_path(ctx: *mut apd_context, x: *const f32, n: u64, y: *const f32, m: u64, dim: u32,
                                params: *const apd_alignment_params, steps: *mut apd_path_step, capacity: u64, n_steps: *mut u64,
                                score: *mut f32) -> c_int;
+    // subsequence alignment
+    pub fn apd_spot(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, pairs: *const u32, n_pairs: u64,
+                    cost: *mut f32, start: *mut u32, capacity: u64, curve_off: *mut u64, best: *mut apd_spot_best) -> c_int;
+    pub fn apd_spot_hits(cost: *const f32, start: *const u32, m: u64, n: u64, threshold: f32, hits: *mut apd_spot_best,
+                         capacity: u64, n_hits: *mut u64) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

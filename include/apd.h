@@ -176,9 +176,9 @@ int apd_batch_nonfinite(apd_context *ctx, const apd_batch *batch, int *nonfinite
  * Resident order: two segments, each in its own length order; which set lies first is the library's choice (the one with the
  * larger mean length) and no result depends on it.  total frames + 2 * sequences >= 2^32 is APD_ERR_INVALID_ARG.
  * A joined batch is an ordinary batch for apd_batch_len / apd_batch_destroy / apd_destroy, apd_batch_nonfinite, apd_align_all*,
- * apd_align_tiles_async / apd_unpack_tiles_async (which use the batch's own order) and apd_align_paths (the warping path between
- * a sequence of one set and one of the other).  apd_batch_refill on it is APD_ERR_INVALID_ARG.  The host-only views that take
- * raw offsets (apd_length_order, apd_rank_tile_list, apd_unpack_tiles_host, apd_align_work) describe LENGTH-ORDERED batches
+ * apd_align_tiles_async / apd_unpack_tiles_async (which use the batch's own order), apd_align_paths (the warping path between
+ * a sequence of one set and one of the other) and apd_spot (templates of one set spotted in recordings of the other).
+ * apd_batch_refill on it is APD_ERR_INVALID_ARG.  The host-only views that take raw offsets (apd_length_order, apd_rank_tile_list, apd_unpack_tiles_host, apd_align_work) describe LENGTH-ORDERED batches
  * only, not joined ones.  The multi-GPU entry points (apd_multi_*, apd_comm_*, apd_align_all_sharded_async) do not take the
  * cross alignment: out of scope. */
 int apd_batch_join(apd_context *ctx, const apd_batch *first, const apd_batch *second, apd_batch **joined);
@@ -392,6 +392,53 @@ int apd_align_paths(apd_context *ctx, const apd_batch *batch, const apd_align_co
 int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
                         const apd_alignment_params *params, apd_path_step *steps, uint64_t capacity, uint64_t *n_steps,
                         float *score);
+
+/* ---- subsequence alignment ("spotting"): where does a template occur in a recording nobody has segmented? -------------------
+ * Open-begin, open-end DTW of a query x (n >= 1 frames) against a stream y (m >= 1 frames): the recurrence above, with another
+ * boundary.  Table T, 0 <= i <= n, 0 <= j <= m, cell (i, j) comparing x[i-1] with y[j-1]; T[0][j] = 0 for every j (an alignment may
+ * start anywhere in the stream), T[i][0] = +INF for i >= 1; for i, j >= 1 alignments.rs:153-159 verbatim: DELETE from (i, j-1) if
+ * del < match && del < ins, INSERT from (i-1, j) if ins < match && ins < del, MATCH from (i-1, j-1) otherwise (an exact DELETE /
+ * INSERT tie takes MATCH even when MATCH is larger, and so does a NaN); value = predecessor + (pen * d rounded on its own), d the
+ * euclidean distance of numerics.rs:114-120.  There is NO band (a band relative to an unknown start is not a DP): the table is
+ * n x m cells and cfg->warping_band_percentage is not read.
+ * Start column S[i][j], 1-based: in row 1 a MATCH or INSERT starts the alignment, S = j; everywhere else S is the S of the
+ * predecessor the select chose (S[i][0] = 0: nothing starts there).
+ * Curves, for j = 1 .. m at index j - 1: cost = T[n][j] (the table's bits), start = S[n][j]; the matched window is y[start-1 .. j-1],
+ * L = j - start + 1 frames, and score(j) = cost / (float)(n + L), one f32 division: alignments.rs:121 with the window in place of y.
+ * The reference reads its score one row and one column short, at (n-1, m-1) (alignments.rs:120); that is NOT carried over: the
+ * reference has no spotting to stay identical to, and row n - 1 would leave a one-frame query without a row.
+ * best: a scan of j ascending that keeps a column only if its score is strictly below the best so far, starting from +INF: the
+ * smallest end wins ties, a NaN is never kept, nothing kept gives {0, 0, +INF, +INF}.
+ * Arithmetic: ALWAYS the literal one, whatever apd_set_distance_mode says, as for the warping paths; a batch outside the fast
+ * feature range needs no routing.
+ * The warping path of a hit: apd_align_pair_path on x and the matched window.  That table is banded and anchored at both ends, so
+ * it is not the same table: its costs need not equal the curve's. */
+typedef struct apd_spot_best {
+    uint32_t end, start;   /* 1-based stream columns of the window's last and first frame; 0, 0: none */
+    float cost, score;
+} apd_spot_best;   /* 16 bytes */
+/* pairs: [n_pairs][2] = (query x, stream y) in the CALLER's sequence numbers of any resident batch -- usually a joined one,
+ * templates joined with recordings; any order, repeats and x == y allowed; results in input order.
+ * curve_off (n_pairs + 1, always written, no GPU work needed for it): pair p owns cost / start [curve_off[p] .. curve_off[p+1]),
+ *   curve_off[p+1] - curve_off[p] = frames of y.  cost and start both NULL: best only (capacity is not read, no curve is stored
+ *   anywhere); exactly one of them NULL, or capacity (in entries) < curve_off[n_pairs]: APD_ERR_INVALID_ARG.  best (n_pairs) may
+ *   be NULL only if the curves are given; all three NULL: sizes only.
+ * A pair index >= the batch's sequence count is APD_ERR_INVALID_ARG, an empty sequence in the batch APD_ERR_EMPTY_SEQUENCE, a query
+ * of more than 16 384 frames (or a stream of 2^32 - 65 536 or more) APD_ERR_UNSUPPORTED, each before anything is launched.  Follows
+ * apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the kernels of the call (all chunks).
+ * One wavefront sweeps one pair, whatever its size: the parallelism is pairs (templates x recordings).  A single long pair runs
+ * on one wavefront; cutting a free-start DP along the stream is not exact and is not attempted.
+ * Workspace: 8 bytes per curve entry on the device; a long list is cut into chunks that keep it under 1 GiB
+ * (APD_SPOT_WORKSPACE_BYTES overrides the cap: tests only), results identical. */
+int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+             float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off, apd_spot_best *best);
+/* Greedy non-overlapping peak picking on ONE pair's curves (m entries, query of n >= 1 frames).  Host only, no context.
+ * Candidates: the columns j with score(j) < threshold (strict, as merge()'s test is; a NaN score is no candidate), taken in
+ * ascending score, the smaller end first among equal scores; a candidate is accepted if its window [start, end] shares no column
+ * with an accepted one.  hits: the accepted windows in acceptance order, at most `capacity` written; *n_hits counts all of them and
+ * may exceed capacity.  n == 0: APD_ERR_INVALID_ARG. */
+int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t m, uint64_t n, float threshold, apd_spot_best *hits,
+                  uint64_t capacity, uint64_t *n_hits);
 
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */

@@ -202,6 +202,7 @@ class Batch {
     Batch(const Batch &) = delete;
     Batch &operator=(const Batch &) = delete;
     apd_batch *get() const { return handle_; }
+    apd_batch *release() { apd_batch *h = handle_; handle_ = nullptr; return h; }
     uint32_t len() const { return apd_batch_len(handle_); }
     uint32_t first_len() const { return apd_batch_first_len(handle_); }
   private:
@@ -268,6 +269,35 @@ class AlignmentWorkers {
         check(apd_align_cross(ctx_.get(), joined.get(), &c, out.first.data(), out.second.data()), ctx_.get());
         return out;
     }
+    // Not in the reference: subsequence alignment (apd.h, "subsequence alignment").  pairs: (query, stream) in this object's sequence
+    // numbers -- with `streams`, in those of the two joined: below data.size() this object's, the others `streams`'.  curves: per
+    // pair the cost and start of every stream column (left empty with with_curves = false); best: the best window per pair.
+    struct Spotted { std::vector<std::vector<float>> cost; std::vector<std::vector<uint32_t>> start; std::vector<apd_spot_best> best; };
+    Spotted spot(const std::vector<std::pair<uint32_t, uint32_t>> &pairs, const Discovery &params, bool with_curves = true,
+                 const AlignmentWorkers *streams = nullptr)
+    {
+        const apd_align_config c = params.config();
+        std::vector<uint32_t> flat;
+        for (const auto &p : pairs) { flat.push_back(p.first); flat.push_back(p.second); }
+        Batch joined(streams ? Batch::join(ctx_, batch_, streams->batch_).release() : nullptr);
+        const apd_batch *b = streams ? joined.get() : batch_;
+        std::vector<uint64_t> off(pairs.size() + 1, 0);
+        Spotted out;
+        out.best.resize(pairs.size());
+        if (!with_curves) {
+            check(apd_spot(ctx_.get(), b, &c, flat.data(), pairs.size(), nullptr, nullptr, 0, off.data(), out.best.data()), ctx_.get());
+            return out;
+        }
+        check(apd_spot(ctx_.get(), b, &c, flat.data(), pairs.size(), nullptr, nullptr, 0, off.data(), nullptr), ctx_.get());   // sizes
+        std::vector<float> cost(std::max<uint64_t>(off.back(), 1));
+        std::vector<uint32_t> start(cost.size());
+        check(apd_spot(ctx_.get(), b, &c, flat.data(), pairs.size(), cost.data(), start.data(), cost.size(), off.data(), out.best.data()), ctx_.get());
+        for (std::size_t p = 0; p < pairs.size(); ++p) {
+            out.cost.emplace_back(cost.begin() + off[p], cost.begin() + off[p + 1]);
+            out.start.emplace_back(start.begin() + off[p], start.begin() + off[p + 1]);
+        }
+        return out;
+    }
     const char *collective() const { return multi_ ? apd_multi_collective(multi_) : "none (one device)"; }
     std::vector<NDSequence> data;
     std::vector<float> result;                                                       // n*n row-major, diagonal 0.0
@@ -281,6 +311,17 @@ class AlignmentWorkers {
     std::vector<uint64_t> offsets;
     uint32_t dim = 1;
 };
+
+// apd_spot_hits: the non-overlapping windows of one pair's curves whose score is strictly below `threshold`, best first.  Host only.
+inline std::vector<apd_spot_best> spot_hits(const std::vector<float> &cost, const std::vector<uint32_t> &start, std::size_t n, float threshold)
+{
+    if (cost.size() != start.size()) throw Error(APD_ERR_INVALID_ARG, "cost and start are the two curves of one pair");
+    uint64_t count = 0;
+    check(apd_spot_hits(cost.data(), start.data(), cost.size(), n, threshold, nullptr, 0, &count));
+    std::vector<apd_spot_best> hits(count);
+    check(apd_spot_hits(cost.data(), start.data(), cost.size(), n, threshold, hits.data(), hits.size(), &count));
+    return hits;
+}
 
 enum class Merge { Sequence2Sequence = 0, Sequence2Cluster = 1, Cluster2Sequence = 2, Cluster2Cluster = 3 };   // clustering.rs:8-13
 struct ClusteringOperation { std::size_t merge_i, merge_j, into; float distance; Merge operation; };              // :19-25
