@@ -144,6 +144,9 @@ SYMBOLS = [
     ("apd_align_cross", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _f32p, _f32p]),
     ("apd_align_cross_device_async", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _vp, _vp]),
     ("apd_cross_linkage", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("apd_cluster_medoids", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _u32p, _u32p, C.c_uint32, _vp, _vp]),
+    ("apd_barycenters", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, _u32p, C.c_uint32, _u32p, C.c_uint32, _vp, C.c_int,
+                                  C.c_uint64, _u64p, _f32p, _u32p]),
     ("apd_align_all_device_async", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _vp]),
     ("apd_tile_size", C.c_uint32, []),
     ("apd_num_tiles", C.c_uint64, [C.c_uint32]),

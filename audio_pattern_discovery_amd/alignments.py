@@ -202,6 +202,7 @@ class AlignmentWorkers:
         """`devices`: HIP device ordinals -- the workers of :33-41 become these GPUs, driven through the library's persistent
         multi-device handle (made here once; every align_all then pays kernels + one all-gather + unpack)."""
         self._multi = None
+        self._aligned = False                             # align_all has filled `result`
         if devices is not None:
             from . import sharding
             self._multi = sharding.Multi(devices)
@@ -230,9 +231,11 @@ class AlignmentWorkers:
         cfg = params.align_config()
         if self._multi is not None:
             self.result[:] = self._multi.align_all(self._batch, cfg).ravel()
+            self._aligned = True
             return self.result
         _lib.check(_lib.lib().apd_align_all(self.ctx.handle, self._batch.handle, C.byref(cfg),
                                             self.result.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
+        self._aligned = True
         return self.result
 
     def paths(self, pairs, params):
@@ -285,6 +288,47 @@ class AlignmentWorkers:
             if streams is not None:
                 batch.close()
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(n_pairs)], best
+
+    def barycenters(self, sets, params, init=None, iterations=10, on_device=False):
+        """DTW barycenter averaging (include/apd.h, "cluster prototypes") of the sets of this object's sequence numbers in `sets`
+        (as cluster_sets returns them), params: Discovery.  init[k]: the sequence whose frames start set k's barycenter; None: the
+        medoids (clustering.medoids) of the last align_all's result -- an empty set then starts from sequence 0, which nothing
+        reads.  Returns (list of [T_k][dim] float32 arrays, inertia [iterations][len(sets)], used [iterations][len(sets)]):
+        apd_barycenters.  on_device=True: (DeviceBuffer holding the packed frames, frame_off, inertia, used) instead -- what
+        Batch(ctx, buf.ptr, frame_off, dim, on_device=True) takes."""
+        if self._multi is not None:
+            raise ValueError("barycenters() runs on one context: make the AlignmentWorkers without `devices`")
+        n_sets = len(sets)
+        if init is None:
+            if not self._aligned:
+                raise ValueError("barycenters(init=None) takes the medoids of the last align_all: call align_all first, or pass init")
+            from . import clustering
+            init = clustering.medoids(self.result, sets, self.ctx)[0].copy()
+            init[init == 0xFFFFFFFF] = 0
+        init = np.ascontiguousarray(init, dtype=np.uint32)
+        if len(init) != n_sets:
+            raise ValueError("one init sequence per set")
+        cfg = params.align_config()
+        members = np.array([m for s in sets for m in s], dtype=np.uint32)
+        set_off = np.zeros(n_sets + 1, dtype=np.uint32)
+        set_off[1:] = np.cumsum([len(s) for s in sets])
+        off = np.zeros(n_sets + 1, dtype=np.uint64)
+        inertia = np.zeros((int(iterations), n_sets), dtype=np.float32)
+        used = np.zeros((int(iterations), n_sets), dtype=np.uint32)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        L = _lib.lib()
+        head = (self.ctx.handle, self._batch.handle, C.byref(cfg), members.ctypes.data_as(u32p), set_off.ctypes.data_as(u32p), n_sets,
+                init.ctypes.data_as(u32p), int(iterations))
+        _lib.check(L.apd_barycenters(*head, None, 0, 0, off.ctypes.data_as(u64p), None, None), self.ctx.handle)          # sizes
+        total = int(off[-1])
+        tail = (total, off.ctypes.data_as(u64p), inertia.ctypes.data_as(f32p), used.ctypes.data_as(u32p))
+        if on_device:
+            buf = self.ctx.alloc(max(total * self._dim * 4, 16))
+            _lib.check(L.apd_barycenters(*head, buf.at(0), 1, *tail), self.ctx.handle)
+            return buf, off, inertia, used
+        frames = np.zeros((max(total, 1), self._dim), dtype=np.float32)
+        _lib.check(L.apd_barycenters(*head, C.c_void_p(frames.ctypes.data), 0, *tail), self.ctx.handle)
+        return [frames[int(off[k]):int(off[k + 1])].copy() for k in range(n_sets)], inertia, used
 
     def cross(self, other, params):
         """Aligns this object's sequences against `other`'s (an AlignmentWorkers of the same context), params: Discovery.  Returns

@@ -86,6 +86,27 @@ def cross_linkage(fs, sf, sets, ctx=None):
     return link_fs, link_sf, nearest, nearest_linkage
 
 
+def medoids(distances, sets, ctx=None):
+    """apd_cluster_medoids: per set of sequence numbers in `sets` (as cluster_sets returns them; any order inside a set) the member
+    whose distances to and from the set's members -- summed ascending in f32, one rounded add per term -- are smallest, from the
+    [n][n] matrix of AlignmentWorkers.align_all.  Returns (medoid, cost): uint32 sequence numbers (the smallest among equal costs;
+    0xFFFFFFFF for an empty set or one whose costs are all +INF / NaN) and float32 costs (+INF there)."""
+    ctx = ctx or _lib.default_context()
+    d = np.ascontiguousarray(distances, dtype=np.float32)
+    n = int(round(d.size ** 0.5))
+    if d.size != n * n:
+        raise ValueError("distances must hold n^2 values")
+    members = np.array([m for s in sets for m in s], dtype=np.uint32)
+    set_off = np.zeros(len(sets) + 1, dtype=np.uint32)
+    set_off[1:] = np.cumsum([len(s) for s in sets])
+    medoid, cost = np.zeros(len(sets), np.uint32), np.zeros(len(sets), np.float32)
+    u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+    _lib.check(_lib.lib().apd_cluster_medoids(ctx.handle, vp(d.ctypes.data), 0, n, members.ctypes.data_as(u32p),
+                                              set_off.ctypes.data_as(u32p), len(sets), vp(medoid.ctypes.data), vp(cost.ctypes.data)),
+               ctx.handle)
+    return medoid, cost
+
+
 def percentile(x, perc, ctx=None):
     """numerics.rs:125-133 on the GPU (apd_percentile)."""
     ctx = ctx or _lib.default_context()

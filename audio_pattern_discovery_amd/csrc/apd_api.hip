@@ -1117,6 +1117,163 @@ extern "C" int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n,
     return rc;
 }
 
+// ------------------------------------------------------------------------------ DTW barycenters
+
+// DBA over sets of a resident batch (kernels: dtw_path.hip).  The pairs (set, member ascending) are cut into chunks under the path
+// workspace cap once; every iteration runs sweep, trace and accumulate per chunk, then one finalize.  ws_bary, uploaded once:
+// [barycenters | sums | counts | score sums | used | bary_off | init positions | pair descriptors | per chunk: pairs of every set |
+//  contributes | inertia, used of every iteration].
+extern "C" int apd_barycenters(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *members,
+                               const uint32_t *set_off, uint32_t n_sets, const uint32_t *init, uint32_t iterations, float *frames,
+                               int frames_on_device, uint64_t capacity, uint64_t *frame_off, float *inertia, uint32_t *used)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || !frame_off || (n_sets && (!set_off || !init))) return APD_ERR_INVALID_ARG;
+    if (n_sets && set_off[0] != 0) return APD_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < n_sets; ++k) if (set_off[k + 1] < set_off[k]) return APD_ERR_INVALID_ARG;
+    const uint32_t n_pairs = n_sets ? set_off[n_sets] : 0u, n_seq = batch->n_seq;
+    if (n_pairs && !members) return APD_ERR_INVALID_ARG;
+    // ascending sequence number inside every set: the order of the contract's sums
+    std::vector<uint32_t> sorted(members, members + n_pairs);
+    for (uint32_t k = 0; k < n_sets; ++k) {
+        if (init[k] >= n_seq) return APD_ERR_INVALID_ARG;
+        std::sort(sorted.begin() + set_off[k], sorted.begin() + set_off[k + 1]);
+        for (uint32_t t = set_off[k]; t < set_off[k + 1]; ++t)
+            if (sorted[t] >= n_seq || (t > set_off[k] && sorted[t] == sorted[t - 1])) return APD_ERR_INVALID_ARG;
+    }
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
+    auto frames_of = [&](uint32_t k) { return set_off[k + 1] > set_off[k] ? len_of(init[k]) : 0u; };   // an empty set has no barycenter
+    frame_off[0] = 0;
+    for (uint32_t k = 0; k < n_sets; ++k) frame_off[k + 1] = frame_off[k] + frames_of(k);
+    if (!frames) return APD_OK;                                           // sizes only
+    if (capacity < frame_off[n_sets]) return APD_ERR_INVALID_ARG;
+    const BandSpec band = band_from_cfg(cfg);
+    const uint64_t n_padded = frame_off[n_sets] + 2ull * n_sets;
+    if (n_padded >= (1ull << 32) || n_padded * batch->dpad >= (1ull << 39)) return APD_ERR_INVALID_ARG;   // one work-item per float, below 2^31 workgroups
+
+    // ---- the plan: pair descriptors, chunks, and per chunk the pairs of every set
+    struct Chunk { uint32_t first, last, c_max; uint64_t words, slots; };
+    std::vector<PathPair> desc(n_pairs);
+    std::vector<Chunk> chunks;
+    const uint64_t cap = path_workspace_cap();
+    constexpr uint32_t kMaxPairsPerLaunch = 1u << 24;                     // 64 work-items per pair, launches stay below 2^31
+    {
+        std::vector<uint32_t> set_of(n_pairs);
+        for (uint32_t k = 0; k < n_sets; ++k) for (uint32_t t = set_off[k]; t < set_off[k + 1]; ++t) set_of[t] = k;
+        Chunk c{0, 0, 2, 0, 0};
+        for (uint32_t p = 0; p < n_pairs; ++p) {
+            const uint32_t n = frames_of(set_of[p]), m = len_of(sorted[p]);
+            const uint32_t w = host_w(band, n, m);
+            if (2ull * w + 1 > kPathMaxOffsets) { ctx->last_error = "band too wide for the path sweep"; return APD_ERR_BAND_TOO_WIDE; }
+            const uint64_t words = path_dir_words(n, m, w), slots = apd_path_bound(n, m);
+            if (p > c.first && ((c.words + words) * sizeof(uint32_t) > cap || (c.slots + slots) * sizeof(apd_path_step) > cap ||
+                                p - c.first >= kMaxPairsPerLaunch)) {
+                c.last = p;
+                chunks.push_back(c);
+                c = Chunk{p, 0, 2, 0, 0};
+            }
+            desc[p] = PathPair{set_of[p], pos[sorted[p]], c.words, c.slots};   // px: the set, whose barycenter is x
+            c.words += words; c.slots += slots;
+            c.c_max = std::max(c.c_max, path_cells_per_lane(w));
+        }
+        if (n_pairs) { c.last = n_pairs; chunks.push_back(c); }
+    }
+    std::vector<uint2> set_pairs(chunks.size() * n_sets);                 // per chunk and set: its pairs [x, y), relative to the chunk
+    uint64_t max_words = 0, max_slots = 0;
+    uint32_t max_np = 0;
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const Chunk &c = chunks[ci];
+        for (uint32_t k = 0; k < n_sets; ++k) {
+            const uint32_t lo = std::min(std::max(set_off[k], c.first), c.last), hi = std::min(std::max(set_off[k + 1], c.first), c.last);
+            set_pairs[ci * n_sets + k] = make_uint2(lo - c.first, hi - c.first);
+        }
+        max_words = std::max(max_words, c.words); max_slots = std::max(max_slots, c.slots); max_np = std::max(max_np, c.last - c.first);
+    }
+    if (n_sets == 0) return APD_OK;
+
+    // ---- device state
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "barycenter launch");
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t bary_bytes = up((size_t)n_padded * batch->dpad * sizeof(float)), cnt_bytes = up((size_t)n_padded * 4);
+    const size_t set_bytes = up((size_t)n_sets * 4), off_bytes = up(((size_t)n_sets + 1) * 4);
+    const size_t desc_bytes = up(desc.size() * sizeof(PathPair)), ranges_bytes = up(set_pairs.size() * sizeof(uint2));
+    const size_t contrib_bytes = up((size_t)max_np * 4), result_bytes = up((size_t)iterations * n_sets * 4);
+    // [bary | sum | cnt | score_sum | used] then the uploaded block [bary_off | init_pos | desc | ranges] then [contrib | inertia | used_out]
+    const size_t o_sum = bary_bytes, o_cnt = o_sum + bary_bytes, o_score = o_cnt + cnt_bytes, o_used = o_score + set_bytes;
+    const size_t o_off = o_used + set_bytes, o_init = o_off + off_bytes, o_desc = o_init + set_bytes, o_ranges = o_desc + desc_bytes;
+    const size_t o_contrib = o_ranges + ranges_bytes, o_inertia = o_contrib + contrib_bytes, o_usedout = o_inertia + result_bytes;
+    rc = reserve_ws(ctx, ctx->ws_bary, o_usedout + result_bytes);
+    if (rc) return rc;
+    rc = reserve_ws(ctx, ctx->ws_path_dirs, std::max<size_t>((size_t)max_words * sizeof(uint32_t), 16));
+    if (rc) return rc;
+    // steps workspace, as apd_align_paths lays it out: [steps | lengths | scores] (the descriptors live in ws_bary)
+    const size_t steps_bytes = (size_t)max_slots * sizeof(apd_path_step);
+    rc = reserve_ws(ctx, ctx->ws_path_steps, steps_bytes + (size_t)max_np * 8 + 16);
+    if (rc) return rc;
+    DeviceBuf d_packed;                                                   // the host form's result on its way out
+    const size_t out_bytes = (size_t)frame_off[n_sets] * batch->src_dim * sizeof(float);
+    if (!frames_on_device && out_bytes) HIP_TRY(ctx, d_packed.alloc(out_bytes));
+    char *base = ctx->ws_bary.as<char>();
+    std::vector<char> upload(o_contrib - o_off, 0);
+    {
+        uint32_t *h_off = (uint32_t *)upload.data(), *h_init = (uint32_t *)(upload.data() + (o_init - o_off));
+        for (uint32_t k = 0; k <= n_sets; ++k) h_off[k] = (uint32_t)(frame_off[k] + 2ull * k);
+        for (uint32_t k = 0; k < n_sets; ++k) h_init[k] = pos[init[k]];
+        if (!desc.empty()) std::memcpy(upload.data() + (o_desc - o_off), desc.data(), desc.size() * sizeof(PathPair));
+        if (!set_pairs.empty()) std::memcpy(upload.data() + (o_ranges - o_off), set_pairs.data(), set_pairs.size() * sizeof(uint2));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // `upload` is a local: it must have left the host
+    BaryLaunch B{};
+    B.d_frames = batch->d_frames.as<float>(); B.d_seq_off = batch->d_seq_off;
+    B.d_bary = (float *)base; B.d_bary_off = (const uint32_t *)(base + o_off);
+    B.n_sets = n_sets; B.n_padded = (uint32_t)n_padded;
+    B.dim = batch->dim; B.src_dim = batch->src_dim; B.dpad = batch->dpad;
+    B.d_sum = (float *)(base + o_sum); B.d_cnt = (uint32_t *)(base + o_cnt);
+    B.d_score_sum = (float *)(base + o_score); B.d_used = (uint32_t *)(base + o_used);
+    B.d_contrib = (uint32_t *)(base + o_contrib);
+    float *d_inertia = (float *)(base + o_inertia);
+    uint32_t *d_used_out = (uint32_t *)(base + o_usedout);
+    char *steps_base = ctx->ws_path_steps.as<char>();
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(ctx, launch_bary_init(B, (const uint32_t *)(base + o_init), ctx->stream));
+    for (uint32_t it = 0; it < iterations; ++it) {
+        HIP_TRY(ctx, hipMemsetAsync(base + o_sum, 0, o_off - o_sum, ctx->stream));   // sums, counts, score sums, used
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const Chunk &c = chunks[ci];
+            const uint32_t np = c.last - c.first;
+            PathLaunch L{};
+            L.d_frames = B.d_frames; L.d_seq_off = B.d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
+            L.d_x_frames = B.d_bary; L.d_x_seq_off = B.d_bary_off;
+            L.d_pairs = (const PathPair *)(base + o_desc) + c.first;
+            L.n_pairs = np;
+            L.d_dirs = ctx->ws_path_dirs.as<uint32_t>();
+            L.d_steps = (apd_path_step *)steps_base;
+            L.d_len = (uint32_t *)(steps_base + steps_bytes);
+            L.d_scores = (float *)(steps_base + steps_bytes + (size_t)max_np * 4);
+            HIP_TRY(ctx, launch_path_sweep(L, c.c_max, ctx->stream));
+            HIP_TRY(ctx, launch_path_trace(L, ctx->stream));
+            B.d_pairs = L.d_pairs; B.d_set_pairs = (const uint2 *)(base + o_ranges) + ci * n_sets;
+            B.d_steps = L.d_steps; B.d_len = L.d_len; B.d_scores = L.d_scores;
+            HIP_TRY(ctx, launch_bary_accumulate(B, ctx->stream));
+        }
+        HIP_TRY(ctx, launch_bary_finalize(B, d_inertia + (size_t)it * n_sets, d_used_out + (size_t)it * n_sets, ctx->stream));
+    }
+    float *d_out = frames_on_device ? frames : d_packed.as<float>();
+    if (out_bytes) HIP_TRY(ctx, launch_bary_pack(B, d_out, ctx->stream));
+    if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+    const size_t res = (size_t)iterations * n_sets * 4;
+    if (!frames_on_device && out_bytes) HIP_TRY(ctx, hipMemcpyAsync(frames, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (inertia && res) HIP_TRY(ctx, hipMemcpyAsync(inertia, d_inertia, res, hipMemcpyDeviceToHost, ctx->stream));
+    if (used && res) HIP_TRY(ctx, hipMemcpyAsync(used, d_used_out, res, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's now
+    return APD_OK;
+}
+
 // ------------------------------------------------------------------------- subsequence alignment
 
 // Cap of the device curves of one chunk of pairs (bytes).

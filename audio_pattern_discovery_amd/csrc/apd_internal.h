@@ -247,9 +247,45 @@ struct PathLaunch {
     apd_path_step *d_steps;
     uint32_t *d_len;       // [n_pairs] steps used
     float *d_scores;       // [n_pairs]
+    // an x side of its own (apd_barycenters: one "sequence" per set, in the resident frame layout); px then indexes d_x_seq_off.
+    // Both null: x comes from d_frames / d_seq_off like y.
+    const float *d_x_frames;
+    const uint32_t *d_x_seq_off;
 };
 hipError_t launch_path_sweep(const PathLaunch &L, uint32_t c_max, hipStream_t stream);
 hipError_t launch_path_trace(const PathLaunch &L, hipStream_t stream);
+
+// ---- DTW barycenters (dtw_path.hip): the averaging around the sweep and the trace.  The barycenters live in the resident frame
+// layout -- set k owns frames d_bary_off[k] .. d_bary_off[k + 1] - 3 of dpad floats, two padding frames behind, d_bary_off[k] =
+// sum of T + 2 k -- so that the path kernels take them as their x side.  d_sum / d_cnt: the running sums and counts of one
+// iteration, per padded frame; d_score_sum / d_used: per set.  The chunk fields describe the paths a trace has just left on the
+// device: d_set_pairs[k] = the chunk's pairs [x, y) of set k, members ascending.
+struct BaryLaunch {
+    const float *d_frames;          // the batch: the y side
+    const uint32_t *d_seq_off;
+    float *d_bary;
+    const uint32_t *d_bary_off;     // [n_sets + 1]
+    uint32_t n_sets, n_padded;      // n_padded = d_bary_off[n_sets]
+    uint32_t dim, src_dim, dpad;
+    float *d_sum;                   // [n_padded][dpad]
+    uint32_t *d_cnt;                // [n_padded]
+    float *d_score_sum;             // [n_sets]
+    uint32_t *d_used;               // [n_sets]
+    const PathPair *d_pairs;
+    const uint2 *d_set_pairs;       // [n_sets]
+    const apd_path_step *d_steps;
+    const uint32_t *d_len;
+    const float *d_scores;
+    uint32_t *d_contrib;            // [pairs of the chunk] 1: the path reached the origin
+};
+// d_init_pos[k]: resident position of the sequence that starts set k's barycenter; writes every float of d_bary
+hipError_t launch_bary_init(const BaryLaunch &L, const uint32_t *d_init_pos, hipStream_t stream);
+// the chunk's contribution to d_score_sum / d_used (and d_contrib), then to d_sum / d_cnt
+hipError_t launch_bary_accumulate(const BaryLaunch &L, hipStream_t stream);
+// ends an iteration: the new frames, d_inertia[k] and d_used_out[k]
+hipError_t launch_bary_finalize(const BaryLaunch &L, float *d_inertia, uint32_t *d_used_out, hipStream_t stream);
+// d_out: [sum of T][src_dim], the caller's packing
+hipError_t launch_bary_pack(const BaryLaunch &L, float *d_out, hipStream_t stream);
 
 // ---- subsequence alignment (dtw_spot.hip): one (query, stream) pair per wavefront, lane l owns ceil(n / 64) consecutive query rows.
 constexpr uint32_t kSpotMaxQuery = 16384;     // frames of a query: 256 rows per lane, 128 KB of LDS for the lane columns
@@ -325,6 +361,9 @@ hipError_t launch_unpack_cross(const float *d_slab, float *d_fs, float *d_sf, co
 hipError_t launch_cross_linkage(const float *d_fs, const float *d_sf, uint32_t n_first, uint32_t n_second, const uint32_t *d_members,
                                 const uint32_t *d_set_off, uint32_t n_sets, float *d_link, uint32_t *d_nearest, float *d_nearest_linkage,
                                 hipStream_t stream);
+// clustering.hip: the two kernels of apd_cluster_medoids.  d_members: sorted ascending per set; d_keys: [n_sets] workspace.
+hipError_t launch_cluster_medoids(const float *d_dist, uint32_t n, const uint32_t *d_members, const uint32_t *d_set_off, uint32_t n_sets,
+                                  uint32_t n_members, unsigned long long *d_keys, uint32_t *d_medoid, float *d_cost, hipStream_t stream);
 hipError_t launch_sqrt_sweep(uint32_t first, uint64_t count, unsigned long long *d_out, hipStream_t stream);
 // The feature range of the fast kernels: a batch is theirs when every feature is 0 or has kFeatureFloor <= |v| < kFeatureBound;
 // any other value (NaN and the infinities included) raises the batch's flag, and the literal kernel aligns every pair.
@@ -442,12 +481,14 @@ struct apd_context {
     float tau = 1.0f / 64.0f;
     std::string last_error;
     // reusable device workspaces, grown through reserve_ws
-    apd::DeviceBuf ws_linkage;        // apd_cross_linkage: [members | set_off | link fs, sf], then the host form's staging
+    apd::DeviceBuf ws_linkage;        // apd_cross_linkage: [members | set_off | link fs, sf], then the host form's staging;
+                                      // apd_cluster_medoids: [members | set_off | keys], then the host form's [matrix | medoid | cost]
     apd::DeviceBuf ws_slab;
     apd::DeviceBuf ws_misc;
     apd::DeviceBuf ws_gather;         // gathered slabs of apd_align_all_sharded_async
     apd::DeviceBuf ws_path_dirs;      // apd_align_paths: direction words of a chunk of pairs
     apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
+    apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters in the resident layout, sums, counts, descriptors of every chunk
     apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)

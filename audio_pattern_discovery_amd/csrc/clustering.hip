@@ -1392,6 +1392,125 @@ hipError_t launch_cross_linkage(const float *d_fs, const float *d_sf, uint32_t n
 }
 }  // namespace apd
 
+// ------------------------------------------------------------------------- the medoid of every set (apd_cluster_medoids)
+namespace {
+
+// f32 bits -> a uint32 that orders like the value (negative values below positive ones); its inverse.  A cost is never -0: the
+// chain starts at +0 and a sum is -0 only when both addends are.
+__device__ __forceinline__ uint32_t ordered_bits(float v)
+{
+    const uint32_t b = __builtin_bit_cast(uint32_t, v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered_bits(uint32_t o)
+{
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+// One lane per (set, member i): the serial chain of the contract over the set's members ascending, then the set's arg-min through
+// one 64-bit integer atomicMin of (ordered cost bits, member) -- the smaller member wins equal costs, as the ascending strict-<
+// scan does; a cost that is not below +INF (NaN included) never enters.  Sets of any size, spanning any number of wavefronts.
+__global__ __launch_bounds__(64) void medoid_cost_kernel(const float *__restrict__ d, uint32_t n, const uint32_t *__restrict__ members,
+                                                         const uint32_t *__restrict__ set_off, uint32_t n_sets, uint32_t n_members,
+                                                         unsigned long long *__restrict__ keys)
+{
+    const uint32_t e = blockIdx.x * 64u + threadIdx.x;
+    if (e >= n_members) return;
+    uint32_t lo = 0, hi = n_sets;                                        // largest k with set_off[k] <= e: empty sets are stepped over
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (set_off[mid] <= e) lo = mid; else hi = mid; }
+    const uint32_t t0 = set_off[lo], t1 = set_off[lo + 1];
+    const uint32_t i = members[e];
+    const float *row = d + (size_t)i * n;
+    float cost = 0.0f;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint32_t j = members[t];
+        cost = cost + row[j];
+        cost = cost + d[(size_t)j * n + i];
+    }
+    if (cost < __builtin_inff()) atomicMin(&keys[lo], ((unsigned long long)ordered_bits(cost) << 32) | i);
+}
+
+__global__ __launch_bounds__(64) void medoid_pick_kernel(const unsigned long long *__restrict__ keys, uint32_t n_sets,
+                                                         uint32_t *__restrict__ medoid, float *__restrict__ cost)
+{
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= n_sets) return;
+    const unsigned long long key = keys[k];
+    const bool none = key == ~0ull;                                      // nothing entered: no ordered cost is all ones (that is a NaN)
+    medoid[k] = none ? 0xFFFFFFFFu : (uint32_t)key;
+    if (cost) cost[k] = none ? __builtin_inff() : from_ordered_bits((uint32_t)(key >> 32));
+}
+
+}  // namespace
+
+namespace apd {
+hipError_t launch_cluster_medoids(const float *d_dist, uint32_t n, const uint32_t *d_members, const uint32_t *d_set_off, uint32_t n_sets,
+                                  uint32_t n_members, unsigned long long *d_keys, uint32_t *d_medoid, float *d_cost, hipStream_t stream)
+{
+    if (n_sets == 0) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(d_keys, 0xFF, (size_t)n_sets * sizeof(unsigned long long), stream); e != hipSuccess) return e;
+    if (n_members) {
+        hipLaunchKernelGGL(medoid_cost_kernel, dim3((n_members + 63) / 64), dim3(64), 0, stream, d_dist, n, d_members, d_set_off, n_sets,
+                           n_members, d_keys);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(medoid_pick_kernel, dim3((n_sets + 63) / 64), dim3(64), 0, stream, d_keys, n_sets, d_medoid, d_cost);
+    return hipGetLastError();
+}
+}  // namespace apd
+
+extern "C" int apd_cluster_medoids(apd_context *ctx, const float *distances, int on_device, uint32_t n, const uint32_t *members,
+                                   const uint32_t *set_off, uint32_t n_sets, uint32_t *medoid, float *cost)
+{
+    if (!ctx) return APD_ERR_INVALID_ARG;
+    if (n_sets == 0) return APD_OK;
+    if (!set_off || !medoid || set_off[0] != 0) return APD_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < n_sets; ++k) if (set_off[k + 1] < set_off[k]) return APD_ERR_INVALID_ARG;
+    const uint32_t n_members = set_off[n_sets];
+    if (n_members && (!members || !distances)) return APD_ERR_INVALID_ARG;
+    // ascending sequence number inside every set: the order of the contract's chain and of its scan
+    std::vector<uint32_t> stage(members, members + n_members);
+    for (uint32_t k = 0; k < n_sets; ++k) {
+        std::sort(stage.begin() + set_off[k], stage.begin() + set_off[k + 1]);
+        for (uint32_t t = set_off[k]; t < set_off[k + 1]; ++t)
+            if (stage[t] >= n || (t > set_off[k] && stage[t] == stage[t - 1])) return APD_ERR_INVALID_ARG;
+    }
+    HIP_TRY(ctx, apd::bind_device(ctx));
+    stage.insert(stage.end(), set_off, set_off + n_sets + 1);
+    // ws_linkage: [members | set_off | keys], then the host form's [matrix | medoid | cost]
+    const size_t meta_bytes = (stage.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t keys_bytes = ((size_t)n_sets * sizeof(unsigned long long) + 255) & ~(size_t)255;
+    const size_t mat_bytes = ((size_t)n * n * sizeof(float) + 255) & ~(size_t)255;
+    const size_t in_off = meta_bytes + keys_bytes;
+    const size_t need = on_device ? in_off : in_off + mat_bytes + (size_t)n_sets * 8;
+    const int rc = reserve_ws(ctx, ctx->ws_linkage, std::max<size_t>(need, 256));
+    if (rc) return rc;
+    char *base = ctx->ws_linkage.as<char>();
+    uint32_t *d_members = (uint32_t *)base, *d_set_off = d_members + n_members;
+    unsigned long long *d_keys = (unsigned long long *)(base + meta_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(d_members, stage.data(), stage.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    const float *d_dist = distances;
+    uint32_t *d_medoid = medoid;
+    float *d_cost = cost;
+    if (!on_device) {
+        if (n_members) HIP_TRY(ctx, hipMemcpyAsync(base + in_off, distances, (size_t)n * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        d_dist = (const float *)(base + in_off);
+        d_medoid = (uint32_t *)(base + in_off + mat_bytes);
+        d_cost = (float *)(d_medoid + n_sets);
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // `stage` is a local: its upload must have left the host
+    APD_AFFINITY(ctx, "medoid launch");
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(ctx, apd::launch_cluster_medoids(d_dist, n, d_members, d_set_off, n_sets, n_members, d_keys, d_medoid, d_cost, ctx->stream));
+    if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+    if (!on_device) {
+        HIP_TRY(ctx, hipMemcpyAsync(medoid, d_medoid, (size_t)n_sets * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (cost) HIP_TRY(ctx, hipMemcpyAsync(cost, d_cost, (size_t)n_sets * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return APD_OK;
+}
+
 extern "C" int apd_percentile(apd_context *ctx, const float *x, uint64_t len, float perc, int x_on_device, float *value)
 {
     if (!ctx || !value || (len && !x)) return APD_ERR_INVALID_ARG;

@@ -56,11 +56,14 @@ __device__ __forceinline__ NodeBranch select_node_branch(float del_v, float ins_
 struct PathPairInfo { const float *X, *Y; int n, m; };
 __device__ __forceinline__ PathPairInfo decode_path_pair(const PathLaunch &L, const PathPair &P)
 {
-    const uint32_t ox = L.d_seq_off[P.px], oy = L.d_seq_off[P.py];
+    // x from a frames / offsets pair of its own when the launch has one (apd_barycenters), from the batch otherwise
+    const float *x_frames = L.d_x_frames ? L.d_x_frames : L.d_frames;
+    const uint32_t *x_off = L.d_x_seq_off ? L.d_x_seq_off : L.d_seq_off;
+    const uint32_t ox = x_off[P.px], oy = L.d_seq_off[P.py];
     PathPairInfo r;
-    r.n = (int)(L.d_seq_off[P.px + 1] - ox) - 2;
+    r.n = (int)(x_off[P.px + 1] - ox) - 2;
     r.m = (int)(L.d_seq_off[P.py + 1] - oy) - 2;
-    r.X = L.d_frames + (uint64_t)ox * L.dpad;
+    r.X = x_frames + (uint64_t)ox * L.dpad;
     r.Y = L.d_frames + (uint64_t)oy * L.dpad;
     return r;
 }
@@ -238,6 +241,144 @@ hipError_t launch_path_trace(const PathLaunch &L, hipStream_t stream)
 {
     if (L.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(dtw_path_trace, dim3(L.n_pairs), dim3(64), 0, stream, L);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// DTW barycenters (apd_barycenters).  An iteration is the sweep and the trace above with the barycenters as the x side, then these
+// kernels over the steps the trace left on the device.  Every sum is a serial f32 chain in the contract's order (members ascending,
+// steps in path order), owned by ONE lane from the first chunk of an iteration to the last: no atomics, and the chunking cannot
+// show in the result.
+// ------------------------------------------------------------------------------------------------
+
+// the set that owns padded barycenter frame f: largest k with d_bary_off[k] <= f
+__device__ __forceinline__ uint32_t bary_set_of(const BaryLaunch &L, uint32_t f)
+{
+    uint32_t lo = 0, hi = L.n_sets;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (L.d_bary_off[mid] <= f) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// One lane per float of d_bary: the frames of init[k] (all dpad slots), zeros in the two padding frames.
+__global__ __launch_bounds__(256) void bary_init_kernel(const BaryLaunch L, const uint32_t *__restrict__ init_pos)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)L.n_padded * L.dpad) return;
+    const uint32_t f = (uint32_t)(e / L.dpad), q = (uint32_t)(e - (uint64_t)f * L.dpad);
+    const uint32_t k = bary_set_of(L, f);
+    const uint32_t t = f - L.d_bary_off[k], T = L.d_bary_off[k + 1] - L.d_bary_off[k] - 2;
+    L.d_bary[e] = t < T ? L.d_frames[(uint64_t)(L.d_seq_off[init_pos[k]] + t) * L.dpad + q] : 0.0f;
+}
+
+// One lane per set: which of the chunk's paths contribute (non-empty, first step START), and the chain of their scores.
+__global__ __launch_bounds__(64) void bary_scores_kernel(const BaryLaunch L)
+{
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= L.n_sets) return;
+    const uint2 range = L.d_set_pairs[k];
+    if (range.x >= range.y) return;
+    float sum = L.d_score_sum[k];
+    uint32_t used = L.d_used[k];
+    for (uint32_t p = range.x; p < range.y; ++p) {
+        const bool contributes = L.d_len[p] > 0 && L.d_steps[L.d_pairs[p].step_off].op == APD_PATH_START;
+        L.d_contrib[p] = contributes ? 1u : 0u;
+        if (contributes) { sum = sum + L.d_scores[p]; ++used; }
+    }
+    L.d_score_sum[k] = sum;
+    L.d_used[k] = used;
+}
+
+// One lane per (set, table row t, frame slot): over the chunk's contributing paths of its set in order, the steps with i == t -- a
+// contiguous range, the steps are monotone in i: a binary search finds its start -- add frame j - 1 of the member, serially, onto
+// the running sum the earlier chunks left.  Slot 0's lane keeps the row's count.
+__global__ __launch_bounds__(256) void bary_accumulate_kernel(const BaryLaunch L)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)L.n_padded * L.dpad) return;
+    const uint32_t f = (uint32_t)(e / L.dpad), q = (uint32_t)(e - (uint64_t)f * L.dpad);
+    const uint32_t k = bary_set_of(L, f);
+    const uint32_t t = f - L.d_bary_off[k] + 1, T = L.d_bary_off[k + 1] - L.d_bary_off[k] - 2;
+    const uint2 range = L.d_set_pairs[k];
+    if (t > T || q >= L.dim || range.x >= range.y) return;
+    float sum = L.d_sum[e];
+    uint32_t cnt = L.d_cnt[f];
+    for (uint32_t p = range.x; p < range.y; ++p) {
+        if (!L.d_contrib[p]) continue;
+        const PathPair P = L.d_pairs[p];
+        const apd_path_step *steps = L.d_steps + P.step_off;
+        const uint32_t len = L.d_len[p];
+        const float *y = L.d_frames + (uint64_t)L.d_seq_off[P.py] * L.dpad + q;
+        uint32_t lo = 0, hi = len;                                   // first step with i >= t
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (steps[mid].i < t) lo = mid + 1; else hi = mid; }
+        for (; lo < len && steps[lo].i == t; ++lo) {                 // t >= 1: never the START step
+            sum = sum + y[(uint64_t)(steps[lo].j - 1) * L.dpad];
+            ++cnt;
+        }
+    }
+    L.d_sum[e] = sum;
+    if (q == 0) L.d_cnt[f] = cnt;
+}
+
+// One lane per (set, row, slot): the mean, or the old frame where nothing warped onto the row; lane (row 1, slot 0) of a set also
+// writes the set's inertia and count.
+__global__ __launch_bounds__(256) void bary_finalize_kernel(const BaryLaunch L, float *__restrict__ inertia, uint32_t *__restrict__ used_out)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)L.n_padded * L.dpad) return;
+    const uint32_t f = (uint32_t)(e / L.dpad), q = (uint32_t)(e - (uint64_t)f * L.dpad);
+    const uint32_t k = bary_set_of(L, f);
+    const uint32_t t = f - L.d_bary_off[k] + 1, T = L.d_bary_off[k + 1] - L.d_bary_off[k] - 2;
+    if (t == T + 1 && q == 0) {                                      // the first padding frame: one lane per set, empty sets too
+        const uint32_t used = L.d_used[k];
+        inertia[k] = used ? L.d_score_sum[k] / (float)used : APD_INF;
+        used_out[k] = used;
+    }
+    if (t > T || q >= L.dim) return;
+    const uint32_t cnt = L.d_cnt[f];
+    if (cnt > 0) L.d_bary[e] = L.d_sum[e] / (float)cnt;
+}
+
+// One lane per (set, frame, component of the caller's dimension): the caller's packing, frame_off[k] = d_bary_off[k] - 2 k.
+__global__ __launch_bounds__(256) void bary_pack_kernel(const BaryLaunch L, float *__restrict__ out)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint64_t)L.n_padded * L.dpad) return;
+    const uint32_t f = (uint32_t)(e / L.dpad), q = (uint32_t)(e - (uint64_t)f * L.dpad);
+    const uint32_t k = bary_set_of(L, f);
+    const uint32_t t = f - L.d_bary_off[k], T = L.d_bary_off[k + 1] - L.d_bary_off[k] - 2;
+    if (t >= T || q >= L.src_dim) return;
+    out[(uint64_t)(f - 2 * k) * L.src_dim + q] = L.d_bary[e];
+}
+
+static uint32_t bary_blocks(const BaryLaunch &L) { return (uint32_t)(((uint64_t)L.n_padded * L.dpad + 255) / 256); }
+
+hipError_t launch_bary_init(const BaryLaunch &L, const uint32_t *d_init_pos, hipStream_t stream)
+{
+    if (L.n_sets == 0) return hipSuccess;
+    hipLaunchKernelGGL(bary_init_kernel, dim3(bary_blocks(L)), dim3(256), 0, stream, L, d_init_pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_bary_accumulate(const BaryLaunch &L, hipStream_t stream)
+{
+    if (L.n_sets == 0) return hipSuccess;
+    hipLaunchKernelGGL(bary_scores_kernel, dim3((L.n_sets + 63) / 64), dim3(64), 0, stream, L);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(bary_accumulate_kernel, dim3(bary_blocks(L)), dim3(256), 0, stream, L);
+    return hipGetLastError();
+}
+
+hipError_t launch_bary_finalize(const BaryLaunch &L, float *d_inertia, uint32_t *d_used_out, hipStream_t stream)
+{
+    if (L.n_sets == 0) return hipSuccess;
+    hipLaunchKernelGGL(bary_finalize_kernel, dim3(bary_blocks(L)), dim3(256), 0, stream, L, d_inertia, d_used_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_bary_pack(const BaryLaunch &L, float *d_out, hipStream_t stream)
+{
+    if (L.n_sets == 0) return hipSuccess;
+    hipLaunchKernelGGL(bary_pack_kernel, dim3(bary_blocks(L)), dim3(256), 0, stream, L, d_out);
     return hipGetLastError();
 }
 

@@ -151,6 +151,55 @@ pub fn spot(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery
     best
 }
 
+/// Not in the reference: DTW barycenter averaging (apd_barycenters) of the sets of sequence numbers in `sets` (as cluster_sets
+/// returns them) on the first device of APD_DEVICES.  init[k]: the sequence whose frames start set k's barycenter (usually
+/// clustering::medoids' choice).  Returns one NDSequence per set, as long as its init sequence (empty for an empty set; the last
+/// frame keeps the init's last frame: the paths end at the reference's score cell), and inertia[it * sets.len() + k].
+pub fn barycenters(data: &[NDSequence], sets: &[Vec<usize>], init: &[usize], iterations: usize, params: &Discovery) -> (Vec<NDSequence>, Vec<f32>) {
+    assert_eq!(sets.len(), init.len());
+    let n = data.len();
+    if n == 0 || sets.is_empty() { return (Vec::new(), Vec::new()); }
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let dim = data[0].n_bins;
+    let mut offsets = vec![0u64; n + 1];
+    let mut all: Vec<f32> = Vec::new();
+    for (s, seq) in data.iter().enumerate() {
+        offsets[s + 1] = offsets[s] + seq.len() as u64;
+        all.extend_from_slice(&seq.frames);
+    }
+    let members: Vec<u32> = sets.iter().flat_map(|s| s.iter().map(|v| *v as u32)).collect();
+    let mut set_off = vec![0u32; sets.len() + 1];
+    for (k, s) in sets.iter().enumerate() { set_off[k + 1] = set_off[k] + s.len() as u32; }
+    let init: Vec<u32> = init.iter().map(|v| *v as u32).collect();
+    let mut frame_off = vec![0u64; sets.len() + 1];
+    let mut inertia = vec![0f32; (iterations * sets.len()).max(1)];
+    let mut frames: Vec<f32>;
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let mut b = std::ptr::null_mut();
+        check(apd_batch_create(ctx, all.as_ptr(), offsets.as_ptr(), n as u32, dim as u32, 0, &mut b));
+        let mut rc = apd_barycenters(ctx, b, &cfg, members.as_ptr(), set_off.as_ptr(), sets.len() as u32, init.as_ptr(), iterations as u32, std::ptr::null_mut(), 0, 0, frame_off.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut());
+        let total = frame_off[sets.len()];
+        frames = vec![0f32; (total as usize * dim).max(1)];
+        if rc == APD_OK {
+            rc = apd_barycenters(ctx, b, &cfg, members.as_ptr(), set_off.as_ptr(), sets.len() as u32, init.as_ptr(), iterations as u32, frames.as_mut_ptr(), 0, total, frame_off.as_mut_ptr(), inertia.as_mut_ptr(), std::ptr::null_mut());
+        }
+        apd_destroy(ctx);                                                 // releases the device side of the batch
+        apd_batch_destroy(b);
+        check(rc);
+    }
+    inertia.truncate(iterations * sets.len());
+    let out = (0..sets.len()).map(|k| NDSequence {
+        frames: frames[frame_off[k] as usize * dim..frame_off[k + 1] as usize * dim].to_vec(), n_bins: dim,
+        dft_win: data[init[k] as usize].dft_win, spectrogram: Vec::new(), audio_id: data[init[k] as usize].audio_id,
+    }).collect();
+    (out, inertia)
+}
+
 /// apd_spot_hits: the non-overlapping windows of one pair's curves whose score is strictly below `threshold`, best first.
 pub fn spot_hits(cost: &[f32], start: &[u32], n: usize, threshold: f32) -> Vec<apd_spot_best> {
     assert_eq!(cost.len(), start.len());

@@ -202,6 +202,12 @@ extern "C" {
     pub fn apd_cross_linkage(ctx: *mut apd_context, fs: *const f32, sf: *const f32, on_device: c_int, n_first: u32, n_second: u32,
                              members: *const u32, set_off: *const u32, n_sets: u32, link_fs: *mut f32, link_sf: *mut f32,
                              nearest: *mut u32, nearest_linkage: *mut f32) -> c_int;
+    // cluster prototypes
+    pub fn apd_cluster_medoids(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, members: *const u32,
+                               set_off: *const u32, n_sets: u32, medoid: *mut u32, cost: *mut f32) -> c_int;
+    pub fn apd_barycenters(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, members: *const u32,
+                           set_off: *const u32, n_sets: u32, init: *const u32, iterations: u32, frames: *mut f32,
+                           frames_on_device: c_int, capacity: u64, frame_off: *mut u64, inertia: *mut f32, used: *mut u32) -> c_int;
     // companions
     pub fn apd_encode(ctx: *mut apd_context, x: *const f32, t: u64, d_in: u32, w_encode: *const f32, b_encode: *const f32,
                       latent: u32, on_device: c_int, out: *mut f32) -> c_int;

@@ -87,6 +87,23 @@ impl AgglomerativeClustering {
         (0..n_queries).map(|q| (if nearest[q] == u32::MAX { None } else { Some(nearest[q] as usize) }, linkage[q])).collect()
     }
 
+    /// Not in the reference: the medoid of every set of `sets` (as cluster_sets returns them) from the n x n matrix of align_all
+    /// (apd_cluster_medoids): per set the member whose summed distances to and from the members (ascending, one f32 add per term)
+    /// are smallest, the smallest sequence number among equals, and that cost; None with an infinite cost for an empty set or one
+    /// whose costs are all +INF / NaN.
+    pub fn medoids(distances: &[f32], n_instances: usize, sets: &[Vec<usize>]) -> Vec<(Option<usize>, f32)> {
+        let members: Vec<u32> = sets.iter().flat_map(|s| s.iter().map(|v| *v as u32)).collect();
+        let mut set_off = vec![0u32; sets.len() + 1];
+        for (k, s) in sets.iter().enumerate() { set_off[k + 1] = set_off[k] + s.len() as u32; }
+        let mut medoid = vec![0u32; sets.len().max(1)];
+        let mut cost = vec![0f32; sets.len().max(1)];
+        with_context(|ctx| unsafe {
+            check(apd_cluster_medoids(ctx, distances.as_ptr(), 0, n_instances as u32, members.as_ptr(), set_off.as_ptr(), sets.len() as u32,
+                                      medoid.as_mut_ptr(), cost.as_mut_ptr()));
+        });
+        (0..sets.len()).map(|k| (if medoid[k] == u32::MAX { None } else { Some(medoid[k] as usize) }, cost[k])).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

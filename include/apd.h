@@ -481,6 +481,57 @@ int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on
                       const uint32_t *members, const uint32_t *set_off, uint32_t n_sets,
                       float *link_fs, float *link_sf, uint32_t *nearest, float *nearest_linkage);
 
+/* ---- cluster prototypes: which member stands for a cluster, and the cluster's average shape ---------------------------------
+ * The medoid of every set: the member closest to all the others, from the [n][n] matrix of apd_align_all.  For set k with its
+ * members sorted ascending j1 < j2 < ..., whatever order `members` lists them in, the cost of member i is
+ *   cost(i) = ((((0 + d[i][j1]) + d[j1][i]) + d[i][j2]) + d[j2][i]) + ...
+ * f32, one rounded add per term; j = i is included (its diagonal entry is 0 in a matrix of apd_align_all).  medoid[k]: scan i
+ * ascending and keep a member only if its cost is strictly below the best so far, starting from +INF -- the smallest sequence
+ * number wins ties, a NaN cost is never kept; cost[k] that value (cost may be NULL).  Nothing kept (all +INF / NaN, or an empty set):
+ * 0xFFFFFFFF and +INF.
+ * members / set_off / n_sets: host arrays, as apd_cluster_sets returns them and apd_cross_linkage takes them; a member >= n or a
+ * sequence listed twice in one set is APD_ERR_INVALID_ARG.  n_sets == 0: APD_OK, nothing written.
+ * distances / medoid / cost: host, or all device pointers if on_device (the matrix and the results stay in HBM; the call waits once
+ * for the upload of the member lists, the kernels are only enqueued on the context's stream, as apd_cross_linkage does). */
+int apd_cluster_medoids(apd_context *ctx, const float *distances, int on_device, uint32_t n,
+                        const uint32_t *members, const uint32_t *set_off, uint32_t n_sets,
+                        uint32_t *medoid, float *cost);
+
+/* DTW barycenter averaging (DBA, Petitjean et al. 2011) of every set: a sequence whose frames are the means of the member frames
+ * that warp onto them.  batch: any resident batch, plain or joined; sequence numbers are the caller's.  members / set_off / n_sets:
+ * as for apd_cluster_medoids.  init[k]: the sequence whose frames start set k's barycenter -- usually the medoid; it need not be a
+ * member.  The barycenter of set k keeps the length of init[k]: T_k frames, 0 for an empty set.
+ * One iteration for set k, current barycenter c (T frames), members s1 < s2 < ... ascending whatever order `members` lists them in:
+ *   for every member s the warping path of the ordered pair (x = c, y = s) exactly as apd_align_paths defines it: band from
+ *     max(T, len s) through cfg, the literal arithmetic whatever apd_set_distance_mode says, the walk from (n-1, m-1);
+ *   a path CONTRIBUTES iff it is non-empty and its first step is START (it reached the origin).  The test is structural: a complete
+ *     path with NaN costs contributes; a member of one frame gives an empty path and is skipped unless T = 1 as well;
+ *   for table rows t = 1 .. T: sum[t][.] = 0, cnt[t] = 0; then over the contributing members ascending, and over each path's steps
+ *     in path order with i == t and op != START: sum[t][d] = sum[t][d] + y_s[j-1][d] (one rounded f32 add per dimension), cnt[t] += 1;
+ *   new c[t-1][d] = sum[t][d] / (float)cnt[t] (one f32 division) where cnt[t] > 0, otherwise c[t-1] keeps its value.
+ * The paths end at the reference's score cell (n-1, m-1) (alignments.rs:120), so row T is never on a path: THE LAST FRAME OF A
+ * BARYCENTER KEEPS THE LAST FRAME OF init[k].  That is the project's alignment, not an accident.  Rows 1 .. T-1 are all visited by a
+ * complete path, so they average at least one frame per contributing member.
+ *   used[it][k] = contributing members; inertia[it][k] = ((0 + score_s1) + score_s2 + ...) / (float)used over the contributing
+ *   members ascending, scores (apd_align_paths' score) measured against the barycenter BEFORE this iteration's update; +INF if
+ *   used == 0.  No monotonicity is promised: the reference's tie rule (alignments.rs:153-159) does not take a minimum.
+ * iterations == 0 returns the init frames unchanged, bit for bit.
+ * frame_off (n_sets + 1 entries, always written, no GPU work needed for it): set k owns frames[frame_off[k] .. frame_off[k+1]), each
+ *   entry one frame of the caller's dim floats.  frames == NULL: sizes only.  capacity (in frames) < frame_off[n_sets]:
+ *   APD_ERR_INVALID_ARG.  frames_on_device: frames is a device pointer and the result stays in HBM, packed exactly as
+ *   apd_batch_create(..., frames_on_device = 1) takes it with frame_off as offsets.  inertia / used: [iterations][n_sets], host,
+ *   either may be NULL.
+ * An index (member or init) >= apd_batch_len or a sequence listed twice in one set is APD_ERR_INVALID_ARG, an empty sequence in the
+ * batch APD_ERR_EMPTY_SEQUENCE, any (T_k, len s) whose band needs 2w+1 > 20 480 offsets APD_ERR_BAND_TOO_WIDE, each before anything is
+ * launched.  Follows apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers all kernels of the call.
+ * The barycenters never visit the host between iterations and no step is downloaded; the pairs run in chunks under
+ * apd_align_paths' workspace cap (APD_PATH_WORKSPACE_BYTES), a set may straddle chunks, results identical whatever the cap. */
+int apd_barycenters(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg,
+                    const uint32_t *members, const uint32_t *set_off, uint32_t n_sets,
+                    const uint32_t *init, uint32_t iterations,
+                    float *frames, int frames_on_device, uint64_t capacity, uint64_t *frame_off,
+                    float *inertia, uint32_t *used);
+
 /* ---- companions ---------------------------------------------------------------------- */
 /* AutoEncoder::predict over every frame = NDSequence::encoded (src/neural.rs:55-71,
  * src/spectrogram.rs:103-121).  x: [t][d_in]; w_encode: [d_in][latent] (Mat{flat, cols=latent},

@@ -298,6 +298,28 @@ class AlignmentWorkers {
         }
         return out;
     }
+    // Not in the reference: DTW barycenter averaging (apd.h, "cluster prototypes") of the sets of this object's sequence numbers in
+    // `sets`; init[k]: the sequence whose frames start set k's barycenter (usually AgglomerativeClustering::medoids' choice).
+    // frames[k]: [T_k][dim] packed, T_k the length of init[k] (0 for an empty set); inertia / used: [iterations][sets.size()].
+    struct Barycenters { std::vector<std::vector<float>> frames; std::vector<float> inertia; std::vector<uint32_t> used; };
+    Barycenters barycenters(const std::vector<std::vector<std::size_t>> &sets, const std::vector<uint32_t> &init, const Discovery &params,
+                            uint32_t iterations = 10)
+    {
+        if (init.size() != sets.size()) throw Error(APD_ERR_INVALID_ARG, "one init sequence per set");
+        const apd_align_config c = params.config();
+        std::vector<uint32_t> members, off(1, 0u);
+        for (const auto &s : sets) { members.insert(members.end(), s.begin(), s.end()); off.push_back((uint32_t)members.size()); }
+        const uint32_t n_sets = (uint32_t)sets.size();
+        std::vector<uint64_t> frame_off(sets.size() + 1, 0);
+        check(apd_barycenters(ctx_.get(), batch_, &c, members.data(), off.data(), n_sets, init.data(), iterations, nullptr, 0, 0,
+                              frame_off.data(), nullptr, nullptr), ctx_.get());                                          // sizes
+        std::vector<float> flat(std::max<uint64_t>(frame_off.back() * dim, 1));
+        Barycenters out{{}, std::vector<float>((std::size_t)iterations * n_sets), std::vector<uint32_t>((std::size_t)iterations * n_sets)};
+        check(apd_barycenters(ctx_.get(), batch_, &c, members.data(), off.data(), n_sets, init.data(), iterations, flat.data(), 0,
+                              frame_off.back(), frame_off.data(), out.inertia.data(), out.used.data()), ctx_.get());
+        for (std::size_t k = 0; k < sets.size(); ++k) out.frames.emplace_back(flat.begin() + frame_off[k] * dim, flat.begin() + frame_off[k + 1] * dim);
+        return out;
+    }
     const char *collective() const { return multi_ ? apd_multi_collective(multi_) : "none (one device)"; }
     std::vector<NDSequence> data;
     std::vector<float> result;                                                       // n*n row-major, diagonal 0.0
@@ -368,6 +390,18 @@ struct AgglomerativeClustering {
                        std::vector<float>(n_first)};
         check(apd_cross_linkage(ctx.get(), fs.data(), sf.data(), 0, (uint32_t)n_first, (uint32_t)n_second, members.data(), off.data(),
                                 (uint32_t)sets.size(), r.link_fs.data(), r.link_sf.data(), r.nearest.data(), r.nearest_linkage.data()), ctx.get());
+        return r;
+    }
+    // Not in the reference: the medoid of every set of `sets` from the n x n matrix of AlignmentWorkers::align_all
+    // (apd_cluster_medoids): the smallest sequence number among the members of least cost, 0xFFFFFFFF / +INF if there is none.
+    static std::pair<std::vector<uint32_t>, std::vector<float>> medoids(Context &ctx, const std::vector<float> &distances, std::size_t n_instances,
+                                                                        const std::vector<std::vector<std::size_t>> &sets)
+    {
+        std::vector<uint32_t> members, off(1, 0u);
+        for (const auto &s : sets) { members.insert(members.end(), s.begin(), s.end()); off.push_back((uint32_t)members.size()); }
+        std::pair<std::vector<uint32_t>, std::vector<float>> r{std::vector<uint32_t>(sets.size()), std::vector<float>(sets.size())};
+        check(apd_cluster_medoids(ctx.get(), distances.data(), 0, (uint32_t)n_instances, members.data(), off.data(), (uint32_t)sets.size(),
+                                  r.first.data(), r.second.data()), ctx.get());
         return r;
     }
 };
