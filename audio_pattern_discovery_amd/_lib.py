@@ -55,6 +55,11 @@ class SpotBest(C.Structure):
     _fields_ = [("end", C.c_uint32), ("start", C.c_uint32), ("cost", C.c_float), ("score", C.c_float)]
 
 
+class SpotWindow(C.Structure):
+    """apd_spot_window: a window of stream y matched to query x -- 1-based columns of its last and first frame, as in apd_spot_best."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("end", C.c_uint32), ("start", C.c_uint32)]
+
+
 class MatView(C.Structure):
     """apd_mat_view: where a Mat { flat, cols } (numerics.rs:171-174) lies in a bincode image."""
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64), ("cols", C.c_uint64)]
@@ -168,6 +173,9 @@ SYMBOLS = [
                                       C.POINTER(PathStep), C.c_uint64, _u64p, _f32p]),
     ("apd_spot", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, _f32p, _u32p, C.c_uint64, _u64p, C.POINTER(SpotBest)]),
     ("apd_spot_hits", C.c_int, [_f32p, _u32p, C.c_uint64, C.c_uint64, C.c_float, C.POINTER(SpotBest), C.c_uint64, _u64p]),
+    ("apd_spot_path_bound", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
+    ("apd_spot_paths", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), C.POINTER(SpotWindow), C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p,
+                                 _u32p, _u32p, _f32p]),
     ("apd_percentile", C.c_int, [_vp, _vp, C.c_uint64, C.c_float, C.c_int, _f32p]),
     ("apd_clustering", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_float, C.POINTER(ClusterOp), _u32p, _u32p,
                                  _u32p, _f32p]),

@@ -92,6 +92,8 @@ class AlignmentParams:
 PATH_STEP = np.dtype([("i", np.uint32), ("j", np.uint32), ("cost", np.float32), ("op", np.uint32)])
 # apd_spot_best as a numpy record: what AlignmentWorkers.spot() and spot_hits() return
 SPOT_BEST = np.dtype([("end", np.uint32), ("start", np.uint32), ("cost", np.float32), ("score", np.float32)])
+# apd_spot_window as a numpy record: what AlignmentWorkers.spot_paths() hands to the library
+SPOT_WINDOW = np.dtype([("x", np.uint32), ("y", np.uint32), ("end", np.uint32), ("start", np.uint32)])
 
 
 class Alignment:
@@ -288,6 +290,40 @@ class AlignmentWorkers:
             if streams is not None:
                 batch.close()
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(n_pairs)], best
+
+    def spot_paths(self, pairs, windows, params, streams=None):
+        """Warping paths of spotted windows (include/apd.h, "warping paths of spotted windows"): window k is columns windows[k]["start"]
+        .. windows[k]["end"] of the stream of pairs[k] = (query, stream) -- `windows` a SPOT_BEST array of len(pairs) records, as
+        spot()'s best or spot_hits() return them (a pair may appear many times, once per hit); numbering and `streams` as for spot().
+        Returns (list of PATH_STEP arrays in input order -- empty for a {0, 0} record and for a start that is not the table's --,
+        found_start, scores): apd_spot_paths."""
+        if self._multi is not None or (streams is not None and streams._multi is not None):
+            raise ValueError("spot_paths() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_windows = len(pr)
+        if len(windows) != n_windows:
+            raise ValueError("one window per pair")
+        win = np.zeros(n_windows, dtype=SPOT_WINDOW)
+        win["x"], win["y"] = pr[:, 0], pr[:, 1]
+        win["end"], win["start"] = windows["end"], windows["start"]
+        L = _lib.lib()
+        off = np.zeros(n_windows + 1, dtype=np.uint64)
+        lens = np.zeros(n_windows, dtype=np.uint32)
+        found = np.zeros(n_windows, dtype=np.uint32)
+        scores = np.zeros(n_windows, dtype=np.float32)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
+        try:
+            head = (self.ctx.handle, batch.handle, C.byref(cfg), win.ctypes.data_as(C.POINTER(_lib.SpotWindow)), n_windows)
+            _lib.check(L.apd_spot_paths(*head, None, 0, off.ctypes.data_as(u64p), None, None, None), self.ctx.handle)       # sizes
+            steps = np.zeros(max(int(off[-1]), 1), dtype=PATH_STEP)
+            _lib.check(L.apd_spot_paths(*head, steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), off.ctypes.data_as(u64p),
+                                        lens.ctypes.data_as(u32p), found.ctypes.data_as(u32p), scores.ctypes.data_as(f32p)), self.ctx.handle)
+        finally:
+            if streams is not None:
+                batch.close()
+        return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_windows)], found, scores
 
     def barycenters(self, sets, params, init=None, iterations=10, on_device=False):
         """DTW barycenter averaging (include/apd.h, "cluster prototypes") of the sets of this object's sequence numbers in `sets`

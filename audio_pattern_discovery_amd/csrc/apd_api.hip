@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <tuple>
 
 #include "apd_internal.h"
 
@@ -1418,6 +1419,191 @@ extern "C" int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t 
         }
     } catch (const std::bad_alloc &) {
         return APD_ERR_OOM;
+    }
+    return APD_OK;
+}
+
+// ------------------------------------------------------------------- warping paths of spotted windows
+
+extern "C" uint64_t apd_spot_path_bound(uint64_t n, uint64_t end, uint64_t start)
+{
+    return (n == 0 || start == 0 || start > end) ? 0 : n + (end - start + 1);
+}
+
+// The windows are taken in input order, a chunk at a time: as many as keep the direction words (counted per window, before the
+// merge makes them fewer) and the steps under the workspace cap, at least one.  Inside a chunk the windows are grouped by (query,
+// stream) pair: one sweep per pair over the union of its windows' columns, one trace per window (kernels: dtw_spot_path.hip).
+// ws_spot_steps: [steps | pairs | intervals | windows | ends] (all but the steps uploaded), then [end cost | end start | lengths |
+// found | scores]; ws_spot_dirs: the intervals' words.
+extern "C" int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const apd_spot_window *windows,
+                              uint64_t n_windows, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
+                              uint32_t *found_start, float *scores)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || !step_off || (n_windows && !windows)) return APD_ERR_INVALID_ARG;
+    const uint32_t n_seq = batch->n_seq;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
+    for (uint64_t p = 0; p < n_windows; ++p)
+        if (windows[p].x >= n_seq || windows[p].y >= n_seq) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    for (uint64_t p = 0; p < n_windows; ++p) {
+        const apd_spot_window &w = windows[p];
+        if (w.end > len_of(w.y) || (w.end && w.start > w.end)) return APD_ERR_INVALID_ARG;
+    }
+    auto slots_of = [&](uint64_t p) { return apd_spot_path_bound(len_of(windows[p].x), windows[p].end, windows[p].start); };
+    step_off[0] = 0;
+    for (uint64_t p = 0; p < n_windows; ++p) step_off[p + 1] = step_off[p] + slots_of(p);
+    if (!steps) return APD_OK;                                            // sizes only
+    if (capacity < step_off[n_windows] || (n_windows && !path_len)) return APD_ERR_INVALID_ARG;
+    if (n_windows == 0) return APD_OK;
+    for (uint64_t p = 0; p < n_windows; ++p)
+        if (len_of(windows[p].x) > kSpotMaxQuery || len_of(windows[p].y) >= kSpotMaxStream) {
+            ctx->last_error = "apd_spot_paths: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
+            return APD_ERR_UNSUPPORTED;
+        }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot path launch");
+    const uint64_t cap = spot_workspace_cap();
+    constexpr uint64_t kMaxWindowsPerLaunch = 1ull << 24;                 // 64 work-items per window, launches stay below 2^31
+    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    std::vector<uint64_t> live;                                           // the chunk's windows that own slots, input order
+    std::vector<uint64_t> by_pair;                                        // the same, grouped by pair, starts ascending
+    std::vector<SpotRecPair> rec_pairs[kClasses];
+    std::vector<SpotInterval> intervals;
+    std::vector<uint32_t> ends;
+    std::vector<SpotTraceWindow> trace;
+    std::vector<char> upload;
+    std::vector<uint32_t> h_len, h_found;
+    std::vector<float> h_scores;
+    bool first_launch = true;
+    for (uint64_t first = 0; first < n_windows;) {
+        uint64_t last = first, est_words = 0;
+        while (last < n_windows && last - first < kMaxWindowsPerLaunch) {
+            const apd_spot_window &w = windows[last];
+            const uint64_t slots = step_off[last + 1] - step_off[last];
+            const uint64_t nw = est_words + (slots ? spot_dir_words(len_of(w.x), (uint64_t)w.end - w.start + 1) : 0);
+            if (last > first && (nw * sizeof(uint32_t) > cap || (step_off[last + 1] - step_off[first]) * sizeof(apd_path_step) > cap)) break;
+            est_words = nw;
+            ++last;
+        }
+        live.clear();
+        for (uint64_t p = first; p < last; ++p) {
+            if (step_off[p + 1] > step_off[p]) { live.push_back(p); continue; }
+            path_len[p] = 0;                                              // no window: nothing to sweep
+            if (found_start) found_start[p] = 0;
+            if (scores) scores[p] = INFINITY;
+        }
+        if (live.empty()) { first = last; continue; }
+        // ---- the plan: per pair its merged intervals and its distinct ends; per window its interval and its end's slot
+        by_pair = live;
+        std::sort(by_pair.begin(), by_pair.end(), [&](uint64_t a, uint64_t b) {
+            const apd_spot_window &u = windows[a], &v = windows[b];
+            return std::make_tuple(u.x, u.y, u.start, u.end, a) < std::make_tuple(v.x, v.y, v.start, v.end, b);
+        });
+        for (auto &v : rec_pairs) v.clear();
+        intervals.clear(); ends.clear();
+        trace.assign(live.size(), SpotTraceWindow{});
+        uint64_t words = 0;
+        uint32_t r_max = 1;
+        for (size_t g = 0; g < by_pair.size();) {
+            size_t g_end = g;
+            const apd_spot_window &head = windows[by_pair[g]];
+            while (g_end < by_pair.size() && windows[by_pair[g_end]].x == head.x && windows[by_pair[g_end]].y == head.y) ++g_end;
+            const uint32_t n = len_of(head.x), c = spot_row_class(batch->dim, n);
+            if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(n));
+            SpotRecPair rp{};
+            rp.px = pos[head.x]; rp.py = pos[head.y];
+            rp.iv_first = (uint32_t)intervals.size(); rp.end_first = (uint32_t)ends.size();
+            for (size_t t = g; t < g_end; ++t) {
+                const apd_spot_window &w = windows[by_pair[t]];
+                if (intervals.size() > rp.iv_first && (uint64_t)w.start <= (uint64_t)intervals.back().b + 1)
+                    intervals.back().b = std::max(intervals.back().b, w.end);   // overlapping or touching: one interval
+                else
+                    intervals.push_back(SpotInterval{w.start, w.end, 0});
+                ends.push_back(w.end);
+                rp.max_end = std::max(rp.max_end, w.end);
+            }
+            std::sort(ends.begin() + rp.end_first, ends.end());
+            ends.erase(std::unique(ends.begin() + rp.end_first, ends.end()), ends.end());
+            rp.n_iv = (uint32_t)intervals.size() - rp.iv_first; rp.n_ends = (uint32_t)ends.size() - rp.end_first;
+            for (uint32_t k = rp.iv_first; k < intervals.size(); ++k) {
+                intervals[k].off = words;
+                words += spot_dir_words(n, (uint64_t)intervals[k].b - intervals[k].a + 1);
+            }
+            for (size_t t = g; t < g_end; ++t) {
+                const uint64_t p = by_pair[t];
+                const apd_spot_window &w = windows[p];
+                SpotTraceWindow &tw = trace[std::lower_bound(live.begin(), live.end(), p) - live.begin()];
+                uint32_t k = rp.iv_first;
+                while (intervals[k].b < w.end) ++k;                       // the interval that holds [start, end]
+                tw.px = rp.px; tw.py = rp.py; tw.end = w.end; tw.start = w.start;
+                tw.a = intervals[k].a; tw.dir_off = intervals[k].off;
+                tw.end_slot = (uint32_t)(std::lower_bound(ends.begin() + rp.end_first, ends.end(), w.end) - ends.begin());
+                tw.step_off = step_off[p] - step_off[first];
+            }
+            rec_pairs[c].push_back(rp);
+            g = g_end;
+        }
+        // ---- workspaces
+        const size_t nt = trace.size(), ne = ends.size();
+        size_t np = 0;
+        for (auto &v : rec_pairs) np += v.size();
+        const size_t steps_bytes = (size_t)(step_off[last] - step_off[first]) * sizeof(apd_path_step);
+        const size_t o_pairs = 0, o_iv = o_pairs + np * sizeof(SpotRecPair), o_win = o_iv + intervals.size() * sizeof(SpotInterval);
+        const size_t o_ends = o_win + nt * sizeof(SpotTraceWindow), upload_bytes = up16(o_ends + ne * 4);
+        const size_t o_end_cost = upload_bytes, o_end_start = o_end_cost + up16(ne * 4), o_len = o_end_start + up16(ne * 4);
+        const size_t o_found = o_len + up16(nt * 4), o_scores = o_found + up16(nt * 4), side_bytes = o_scores + up16(nt * 4);
+        rc = reserve_ws(ctx, ctx->ws_spot_dirs, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
+        if (rc) return rc;
+        rc = reserve_ws(ctx, ctx->ws_spot_steps, steps_bytes + side_bytes + 16);
+        if (rc) return rc;
+        upload.assign(upload_bytes, 0);
+        size_t class_first[kClasses], at = 0;
+        for (uint32_t c = 0; c < kClasses; ++c) {
+            class_first[c] = at;
+            if (!rec_pairs[c].empty()) std::memcpy(upload.data() + o_pairs + at * sizeof(SpotRecPair), rec_pairs[c].data(), rec_pairs[c].size() * sizeof(SpotRecPair));
+            at += rec_pairs[c].size();
+        }
+        std::memcpy(upload.data() + o_iv, intervals.data(), intervals.size() * sizeof(SpotInterval));
+        std::memcpy(upload.data() + o_win, trace.data(), nt * sizeof(SpotTraceWindow));
+        std::memcpy(upload.data() + o_ends, ends.data(), ne * 4);
+        char *base = ctx->ws_spot_steps.as<char>(), *side = base + steps_bytes;
+        SpotPathLaunch L{};
+        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
+        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
+        L.d_intervals = (const SpotInterval *)(side + o_iv);
+        L.d_ends = (const uint32_t *)(side + o_ends);
+        L.d_end_cost = (float *)(side + o_end_cost); L.d_end_start = (uint32_t *)(side + o_end_start);
+        L.d_dirs = ctx->ws_spot_dirs.as<uint32_t>();
+        L.d_windows = (const SpotTraceWindow *)(side + o_win); L.n_windows = (uint32_t)nt;
+        L.d_steps = (apd_path_step *)base;
+        L.d_len = (uint32_t *)(side + o_len); L.d_found = (uint32_t *)(side + o_found); L.d_scores = (float *)(side + o_scores);
+        HIP_TRY(ctx, hipMemcpyAsync(side, upload.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->timing && first_launch) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        first_launch = false;
+        for (uint32_t c = 0; c < kClasses; ++c) {
+            L.d_pairs = (const SpotRecPair *)(side + o_pairs) + class_first[c];
+            L.n_pairs = (uint32_t)rec_pairs[c].size();
+            HIP_TRY(ctx, launch_spot_record(L, c, r_max, ctx->stream));
+        }
+        HIP_TRY(ctx, launch_spot_trace(L, ctx->stream));
+        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }   // the last chunk's record stands
+        h_len.resize(nt); h_found.resize(nt); h_scores.resize(nt);
+        HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), L.d_len, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_found.data(), L.d_found, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), L.d_scores, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspaces (and `upload`)
+        for (size_t t = 0; t < nt; ++t) {
+            const uint64_t p = live[t];
+            path_len[p] = h_len[t];
+            if (found_start) found_start[p] = h_found[t];
+            if (scores) scores[p] = h_scores[t];
+        }
+        first = last;
     }
     return APD_OK;
 }

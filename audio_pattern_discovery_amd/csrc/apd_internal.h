@@ -319,6 +319,55 @@ size_t spot_lds_bytes(uint32_t rows_per_lane);
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
 
+// ---- warping paths of spotted windows (dtw_spot_path.hip): the sweep above once per distinct (query, stream) pair of a chunk,
+// recording the branch of every cell whose column some window of the pair covers, then one wavefront per window walking back.
+// Columns [a, b] of a stream whose branches are kept, and the first of the interval's words in d_dirs (dtw_spot_sweep.h).
+struct SpotInterval {
+    uint32_t a, b;
+    uint64_t off;
+};
+// Direction words an interval of `columns` columns owns for a query of n frames: 2 bits per cell, 16 rows of a lane per word.
+constexpr uint64_t spot_dir_words(uint32_t n, uint64_t columns) { return (columns + 63) * ((spot_rows_per_lane(n) + 15) / 16) * 64; }
+struct SpotRecPair {
+    uint32_t px, py;       // resident positions of the query x and the stream y
+    uint32_t max_end;      // the last column swept: the pair's largest requested end
+    uint32_t n_iv;         // the pair's intervals: d_intervals[iv_first .. iv_first + n_iv), ascending and disjoint
+    uint32_t iv_first;
+    uint32_t n_ends;       // the pair's requested ends: d_ends[end_first .. end_first + n_ends), ascending and distinct
+    uint32_t end_first;
+    uint32_t pad;
+};
+struct SpotTraceWindow {
+    uint32_t px, py;
+    uint32_t end, start;   // the caller's window
+    uint32_t a;            // first column of the interval that holds the window
+    uint32_t end_slot;     // where the sweep left T[n][end] and S[n][end]: d_end_cost / d_end_start
+    uint64_t dir_off;      // first word of that interval in d_dirs
+    uint64_t step_off;     // first step slot of the window in d_steps
+};
+struct SpotPathLaunch {
+    const float *d_frames;
+    const uint32_t *d_seq_off;
+    uint32_t dim, dpad;
+    float ins, del, mat;
+    const SpotRecPair *d_pairs;        // the sweep's grid
+    uint32_t n_pairs;
+    const SpotInterval *d_intervals;
+    const uint32_t *d_ends;
+    float *d_end_cost;
+    uint32_t *d_end_start;
+    uint32_t *d_dirs;
+    const SpotTraceWindow *d_windows;  // the trace's grid
+    uint32_t n_windows;
+    apd_path_step *d_steps;
+    uint32_t *d_len;                   // [n_windows] steps used
+    uint32_t *d_found;                 // [n_windows] S[n][end]
+    float *d_scores;                   // [n_windows]
+};
+// The pairs of L all have row class `rt`, as for launch_spot.
+hipError_t launch_spot_record(const SpotPathLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
+hipError_t launch_spot_trace(const SpotPathLaunch &L, hipStream_t stream);
+
 // One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
 hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);
 // The generic kernel over ALL tiles of L as a small persistent grid that does nothing unless *L.d_nonfinite is set.
@@ -490,6 +539,8 @@ struct apd_context {
     apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
     apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters in the resident layout, sums, counts, descriptors of every chunk
     apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]
+    apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
+    apd::DeviceBuf ws_spot_steps;     // ... its steps, then [pairs | intervals | ends | end cost | end start | windows | lengths | found | scores]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

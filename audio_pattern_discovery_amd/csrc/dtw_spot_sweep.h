@@ -1,0 +1,291 @@
+// The sweep of the free-start table (gfx950), shared by apd_spot (dtw_spot.hip, REC = false) and by the recording sweep of
+// apd_spot_paths (dtw_spot_path.hip, REC = true): ONE text for the lane mapping, the macro-step and the arithmetic, so that the
+// branches the second records are the branches of the very table the first reports.  What REC adds is compiled out of apd_spot's
+// instantiations (`if constexpr`): the same instruction mix, no scratch, registers within 2 of what they were and the same measured
+// speed as before this header existed.
+//
+// One wavefront per (query, stream) pair.  Rows go on lanes, the stream flows through: lane l owns the R = ceil(n / 64) query rows
+// l R + 1 .. l R + R, macro-step tau gives it stream column j = tau - l + 1, and m + (lane of row n) macro-steps cover the pair.
+// What a cell needs:
+//   DELETE  (i, j-1): the lane's own previous column -- R values and R starts, in registers for R <= 4 (RT = R), else in dynamic LDS
+//                     laid out [r][lane] (RT = 0; conflict-free, as the path sweep keeps its row);
+//   INSERT  (i-1, j): the row above in the same macro-step; for the lane's first row the lower lane's last row of column j, which
+//                     that lane computed one macro-step earlier: one from_lower_lane each for value and start;
+//   MATCH (i-1, j-1): the row above one column earlier; for the first row what arrived from the lower lane one macro-step earlier.
+// Lane 0 has no lower lane: it reads row 0, value 0 and start j.  Cells of columns outside 1 .. m and of rows beyond n hold +INF
+// (start 0) and reach no output.
+//
+// Arithmetic: numerics.rs:114-120 / alignments.rs:153-159 operation for operation, always (the context's distance mode is not
+// read).  D: the resident frame dimension as a compile-time constant (frames in registers), 0 = any dimension (frames re-read per
+// cell, as dtw_path.hip does).  The register variants take the square roots of a macro-step with sqrt_rn_finite when every squared
+// distance of the wavefront is inside its domain, and with the compiler's general sequence otherwise (identical frames, infinities,
+// NaN): the bits are the same either way (dtw_common.h).
+#pragma once
+#include "dtw_common.h"
+
+namespace apd {
+
+// the select of dtw_path.hip's select_node_branch, carrying the start column of the chosen predecessor beside the branch
+struct SpotNode { float value; uint32_t start; uint32_t op; };
+template <bool REC>
+__device__ __forceinline__ SpotNode spot_select(float del_v, uint32_t del_s, float ins_v, uint32_t ins_s, float m_v, uint32_t m_s, float d,
+                                                float del_pen, float ins_pen, float mat_pen)
+{
+    const bool pick_d = (del_v < m_v) & (del_v < ins_v);
+    const bool pick_i = (ins_v < m_v) & (ins_v < del_v);
+    float base = pick_i ? ins_v : m_v;
+    base = pick_d ? del_v : base;
+    float pen = pick_i ? ins_pen : mat_pen;
+    pen = pick_d ? del_pen : pen;
+    uint32_t s = pick_i ? ins_s : m_s;
+    s = pick_d ? del_s : s;
+    const float weighted = pen * d;                               // rounded on its own (alignments.rs:154-158)
+    uint32_t op = 0u;                                             // the branch: the recording sweep only
+    if constexpr (REC) op = pick_d ? (uint32_t)APD_PATH_DELETE : pick_i ? (uint32_t)APD_PATH_INSERT : (uint32_t)APD_PATH_MATCH;
+    return {base + weighted, s, op};
+}
+
+// numerics.rs:114-120 up to the square root: every difference, square and partial sum rounded on its own
+template <int D, int DN>
+__device__ __forceinline__ float spot_sq_distance(const float (&x)[DN], const float (&y)[DN])
+{
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const float t = x[k] - y[k];
+        const float sq = t * t;
+        acc = acc + sq;
+    }
+    return acc;
+}
+// the same for any dimension, both frames from memory (slots >= dim of a resident frame hold the squared norm / padding)
+__device__ __forceinline__ float spot_sq_distance_any(const float4 *xa, const float4 *yb, int dp4, int dim)
+{
+    float acc = 0.0f;
+    for (int q = 0; q < dp4; ++q) {
+        const float4 xv = xa[q], yv = yb[q];
+        const int k0 = 4 * q;
+        float t = xv.x - yv.x, sq = t * t;
+        acc = (k0 < dim) ? acc + sq : acc;
+        t = xv.y - yv.y; sq = t * t; acc = (k0 + 1 < dim) ? acc + sq : acc;
+        t = xv.z - yv.z; sq = t * t; acc = (k0 + 2 < dim) ? acc + sq : acc;
+        t = xv.w - yv.w; sq = t * t; acc = (k0 + 3 < dim) ? acc + sq : acc;
+    }
+    return acc;
+}
+
+template <int DN>
+__device__ __forceinline__ void spot_load_frame(float (&f)[DN], const float *p)
+{
+#pragma unroll
+    for (int q = 0; q < DN / 4; ++q) {
+        const float4 v = reinterpret_cast<const float4 *>(p)[q];
+        f[4 * q] = v.x; f[4 * q + 1] = v.y; f[4 * q + 2] = v.z; f[4 * q + 3] = v.w;
+    }
+}
+
+__device__ __forceinline__ uint32_t from_lower_lane_u32(uint32_t v, uint32_t fill)
+{
+    return __builtin_bit_cast(uint32_t, from_lower_lane(__builtin_bit_cast(float, v), __builtin_bit_cast(float, fill)));
+}
+
+// What the recording sweep (REC) is given for its pair; apd_spot passes an empty one that nothing reads.
+//   iv[0 .. n_iv): the columns whose branches are wanted, as sorted disjoint intervals [a, b] with the first word of each in dirs.
+//     A live cell of column j in interval k belongs to macro-step j - 1 + lane; the lane packs the branches of its R rows at 2 bits
+//     each, 16 rows per word, WPL = ceil(R / 16) words, at dirs[off_k + ((j - a_k + lane) * WPL + w) * 64 + lane]: indexed by
+//     macro-step, so the 64 lanes of a store are 64 consecutive words; an interval of L columns owns (L + 63) WPL 64 words.
+//   ends[0 .. n_ends): the columns, ascending, whose T[n][j] and S[n][j] go to end_cost / end_start at the same index.
+//   max_end: the last column swept (the largest of ends).
+struct SpotRecord {
+    const SpotInterval *iv;
+    uint32_t n_iv;
+    const uint32_t *ends;
+    uint32_t n_ends;
+    float *end_cost;
+    uint32_t *end_start;
+    uint32_t *dirs;
+    uint32_t max_end;
+};
+
+template <int RT, int D, bool REC>
+__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec)
+{
+    static_assert(RT == 0 || D > 0, "rows in registers need the frame dimension at compile time");
+    extern __shared__ __attribute__((aligned(16))) float spot_column[];   // RT == 0: [r][lane] values, then [r][lane] starts
+    constexpr int DN = D > 0 ? ((D + 4) & ~3) : 4;                          // floats of a resident frame
+    const int lane = threadIdx.x;
+    const uint32_t ox = L.d_seq_off[P.px], oy = L.d_seq_off[P.py];
+    const int n = (int)(L.d_seq_off[P.px + 1] - ox) - 2;                    // <= kSpotMaxQuery
+    const uint32_t m = REC ? rec.max_end : L.d_seq_off[P.py + 1] - oy - 2;  // REC: column j depends on columns <= j only
+    const float *X = L.d_frames + (uint64_t)ox * L.dpad;
+    const float *Y = L.d_frames + (uint64_t)oy * L.dpad;
+    const float ins = L.ins, del = L.del, mat = L.mat;
+    const int R = RT > 0 ? RT : (n + 63) / 64;
+    const int row0 = lane * R;                                              // 0-based first query row of the lane
+    const int rows_live = min(max(n - row0, 0), R);
+    const int lane_n = (n - 1) / R, r_n = (n - 1) - lane_n * R;             // where row n lives
+    const bool curves = !REC && L.d_cost != nullptr;
+    float *cost = curves ? L.d_cost + P.curve_off : nullptr;
+    uint32_t *start = curves ? L.d_start + P.curve_off : nullptr;
+    uint32_t *col_start = reinterpret_cast<uint32_t *>(spot_column) + (size_t)R * 64;
+
+    float pv[RT > 0 ? RT : 1];                                              // the lane's previous column
+    uint32_t ps[RT > 0 ? RT : 1];
+    float xr[RT > 0 ? RT : 1][DN];                                          // the lane's query rows (RT > 0 and D > 0)
+    if constexpr (RT > 0) {
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            pv[r] = APD_INF;
+            ps[r] = 0u;
+            spot_load_frame<DN>(xr[r], X + (uint64_t)min(row0 + r, n - 1) * L.dpad);
+        }
+    } else {
+        for (int r = 0; r < R; ++r) {
+            spot_column[r * 64 + lane] = APD_INF;
+            col_start[r * 64 + lane] = 0u;
+        }
+    }
+
+    // REC: the lane's cursor into the intervals (its columns only ascend), and the cursor of row n's lane into the ends
+    [[maybe_unused]] const uint64_t row_words = (uint64_t)((R + 15) >> 4) * 64;
+    [[maybe_unused]] uint32_t iv_k = 0, iv_a = 1u, iv_b = 0u, end_k = 0, end_next = 0;
+    [[maybe_unused]] uint64_t iv_off = 0;
+    if constexpr (REC) {
+        if (rec.n_iv) { const SpotInterval v = rec.iv[0]; iv_a = v.a; iv_b = v.b; iv_off = v.off; }
+        if (rec.n_ends) end_next = rec.ends[0];
+    }
+
+    const int dp4 = (int)L.dpad / 4, dim = (int)L.dim;
+    float y_even[DN], y_odd[DN];                                            // column j's frame and the next macro-step's, taking turns (D > 0)
+    uint32_t jm1 = 0u - (uint32_t)lane;                                     // j - 1; wraps above m while the lane waits for column 1
+    if constexpr (D > 0) spot_load_frame<DN>(y_even, Y + (uint64_t)min(jm1, m - 1) * L.dpad);
+    float in_prev = lane == 0 ? 0.0f : APD_INF;                             // T[row0][j-1]: row 0 reads 0, column 0 below it +INF
+    uint32_t in_prev_s = 0u;
+    float last = APD_INF;
+    uint32_t last_s = 0u;
+    [[maybe_unused]] uint32_t best_end = 0u, best_start = 0u;
+    [[maybe_unused]] float best_cost = APD_INF, best_score = APD_INF;
+    const uint64_t total = (uint64_t)m + (uint64_t)lane_n;
+    // one macro-step: yv holds column j's frame, yn receives the next column's while this one is computed
+    auto macro_step = [&](const float (&yv)[DN], float (&yn)[DN]) {
+        const uint32_t j = jm1 + 1u;
+        const bool column_live = jm1 < m;
+        if constexpr (D > 0) spot_load_frame<DN>(yn, Y + (uint64_t)min(jm1 + 1u, m - 1) * L.dpad);
+        const float4 *yb = reinterpret_cast<const float4 *>(Y + (uint64_t)min(jm1, m - 1) * L.dpad);
+        // REC: where this column's branch words go, if it lies in an interval
+        [[maybe_unused]] uint32_t *rec_words = nullptr;
+        [[maybe_unused]] uint32_t word = 0;
+        if constexpr (REC) {
+            if (column_live) {
+                while (iv_k < rec.n_iv && j > iv_b) {
+                    if (++iv_k < rec.n_iv) { const SpotInterval v = rec.iv[iv_k]; iv_a = v.a; iv_b = v.b; iv_off = v.off; }
+                }
+                if ((rows_live > 0) & (j >= iv_a) & (j <= iv_b)) rec_words = rec.dirs + iv_off + ((uint64_t)(j - iv_a) + lane) * row_words + lane;
+            }
+        }
+        // T[row0][j] from the lower lane (lane 0: row 0 of the table, value 0, start j)
+        float up = from_lower_lane(last, 0.0f);
+        uint32_t up_s = from_lower_lane_u32(last_s, 0u);
+        up_s = lane == 0 ? j : up_s;
+        const float in_cur = up;
+        const uint32_t in_cur_s = up_s;
+        float diag = in_prev;
+        uint32_t diag_s = lane == 0 ? j : in_prev_s;
+        float cap_v = APD_INF;
+        uint32_t cap_s = 0u;
+        if constexpr (RT > 0) {
+            float d[RT];
+            {
+                bool in_domain = true;
+#pragma unroll
+                for (int r = 0; r < RT; ++r) {
+                    d[r] = spot_sq_distance<D, DN>(xr[r], yv);
+                    in_domain &= (d[r] >= 0x1p-96f) & (d[r] < APD_INF);
+                }
+                if (__builtin_expect(__ballot(!in_domain) != 0ull, 0)) {
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) d[r] = __builtin_sqrtf(d[r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) d[r] = sqrt_rn_finite(d[r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < RT; ++r) {
+                const float left = pv[r];
+                const uint32_t left_s = ps[r];
+                const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, d[r], del, ins, mat);
+                const bool live = column_live & (r < rows_live);
+                const float v = live ? node.value : APD_INF;
+                const uint32_t s = live ? node.start : 0u;
+                diag = left; diag_s = left_s;                               // (i, j-1) is the next row's MATCH predecessor
+                pv[r] = v; ps[r] = s;
+                up = v; up_s = s;
+                if (r == r_n) { cap_v = v; cap_s = s; }
+                if constexpr (REC) word |= node.op << (2 * r);
+            }
+            if constexpr (REC) if (rec_words) rec_words[0] = word;
+        } else {
+            for (int r = 0; r < R; ++r) {
+                const float *xrow = X + (uint64_t)min(row0 + r, n - 1) * L.dpad;
+                float dist;
+                if constexpr (D > 0) {
+                    float xf[DN];
+                    spot_load_frame<DN>(xf, xrow);
+                    dist = __builtin_sqrtf(spot_sq_distance<D, DN>(xf, yv));
+                } else {
+                    dist = __builtin_sqrtf(spot_sq_distance_any(reinterpret_cast<const float4 *>(xrow), yb, dp4, dim));
+                }
+                const float left = spot_column[r * 64 + lane];
+                const uint32_t left_s = col_start[r * 64 + lane];
+                const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, dist, del, ins, mat);
+                const bool live = column_live & (r < rows_live);
+                const float v = live ? node.value : APD_INF;
+                const uint32_t s = live ? node.start : 0u;
+                diag = left; diag_s = left_s;
+                spot_column[r * 64 + lane] = v;
+                col_start[r * 64 + lane] = s;
+                up = v; up_s = s;
+                if (r == r_n) { cap_v = v; cap_s = s; }
+                if constexpr (REC) {
+                    word |= node.op << (2 * (r & 15));
+                    if (((r & 15) == 15) | (r == R - 1)) {
+                        if (rec_words) rec_words[(r >> 4) * 64] = word;
+                        word = 0;
+                    }
+                }
+            }
+        }
+        in_prev = in_cur; in_prev_s = in_cur_s;
+        last = up; last_s = up_s;
+        if ((lane == lane_n) & column_live) {                               // row n of column j
+            if constexpr (REC) {
+                if (end_k < rec.n_ends && j == end_next) {
+                    rec.end_cost[end_k] = cap_v;
+                    rec.end_start[end_k] = cap_s;
+                    if (++end_k < rec.n_ends) end_next = rec.ends[end_k];
+                }
+            } else {
+                if (curves) { cost[jm1] = cap_v; start[jm1] = cap_s; }
+                const uint32_t window = j - cap_s + 1u;                     // frames of y the alignment covers
+                const float score = cap_v / (float)((uint32_t)n + window);  // one f32 division (alignments.rs:121 with the window for m); < 2^32: kSpotMaxStream
+                if (score < best_score) { best_end = j; best_start = cap_s; best_cost = cap_v; best_score = score; }
+            }
+        }
+        ++jm1;
+    };
+    // two macro-steps per turn, the frame buffers swapping roles; a step beyond `total` computes nothing that is live
+    for (uint64_t tau = 0; tau < total; tau += 2) {
+        macro_step(y_even, y_odd);
+        macro_step(y_odd, y_even);
+    }
+    if constexpr (!REC) {
+        if (lane == lane_n) {
+            apd_spot_best b;
+            b.end = best_end; b.start = best_start; b.cost = best_cost; b.score = best_score;
+            L.d_best[P.out] = b;
+        }
+    }
+}
+
+}  // namespace apd

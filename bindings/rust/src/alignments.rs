@@ -151,6 +151,52 @@ pub fn spot(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery
     best
 }
 
+/// Not in the reference: the warping paths of spotted windows (apd_batch_join + apd_spot_paths) on the first device of APD_DEVICES.
+/// windows[k]: x a template number, y a stream number (NOT offset by templates.len(): that is done here), end and start as spot()
+/// or spot_hits() reported them.  Returns per window (steps origin first with (n, end) last, found_start, score); the steps are
+/// empty for a (0, 0) window and for a start that is not the table's -- found_start then says which start to ask again with.
+pub fn spot_paths(templates: &[NDSequence], streams: &[NDSequence], windows: &[apd_spot_window], params: &Discovery)
+                  -> Vec<(Vec<apd_path_step>, u32, f32)> {
+    let (n1, n2, k) = (templates.len(), streams.len(), windows.len());
+    if n1 == 0 || n2 == 0 || k == 0 { return Vec::new(); }
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let pack = |set: &[NDSequence]| {
+        let mut offsets = vec![0u64; set.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in set.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        (frames, offsets)
+    };
+    let dim = templates[0].n_bins as u32;
+    let ((fa, oa), (fb, ob)) = (pack(templates), pack(streams));
+    let joined: Vec<apd_spot_window> = windows.iter().map(|w| apd_spot_window { x: w.x, y: w.y + n1 as u32, end: w.end, start: w.start }).collect();
+    let mut step_off = vec![0u64; k + 1];
+    let (mut len, mut found, mut scores) = (vec![0u32; k], vec![0u32; k], vec![0f32; k]);
+    let mut steps: Vec<apd_path_step>;
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let (mut a, mut b, mut j) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        check(apd_batch_create(ctx, fa.as_ptr(), oa.as_ptr(), n1 as u32, dim, 0, &mut a));
+        check(apd_batch_create(ctx, fb.as_ptr(), ob.as_ptr(), n2 as u32, dim, 0, &mut b));
+        check(apd_batch_join(ctx, a, b, &mut j));
+        let mut rc = apd_spot_paths(ctx, j, &cfg, joined.as_ptr(), k as u64, std::ptr::null_mut(), 0, step_off.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        steps = vec![apd_path_step::default(); (step_off[k] as usize).max(1)];
+        if rc == APD_OK {
+            rc = apd_spot_paths(ctx, j, &cfg, joined.as_ptr(), k as u64, steps.as_mut_ptr(), steps.len() as u64, step_off.as_mut_ptr(), len.as_mut_ptr(), found.as_mut_ptr(), scores.as_mut_ptr());
+        }
+        apd_destroy(ctx);                                                 // releases the device side of the three batches
+        for h in [j, b, a] { apd_batch_destroy(h); }
+        check(rc);
+    }
+    (0..k).map(|p| (steps[step_off[p] as usize..step_off[p] as usize + len[p] as usize].to_vec(), found[p], scores[p])).collect()
+}
+
 /// Not in the reference: DTW barycenter averaging (apd_barycenters) of the sets of sequence numbers in `sets` (as cluster_sets
 /// returns them) on the first device of APD_DEVICES.  init[k]: the sequence whose frames start set k's barycenter (usually
 /// clustering::medoids' choice).  Returns one NDSequence per set, as long as its init sequence (empty for an empty set; the last

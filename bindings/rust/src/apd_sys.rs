@@ -65,6 +65,15 @@ pub struct apd_spot_best {
     pub score: f32,
 }
 
+/// A window of stream y matched to query x (apd_spot_paths): end and start as in apd_spot_best.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct apd_spot_window {
+    pub x: u32,
+    pub y: u32,
+    pub end: u32,
+    pub start: u32,
+}
+
 /// ClusteringOperation (clustering.rs:19-25); operation: 0 S2S, 1 S2C, 2 C2S, 3 C2C (clustering.rs:8-13).
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct apd_cluster_op {
@@ -193,6 +202,11 @@ extern "C" {
                     cost: *mut f32, start: *mut u32, capacity: u64, curve_off: *mut u64, best: *mut apd_spot_best) -> c_int;
     pub fn apd_spot_hits(cost: *const f32, start: *const u32, m: u64, n: u64, threshold: f32, hits: *mut apd_spot_best,
                          capacity: u64, n_hits: *mut u64) -> c_int;
+    // warping paths of spotted windows
+    pub fn apd_spot_path_bound(n: u64, end: u64, start: u64) -> u64;
+    pub fn apd_spot_paths(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, windows: *const apd_spot_window,
+                          n_windows: u64, steps: *mut apd_path_step, capacity: u64, step_off: *mut u64, path_len: *mut u32,
+                          found_start: *mut u32, scores: *mut f32) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

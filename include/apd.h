@@ -411,8 +411,8 @@ int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n, const floa
  * smallest end wins ties, a NaN is never kept, nothing kept gives {0, 0, +INF, +INF}.
  * Arithmetic: ALWAYS the literal one, whatever apd_set_distance_mode says, as for the warping paths; a batch outside the fast
  * feature range needs no routing.
- * The warping path of a hit: apd_align_pair_path on x and the matched window.  That table is banded and anchored at both ends, so
- * it is not the same table: its costs need not equal the curve's. */
+ * The warping path of a hit: apd_spot_paths below, which walks back through this very table.  (apd_align_pair_path on x and the
+ * matched window fills another table, banded and anchored at both ends: its costs need not equal the curve's.) */
 typedef struct apd_spot_best {
     uint32_t end, start;   /* 1-based stream columns of the window's last and first frame; 0, 0: none */
     float cost, score;
@@ -439,6 +439,47 @@ int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *c
  * may exceed capacity.  n == 0: APD_ERR_INVALID_ARG. */
 int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t m, uint64_t n, float threshold, apd_spot_best *hits,
                   uint64_t capacity, uint64_t *n_hits);
+
+/* ---- warping paths of spotted windows: which query frame was matched to which stream frame inside a window ----------------------
+ * Table: exactly apd_spot's T and S -- free start, no band, always the literal arithmetic -- with every cell also remembering the
+ * branch alignments.rs:153-159 took: DELETE from (i, j-1), INSERT from (i-1, j), MATCH from (i-1, j-1) otherwise.  Not a table of
+ * the window alone: an exact DELETE / INSERT tie takes MATCH even when MATCH is larger, so the cells inside a window depend on the
+ * columns before it (x = [0, 1], y = [0, 1, 0], end 3: the curve says start 2, cost 2.0; columns 2..3 alone give cost 1.0).
+ * Window: query x, stream y in the CALLER's sequence numbers of any resident batch, plain or joined; end and start are 1-based
+ * stream columns as apd_spot's curves, best and apd_spot_hits report them.  end == 0 or start == 0 is "no window" (apd_spot's none
+ * record, or a column whose alignment ran through column 0): 0 slots, path length 0, found_start 0, score +INF; not an error.
+ * Walk: from (n, end) back; each cell is emitted with its branch and its table value and the walk moves to the branch's
+ * predecessor; on reaching row 0 at column j0 it emits (0, j0, 0.0, APD_PATH_START) and stops.  j0 = S - 1 after a MATCH in row 1,
+ * S after an INSERT in row 1; it may be 0.  The path is reported origin first, (n, end) last.  i, j are 1-based table indices, j
+ * the absolute stream column; cost holds the bits of T[i][j], so the last step's cost is bit-identical to apd_spot's cost curve at
+ * `end`.  With S >= 1 the walk never enters column 0 and stays inside columns S .. end; its first cell after START is (1, S) with
+ * MATCH or INSERT; it has between max(n, L) + 1 and n + L steps, L = end - S + 1.
+ * The caller's start is checked, not trusted: found_start[p] = S[n][end] as the sweep carried it, scores[p] = T[n][end] /
+ * (float)(n + end - S + 1), the bits of apd_spot's score at that column -- both written whether or not the start matches, either
+ * may be NULL.  found_start[p] != start (S = 0 with a start >= 1 included): path_len[p] = 0, the window's slots zeroed, the call
+ * still APD_OK; ask again with the start found. */
+typedef struct apd_spot_window {
+    uint32_t x, y;         /* query and stream */
+    uint32_t end, start;   /* 1-based stream columns of the window's last and first frame, as in apd_spot_best */
+} apd_spot_window;   /* 16 bytes */
+/* Step slots a window owns: n + (end - start + 1) for n >= 1 and 1 <= start <= end, else 0.  Host only. */
+uint64_t apd_spot_path_bound(uint64_t n, uint64_t end, uint64_t start);
+/* windows: any order, repeats, overlaps and windows of one pair allowed; results in input order.
+ * step_off (n_windows + 1, always written, no GPU work needed for it): window p owns steps[step_off[p] .. step_off[p+1]),
+ *   step_off[p+1] - step_off[p] = apd_spot_path_bound(len x, end, start); path_len[p] of those slots are used, the others zeroed.
+ * steps == NULL: sizes only.  capacity (in steps) < step_off[n_windows]: APD_ERR_INVALID_ARG.
+ * x or y >= the batch's sequence count, start > end, or end > frames of y: APD_ERR_INVALID_ARG; an empty sequence in the batch
+ * APD_ERR_EMPTY_SEQUENCE; a query of more than 16 384 frames or a stream at apd_spot's limit APD_ERR_UNSUPPORTED; each before
+ * anything is launched.  Follows apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers all kernels of the
+ * call.  apd_set_distance_mode is not read; a batch outside the fast feature range needs no routing.
+ * A (query, stream) pair is swept ONCE per chunk however many of its windows the chunk holds, from column 1 to the largest end
+ * asked for; the branches are kept only for the columns the windows cover (merged into disjoint intervals).  Workspace: 2 bits per
+ * kept cell in words of 16 rows per lane, (L + 63) * ceil(ceil(n / 64) / 16) * 256 bytes per interval of L columns, plus the
+ * steps; a long list is cut into chunks that keep each under 1 GiB (APD_SPOT_WORKSPACE_BYTES overrides the cap: tests only); a
+ * chunk holds at least one window; results identical whatever the cap. */
+int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const apd_spot_window *windows,
+                   uint64_t n_windows, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
+                   uint32_t *found_start, float *scores);
 
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */

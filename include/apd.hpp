@@ -298,6 +298,29 @@ class AlignmentWorkers {
         }
         return out;
     }
+    // Not in the reference: the warping paths of spotted windows (apd.h, "warping paths of spotted windows").  windows: x, y numbered as
+    // spot()'s pairs, end and start as Spotted::best or spot_hits() reported them; a pair may appear once per hit.  steps[k]: origin
+    // first, (n, end) last; empty for a {0, 0} window and for a start that is not the table's -- found_start[k] then says which
+    // start to ask again with.
+    struct SpotPaths { std::vector<std::vector<apd_path_step>> steps; std::vector<uint32_t> found_start; std::vector<float> scores; };
+    SpotPaths spot_paths(const std::vector<apd_spot_window> &windows, const Discovery &params, const AlignmentWorkers *streams = nullptr)
+    {
+        const apd_align_config c = params.config();
+        Batch joined(streams ? Batch::join(ctx_, batch_, streams->batch_).release() : nullptr);
+        const apd_batch *b = streams ? joined.get() : batch_;
+        const std::size_t k = windows.size();
+        std::vector<uint64_t> off(k + 1, 0);
+        std::vector<uint32_t> len(k, 0);
+        SpotPaths out;
+        out.found_start.resize(k);
+        out.scores.resize(k);
+        check(apd_spot_paths(ctx_.get(), b, &c, windows.data(), k, nullptr, 0, off.data(), nullptr, nullptr, nullptr), ctx_.get());   // sizes
+        std::vector<apd_path_step> steps(std::max<uint64_t>(off.back(), 1));
+        check(apd_spot_paths(ctx_.get(), b, &c, windows.data(), k, steps.data(), steps.size(), off.data(), len.data(), out.found_start.data(),
+                             out.scores.data()), ctx_.get());
+        for (std::size_t p = 0; p < k; ++p) out.steps.emplace_back(steps.begin() + off[p], steps.begin() + off[p] + len[p]);
+        return out;
+    }
     // Not in the reference: DTW barycenter averaging (apd.h, "cluster prototypes") of the sets of this object's sequence numbers in
     // `sets`; init[k]: the sequence whose frames start set k's barycenter (usually AgglomerativeClustering::medoids' choice).
     // frames[k]: [T_k][dim] packed, T_k the length of init[k] (0 for an empty set); inertia / used: [iterations][sets.size()].
