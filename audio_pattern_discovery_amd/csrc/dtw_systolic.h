@@ -534,14 +534,15 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic(const AlignLaunch L)
 // left.  A fourth ds_read_b128 for a tail of two floats would need a register quad of its own (or one that overlaps the
 // neighbouring piece's, with a wait for the LDS in between): the shared-column kernel reads two frames per macro-step this way.
 typedef float apd_f32x2 __attribute__((ext_vector_type(2)));
+// 16-byte piece `piece` of that frame (floats 4 piece .. 4 piece + 3, as far as the frame goes) on its own
 template <int DN>
-__device__ __forceinline__ void read_frame_lds(float (&dst)[DN], const float *p)
+__device__ __forceinline__ void read_frame_piece_lds(float (&dst)[DN], const float *p, int piece)
 {
     constexpr int FULL = DN / 4, TAIL = DN % 4;
-#pragma unroll
-    for (int k = 0; k < FULL; ++k) {
-        const apd_f32x4 t = *reinterpret_cast<const apd_f32x4 *>(p + 4 * k);
-        dst[4 * k + 0] = t.x; dst[4 * k + 1] = t.y; dst[4 * k + 2] = t.z; dst[4 * k + 3] = t.w;
+    if (piece < FULL) {
+        const apd_f32x4 t = *reinterpret_cast<const apd_f32x4 *>(p + 4 * piece);
+        dst[4 * piece + 0] = t.x; dst[4 * piece + 1] = t.y; dst[4 * piece + 2] = t.z; dst[4 * piece + 3] = t.w;
+        return;
     }
     if (TAIL >= 2) {
         const apd_f32x2 t = *reinterpret_cast<const apd_f32x2 *>(p + 4 * FULL);
@@ -550,6 +551,18 @@ __device__ __forceinline__ void read_frame_lds(float (&dst)[DN], const float *p)
     if (TAIL == 1) dst[4 * FULL] = p[4 * FULL];
     if (TAIL == 3) dst[4 * FULL + 2] = p[4 * FULL + 2];
 }
+template <int DN>
+__device__ __forceinline__ void read_frame_lds(float (&dst)[DN], const float *p)
+{
+#pragma unroll
+    for (int piece = 0; piece < (DN + 3) / 4; ++piece) read_frame_piece_lds<DN>(dst, p, piece);
+}
+
+// A pointer into LDS as the 32-bit address the ds instructions take, and back: a block's base kept as such an address needs no
+// add of the LDS segment's own base in front of every read.
+typedef __attribute__((address_space(3))) const char apd_lds_cchar;
+__device__ __forceinline__ uint32_t lds_address(const void *p) { return (uint32_t)(uintptr_t)(apd_lds_cchar *)p; }
+__device__ __forceinline__ const float *lds_floats_at(uint32_t a) { return (const float *)(apd_lds_cchar *)(uintptr_t)a; }
 
 // Floats of one column ring: RC frames and a copy of the first U behind them (as the row ring has: the U consecutive slots a lane
 // reads during one unrolled block are contiguous), 16 bytes of padding per 8 frames, rounded to whole 256-byte bank rows so
@@ -569,7 +582,12 @@ constexpr int shared_column_ring_floats(int rc, int u, int dp) { return (((rc + 
 //    16 bytes behind every eighth frame make the lane stride an odd number of 16-byte bank slots, conflict-free except where
 //    the ring wraps inside the group.  A copy of the first U frames sits behind the ring, so the U consecutive slots a lane
 //    reads during one unrolled block are contiguous: one base per block, the frame offsets are immediates of the ds_read and
-//    only the padding term is computed per macro-step (3 integer operations);
+//    only the padding term is computed per macro-step (2 integer operations: slot p is at (ring + p (FB + 2)) & ~15).  The
+//    fetch offsets of the fills run along, clamped, as the DPP kernel's column offset does;
+//  * the row frame of macro-step tau + 1 is read into the registers of macro-step tau's, one 16-byte piece at a time, as soon as
+//    the nine distance chains are through with that piece: the reads are issued in front of the threshold test and its branch
+//    instead of behind them, where their first use followed at once.  The rare recompute branch, which needs the frame of its own
+//    step, reads it a second time from the ring and asks for the next one again;
 //  * with the fill of block b + 1 written while other wavefronts still read block b, the ring spans the lanes' window,
 //    2 U columns and the spread of w inside the workgroup (apd_internal.h, shared_column_ring_frames); the tile plan sends
 //    only tiles within that spread here (shared_columns_qualify);
@@ -749,51 +767,97 @@ __global__ __launch_bounds__(256) void dtw_fused_systolic_shared(const AlignLaun
     // this lane's reads: the column entering at macro-step 1 first
     const float *const cring_read = crings + (lane / G) * CRING;
     uint32_t pr = (uint32_t)ring_slot(1 + (C - 1) * (gl + 1) - w);   // slot read in the first macro-step of the coming block
-    // step q of a block reads slot pr + q (< RC + U: the copy): the frame offset is an immediate, only the padding term moves
-    auto read_col = [&](float (&dst)[DN], const float *block_base, int q) __attribute__((always_inline)) {
-        read_frame_lds<DN>(dst, block_base + q * DP + (((pr + (uint32_t)q) >> 3) << 2));
+    // Fetch offsets of the two fills, kept running (yo_cur / yo_cap of dtw_fused_systolic): every block fetches the U frames
+    // behind the last block's, clamped at the sequence's last frame; lanes without a share stay out of range (step 0).  The
+    // columns fetched here are tau0 + col_hi0 + 1 + fill_f >= U + (C-1) G + 1 - w_lo > 0 (2 w_lo + 1 <= G C): never the sentinel.
+    const uint32_t ro_step = fill_act ? (uint32_t)U * FB : 0u;
+    const uint32_t ro_cap = fill_act ? a_off_w + (uint32_t)(n_w - 1) * FB + 16u * fill_q : kNoFrame;
+    uint32_t ro_cur = fill_act ? min(a_off_w + (uint32_t)(U + fill_f) * FB + 16u * fill_q, ro_cap) : kNoFrame;   // row U + 1 + fill_f
+    const bool col_act = fill_act & cvalid;
+    const uint32_t co_step = col_act ? (uint32_t)U * FB : 0u;
+    const uint32_t co_cap = col_act ? cb_off + (uint32_t)(cm - 1) * FB + 16u * fill_q : kNoFrame;
+    uint32_t co_cur = col_act ? min(cb_off + (uint32_t)(col_hi0 + fill_f) * FB + 16u * fill_q, co_cap) : kNoFrame;   // column col_hi0 + 1 + fill_f
+    // Byte address of ring slot p of this lane's column ring: ring + p FB + (p / 8) 16 = (ring + p (FB + 2)) & ~15, the ring
+    // being 16-byte aligned.  col_base holds ring + pr (FB + 2) for the block; step q adds 2 q and masks, the frames between
+    // (q FB) are the immediate of the ds_read: two integer operations per macro-step.
+    const uint32_t cring_read_b = lds_address(cring_read);
+    uint32_t col_base = 0u;
+    auto read_col = [&](float (&dst)[DN], int q) __attribute__((always_inline)) {
+        const uint32_t b = (col_base + 2u * (uint32_t)q) & ~15u;
+        read_frame_lds<DN>(dst, lds_floats_at(b) + q * DP);
     };
     __syncthreads();
-    auto read_row_at = [&](float (&dst)[DN], const float *p) __attribute__((always_inline)) { read_frame_lds<DN>(dst, p); };
     float xs[DN];
-    read_row_at(xs, &xring[((0 - gl) & (R - 1)) * RS]);          // macro-step 0: row -gl
+    read_frame_lds<DN>(xs, &xring[((0 - gl) & (R - 1)) * RS]);   // macro-step 0: row -gl
+    // The hit path of a macro-step reads its row frame a second time (below).  The oldest such row in block tau0 is
+    // tau0 - (G - 1) (lane G - 1, first step: fetched by the previous block), the newest row stored before the block ends is
+    // tau0 + U (the previous block's fill): R > U + G - 1 keeps them in different slots.
+    static_assert(R > U + G - 1, "a macro-step's row frame must survive in the ring until the block's fill_store");
 
     auto macro_steps = [&](int tau_begin, int tau_end, auto slow_tag) __attribute__((always_inline)) {
         constexpr bool SLOW = decltype(slow_tag)::value;
         for (int tau0 = tau_begin; tau0 < tau_end; tau0 += U) {
             apd_f32x4 fill_regs[NFILL];
-            fill_load(tau0 + U + 1, fill_regs);                  // rows and columns of the NEXT block, stored at this block's end
-            const apd_f32x4 col_regs = col_load(tau0 + col_hi0 + 1 + fill_f, fill_act);
-            const float *const xrows = &xring[((tau0 + 1 - gl) & (R - 1)) * RS];
-            const float *const ycols = cring_read + pr * DP;
+            // rows and columns of the NEXT block, stored at this block's end
+            fill_regs[0] = __builtin_bit_cast(apd_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, ro_cur, 0, 0));
+            const apd_f32x4 col_regs = __builtin_bit_cast(apd_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, co_cur, 0, 0));
+            ro_cur = min(ro_cur + ro_step, ro_cap);
+            co_cur = min(co_cur + co_step, co_cap);
+            // the two LDS bases of the block, in registers of their own (opaque: not recomputed from tau0 / pr in every macro-step)
+            uint32_t xrows_b = lds_address(xring) + (uint32_t)(((tau0 + 1 - gl) & (R - 1)) * RS) * 4u;
+            col_base = cring_read_b + __umul24(pr, FB + 2u);
+            asm volatile("" : "+v"(xrows_b), "+v"(col_base));
+            const float *const xrows = lds_floats_at(xrows_b);   // rows tau0 + 1 - gl ... + U - 1, contiguous (the copy behind the ring)
 #pragma unroll
             for (int q = 0; q < U; ++q) {
                 const int tau = tau0 + q;
                 const int r = q % S;               // slot of this step's first column
                 const int e = (r + C) % S;         // slot of the column entering at tau + 1 (dead during this step)
                 float d[C];
+                // the entering column first: its slot is dead since the previous macro-step's branch
+                read_col(yf[e], q);
+                // The row frame of the NEXT macro-step replaces this one's piece by piece, each 16-byte piece as soon as the nine
+                // chains are through with it (k ascending in every chain, as frame_sq_expanded_pre has it: the same bits), so
+                // that the reads have the rest of the chains, the minimum and the branch in front of their first use.  The
+                // empty asm statements keep the scheduler from sinking a read to its first use or the chains past it.
+                const float *const xnext = xrows + q * RS;
+                const float thr = (xs[D] + nmax_b) * tau_thr;
 #pragma unroll
-                for (int c = 0; c < C; ++c) d[c] = frame_sq_expanded_pre<D>(xs, yf[(r + c) % S]);
+                for (int c = 0; c < C; ++c) d[c] = xs[D] + yf[(r + c) % S][D];
+#pragma unroll
+                for (int piece = 0; piece < LPF; ++piece) {
+#pragma unroll
+                    for (int k = 4 * piece; k < 4 * piece + 4 && k < D; ++k)
+#pragma unroll
+                        for (int c = 0; c < C; ++c) d[c] = __builtin_fmaf(xs[k], yf[(r + c) % S][k], d[c]);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) asm volatile("" : "+v"(d[c]) : : "memory");
+                    read_frame_piece_lds<DN>(xs, xnext, piece);
+                }
                 float dmin = d[0];
 #pragma unroll
                 for (int c = 1; c + 1 < C; c += 2) dmin = __builtin_fminf(__builtin_fminf(dmin, d[c]), d[c + 1]);
                 if (C % 2 == 0) dmin = __builtin_fminf(dmin, d[C - 1]);
-                const bool any = dmin < (xs[D] + nmax_b) * tau_thr;
-                // the entering column, between the test and the branch on it (where the DPP kernel moves its window)
-                read_col(yf[e], ycols, q);
+                const bool any = dmin < thr;
+                asm volatile("" : : : "memory");
                 if (__builtin_expect(__ballot(any) != 0ull, 0)) {
-                    float nx = xs[D];
+                    // rare: this step's row frame once more (xs is on its way to the next one), the exact form where the cell's
+                    // own test asks for it, then the next row's reads again -- the registers are the same on both paths
+                    float xc[DN];
+                    read_frame_lds<DN>(xc, &xring[((tau - gl) & (R - 1)) * RS]);
+                    float nx = xc[D];
                     asm volatile("" : "+v"(nx));
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         const float sc = nx + yf[(r + c) % S][D];
-                        const float ex = frame_sq_exact_pre<D>(xs, yf[(r + c) % S]);
+                        const float ex = frame_sq_exact_pre<D>(xc, yf[(r + c) % S]);
                         d[c] = (d[c] < sc * tau_thr) ? ex : d[c];
                     }
+                    asm volatile("" : : : "memory");
+                    read_frame_lds<DN>(xs, xnext);
                 }
 #pragma unroll
                 for (int c = 0; c < C; ++c) d[c] = __builtin_amdgcn_sqrtf(d[c]);
-                read_row_at(xs, xrows + q * RS);
                 dp_rows_step<C, G, true>(prev1, prev2, d, g1, g2, del, ins, mat, gl);
                 if (SLOW) slow_phase_captures<C>(prev1, prev2, res1, res2, tau, gl, tau_cap, cw, cstar);
             }
