@@ -316,6 +316,11 @@ struct SpotLaunch {
     apd_spot_best *d_best;
 };
 size_t spot_lds_bytes(uint32_t rows_per_lane);
+// Under APD_DEBUG_PLAN, one stderr line per launch of a spotting kernel, printed where the template arguments are chosen:
+//   [apd] spot <kind> kernel <RT, D>: <n> pairs                                  (rows in registers)
+//   [apd] spot <kind> kernel <0, D>: <n> pairs, r_max <r>, lds <b> bytes         (lane columns in LDS; D = 0: any dimension)
+// kind: "sweep" (dtw_spot) or "record" (dtw_spot_record).  The only report of which spotting kernel ran.
+void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t r_max, size_t lds_bytes);
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
 

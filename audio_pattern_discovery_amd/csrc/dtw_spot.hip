@@ -10,6 +10,9 @@
 // The sweep itself -- lane mapping, macro-step, arithmetic -- is spot_sweep (dtw_spot_sweep.h), which apd_spot_paths' recording
 // sweep shares; here it runs with REC = false: the lane that owns row n stores the curves (when the caller asked for them) and keeps
 // the running best -- the scan over j is serial there already, no atomics, no reduction.
+#include <cstdio>
+#include <cstdlib>
+
 #include "dtw_spot_sweep.h"
 
 namespace apd {
@@ -23,12 +26,22 @@ __global__ __launch_bounds__(64) void dtw_spot(const SpotLaunch L)
 
 size_t spot_lds_bytes(uint32_t rows_per_lane) { return (size_t)rows_per_lane * 64 * (sizeof(float) + sizeof(uint32_t)); }
 
+void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t r_max, size_t lds_bytes)
+{
+    if (!std::getenv("APD_DEBUG_PLAN")) return;
+    if (rt > 0)
+        std::fprintf(stderr, "[apd] spot %s kernel <%d, %d>: %u pairs\n", kind, rt, d, n_pairs);
+    else
+        std::fprintf(stderr, "[apd] spot %s kernel <0, %d>: %u pairs, r_max %u, lds %zu bytes\n", kind, d, n_pairs, r_max, lds_bytes);
+}
+
 namespace {
 
 template <int RT, int D>
 hipError_t launch_spot_as(const SpotLaunch &L, uint32_t r_max, hipStream_t stream)
 {
     const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
+    spot_debug_line("sweep", RT, D, L.n_pairs, r_max, lds_bytes);
     if (lds_bytes > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_spot<RT, D>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lds_bytes);

@@ -141,6 +141,7 @@ template <int RT, int D>
 hipError_t launch_record_as(const SpotPathLaunch &L, uint32_t r_max, hipStream_t stream)
 {
     const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
+    spot_debug_line("record", RT, D, L.n_pairs, r_max, lds_bytes);
     if (lds_bytes > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_spot_record<RT, D>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

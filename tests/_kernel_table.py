@@ -4,8 +4,11 @@ The five APD_*_GEOMS(X) lists and kKernelDims are read from the header (continua
 clamps have a literal Python mirror here, which tests/test_kernel_table.py compares with the header's expressions.  A geometry
 added to a list becomes a new test case of tests/test_gpu_kernel_matrix.py without an edit to the tests.  Also here: the reader
 of the APD_DEBUG_PLAN lines (which geometry took how many tiles), the only report of which kernel ran, the header's fast-path
-feature range (kFeatureFloor, kFeatureBound) and the mixed-magnitude corpus that the CPU and the GPU range tests share.
+feature range (kFeatureFloor, kFeatureBound) and the mixed-magnitude corpus that the CPU and the GPU range tests share.  For the
+spotting kernels: kSpotRegisterRows, a mirror of kernel_dim / spot_rows_per_lane / spot_row_class, the list of instantiations
+<RT, D> the header implies, and the reader of their own APD_DEBUG_PLAN lines.
 """
+import contextlib
 import os
 import re
 
@@ -174,6 +177,89 @@ def read_plan(stderr_text):
     for code, tiles in re.findall(r"geometry (\d+): (\d+) tiles", stderr_text):
         plan[int(code)] = plan.get(int(code), 0) + int(tiles)
     return plan
+
+
+# ---- the spotting kernels: dtw_spot<RT, D> and dtw_spot_record<RT, D> (csrc/dtw_spot.hip, csrc/dtw_spot_path.hip)
+SPOT_KINDS = ("sweep", "record")
+
+
+def parse_spot_register_rows(text=None):
+    """kSpotRegisterRows of the header: the most query rows per lane the spotting kernels hold in registers."""
+    text = header_text() if text is None else text
+    m = re.search(r"constexpr\s+uint32_t\s+kSpotRegisterRows\s*=\s*(\d+)\s*;", text)
+    if m is None:
+        raise ValueError("no 'constexpr uint32_t kSpotRegisterRows = <n>;' in %s" % HEADER)
+    return int(m.group(1))
+
+
+# literal mirror of the header's kernel_dim, spot_rows_per_lane and spot_row_class (hand values: tests/test_kernel_table.py)
+def kernel_dim(d, dims=None):
+    """The resident frame dimension of a batch of dimension d: the first kernel dimension >= d, else d itself."""
+    for k in parse_dims(header_text()) if dims is None else dims:
+        if k >= d:
+            return k
+    return d
+
+
+def spot_rows_per_lane(n):
+    return (n + 63) // 64
+
+
+def spot_row_class(dim, n, dims=None, register_rows=None):
+    """The RT a query of n frames runs with at RESIDENT dimension dim: its rows per lane in registers, or 0 (lane columns in LDS)."""
+    dims = parse_dims(header_text()) if dims is None else dims
+    register_rows = parse_spot_register_rows() if register_rows is None else register_rows
+    r = spot_rows_per_lane(n)
+    return r if dim in dims and r <= register_rows else 0
+
+
+def spot_row_n(n):
+    """(lane, row of the lane) that hold query row n: spot_sweep's lane_n and r_n."""
+    r = spot_rows_per_lane(n)
+    return (n - 1) // r, (n - 1) % r
+
+
+def spot_kernels(text=None):
+    """[(RT, D)] of every instantiation the header implies, for the sweep and for the recording sweep alike: RT = 1 ..
+    kSpotRegisterRows and 0 at every kernel dimension, and <0, 0> for any other dimension."""
+    text = header_text() if text is None else text
+    rows = parse_spot_register_rows(text)
+    return [(rt, d) for d in parse_dims(text) for rt in list(range(1, rows + 1)) + [0]] + [(0, 0)]
+
+
+_SPOT_LINE = re.compile(r"\[apd\] spot (\w+) kernel <(\d+), (\d+)>: (\d+) pairs(?:, r_max (\d+), lds (\d+) bytes)?")
+
+
+def read_spot_launches(stderr_text):
+    """One dict per '[apd] spot <kind> kernel <RT, D>: <n> pairs[, r_max <r>, lds <b> bytes]' line of APD_DEBUG_PLAN=1, in order:
+    kind, rt, d, pairs, and for the LDS class r_max and lds (None for the register classes)."""
+    out = []
+    for kind, rt, d, pairs, r_max, lds in _SPOT_LINE.findall(stderr_text):
+        out.append(dict(kind=kind, rt=int(rt), d=int(d), pairs=int(pairs), r_max=int(r_max) if r_max else None,
+                        lds=int(lds) if lds else None))
+    return out
+
+
+def read_spot_plan(stderr_text):
+    """{(kind, RT, D): pairs} of the spotting kernels' APD_DEBUG_PLAN lines: which instantiation took how many pairs."""
+    plan = {}
+    for launch in read_spot_launches(stderr_text):
+        key = (launch["kind"], launch["rt"], launch["d"])
+        plan[key] = plan.get(key, 0) + launch["pairs"]
+    return plan
+
+
+@contextlib.contextmanager
+def debug_plan(capfd):
+    """The body runs under APD_DEBUG_PLAN=1; the yielded list holds the stderr it wrote once the body has ended."""
+    captured = []
+    os.environ["APD_DEBUG_PLAN"] = "1"
+    capfd.readouterr()
+    try:
+        yield captured
+    finally:
+        os.environ.pop("APD_DEBUG_PLAN", None)
+        captured.append(capfd.readouterr().err)
 
 
 # ---- the fast kernels' feature range, and the corpus that leaves it at both ends

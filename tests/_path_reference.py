@@ -23,15 +23,21 @@ def band_from_pct(pct, length):
     return int(v)
 
 
-def distances(x, y):
-    """d[a][b] = euclidean(x[a], y[b]) (numerics.rs:114-120), every operation an f32 array operation that rounds once."""
+def sq_distances(x, y):
+    """numerics.rs:114-120 up to the square root: every difference, square and partial sum an f32 array operation that rounds once."""
     x, y = np.asarray(x, dtype=F), np.asarray(y, dtype=F)
     acc = np.zeros((len(x), len(y)), dtype=F)
     with np.errstate(all="ignore"):
         for k in range(x.shape[1]):
             t = x[:, None, k] - y[None, :, k]
             acc = acc + t * t
-        return np.sqrt(acc)
+    return acc
+
+
+def distances(x, y):
+    """d[a][b] = euclidean(x[a], y[b]) (numerics.rs:114-120), every operation an f32 array operation that rounds once."""
+    with np.errstate(all="ignore"):
+        return np.sqrt(sq_distances(x, y))
 
 
 def table(x, y, band, ins=1.0, dele=1.0, match=1.0):

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import _kernel_table as kt
 import _spot_reference as ref
 
 pytestmark = pytest.mark.gpu
@@ -136,7 +137,7 @@ def test_hand_cases_through_both_entry_points(apd, ctx):
     assert (int(best[0]["end"]), int(best[0]["start"]), float(best[0]["cost"]), float(best[0]["score"])) == (3, 2, 0.0, 0.0)
 
 
-QUERY_LENGTHS = (1, 2, 63, 64, 65, 128, 130)      # R = 1, 2, 3 rows per lane; last lane full, one row over, one lane over
+QUERY_LENGTHS = (1, 2, 63, 64, 65, 128, 130)      # R = 1, 2, 3 rows per lane in registers (D = 13); last lane full, one row over, one lane over
 STREAM_LENGTHS = (1, 2, 63, 64, 65, 200)
 
 
@@ -150,11 +151,15 @@ def test_lane_and_row_block_edges(apd, ctx):
     assert np.all(best["end"] >= 1) and np.all(np.isfinite(best["score"]))
 
 
-def test_rows_in_registers_and_in_lds(apd, ctx):
+def test_rows_in_registers_and_in_lds(apd, ctx, capfd):
     """R = 3, 4 (registers), R = 5 (the first query length whose lane columns live in LDS), and the row-block edges around them."""
     seqs = gauss_seqs((192, 256, 257, 320, 70, 33), 13, 102)
-    check_batch(apd, ctx, "classes", seqs, UNIT, [(q, s) for q in range(4) for s in (4, 5)])
-    check_batch(apd, ctx, "classes", seqs, SKEWED, [(1, 4), (2, 5)])
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "classes", seqs, UNIT, [(q, s) for q in range(4) for s in (4, 5)])
+    assert kt.read_spot_plan(err[0]) == {("sweep", 3, 13): 2, ("sweep", 4, 13): 2, ("sweep", 0, 13): 4}, err[0]
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "classes", seqs, SKEWED, [(1, 4), (2, 5)])
+    assert kt.read_spot_plan(err[0]) == {("sweep", 4, 13): 1, ("sweep", 0, 13): 1}, err[0]
 
 
 @pytest.mark.parametrize("dim", [1, 13])
@@ -170,9 +175,12 @@ def test_dimensions(apd, ctx, dim):
     check_batch(apd, ctx, "dim%d" % dim, seqs, UNIT, [(0, 1)])
 
 
-def test_dimension_without_kernels_of_its_own_with_a_long_query(apd, ctx):
+def test_dimension_without_kernels_of_its_own_with_a_long_query(apd, ctx, capfd):
     seqs = gauss_seqs((330, 20), 40, 125)                                      # D = 40: frames re-read per cell, R = 6 in LDS
-    check_batch(apd, ctx, "dim40long", seqs, SKEWED, [(0, 1), (1, 0)])
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "dim40long", seqs, SKEWED, [(0, 1), (1, 0)])     # the 20-frame query too: one launch, LDS for R = 6
+    assert kt.read_spot_plan(err[0]) == {("sweep", 0, 0): 2}, err[0]
+    assert [(v["r_max"], v["lds"]) for v in kt.read_spot_launches(err[0])] == [(6, 6 * 64 * 8)]
 
 
 def test_embedded_copies(apd, ctx):
@@ -340,14 +348,24 @@ def test_spot_follows_a_refill(apd, ctx, mixed):
     assert before[0][0].tobytes() != after[0][0].tobytes()
 
 
-def test_a_long_query(apd, ctx):
+def test_a_long_query(apd, ctx, capfd):
     seqs = gauss_seqs((4096, 96), 13, 190)                                     # R = 64 rows per lane, 32 KB of LDS
-    check_batch(apd, ctx, "long", seqs, UNIT, [(0, 1)])
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "long", seqs, UNIT, [(0, 1)])
+    assert [(v["kind"], v["rt"], v["d"], v["r_max"], v["lds"]) for v in kt.read_spot_launches(err[0])] == [("sweep", 0, 13, 64, 32 * 1024)]
 
 
-def test_lane_columns_beyond_64_kib_of_lds_and_the_longest_query(apd, ctx):
-    seqs = gauss_seqs((8200, 16384, 3, 2), 1, 191)                             # R = 129: 66 KB (the launch has to ask for it); R = 256: the limit
-    check_batch(apd, ctx, "lds", seqs, UNIT, [(0, 2), (1, 3)])
+def test_lane_columns_beyond_64_kib_of_lds_and_the_longest_query(apd, ctx, capfd):
+    """dim = 1 is resident as D = 8: kernel <0, 8>.  R = 256 is the limit; both pairs go in ONE launch, sized for the longer query
+    (128 KB), so the R = 129 pair is also run alone: 64.5 KB, the smallest size the launch has to ask for."""
+    seqs = gauss_seqs((8200, 16384, 3, 2), 1, 191)
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "lds", seqs, UNIT, [(0, 2), (1, 3)])
+    d = kt.kernel_dim(1)
+    assert [(v["kind"], v["rt"], v["d"], v["pairs"], v["r_max"], v["lds"]) for v in kt.read_spot_launches(err[0])] == [("sweep", 0, d, 2, 256, 128 * 1024)]
+    with kt.debug_plan(capfd) as err:
+        check_batch(apd, ctx, "lds", seqs, UNIT, [(0, 2)])
+    assert [(v["kind"], v["rt"], v["d"], v["pairs"], v["r_max"], v["lds"]) for v in kt.read_spot_launches(err[0])] == [("sweep", 0, d, 1, 129, 129 * 512)]
 
 
 def test_timing_covers_the_call(apd, ctx, mixed):

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import _kernel_table as kt
 import _spot_path_reference as ref
 import _spot_reference as spot_ref
 
@@ -204,23 +205,38 @@ def check_edges(apd, ctx, key, queries, dim, seed):
         batch.close()
 
 
-def test_lane_and_row_block_edges_in_registers(apd, ctx):
-    check_edges(apd, ctx, "edges", QUERY_LENGTHS, 13, 301)
+def test_lane_and_row_block_edges_in_registers(apd, ctx, capfd):
+    with kt.debug_plan(capfd) as err:
+        check_edges(apd, ctx, "edges", QUERY_LENGTHS, 13, 301)
+    assert set(kt.read_spot_plan(err[0])) == {(kind, rt, 13) for kind in kt.SPOT_KINDS for rt in (1, 2, 3)}, err[0]
 
 
-def test_lane_and_row_block_edges_in_lds(apd, ctx):
-    check_edges(apd, ctx, "edges-lds", LDS_QUERY_LENGTHS, 13, 302)
+def test_lane_and_row_block_edges_in_lds(apd, ctx, capfd):
+    with kt.debug_plan(capfd) as err:
+        check_edges(apd, ctx, "edges-lds", LDS_QUERY_LENGTHS, 13, 302)
+    assert set(kt.read_spot_plan(err[0])) == {("sweep", 0, 13), ("record", 0, 13)}, err[0]
 
 
-def test_two_branch_words_per_lane(apd, ctx):
-    check_edges(apd, ctx, "edges-wpl2", (1100,), 13, 303)                           # R = 18: WPL = 2
+def test_two_branch_words_per_lane(apd, ctx, capfd):
+    with kt.debug_plan(capfd) as err:
+        check_edges(apd, ctx, "edges-wpl2", (1100,), 13, 303)                       # R = 18 in LDS: WPL = 2
+    assert {(v["kind"], v["rt"], v["d"], v["r_max"]) for v in kt.read_spot_launches(err[0])} == {("sweep", 0, 13, 18), ("record", 0, 13, 18)}
 
 
-def test_dimension_without_kernels_of_its_own(apd, ctx):
-    seqs = gauss_seqs((130, 100), 5, 304)                                          # frames re-read per cell, R = 3 in LDS
-    records = curve_windows(apd, ctx, seqs, SKEWED, [(0, 1)], lambda m: range(1, m + 1))
-    paths, _, _ = check_windows(apd, ctx, "dim5", seqs, SKEWED, records)
-    assert len(paths) == 100 and all(len(p) > 130 for p in paths)
+def test_dimension_without_kernels_of_its_own(apd, ctx, capfd):
+    """A dimension above the largest kernel dimension runs <0, 0>: frames re-read per cell, R = 3 rows per lane in LDS.  A small one
+    does not: dim = 5 is made resident as kernel_dim(5) = 8 and runs <3, 8>, everything in registers."""
+    top = max(kt.parse_dims(kt.header_text()))
+    for dim, kernel, seed in ((top + 5, (0, 0), 305), (5, (3, kt.kernel_dim(5)), 304)):
+        assert kt.spot_row_class(kt.kernel_dim(dim), 130) == kernel[0]
+        seqs = gauss_seqs((130, 100), dim, seed)
+        with kt.debug_plan(capfd) as err:
+            records = curve_windows(apd, ctx, seqs, SKEWED, [(0, 1)], lambda m: range(1, m + 1))
+            paths, _, _ = check_windows(apd, ctx, "dim%d" % dim, seqs, SKEWED, records)
+        assert kt.read_spot_plan(err[0]) == {("sweep",) + kernel: 1, ("record",) + kernel: 1}, err[0]
+        if kernel == (0, 0):
+            assert {(v["r_max"], v["lds"]) for v in kt.read_spot_launches(err[0])} == {(3, 3 * 64 * 8)}
+        assert len(paths) == 100 and all(len(p) > 130 for p in paths)
 
 
 @pytest.mark.parametrize("dim", [3, 8, 13, 16, 40])

@@ -63,3 +63,72 @@ def test_plan_lines_are_read_per_geometry():
            "[apd] rank 0/1: geometry 0: 1 tiles, w_max 9, n_max 30\n[apd] rank 1/2: geometry 1609: 3 tiles, w_max 70, n_max 304\n")
     assert kt.read_plan(err) == {1609: 5, 0: 1}
     assert kt.read_plan("") == {}
+
+
+# ---- the spotting kernels (tests/test_gpu_spot_matrix.py)
+
+def test_the_spot_register_rows_parse():
+    assert kt.parse_spot_register_rows() >= 1
+    assert kt.parse_spot_register_rows("constexpr uint32_t kSpotRegisterRows = 7;     // rows") == 7
+    with pytest.raises(ValueError, match="kSpotRegisterRows"):
+        kt.parse_spot_register_rows("constexpr int kSpotRows = 4;")
+
+
+def test_the_spot_mirror_at_hand_values():
+    dims = [8, 10, 13, 16, 20, 26]
+    assert [kt.kernel_dim(d, dims) for d in (1, 5, 8, 9, 27)] == [8, 8, 8, 10, 27]
+    assert [kt.spot_rows_per_lane(n) for n in (1, 64, 65, 256, 257)] == [1, 1, 2, 4, 5]
+    assert [kt.spot_row_class(8, n, dims, 4) for n in (64, 65, 256, 257)] == [1, 2, 4, 0]
+    assert [kt.spot_row_class(27, n, dims, 4) for n in (64, 65, 256, 257)] == [0, 0, 0, 0]      # no kernel dimension: LDS whatever R
+    assert [kt.spot_row_class(kt.kernel_dim(d, dims), 65, dims, 4) for d in (1, 5, 8, 9, 27)] == [2, 2, 2, 2, 0]
+    assert kt.spot_row_class(13, 257, dims, 5) == 5 and kt.spot_row_class(13, 65, dims, 1) == 0
+    # (lane, row of the lane) of query row n: spot_sweep's lane_n = (n - 1) / R, r_n = (n - 1) - lane_n * R
+    assert [kt.spot_row_n(n) for n in (1, 64, 65, 193, 222, 231, 256, 257)] == [(0, 0), (63, 0), (32, 0), (48, 0), (55, 1), (57, 2), (63, 3), (51, 1)]
+    # the header this tree has: the mirror's defaults read it
+    assert kt.kernel_dim(1) == min(kt.parse_dims(kt.header_text())) and kt.spot_row_class(kt.kernel_dim(1), 1) == 1
+
+
+def test_spot_kernels_are_every_row_class_at_every_dimension_and_the_any_dimension_one():
+    text = "constexpr int kKernelDims[] = {4, 6};\nconstexpr uint32_t kSpotRegisterRows = 2;\n"
+    assert kt.spot_kernels(text) == [(1, 4), (2, 4), (0, 4), (1, 6), (2, 6), (0, 6), (0, 0)]
+    kernels = kt.spot_kernels()
+    _, dims = kt.parse_table()
+    assert len(kernels) == len(set(kernels)) == len(dims) * (kt.parse_spot_register_rows() + 1) + 1
+
+
+def test_spot_plan_lines_are_read_per_kernel_and_leave_the_tile_plan_alone():
+    old = "[apd] rank 0/1: geometry 1609: 2 tiles, w_max 70, n_max 304\n"
+    err = (old + "[apd] spot sweep kernel <2, 13>: 5 pairs\nnoise\n[apd] spot record kernel <0, 0>: 3 pairs, r_max 6, lds 3072 bytes\n"
+           "[apd] spot sweep kernel <2, 13>: 1 pairs\n[apd] spot sweep kernel <0, 26>: 2 pairs, r_max 129, lds 66048 bytes\n")
+    assert kt.read_spot_plan(err) == {("sweep", 2, 13): 6, ("record", 0, 0): 3, ("sweep", 0, 26): 2}
+    launches = kt.read_spot_launches(err)
+    assert [(v["kind"], v["rt"], v["d"], v["pairs"], v["r_max"], v["lds"]) for v in launches] == [
+        ("sweep", 2, 13, 5, None, None), ("record", 0, 0, 3, 6, 3072), ("sweep", 2, 13, 1, None, None), ("sweep", 0, 26, 2, 129, 66048)]
+    assert kt.read_plan(err) == {1609: 2}                     # the tile-plan reader sees what it saw before
+    assert kt.read_spot_plan(old) == {} and kt.read_spot_plan("") == {}
+
+
+def test_the_spot_matrix_cases_cover_every_kernel_exactly():
+    import _spot_matrix as sm
+    rows, dims = kt.parse_spot_register_rows(), kt.parse_dims(kt.header_text())
+    kernels = sm.register_kernels()
+    any_dims = sm.any_dimensions(dims)
+    covered = [sm.register_case(*k).kernel for k in kernels] + sorted({sm.any_case(d).kernel for d in any_dims})
+    for kind in kt.SPOT_KINDS:                                # the sweep and the recording sweep run the same cases
+        assert sorted((kind,) + k for k in covered) == sorted((kind,) + k for k in kt.spot_kernels())
+    assert len(covered) == len(dims) * (rows + 1) + 1
+    for rt, d in kernels:                                     # each case reaches its own kernel and no other
+        case = sm.register_case(rt, d)
+        pairs = case.unit_pairs + case.skewed_pairs + case.gate_pairs
+        assert {kt.spot_row_class(kt.kernel_dim(case.dim), case.lengths[x]) for x, _ in pairs} == {rt} and kt.kernel_dim(case.dim) == d
+        assert len(case.gate_pairs) == (3 if rt else 0)
+    for rt in range(1, rows + 1):
+        lengths = sm.query_lengths(rt, rows)
+        assert lengths[0] == 64 * (rt - 1) + 1 and lengths[-1] == 64 * rt
+        assert {kt.spot_row_n(n)[1] for n in lengths} == set(range(rt)), lengths
+    assert sm.query_lengths(4, 4) == [193, 222, 231, 256]
+    assert [kt.spot_rows_per_lane(n) for n in sm.query_lengths(0, rows)] == [rows + 1, rows + 2]
+    assert {d % 4 for d in any_dims[:4]} == {0, 1, 2, 3} and min(any_dims) > max(dims)      # the squared-norm slot in each float4 component
+    assert all(kt.kernel_dim(d) == d and kt.spot_row_class(d, 1) == 0 for d in any_dims)
+    far = sm.any_case(any_dims[-1])
+    assert sorted({kt.spot_rows_per_lane(far.lengths[x]) for x, _ in far.unit_pairs}) == [1, rows + 2]
