@@ -176,6 +176,11 @@ SYMBOLS = [
     ("apd_spot_path_bound", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
     ("apd_spot_paths", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), C.POINTER(SpotWindow), C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p,
                                  _u32p, _u32p, _f32p]),
+    ("apd_spot_stream_create", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    ("apd_spot_stream_destroy", C.c_int, [_vp]),
+    ("apd_spot_stream_reset", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64]),
+    ("apd_spot_stream_columns", C.c_int, [_vp, C.c_uint32, _u64p]),
+    ("apd_spot_stream_push", C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, C.c_int, _f32p, _u32p, C.c_uint64, _u64p, C.POINTER(SpotBest)]),
     ("apd_percentile", C.c_int, [_vp, _vp, C.c_uint64, C.c_float, C.c_int, _f32p]),
     ("apd_clustering", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_float, C.POINTER(ClusterOp), _u32p, _u32p,
                                  _u32p, _f32p]),

@@ -325,6 +325,14 @@ class AlignmentWorkers:
                 batch.close()
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_windows)], found, scores
 
+    def spot_stream(self, queries, params, channels=1):
+        """A streaming spotting session (include/apd.h, "streaming spotting"): the sequences `queries` of this object (repeats allowed)
+        as templates against `channels` independent streams that arrive in chunks; params: Discovery (penalties only).  This object
+        must stay open as long as the session: SpotStream."""
+        if self._multi is not None:
+            raise ValueError("spot_stream() runs on one context: make the AlignmentWorkers without `devices`")
+        return SpotStream(self, queries, params, channels)
+
     def barycenters(self, sets, params, init=None, iterations=10, on_device=False):
         """DTW barycenter averaging (include/apd.h, "cluster prototypes") of the sets of this object's sequence numbers in `sets`
         (as cluster_sets returns them), params: Discovery.  init[k]: the sequence whose frames start set k's barycenter; None: the
@@ -391,6 +399,81 @@ class AlignmentWorkers:
         if self._multi is not None:
             self._multi.close()
             self._multi = None
+
+
+class SpotStream:
+    """apd_spot_stream: AlignmentWorkers.spot_stream() makes it.  Pair p = channel * len(queries) + q; the curves of the pushes, one
+    after the other, are spot()'s curves of the whole stream, bit for bit, whatever the chunking."""
+
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, workers, queries, params, channels=1):
+        self._workers = workers                                   # keeps the templates' batch alive
+        self.ctx = workers.ctx
+        self.dim = int(workers._dim)
+        self.queries = np.ascontiguousarray(queries, dtype=np.uint32).ravel()
+        self.channels = int(channels)
+        self.n_pairs = len(self.queries) * self.channels
+        self.handle = C.c_void_p()
+        cfg = params.align_config()
+        _lib.check(_lib.lib().apd_spot_stream_create(self.ctx.handle, workers._batch.handle, C.byref(cfg),
+                                                     self.queries.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.queries), self.channels,
+                                                     C.byref(self.handle)), self.ctx.handle)
+
+    def push(self, chunks, curves=True, on_device=False):
+        """One chunk per channel: a list of (frames, dim) float32 arrays, zero frames allowed; with on_device=True the pair
+        (device pointer of the packed frames, chunk_off array of channels + 1 entries).  Returns (list of (cost, start) arrays per pair
+        -- empty with curves=False --, the running `best` as a SPOT_BEST array)."""
+        L = _lib.lib()
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        if on_device:
+            ptr, chunk_off = chunks
+            chunk_off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+            frames = C.c_void_p(int(ptr))
+        else:
+            if len(chunks) != self.channels:
+                raise ValueError("one chunk per channel")
+            arrays = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, self.dim) for c in chunks]
+            chunk_off = np.zeros(self.channels + 1, dtype=np.uint64)
+            chunk_off[1:] = np.cumsum([len(a) for a in arrays])
+            host = np.ascontiguousarray(np.concatenate(arrays, axis=0)) if arrays else np.zeros((0, self.dim), np.float32)
+            frames = C.c_void_p(host.ctypes.data)
+        if len(chunk_off) != self.channels + 1:
+            raise ValueError("chunk_off needs channels + 1 entries")
+        off = np.zeros(self.n_pairs + 1, dtype=np.uint64)
+        best = np.zeros(self.n_pairs, dtype=SPOT_BEST)
+        head = (self.ctx.handle, self.handle, frames, chunk_off.ctypes.data_as(u64p), self.dim, int(bool(on_device)))
+        tail = (off.ctypes.data_as(u64p), best.ctypes.data_as(C.POINTER(_lib.SpotBest)))
+        if not curves:
+            _lib.check(L.apd_spot_stream_push(*head, None, None, 0, *tail), self.ctx.handle)
+            return [], best
+        entries = int(chunk_off[-1]) * len(self.queries)
+        cost = np.zeros(max(entries, 1), dtype=np.float32)
+        start = np.zeros(len(cost), dtype=np.uint32)
+        _lib.check(L.apd_spot_stream_push(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
+        return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(self.n_pairs)], best
+
+    def reset(self, channel=None, first_column=0):
+        """A fresh table for `channel` (None: every channel); its next frame is absolute column first_column + 1."""
+        _lib.check(_lib.lib().apd_spot_stream_reset(self.ctx.handle, self.handle, self.ALL if channel is None else int(channel),
+                                                    int(first_column)), self.ctx.handle)
+
+    def columns(self, channel):
+        """Absolute column of the channel's last pushed frame."""
+        out = C.c_uint64(0)
+        _lib.check(_lib.lib().apd_spot_stream_columns(self.handle, int(channel), C.byref(out)))
+        return int(out.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.lib().apd_spot_stream_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def spot_hits(cost, start, n, threshold):

@@ -1608,6 +1608,229 @@ extern "C" int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const ap
     return APD_OK;
 }
 
+// ------------------------------------------------------------------------------------ streaming spotting
+
+// A resident spotting session (include/apd.h, "streaming spotting"; kernels: dtw_spot_stream.hip).  Everything a push needs lives
+// here and grows only: the pair descriptors (grouped by kernel class once, at create), the two halves of the carried columns, the
+// running bests, the words a push uploads, the staged chunk and the curves.
+struct apd_spot_stream : apd::ContextChild {
+    static constexpr uint32_t kClasses = kSpotRegisterRows + 1;             // spot_row_class
+    const apd_batch *templates = nullptr;
+    uint32_t n_queries = 0, n_channels = 0, n_pairs = 0;
+    float ins = 0.0f, del = 0.0f, mat = 0.0f;
+    std::vector<uint64_t> columns;      // per channel: absolute column of the last frame pushed (first_column after a reset)
+    std::vector<uint32_t> parity;       // per channel: the half of d_state that holds its column
+    std::vector<SpotStreamPair> h_pairs;
+    std::vector<uint32_t> h_push;       // host image of d_push, alive as long as the session (the upload is asynchronous)
+    uint32_t class_first[kClasses] = {}, class_count[kClasses] = {};
+    uint32_t r_max = 1;
+    uint64_t state_half = 0;            // floats
+    apd::DeviceBuf d_pairs, d_state, d_best;
+    apd::DeviceBuf d_push;              // [chunk first n_channels + 1 | base n_channels | parity n_channels | the repack's words, kPadWords]
+    apd::DeviceBuf d_raw;               // host chunks on their way to the repack kernel
+    apd::DeviceBuf d_stage;             // the chunks in the resident layout, two sentinel frames behind them
+    apd::DeviceBuf d_curves;            // [cost | start]
+    // the staged chunks are ONE sequence to the repack kernel: [seq_off 2 | src_off 1 | unused 1 | flags 4 | norm maximum 1 | unused 3]
+    static constexpr uint32_t kPadWords = 12;
+    size_t push_words() const { return 3 * (size_t)n_channels + 1 + kPadWords; }
+    SpotStreamLaunch launch() const
+    {
+        SpotStreamLaunch S{};
+        S.d_frames = templates->d_frames.as<float>(); S.d_seq_off = templates->d_seq_off;
+        S.d_stage = d_stage.as<float>(); S.d_push = d_push.as<uint32_t>();
+        S.n_channels = n_channels; S.n_queries = n_queries; S.dim = templates->dim; S.dpad = templates->dpad;
+        S.ins = ins; S.del = del; S.mat = mat;
+        S.d_pairs = d_pairs.as<SpotStreamPair>(); S.n_pairs = n_pairs;
+        S.d_state = d_state.as<float>(); S.state_half = state_half;
+        S.d_best = d_best.as<apd_spot_best>();
+        return S;
+    }
+    void release_device() override
+    {
+        d_pairs.reset(); d_state.reset(); d_best.reset(); d_push.reset(); d_raw.reset(); d_stage.reset(); d_curves.reset();
+    }
+};
+
+extern "C" int apd_spot_stream_create(apd_context *ctx, const apd_batch *templates, const apd_align_config *cfg, const uint32_t *queries,
+                                      uint32_t n_queries, uint32_t n_channels, apd_spot_stream **stream)
+{
+    if (!ctx || !templates || !cfg || !stream || !queries || templates->ctx != ctx) return APD_ERR_INVALID_ARG;
+    *stream = nullptr;
+    const uint64_t n_pairs = (uint64_t)n_queries * n_channels;
+    if (n_pairs == 0 || n_pairs >= (1ull << 24)) return APD_ERR_INVALID_ARG;   // 64 work-items per pair: a launch stays below 2^31
+    const uint32_t n_seq = templates->n_seq;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (queries[q] >= n_seq) return APD_ERR_INVALID_ARG;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[templates->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(templates->offsets[pos[s] + 1] - templates->offsets[pos[s]]); };
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (len_of(queries[q]) == 0) return APD_ERR_EMPTY_SEQUENCE;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (len_of(queries[q]) > kSpotMaxQuery) {
+            ctx->last_error = "apd_spot_stream_create: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
+            return APD_ERR_UNSUPPORTED;
+        }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream allocation");
+    apd_spot_stream *s = new (std::nothrow) apd_spot_stream();
+    if (!s) return APD_ERR_OOM;
+    s->templates = templates; s->n_queries = n_queries; s->n_channels = n_channels; s->n_pairs = (uint32_t)n_pairs;
+    s->ins = cfg->insertion_penalty; s->del = cfg->deletion_penalty; s->mat = cfg->match_penalty;
+    s->columns.assign(n_channels, 0);
+    s->parity.assign(n_channels, 0u);
+    s->h_push.assign(s->push_words(), 0u);
+    // the descriptors, grouped by kernel class (one launch each per push); `out` keeps p = channel n_queries + q
+    constexpr uint32_t kClasses = apd_spot_stream::kClasses;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const uint32_t n = len_of(queries[q]), c = spot_row_class(templates->dim, n);
+        s->class_count[c] += n_channels;
+        if (c == 0) s->r_max = std::max(s->r_max, spot_rows_per_lane(n));
+    }
+    for (uint32_t c = 1; c < kClasses; ++c) s->class_first[c] = s->class_first[c - 1] + s->class_count[c - 1];
+    uint32_t fill[kClasses];
+    std::copy(s->class_first, s->class_first + kClasses, fill);
+    s->h_pairs.resize(n_pairs);
+    uint64_t state_floats = 0;
+    for (uint32_t k = 0; k < n_channels; ++k)
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            const uint32_t n = len_of(queries[q]);
+            SpotStreamPair &d = s->h_pairs[fill[spot_row_class(templates->dim, n)]++];
+            d.px = pos[queries[q]];
+            d.channel = k;
+            d.out = k * n_queries + q;
+            d.rows = spot_rows_per_lane(n);
+            d.state_off = state_floats;
+            state_floats += 2ull * d.rows * 64;                           // values, then starts
+        }
+    s->state_half = state_floats;
+    s->ctx = ctx;
+    ctx->children.insert(s);                                              // from here on apd_spot_stream_destroy undoes everything
+    auto fail = [&](int rc) { apd_spot_stream_destroy(s); return rc; };
+    const size_t pair_bytes = (size_t)n_pairs * sizeof(SpotStreamPair);
+    if (s->d_pairs.alloc(pair_bytes) != hipSuccess || s->d_state.alloc((size_t)state_floats * 2 * sizeof(float)) != hipSuccess ||
+        s->d_best.alloc((size_t)n_pairs * sizeof(apd_spot_best)) != hipSuccess ||
+        s->d_push.alloc(s->push_words() * sizeof(uint32_t)) != hipSuccess)
+        return fail(APD_ERR_OOM);
+    hipError_t e = hipMemcpyAsync(s->d_pairs.ptr, s->h_pairs.data(), pair_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = launch_spot_stream_reset(s->launch(), 0xFFFFFFFFu, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->last_error = std::string("apd_spot_stream_create: ") + hipGetErrorString(e); return fail(APD_ERR_HIP); }
+    *stream = s;
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_destroy(apd_spot_stream *stream) { return destroy_child(stream); }
+
+extern "C" int apd_spot_stream_reset(apd_context *ctx, apd_spot_stream *stream, uint32_t channel, uint64_t first_column)
+{
+    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
+    const bool all = channel == 0xFFFFFFFFu;
+    if (!all && channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
+    if (first_column >= kSpotMaxStream) {
+        ctx->last_error = "apd_spot_stream_reset: first_column at or beyond " + std::to_string(kSpotMaxStream);
+        return APD_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream reset");
+    HIP_TRY(ctx, launch_spot_stream_reset(stream->launch(), channel, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t k = 0; k < stream->n_channels; ++k)
+        if (all || k == channel) stream->columns[k] = first_column;       // either half holds column 0 now: the parity stays
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_columns(const apd_spot_stream *stream, uint32_t channel, uint64_t *columns)
+{
+    if (!stream || !columns || channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
+    *columns = stream->columns[channel];
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, const float *frames, const uint64_t *chunk_off, uint32_t dim,
+                                    int frames_on_device, float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off,
+                                    apd_spot_best *best)
+{
+    if (!ctx || !stream || stream->ctx != ctx || !chunk_off || !curve_off) return APD_ERR_INVALID_ARG;
+    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
+    apd_spot_stream *s = stream;
+    const apd_batch *t = s->templates;
+    if (t->ctx != ctx || dim != t->src_dim) return APD_ERR_INVALID_ARG;
+    const uint32_t n_ch = s->n_channels, n_q = s->n_queries;
+    if (chunk_off[0] != 0) return APD_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < n_ch; ++k)
+        if (chunk_off[k + 1] < chunk_off[k]) return APD_ERR_INVALID_ARG;
+    const uint64_t total = chunk_off[n_ch];
+    if (total + 2 >= (1ull << 32) || (total > 0 && !frames)) return APD_ERR_INVALID_ARG;   // one resident "sequence", as a batch's limit
+    for (uint32_t k = 0; k < n_ch; ++k)
+        if (s->columns[k] + (chunk_off[k + 1] - chunk_off[k]) >= kSpotMaxStream) {
+            ctx->last_error = "apd_spot_stream_push: channel " + std::to_string(k) + " would reach column " + std::to_string(kSpotMaxStream);
+            return APD_ERR_UNSUPPORTED;
+        }
+    curve_off[0] = 0;
+    for (uint32_t k = 0; k < n_ch; ++k)
+        for (uint32_t q = 0; q < n_q; ++q) {
+            const uint64_t p = (uint64_t)k * n_q + q;
+            curve_off[p + 1] = curve_off[p] + (chunk_off[k + 1] - chunk_off[k]);
+        }
+    const bool curves = cost != nullptr;
+    if (!curves && !best) return APD_OK;                                  // sizes only: the state is not advanced
+    const uint64_t entries = curve_off[s->n_pairs];
+    if (curves && capacity < entries) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream launch");
+    SpotStreamLaunch S = s->launch();
+    const size_t best_bytes = (size_t)s->n_pairs * sizeof(apd_spot_best);
+    if (total > 0) {
+        // buffers: grown to the largest push seen, then reused
+        const size_t curve_bytes = curves ? ((size_t)entries * 4 + 15) / 16 * 16 : 0;
+        HIP_TRY(ctx, s->d_stage.reserve((size_t)(total + 2) * t->dpad * sizeof(float)));
+        if (curves) HIP_TRY(ctx, s->d_curves.reserve(2 * curve_bytes));
+        const size_t raw_bytes = (size_t)total * dim * sizeof(float);
+        if (!frames_on_device) HIP_TRY(ctx, s->d_raw.reserve(raw_bytes));
+        S = s->launch();
+        S.d_cost = curves ? s->d_curves.as<float>() : nullptr;
+        S.d_start = curves ? (uint32_t *)(s->d_curves.as<char>() + curve_bytes) : nullptr;
+        // the words of this push
+        uint32_t *w = s->h_push.data(), *pad = w + 3 * (size_t)n_ch + 1;
+        for (uint32_t k = 0; k <= n_ch; ++k) w[k] = (uint32_t)chunk_off[k];
+        for (uint32_t k = 0; k < n_ch; ++k) {
+            w[n_ch + 1 + k] = (uint32_t)s->columns[k];
+            w[2 * n_ch + 1 + k] = s->parity[k];
+        }
+        std::fill(pad, pad + apd_spot_stream::kPadWords, 0u);
+        pad[1] = (uint32_t)total + 2;                                     // seq_off = {0, total + 2}, src_off = {0}, flags and norm maximum zeroed
+        uint32_t *d_w = s->d_push.as<uint32_t>(), *d_pad = d_w + 3 * (size_t)n_ch + 1;
+        HIP_TRY(ctx, hipMemcpyAsync(d_w, w, s->push_words() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        const float *d_src = frames;
+        if (!frames_on_device) {
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_raw.ptr, frames, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
+            d_src = s->d_raw.as<float>();
+        }
+        if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        HIP_TRY(ctx, launch_pad(d_src, s->d_stage.as<float>(), d_pad, d_pad + 2, 1, total + 2, dim, t->dim, t->dpad, d_pad + 4,
+                                reinterpret_cast<float *>(d_pad + 8), ctx->stream));
+        for (uint32_t c = 0; c < apd_spot_stream::kClasses; ++c) {
+            S.d_pairs = s->d_pairs.as<SpotStreamPair>() + s->class_first[c];
+            S.n_pairs = s->class_count[c];
+            HIP_TRY(ctx, launch_spot_stream(S, c, s->r_max, ctx->stream));
+        }
+        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        // the table has moved on, whatever the copies below do
+        for (uint32_t k = 0; k < n_ch; ++k) {
+            const uint64_t m = chunk_off[k + 1] - chunk_off[k];
+            if (m) { s->columns[k] += m; s->parity[k] ^= 1u; }
+        }
+        if (curves) {
+            HIP_TRY(ctx, hipMemcpyAsync(cost, S.d_cost, (size_t)entries * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(start, S.d_start, (size_t)entries * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    if (best) HIP_TRY(ctx, hipMemcpyAsync(best, S.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's, `frames` is free again
+    return APD_OK;
+}
+
 // ------------------------------------------------------------------------------- work accounting
 
 extern "C" int apd_align_work(const uint64_t *offsets, uint32_t n_seq, uint32_t dim, const apd_align_config *cfg,

@@ -319,10 +319,43 @@ size_t spot_lds_bytes(uint32_t rows_per_lane);
 // Under APD_DEBUG_PLAN, one stderr line per launch of a spotting kernel, printed where the template arguments are chosen:
 //   [apd] spot <kind> kernel <RT, D>: <n> pairs                                  (rows in registers)
 //   [apd] spot <kind> kernel <0, D>: <n> pairs, r_max <r>, lds <b> bytes         (lane columns in LDS; D = 0: any dimension)
-// kind: "sweep" (dtw_spot) or "record" (dtw_spot_record).  The only report of which spotting kernel ran.
+// kind: "sweep" (dtw_spot), "record" (dtw_spot_record) or "stream" (dtw_spot_stream).  The only report of which spotting kernel ran.
 void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t r_max, size_t lds_bytes);
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
+
+// ---- streaming spotting (dtw_spot_stream.hip): the sweep above entered and left in mid-stream.  A session (apd_spot_stream) keeps,
+// per pair p = channel n_queries + q, the last pushed column of the table and the running best on the device; a push sweeps every
+// channel's chunk from there.  Query rows come from the templates' batch, stream columns from the session's staging buffer.
+struct SpotStreamPair {
+    uint32_t px;           // resident position of the query in the templates' batch
+    uint32_t channel;
+    uint32_t out;          // p: the pair's record in d_best, and its place in the curves
+    uint32_t rows;         // rows per lane R = spot_rows_per_lane(n): the pair's state is [R][64] values, then [R][64] starts
+    uint64_t state_off;    // first float of the pair's state in either half of d_state
+};
+struct SpotStreamLaunch {
+    const float *d_frames;           // the templates
+    const uint32_t *d_seq_off;
+    const float *d_stage;            // the chunks of this push, packed, in the resident layout (dpad floats per frame)
+    // what a push uploads, n_channels + 1 | n_channels | n_channels words: first staged frame of every channel's chunk (and the
+    // total); absolute column of the channel's last frame before this push; which half of d_state holds the channel's column
+    const uint32_t *d_push;
+    uint32_t n_channels, n_queries;
+    uint32_t dim, dpad;
+    float ins, del, mat;
+    const SpotStreamPair *d_pairs;
+    uint32_t n_pairs;
+    float *d_state;                  // two halves of state_half floats: a sweep reads one and writes the other
+    uint64_t state_half;
+    float *d_cost;                   // both null: best only
+    uint32_t *d_start;
+    apd_spot_best *d_best;           // [n_queries n_channels], the session's: read at the start of a sweep, written at its end
+};
+// The pairs of S all have row class `rt`, as for launch_spot; kind "stream" on the APD_DEBUG_PLAN line.
+hipError_t launch_spot_stream(const SpotStreamLaunch &S, uint32_t rt, uint32_t r_max, hipStream_t stream);
+// S.d_pairs: every pair of the session; resets those of `channel` (0xFFFFFFFF: all) to column 0 and no best.
+hipError_t launch_spot_stream_reset(const SpotStreamLaunch &S, uint32_t channel, hipStream_t stream);
 
 // ---- warping paths of spotted windows (dtw_spot_path.hip): the sweep above once per distinct (query, stream) pair of a chunk,
 // recording the branch of every cell whose column some window of the pair covers, then one wavefront per window walking back.

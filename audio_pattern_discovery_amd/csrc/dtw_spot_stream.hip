@@ -1,0 +1,108 @@
+// Streaming spotting (gfx950): the kernels of an apd_spot_stream session.  apd_spot's free-start table, entered and left in
+// mid-stream: column j of the table depends on column j - 1 and on nothing else, so a session that keeps rows 1 .. n of the last
+// pushed column (value and start) in HBM continues the very same table with the next chunk, and the curves of the pushes, one after
+// the other, are the bits of apd_spot on the whole stream (include/apd.h, "streaming spotting").
+//
+// The sweep is spot_sweep (dtw_spot_sweep.h) with CARRY = true -- one text with apd_spot for the lane mapping, the macro-step and
+// the arithmetic.  What a push adds around it is here: where the pair's chunk, carried column and curves lie.  The query rows come
+// from the templates' batch, the stream columns from the session's staging buffer (the chunk in the resident layout), the carried
+// column from one half of the state buffer and the new one goes to the other half (the per-channel parity word says which).
+#include <cstdio>
+#include <cstdlib>
+
+#include "dtw_spot_sweep.h"
+
+namespace apd {
+
+template <int RT, int D>
+__global__ __launch_bounds__(64) void dtw_spot_stream(const SpotStreamLaunch S)
+{
+    const SpotStreamPair Q = S.d_pairs[blockIdx.x];
+    const uint32_t first = S.d_push[Q.channel], m = S.d_push[Q.channel + 1] - first;
+    if (m == 0) return;                                                     // nothing pushed on this channel: state, best and parity stay
+    const uint32_t base = S.d_push[S.n_channels + 1 + Q.channel];
+    const uint32_t parity = S.d_push[2 * S.n_channels + 1 + Q.channel] & 1u;
+    SpotLaunch L{};
+    L.d_frames = S.d_frames; L.d_seq_off = S.d_seq_off; L.dim = S.dim; L.dpad = S.dpad;
+    L.ins = S.ins; L.del = S.del; L.mat = S.mat;
+    L.d_cost = S.d_cost; L.d_start = S.d_start; L.d_best = S.d_best;
+    SpotPair P{};
+    P.px = Q.px; P.out = Q.out;
+    // pair p = channel n_queries + q owns m entries behind those of the pairs before it
+    P.curve_off = (uint64_t)S.n_queries * first + (uint64_t)(Q.out - Q.channel * S.n_queries) * m;
+    const uint64_t column = (uint64_t)Q.rows * 64;                          // floats of a pair's values; its starts lie behind them
+    float *in = S.d_state + parity * S.state_half + Q.state_off, *out = S.d_state + (parity ^ 1u) * S.state_half + Q.state_off;
+    SpotCarry C;
+    C.y = S.d_stage + (uint64_t)first * S.dpad;
+    C.m = m; C.base = base;
+    C.in_v = in; C.in_s = reinterpret_cast<const uint32_t *>(in + column);
+    C.out_v = out; C.out_s = reinterpret_cast<uint32_t *>(out + column);
+    spot_sweep<RT, D, false, true>(L, P, SpotRecord{}, C);
+}
+
+// A fresh table for the pairs of `channel` (0xFFFFFFFF: every channel): column 0 (+INF / 0) in both halves of the state, best none.
+__global__ __launch_bounds__(64) void spot_stream_reset_kernel(const SpotStreamLaunch S, uint32_t channel)
+{
+    const SpotStreamPair Q = S.d_pairs[blockIdx.x];
+    if (channel != 0xFFFFFFFFu && Q.channel != channel) return;
+    const uint32_t column = Q.rows * 64u;
+    for (uint32_t half = 0; half < 2; ++half) {
+        float *v = S.d_state + half * S.state_half + Q.state_off;
+        uint32_t *s = reinterpret_cast<uint32_t *>(v + column);
+        for (uint32_t e = threadIdx.x; e < column; e += 64) { v[e] = APD_INF; s[e] = 0u; }
+    }
+    if (threadIdx.x == 0) {
+        apd_spot_best b;
+        b.end = 0u; b.start = 0u; b.cost = APD_INF; b.score = APD_INF;
+        S.d_best[Q.out] = b;
+    }
+}
+
+namespace {
+
+template <int RT, int D>
+hipError_t launch_spot_stream_as(const SpotStreamLaunch &S, uint32_t r_max, hipStream_t stream)
+{
+    const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
+    spot_debug_line("stream", RT, D, S.n_pairs, r_max, lds_bytes);
+    if (lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_spot_stream<RT, D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((dtw_spot_stream<RT, D>), dim3(S.n_pairs), dim3(64), lds_bytes, stream, S);
+    return hipGetLastError();
+}
+
+template <int D>
+hipError_t launch_spot_stream_rows(const SpotStreamLaunch &S, uint32_t rt, uint32_t r_max, hipStream_t stream)
+{
+    switch (rt) {
+        case 1: return launch_spot_stream_as<1, D>(S, r_max, stream);
+        case 2: return launch_spot_stream_as<2, D>(S, r_max, stream);
+        case 3: return launch_spot_stream_as<3, D>(S, r_max, stream);
+        case 4: return launch_spot_stream_as<4, D>(S, r_max, stream);
+        default: return launch_spot_stream_as<0, D>(S, r_max, stream);
+    }
+}
+
+}  // namespace
+
+// The pairs of S all belong to one class (spot_row_class), as for launch_spot.
+hipError_t launch_spot_stream(const SpotStreamLaunch &S, uint32_t rt, uint32_t r_max, hipStream_t stream)
+{
+    if (S.n_pairs == 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    const bool typed = with_kernel_dim(S.dim, [&](auto d) { e = launch_spot_stream_rows<decltype(d)::value>(S, rt, r_max, stream); });
+    if (!typed) e = launch_spot_stream_as<0, 0>(S, r_max, stream);       // any other dimension: frames re-read per cell, column in LDS
+    return e;
+}
+
+hipError_t launch_spot_stream_reset(const SpotStreamLaunch &S, uint32_t channel, hipStream_t stream)
+{
+    if (S.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(spot_stream_reset_kernel, dim3(S.n_pairs), dim3(64), 0, stream, S, channel);
+    return hipGetLastError();
+}
+
+}  // namespace apd

@@ -2,7 +2,9 @@
 // apd_spot_paths (dtw_spot_path.hip, REC = true): ONE text for the lane mapping, the macro-step and the arithmetic, so that the
 // branches the second records are the branches of the very table the first reports.  What REC adds is compiled out of apd_spot's
 // instantiations (`if constexpr`): the same instruction mix, no scratch, registers within 2 of what they were and the same measured
-// speed as before this header existed.
+// speed as before this header existed.  The streaming session (dtw_spot_stream.hip, CARRY = true) enters the
+// same table behind any column and leaves it for the next chunk; what CARRY adds is compiled out of the other two likewise
+// (DESIGN.md section 4.13).
 //
 // One wavefront per (query, stream) pair.  Rows go on lanes, the stream flows through: lane l owns the R = ceil(n / 64) query rows
 // l R + 1 .. l R + R, macro-step tau gives it stream column j = tau - l + 1, and m + (lane of row n) macro-steps cover the pair.
@@ -107,18 +109,39 @@ struct SpotRecord {
     uint32_t max_end;
 };
 
-template <int RT, int D, bool REC>
-__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec)
+// What the streaming sweep (CARRY) is given for its pair: the table is entered behind absolute column `base` and left behind column
+// base + m.  The stream side is the chunk alone -- m >= 1 frames at y in the resident layout, L's frames and offsets serve the
+// query only and P.py is not read -- and the column the table was left in last time comes from in_v / in_s, laid out [r][lane] like
+// the LDS column: T[i][base] and S[i][base] of the lane's rows, +INF / 0 for column 0 and for rows beyond n.  Every lane with a
+// live row stores its column base + m to out_v / out_s behind the loop.  The session keeps in and out apart (two buffers taking
+// turns), so that nothing depends on the order in which the lanes of a wavefront read the old column and write the new one.
+// The running best starts from L.d_best[P.out] instead of +INF, and starts and ends are absolute columns.
+struct SpotCarry {
+    const float *y;
+    uint32_t m;
+    uint32_t base;
+    const float *in_v;
+    const uint32_t *in_s;
+    float *out_v;
+    uint32_t *out_s;
+};
+
+template <int RT, int D, bool REC, bool CARRY = false>
+__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec, const SpotCarry carry = SpotCarry{})
 {
     static_assert(RT == 0 || D > 0, "rows in registers need the frame dimension at compile time");
+    static_assert(!(REC && CARRY), "a carried table has no column 1 to record from");
     extern __shared__ __attribute__((aligned(16))) float spot_column[];   // RT == 0: [r][lane] values, then [r][lane] starts
     constexpr int DN = D > 0 ? ((D + 4) & ~3) : 4;                          // floats of a resident frame
     const int lane = threadIdx.x;
-    const uint32_t ox = L.d_seq_off[P.px], oy = L.d_seq_off[P.py];
+    uint32_t ox = L.d_seq_off[P.px], oy = 0u;
+    if constexpr (!CARRY) oy = L.d_seq_off[P.py];
     const int n = (int)(L.d_seq_off[P.px + 1] - ox) - 2;                    // <= kSpotMaxQuery
-    const uint32_t m = REC ? rec.max_end : L.d_seq_off[P.py + 1] - oy - 2;  // REC: column j depends on columns <= j only
+    uint32_t m;
+    if constexpr (CARRY) m = carry.m;
+    else m = REC ? rec.max_end : L.d_seq_off[P.py + 1] - oy - 2;            // REC: column j depends on columns <= j only
     const float *X = L.d_frames + (uint64_t)ox * L.dpad;
-    const float *Y = L.d_frames + (uint64_t)oy * L.dpad;
+    const float *Y = CARRY ? carry.y : L.d_frames + (uint64_t)oy * L.dpad;
     const float ins = L.ins, del = L.del, mat = L.mat;
     const int R = RT > 0 ? RT : (n + 63) / 64;
     const int row0 = lane * R;                                              // 0-based first query row of the lane
@@ -135,14 +158,14 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
     if constexpr (RT > 0) {
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
-            pv[r] = APD_INF;
-            ps[r] = 0u;
+            pv[r] = CARRY ? carry.in_v[r * 64 + lane] : APD_INF;
+            ps[r] = CARRY ? carry.in_s[r * 64 + lane] : 0u;
             spot_load_frame<DN>(xr[r], X + (uint64_t)min(row0 + r, n - 1) * L.dpad);
         }
     } else {
         for (int r = 0; r < R; ++r) {
-            spot_column[r * 64 + lane] = APD_INF;
-            col_start[r * 64 + lane] = 0u;
+            spot_column[r * 64 + lane] = CARRY ? carry.in_v[r * 64 + lane] : APD_INF;
+            col_start[r * 64 + lane] = CARRY ? carry.in_s[r * 64 + lane] : 0u;
         }
     }
 
@@ -165,11 +188,25 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
     uint32_t last_s = 0u;
     [[maybe_unused]] uint32_t best_end = 0u, best_start = 0u;
     [[maybe_unused]] float best_cost = APD_INF, best_score = APD_INF;
+    if constexpr (CARRY) {
+        // what the lane above takes as its MATCH predecessor at its first live step: this lane's last row of the carried column.
+        // A waiting lane hands it on unchanged (below); lane 0 never waits, so it starts out with it.
+        if constexpr (RT > 0) { last = pv[RT - 1]; last_s = ps[RT - 1]; }
+        else { last = spot_column[(R - 1) * 64 + lane]; last_s = col_start[(R - 1) * 64 + lane]; }
+        const apd_spot_best b = L.d_best[P.out];
+        best_end = b.end; best_start = b.start; best_cost = b.cost; best_score = b.score;
+    }
     const uint64_t total = (uint64_t)m + (uint64_t)lane_n;
     // one macro-step: yv holds column j's frame, yn receives the next column's while this one is computed
     auto macro_step = [&](const float (&yv)[DN], float (&yn)[DN]) {
         const uint32_t j = jm1 + 1u;
         const bool column_live = jm1 < m;
+        // CARRY: the absolute column.  Outside its columns 1 .. m a lane keeps its column instead of the +INF of a dead cell: while it
+        // waits for column 1 (jm1 = -lane .. -1 has wrapped) that is the carried column, once it has drained it is column m, which
+        // goes to the state behind the loop.  No live cell reads a drained lane: the lane above takes its INSERT and MATCH
+        // predecessors from this lane's live steps only.
+        uint32_t ja = j;
+        if constexpr (CARRY) ja = carry.base + j;
         if constexpr (D > 0) spot_load_frame<DN>(yn, Y + (uint64_t)min(jm1 + 1u, m - 1) * L.dpad);
         const float4 *yb = reinterpret_cast<const float4 *>(Y + (uint64_t)min(jm1, m - 1) * L.dpad);
         // REC: where this column's branch words go, if it lies in an interval
@@ -186,11 +223,11 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         // T[row0][j] from the lower lane (lane 0: row 0 of the table, value 0, start j)
         float up = from_lower_lane(last, 0.0f);
         uint32_t up_s = from_lower_lane_u32(last_s, 0u);
-        up_s = lane == 0 ? j : up_s;
+        up_s = lane == 0 ? ja : up_s;
         const float in_cur = up;
         const uint32_t in_cur_s = up_s;
         float diag = in_prev;
-        uint32_t diag_s = lane == 0 ? j : in_prev_s;
+        uint32_t diag_s = lane == 0 ? ja : in_prev_s;
         float cap_v = APD_INF;
         uint32_t cap_s = 0u;
         if constexpr (RT > 0) {
@@ -216,8 +253,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 const uint32_t left_s = ps[r];
                 const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, d[r], del, ins, mat);
                 const bool live = column_live & (r < rows_live);
-                const float v = live ? node.value : APD_INF;
-                const uint32_t s = live ? node.start : 0u;
+                float v = live ? node.value : APD_INF;
+                uint32_t s = live ? node.start : 0u;
+                if constexpr (CARRY) { v = column_live ? v : left; s = column_live ? s : left_s; }
                 diag = left; diag_s = left_s;                               // (i, j-1) is the next row's MATCH predecessor
                 pv[r] = v; ps[r] = s;
                 up = v; up_s = s;
@@ -240,8 +278,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 const uint32_t left_s = col_start[r * 64 + lane];
                 const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, dist, del, ins, mat);
                 const bool live = column_live & (r < rows_live);
-                const float v = live ? node.value : APD_INF;
-                const uint32_t s = live ? node.start : 0u;
+                float v = live ? node.value : APD_INF;
+                uint32_t s = live ? node.start : 0u;
+                if constexpr (CARRY) { v = column_live ? v : left; s = column_live ? s : left_s; }
                 diag = left; diag_s = left_s;
                 spot_column[r * 64 + lane] = v;
                 col_start[r * 64 + lane] = s;
@@ -267,9 +306,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 }
             } else {
                 if (curves) { cost[jm1] = cap_v; start[jm1] = cap_s; }
-                const uint32_t window = j - cap_s + 1u;                     // frames of y the alignment covers
+                const uint32_t window = ja - cap_s + 1u;                    // frames of y the alignment covers
                 const float score = cap_v / (float)((uint32_t)n + window);  // one f32 division (alignments.rs:121 with the window for m); < 2^32: kSpotMaxStream
-                if (score < best_score) { best_end = j; best_start = cap_s; best_cost = cap_v; best_score = score; }
+                if (score < best_score) { best_end = ja; best_start = cap_s; best_cost = cap_v; best_score = score; }
             }
         }
         ++jm1;
@@ -278,6 +317,21 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
     for (uint64_t tau = 0; tau < total; tau += 2) {
         macro_step(y_even, y_odd);
         macro_step(y_odd, y_even);
+    }
+    if constexpr (CARRY) {
+        // every lane with a live row holds column m of its rows now (dead rows: +INF / 0): the state the next chunk enters with.
+        // Lanes without a live row never hold anything but the +INF / 0 the reset wrote.
+        if (rows_live > 0) {
+            if constexpr (RT > 0) {
+#pragma unroll
+                for (int r = 0; r < RT; ++r) { carry.out_v[r * 64 + lane] = pv[r]; carry.out_s[r * 64 + lane] = ps[r]; }
+            } else {
+                for (int r = 0; r < R; ++r) {
+                    carry.out_v[r * 64 + lane] = spot_column[r * 64 + lane];
+                    carry.out_s[r * 64 + lane] = col_start[r * 64 + lane];
+                }
+            }
+        }
     }
     if constexpr (!REC) {
         if (lane == lane_n) {

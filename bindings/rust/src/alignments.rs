@@ -151,6 +151,82 @@ pub fn spot(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery
     best
 }
 
+/// Not in the reference: a streaming spotting session on the first device of APD_DEVICES (apd_spot_stream_*): every template against
+/// `channels` streams that arrive in chunks.  Pair p = channel * templates.len() + t; the curves of the pushes, one after the other,
+/// are apd_spot's curves of the whole stream, bit for bit, whatever the chunking.  Owns its context and the templates' batch.
+pub struct SpotStream {
+    ctx: *mut apd_context,
+    batch: *mut apd_batch,
+    handle: *mut apd_spot_stream,
+    dim: u32,
+    n_pairs: usize,
+    channels: usize,
+}
+
+impl SpotStream {
+    pub fn new(templates: &[NDSequence], params: &Discovery, channels: usize) -> SpotStream {
+        assert!(!templates.is_empty() && channels > 0);
+        let cfg = apd_align_config {
+            warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+            deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+        };
+        let mut offsets = vec![0u64; templates.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in templates.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        let dim = templates[0].n_bins as u32;
+        let queries: Vec<u32> = (0..templates.len() as u32).collect();
+        let mut s = SpotStream { ctx: std::ptr::null_mut(), batch: std::ptr::null_mut(), handle: std::ptr::null_mut(), dim,
+                                 n_pairs: templates.len() * channels, channels };
+        unsafe {
+            check(apd_create(devices()[0], &mut s.ctx));
+            check(apd_batch_create(s.ctx, frames.as_ptr(), offsets.as_ptr(), templates.len() as u32, dim, 0, &mut s.batch));
+            check(apd_spot_stream_create(s.ctx, s.batch, &cfg, queries.as_ptr(), queries.len() as u32, channels as u32, &mut s.handle));
+        }
+        s
+    }
+    /// chunks[k]: channel k's frames, [m_k][dim] packed, m_k = 0 allowed.  Returns (cost, start, curve_off, best): pair p owns
+    /// cost / start [curve_off[p] .. curve_off[p + 1]); best is the running best per pair, columns absolute.
+    pub fn push(&mut self, chunks: &[&[f32]]) -> (Vec<f32>, Vec<u32>, Vec<u64>, Vec<apd_spot_best>) {
+        assert_eq!(chunks.len(), self.channels);
+        let mut chunk_off = vec![0u64; self.channels + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (k, c) in chunks.iter().enumerate() {
+            chunk_off[k + 1] = chunk_off[k] + (c.len() / self.dim as usize) as u64;
+            frames.extend_from_slice(c);
+        }
+        let entries = (chunk_off[self.channels] as usize * (self.n_pairs / self.channels)).max(1);
+        let (mut cost, mut start) = (vec![0f32; entries], vec![0u32; entries]);
+        let mut curve_off = vec![0u64; self.n_pairs + 1];
+        let mut best = vec![apd_spot_best::default(); self.n_pairs];
+        unsafe {
+            check(apd_spot_stream_push(self.ctx, self.handle, frames.as_ptr(), chunk_off.as_ptr(), self.dim, 0, cost.as_mut_ptr(), start.as_mut_ptr(), entries as u64, curve_off.as_mut_ptr(), best.as_mut_ptr()));
+        }
+        (cost, start, curve_off, best)
+    }
+    /// channel None: every channel.  The channel's next frame is absolute column first_column + 1.
+    pub fn reset(&mut self, channel: Option<u32>, first_column: u64) {
+        unsafe { check(apd_spot_stream_reset(self.ctx, self.handle, channel.unwrap_or(0xFFFF_FFFF), first_column)); }
+    }
+    pub fn columns(&self, channel: u32) -> u64 {
+        let mut c: u64 = 0;
+        unsafe { check(apd_spot_stream_columns(self.handle, channel, &mut c)); }
+        c
+    }
+}
+
+impl Drop for SpotStream {
+    fn drop(&mut self) {
+        unsafe {
+            if !self.handle.is_null() { apd_spot_stream_destroy(self.handle); }
+            if !self.batch.is_null() { apd_batch_destroy(self.batch); }
+            if !self.ctx.is_null() { apd_destroy(self.ctx); }
+        }
+    }
+}
+
 /// Not in the reference: the warping paths of spotted windows (apd_batch_join + apd_spot_paths) on the first device of APD_DEVICES.
 /// windows[k]: x a template number, y a stream number (NOT offset by templates.len(): that is done here), end and start as spot()
 /// or spot_hits() reported them.  Returns per window (steps origin first with (n, end) last, found_start, score); the steps are

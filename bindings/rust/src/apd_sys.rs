@@ -6,6 +6,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)] pub struct apd_context { _p: [u8; 0] }
 #[repr(C)] pub struct apd_batch { _p: [u8; 0] }
+#[repr(C)] pub struct apd_spot_stream { _p: [u8; 0] }
 #[repr(C)] pub struct apd_comm { _p: [u8; 0] }
 #[repr(C)] pub struct apd_multi { _p: [u8; 0] }
 #[repr(C)] pub struct apd_multi_batch { _p: [u8; 0] }
@@ -207,6 +208,15 @@ extern "C" {
     pub fn apd_spot_paths(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, windows: *const apd_spot_window,
                           n_windows: u64, steps: *mut apd_path_step, capacity: u64, step_off: *mut u64, path_len: *mut u32,
                           found_start: *mut u32, scores: *mut f32) -> c_int;
+    // streaming spotting
+    pub fn apd_spot_stream_create(ctx: *mut apd_context, templates: *const apd_batch, cfg: *const apd_align_config, queries: *const u32,
+                                  n_queries: u32, n_channels: u32, stream: *mut *mut apd_spot_stream) -> c_int;
+    pub fn apd_spot_stream_destroy(stream: *mut apd_spot_stream) -> c_int;
+    pub fn apd_spot_stream_reset(ctx: *mut apd_context, stream: *mut apd_spot_stream, channel: u32, first_column: u64) -> c_int;
+    pub fn apd_spot_stream_columns(stream: *const apd_spot_stream, channel: u32, columns: *mut u64) -> c_int;
+    pub fn apd_spot_stream_push(ctx: *mut apd_context, stream: *mut apd_spot_stream, frames: *const f32, chunk_off: *const u64, dim: u32,
+                                frames_on_device: c_int, cost: *mut f32, start: *mut u32, capacity: u64, curve_off: *mut u64,
+                                best: *mut apd_spot_best) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

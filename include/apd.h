@@ -427,7 +427,8 @@ typedef struct apd_spot_best {
  * of more than 16 384 frames (or a stream of 2^32 - 65 536 or more) APD_ERR_UNSUPPORTED, each before anything is launched.  Follows
  * apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the kernels of the call (all chunks).
  * One wavefront sweeps one pair, whatever its size: the parallelism is pairs (templates x recordings).  A single long pair runs
- * on one wavefront; cutting a free-start DP along the stream is not exact and is not attempted.
+ * on one wavefront; cutting a free-start DP along the stream into independent pieces is not exact and is not attempted
+ * (sequential chunks that carry the last column are: "streaming spotting" below).
  * Workspace: 8 bytes per curve entry on the device; a long list is cut into chunks that keep it under 1 GiB
  * (APD_SPOT_WORKSPACE_BYTES overrides the cap: tests only), results identical. */
 int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
@@ -480,6 +481,57 @@ uint64_t apd_spot_path_bound(uint64_t n, uint64_t end, uint64_t start);
 int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const apd_spot_window *windows,
                    uint64_t n_windows, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
                    uint32_t *found_start, float *scores);
+
+/* ---- streaming spotting: a recording that arrives in chunks, the table's last column kept on the device --------------------------
+ * apd_spot needs the whole recording resident.  Spotting each piece on its own is wrong, not merely approximate (the tie rule makes
+ * the cells of a window depend on the columns before it, see above), but SEQUENTIAL chunks are exact: column j of T and S depends
+ * on column j - 1 and on nothing else.  A session keeps, for every pair, rows 1 .. n of the last pushed column (value and start)
+ * and the running best on the device, and a push continues that very table.
+ * The promise: take any split of a stream y into chunks, zero-length ones included, and concatenate the curves of the pushes in
+ * order: the result is bit-identical to apd_spot of (x, y) in a joined batch; best after any push is apd_spot's best of the prefix
+ * pushed so far, bit for bit.  With first_column = b every start and end is shifted by b; costs and scores keep their bits.
+ * templates: any resident batch, plain or joined; it must outlive the session.  queries (n_queries of them, repeats allowed): the
+ *   caller's sequence numbers.  The session reads the batch's resident frames at every push: it follows apd_batch_refill, and a
+ *   refill in mid-stream continues the OLD table with the NEW rows (call apd_spot_stream_reset for a fresh one).  Of cfg only the
+ *   three penalties are read; there is no band.
+ * n_channels independent streams (microphones, files); pair p = channel * n_queries + q.  Device state per pair: 8 bytes per row
+ *   (rounded up to whole rows per lane) twice -- a push reads one copy and writes the other -- plus a 16-byte best.  A fresh or
+ *   reset channel holds column 0 of the table (+INF / 0) and best {0, 0, +INF, +INF}.
+ * Arithmetic: the literal one, always; apd_set_distance_mode is not read, no feature-range routing.  One wavefront per pair, as for
+ * apd_spot: the parallelism is templates x channels.  A chunk of m columns costs m + (lane of row n) macro-steps, so chunks much
+ * shorter than 64 columns pay mostly for filling the wavefront.
+ * Not offered: warping paths of windows found while streaming.  apd_spot_paths needs the table from column 1; keep the recording
+ * and ask it. */
+typedef struct apd_spot_stream apd_spot_stream;
+/* A query index >= the batch's sequence count, n_queries * n_channels == 0 or >= 2^24, or a batch of another context:
+ * APD_ERR_INVALID_ARG; an empty query APD_ERR_EMPTY_SEQUENCE; one of more than 16 384 frames APD_ERR_UNSUPPORTED.  Blocking. */
+int apd_spot_stream_create(apd_context *ctx, const apd_batch *templates, const apd_align_config *cfg, const uint32_t *queries,
+                           uint32_t n_queries, uint32_t n_channels, apd_spot_stream **stream);
+/* As for batches: apd_destroy releases the device side of a session still alive, and afterwards only this call is legal on it. */
+int apd_spot_stream_destroy(apd_spot_stream *stream);
+/* channel (0xFFFFFFFF: every channel) starts over: column 0, no best, and its next frame is absolute column first_column + 1.
+ * channel >= n_channels: APD_ERR_INVALID_ARG; first_column >= 2^32 - 65 536: APD_ERR_UNSUPPORTED.  Blocking. */
+int apd_spot_stream_reset(apd_context *ctx, apd_spot_stream *stream, uint32_t channel, uint64_t first_column);
+/* *columns = absolute column of the channel's last pushed frame: first_column + frames pushed since the reset.  Host only. */
+int apd_spot_stream_columns(const apd_spot_stream *stream, uint32_t channel, uint64_t *columns);
+/* frames: packed [chunk_off[n_channels]][dim] f32, host or (frames_on_device != 0) device -- device frames never visit the host;
+ *   channel k's chunk is frames[chunk_off[k] .. chunk_off[k+1]), chunk_off[0] = 0.  dim must be the frame dimension the templates
+ *   were created with.  Lengths may differ per channel and may be 0: a no-op for that channel.
+ * curve_off (n_pairs + 1, always written, no GPU work needed for it): pair p owns as many entries as its channel's chunk has frames.
+ * cost[e], start[e]: T[n][J] and S[n][J] of the chunk's columns, J and S absolute (J = apd_spot_stream_columns before the push + 1,
+ *   + 2, ...).  best[p]: apd_spot's scan (strict <: the smallest end wins, a NaN is never kept) continued over everything pushed
+ *   since the reset, end and start absolute.
+ * cost and start both NULL: best only, no curve is stored anywhere; exactly one of them NULL, or capacity (in entries) <
+ * curve_off[n_pairs]: APD_ERR_INVALID_ARG; best may be NULL only if the curves are given; all three NULL: sizes only, the state is
+ * not advanced.
+ * Errors, each before anything is launched and with the state untouched: a dim mismatch, a foreign context, descending chunk_off or
+ * 2^32 - 2 frames or more in one push: APD_ERR_INVALID_ARG; a push that would take a channel's absolute column to 2^32 - 65 536 or
+ * beyond: APD_ERR_UNSUPPORTED.  After APD_ERR_HIP / APD_ERR_OOM the state is undefined until apd_spot_stream_reset.
+ * Blocking; one synchronisation per push, no allocation once the session's buffers have grown to the largest push seen.  With
+ * apd_set_timing on, apd_last_kernel_ms covers the push's kernels: the repack of the chunk and one sweep per kernel class. */
+int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, const float *frames, const uint64_t *chunk_off, uint32_t dim,
+                         int frames_on_device, float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off,
+                         apd_spot_best *best);
 
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */

@@ -209,6 +209,69 @@ class Batch {
     apd_batch *handle_ = nullptr;
 };
 
+// Not in the reference: a streaming spotting session (apd.h, "streaming spotting"), made by AlignmentWorkers::spot_stream.  Pair p =
+// channel * n_queries + q; the curves of the pushes, one after the other, are spot()'s curves of the whole stream, bit for bit.
+class SpotStream {
+  public:
+    SpotStream(Context &ctx, const apd_batch *templates, uint32_t dim, const std::vector<uint32_t> &queries, const Discovery &params,
+               uint32_t channels)
+        : ctx_(ctx), dim_(dim), n_queries_((uint32_t)queries.size()), channels_(channels)
+    {
+        const apd_align_config c = params.config();
+        check(apd_spot_stream_create(ctx_.get(), templates, &c, queries.data(), n_queries_, channels_, &handle_), ctx_.get());
+    }
+    ~SpotStream() { if (handle_) apd_spot_stream_destroy(handle_); }
+    SpotStream(SpotStream &&o) noexcept : ctx_(o.ctx_), handle_(o.handle_), dim_(o.dim_), n_queries_(o.n_queries_), channels_(o.channels_) { o.handle_ = nullptr; }
+    SpotStream(const SpotStream &) = delete;
+    SpotStream &operator=(const SpotStream &) = delete;
+    // chunks[k]: channel k's frames, [m_k][dim] packed, m_k = 0 allowed.  cost / start: per pair, one entry per pushed column (left
+    // empty with with_curves = false); best: the running best per pair, columns absolute.
+    struct Pushed { std::vector<std::vector<float>> cost; std::vector<std::vector<uint32_t>> start; std::vector<apd_spot_best> best; };
+    Pushed push(const std::vector<std::vector<float>> &chunks, bool with_curves = true)
+    {
+        if (chunks.size() != channels_) throw Error(APD_ERR_INVALID_ARG, "one chunk per channel");
+        std::vector<uint64_t> chunk_off(channels_ + 1, 0);
+        std::vector<float> frames;
+        for (uint32_t k = 0; k < channels_; ++k) {
+            chunk_off[k + 1] = chunk_off[k] + chunks[k].size() / dim_;
+            frames.insert(frames.end(), chunks[k].begin(), chunks[k].end());
+        }
+        const std::size_t n_pairs = (std::size_t)n_queries_ * channels_;
+        std::vector<uint64_t> off(n_pairs + 1, 0);
+        Pushed out;
+        out.best.resize(n_pairs);
+        if (!with_curves) {
+            check(apd_spot_stream_push(ctx_.get(), handle_, frames.data(), chunk_off.data(), dim_, 0, nullptr, nullptr, 0, off.data(),
+                                       out.best.data()), ctx_.get());
+            return out;
+        }
+        std::vector<float> cost(std::max<uint64_t>(chunk_off.back() * n_queries_, 1));
+        std::vector<uint32_t> start(cost.size());
+        check(apd_spot_stream_push(ctx_.get(), handle_, frames.data(), chunk_off.data(), dim_, 0, cost.data(), start.data(), cost.size(),
+                                   off.data(), out.best.data()), ctx_.get());
+        for (std::size_t p = 0; p < n_pairs; ++p) {
+            out.cost.emplace_back(cost.begin() + off[p], cost.begin() + off[p + 1]);
+            out.start.emplace_back(start.begin() + off[p], start.begin() + off[p + 1]);
+        }
+        return out;
+    }
+    static constexpr uint32_t kAllChannels = 0xFFFFFFFFu;
+    void reset(uint32_t channel = kAllChannels, uint64_t first_column = 0)
+    {
+        check(apd_spot_stream_reset(ctx_.get(), handle_, channel, first_column), ctx_.get());
+    }
+    uint64_t columns(uint32_t channel) const
+    {
+        uint64_t c = 0;
+        check(apd_spot_stream_columns(handle_, channel, &c));
+        return c;
+    }
+  private:
+    Context &ctx_;
+    apd_spot_stream *handle_ = nullptr;
+    uint32_t dim_ = 1, n_queries_ = 0, channels_ = 1;
+};
+
 // alignments.rs:11-68
 class AlignmentWorkers {
   public:
@@ -320,6 +383,12 @@ class AlignmentWorkers {
                              out.scores.data()), ctx_.get());
         for (std::size_t p = 0; p < k; ++p) out.steps.emplace_back(steps.begin() + off[p], steps.begin() + off[p] + len[p]);
         return out;
+    }
+    // Not in the reference: streaming spotting (apd.h, "streaming spotting").  queries: this object's sequence numbers, repeats
+    // allowed; this object must outlive the session.
+    SpotStream spot_stream(const std::vector<uint32_t> &queries, const Discovery &params, uint32_t channels = 1)
+    {
+        return SpotStream(ctx_, batch_, dim, queries, params, channels);
     }
     // Not in the reference: DTW barycenter averaging (apd.h, "cluster prototypes") of the sets of this object's sequence numbers in
     // `sets`; init[k]: the sequence whose frames start set k's barycenter (usually AgglomerativeClustering::medoids' choice).
