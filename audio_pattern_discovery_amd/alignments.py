@@ -325,13 +325,14 @@ class AlignmentWorkers:
                 batch.close()
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_windows)], found, scores
 
-    def spot_stream(self, queries, params, channels=1):
+    def spot_stream(self, queries, params, channels=1, history=0):
         """A streaming spotting session (include/apd.h, "streaming spotting"): the sequences `queries` of this object (repeats allowed)
-        as templates against `channels` independent streams that arrive in chunks; params: Discovery (penalties only).  This object
-        must stay open as long as the session: SpotStream."""
+        as templates against `channels` independent streams that arrive in chunks; params: Discovery (penalties only).  history: the
+        columns the session keeps for SpotStream.paths() (0: none, SpotStream.keep() changes it).  This object must stay open as
+        long as the session: SpotStream."""
         if self._multi is not None:
             raise ValueError("spot_stream() runs on one context: make the AlignmentWorkers without `devices`")
-        return SpotStream(self, queries, params, channels)
+        return SpotStream(self, queries, params, channels, history)
 
     def barycenters(self, sets, params, init=None, iterations=10, on_device=False):
         """DTW barycenter averaging (include/apd.h, "cluster prototypes") of the sets of this object's sequence numbers in `sets`
@@ -407,7 +408,7 @@ class SpotStream:
 
     ALL = 0xFFFFFFFF
 
-    def __init__(self, workers, queries, params, channels=1):
+    def __init__(self, workers, queries, params, channels=1, history=0):
         self._workers = workers                                   # keeps the templates' batch alive
         self.ctx = workers.ctx
         self.dim = int(workers._dim)
@@ -419,6 +420,39 @@ class SpotStream:
         _lib.check(_lib.lib().apd_spot_stream_create(self.ctx.handle, workers._batch.handle, C.byref(cfg),
                                                      self.queries.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.queries), self.channels,
                                                      C.byref(self.handle)), self.ctx.handle)
+        if history:
+            self.keep(history)
+
+    def keep(self, history):
+        """From now on the session keeps its last `history` pushed columns of every channel (0: none): apd_spot_stream_keep.  The
+        history starts empty behind each channel's current column; the table, the curves and the bests are not touched."""
+        _lib.check(_lib.lib().apd_spot_stream_keep(self.ctx.handle, self.handle, int(history)), self.ctx.handle)
+
+    def history(self, channel):
+        """(first, last): the absolute columns of `channel` whose cells are kept; first == last + 1: none."""
+        first, last = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().apd_spot_stream_history(self.handle, int(channel), C.byref(first), C.byref(last)))
+        return int(first.value), int(last.value)
+
+    def paths(self, windows):
+        """Warping paths of windows found while streaming (include/apd.h, "a kept history of columns"): `windows` a SPOT_WINDOW array
+        -- x an index into the session's queries, y a channel, end and start absolute columns as push() reports them.  Returns what
+        AlignmentWorkers.spot_paths returns: (list of PATH_STEP arrays in input order -- empty for a window that has aged out of the
+        history, for a {0, 0} record and for a start that is not the table's --, found_start, scores): apd_spot_stream_paths."""
+        win = np.ascontiguousarray(windows, dtype=SPOT_WINDOW)
+        n_windows = len(win)
+        L = _lib.lib()
+        off = np.zeros(n_windows + 1, dtype=np.uint64)
+        lens = np.zeros(n_windows, dtype=np.uint32)
+        found = np.zeros(n_windows, dtype=np.uint32)
+        scores = np.zeros(n_windows, dtype=np.float32)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        head = (self.ctx.handle, self.handle, win.ctypes.data_as(C.POINTER(_lib.SpotWindow)), n_windows)
+        _lib.check(L.apd_spot_stream_paths(*head, None, 0, off.ctypes.data_as(u64p), None, None, None), self.ctx.handle)       # sizes
+        steps = np.zeros(max(int(off[-1]), 1), dtype=PATH_STEP)
+        _lib.check(L.apd_spot_stream_paths(*head, steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), off.ctypes.data_as(u64p),
+                                           lens.ctypes.data_as(u32p), found.ctypes.data_as(u32p), scores.ctypes.data_as(f32p)), self.ctx.handle)
+        return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_windows)], found, scores
 
     def push(self, chunks, curves=True, on_device=False):
         """One chunk per channel: a list of (frames, dim) float32 arrays, zero frames allowed; with on_device=True the pair

@@ -1630,6 +1630,30 @@ struct apd_spot_stream : apd::ContextChild {
     apd::DeviceBuf d_raw;               // host chunks on their way to the repack kernel
     apd::DeviceBuf d_stage;             // the chunks in the resident layout, two sentinel frames behind them
     apd::DeviceBuf d_curves;            // [cost | start]
+    // the history (apd_spot_stream_keep; kernels: dtw_spot_stream_rec.hip): the last `history` columns of every pair's branches and
+    // row-n curve and of every channel's frames, in rings; 0: none kept, and a push runs the kernels it ran before there was one
+    uint32_t history = 0;
+    std::vector<uint64_t> origin;       // per channel: the column behind which the history starts (cells of columns > origin are kept)
+    std::vector<uint32_t> q_len, q_pos; // per query: frames, resident position
+    std::vector<uint32_t> wpl_before;   // per pair p: the sum of ceil(R / 16) over the pairs before it (and the total behind the last)
+    apd::DeviceBuf d_hist_dirs, d_hist_curves, d_hist_frames, d_hist_wpl;
+    SpotHistory rings() const
+    {
+        SpotHistory H{};
+        H.rows = history;
+        H.d_dirs = d_hist_dirs.as<uint32_t>(); H.d_wpl_before = d_hist_wpl.as<uint32_t>();
+        H.d_curve_v = d_hist_curves.as<float>();
+        H.d_curve_s = d_hist_curves.as<uint32_t>() + (size_t)n_pairs * history;
+        H.d_frames = d_hist_frames.as<float>();
+        return H;
+    }
+    // [first, last] of the channel's kept columns; first = last + 1: none
+    void kept(uint32_t channel, uint64_t *first, uint64_t *last) const
+    {
+        const uint64_t end = columns[channel], from_ring = end + 1 > history ? end + 1 - history : 0;
+        *last = end;
+        *first = history ? std::max(origin[channel] + 1, from_ring) : end + 1;
+    }
     // the staged chunks are ONE sequence to the repack kernel: [seq_off 2 | src_off 1 | unused 1 | flags 4 | norm maximum 1 | unused 3]
     static constexpr uint32_t kPadWords = 12;
     size_t push_words() const { return 3 * (size_t)n_channels + 1 + kPadWords; }
@@ -1648,6 +1672,7 @@ struct apd_spot_stream : apd::ContextChild {
     void release_device() override
     {
         d_pairs.reset(); d_state.reset(); d_best.reset(); d_push.reset(); d_raw.reset(); d_stage.reset(); d_curves.reset();
+        d_hist_dirs.reset(); d_hist_curves.reset(); d_hist_frames.reset(); d_hist_wpl.reset();
     }
 };
 
@@ -1679,7 +1704,11 @@ extern "C" int apd_spot_stream_create(apd_context *ctx, const apd_batch *templat
     s->ins = cfg->insertion_penalty; s->del = cfg->deletion_penalty; s->mat = cfg->match_penalty;
     s->columns.assign(n_channels, 0);
     s->parity.assign(n_channels, 0u);
+    s->origin.assign(n_channels, 0);
     s->h_push.assign(s->push_words(), 0u);
+    for (uint32_t q = 0; q < n_queries; ++q) { s->q_len.push_back(len_of(queries[q])); s->q_pos.push_back(pos[queries[q]]); }
+    s->wpl_before.assign(n_pairs + 1, 0u);
+    for (uint64_t p = 0; p < n_pairs; ++p) s->wpl_before[p + 1] = s->wpl_before[p] + (spot_rows_per_lane(s->q_len[p % n_queries]) + 15) / 16;
     // the descriptors, grouped by kernel class (one launch each per push); `out` keeps p = channel n_queries + q
     constexpr uint32_t kClasses = apd_spot_stream::kClasses;
     for (uint32_t q = 0; q < n_queries; ++q) {
@@ -1736,7 +1765,7 @@ extern "C" int apd_spot_stream_reset(apd_context *ctx, apd_spot_stream *stream, 
     HIP_TRY(ctx, launch_spot_stream_reset(stream->launch(), channel, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t k = 0; k < stream->n_channels; ++k)
-        if (all || k == channel) stream->columns[k] = first_column;       // either half holds column 0 now: the parity stays
+        if (all || k == channel) stream->columns[k] = stream->origin[k] = first_column;   // either half holds column 0 now: the parity stays; the history is empty
     return APD_OK;
 }
 
@@ -1810,10 +1839,13 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
         if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
         HIP_TRY(ctx, launch_pad(d_src, s->d_stage.as<float>(), d_pad, d_pad + 2, 1, total + 2, dim, t->dim, t->dpad, d_pad + 4,
                                 reinterpret_cast<float *>(d_pad + 8), ctx->stream));
+        SpotStreamRecLaunch A{S, s->rings()};
+        if (s->history) HIP_TRY(ctx, launch_spot_stream_frames(A, (uint32_t)total, ctx->stream));
         for (uint32_t c = 0; c < apd_spot_stream::kClasses; ++c) {
-            S.d_pairs = s->d_pairs.as<SpotStreamPair>() + s->class_first[c];
-            S.n_pairs = s->class_count[c];
-            HIP_TRY(ctx, launch_spot_stream(S, c, s->r_max, ctx->stream));
+            A.S.d_pairs = S.d_pairs = s->d_pairs.as<SpotStreamPair>() + s->class_first[c];
+            A.S.n_pairs = S.n_pairs = s->class_count[c];
+            if (s->history) HIP_TRY(ctx, launch_spot_stream_record(A, c, s->r_max, ctx->stream));
+            else HIP_TRY(ctx, launch_spot_stream(S, c, s->r_max, ctx->stream));
         }
         if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
         // the table has moved on, whatever the copies below do
@@ -1828,6 +1860,146 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
     }
     if (best) HIP_TRY(ctx, hipMemcpyAsync(best, S.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's, `frames` is free again
+    return APD_OK;
+}
+
+// ---- the history of a session: apd_spot_stream_keep / _history / _paths (include/apd.h; kernels: dtw_spot_stream_rec.hip)
+
+extern "C" int apd_spot_stream_keep(apd_context *ctx, apd_spot_stream *stream, uint32_t history_columns)
+{
+    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
+    apd_spot_stream *s = stream;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream history");
+    const uint64_t H = history_columns;
+    apd::DeviceBuf dirs, curves, frames;
+    if (H) {
+        // the new rings first: a refusal leaves the session with the ones it has
+        const uint64_t dir_bytes = (uint64_t)s->wpl_before[s->n_pairs] * H * 64 * sizeof(uint32_t);
+        const uint64_t curve_bytes = (uint64_t)s->n_pairs * H * 8, frame_bytes = (uint64_t)s->n_channels * H * s->templates->dpad * sizeof(float);
+        if (dirs.alloc((size_t)dir_bytes) != hipSuccess || curves.alloc((size_t)curve_bytes) != hipSuccess ||
+            frames.alloc((size_t)frame_bytes) != hipSuccess || (!s->d_hist_wpl.ptr && s->d_hist_wpl.alloc((size_t)s->n_pairs * sizeof(uint32_t)) != hipSuccess)) {
+            (void)hipGetLastError();
+            ctx->last_error = "apd_spot_stream_keep: no device memory for " + std::to_string(H) + " columns of history";
+            return APD_ERR_OOM;
+        }
+        // nothing reads a row before a push has written it; zeros all the same, so that no run depends on what the memory held
+        HIP_TRY(ctx, hipMemsetAsync(dirs.ptr, 0, (size_t)dir_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(curves.ptr, 0, (size_t)curve_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(frames.ptr, 0, (size_t)frame_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s->d_hist_wpl.ptr, s->wpl_before.data(), (size_t)s->n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    s->d_hist_dirs = std::move(dirs); s->d_hist_curves = std::move(curves); s->d_hist_frames = std::move(frames);
+    s->history = history_columns;
+    s->origin = s->columns;                                               // the history starts empty, behind every channel's current column
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_history(const apd_spot_stream *stream, uint32_t channel, uint64_t *first, uint64_t *last)
+{
+    if (!stream || !first || !last || channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
+    stream->kept(channel, first, last);
+    return APD_OK;
+}
+
+// The windows are taken in input order, a chunk at a time: as many as keep the steps under the workspace cap, at least one.  What
+// the rings no longer hold is decided here: a window whose end lies before the channel's first kept column never reaches the
+// device; one whose end is kept is given to the trace, which reads S[n][end] and walks only if that start is kept as well.
+// ws_spot_steps: [steps | windows (uploaded) | lengths | found | scores].
+extern "C" int apd_spot_stream_paths(apd_context *ctx, apd_spot_stream *stream, const apd_spot_window *windows, uint64_t n_windows,
+                                     apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
+                                     uint32_t *found_start, float *scores)
+{
+    if (!ctx || !stream || stream->ctx != ctx || !step_off || (n_windows && !windows)) return APD_ERR_INVALID_ARG;
+    const apd_spot_stream *s = stream;
+    const apd_batch *t = s->templates;
+    if (t->ctx != ctx) return APD_ERR_INVALID_ARG;
+    for (uint64_t p = 0; p < n_windows; ++p) {
+        const apd_spot_window &w = windows[p];
+        if (w.x >= s->n_queries || w.y >= s->n_channels) return APD_ERR_INVALID_ARG;
+        if (w.end > s->columns[w.y] || (w.end && w.start > w.end)) return APD_ERR_INVALID_ARG;
+    }
+    step_off[0] = 0;
+    for (uint64_t p = 0; p < n_windows; ++p)
+        step_off[p + 1] = step_off[p] + apd_spot_path_bound(s->q_len[windows[p].x], windows[p].end, windows[p].start);
+    if (!steps) return APD_OK;                                            // sizes only
+    if (capacity < step_off[n_windows] || (n_windows && !path_len)) return APD_ERR_INVALID_ARG;
+    if (!s->history) {
+        ctx->last_error = "apd_spot_stream_paths: the session keeps no history (apd_spot_stream_keep)";
+        return APD_ERR_UNSUPPORTED;
+    }
+    if (n_windows == 0) return APD_OK;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream path launch");
+    const uint64_t cap = spot_workspace_cap();
+    constexpr uint64_t kMaxWindowsPerLaunch = 1ull << 24;                 // 64 work-items per window, launches stay below 2^31
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    std::vector<uint64_t> live;                                           // the chunk's windows that reach the trace, input order
+    std::vector<SpotRingWindow> trace;
+    std::vector<uint32_t> h_len, h_found;
+    std::vector<float> h_scores;
+    bool first_launch = true;
+    for (uint64_t first = 0; first < n_windows;) {
+        uint64_t last = first;
+        while (last < n_windows && last - first < kMaxWindowsPerLaunch) {
+            if (last > first && (step_off[last + 1] - step_off[first]) * sizeof(apd_path_step) > cap) break;
+            ++last;
+        }
+        live.clear(); trace.clear();
+        for (uint64_t p = first; p < last; ++p) {
+            const apd_spot_window &w = windows[p];
+            uint64_t kept_first, kept_last;
+            s->kept(w.y, &kept_first, &kept_last);
+            if (step_off[p + 1] > step_off[p] && w.end >= kept_first) {
+                SpotRingWindow r{};
+                r.px = s->q_pos[w.x]; r.channel = w.y; r.pair = w.y * s->n_queries + w.x;
+                r.end = w.end; r.start = w.start; r.first = (uint32_t)kept_first;
+                r.step_off = step_off[p] - step_off[first];
+                live.push_back(p); trace.push_back(r);
+                continue;
+            }
+            path_len[p] = 0;                                              // no window, or its end has aged out: nothing to read
+            if (found_start) found_start[p] = 0;
+            if (scores) scores[p] = INFINITY;
+            std::memset(steps + step_off[p], 0, (size_t)(step_off[p + 1] - step_off[p]) * sizeof(apd_path_step));
+        }
+        if (live.empty()) { first = last; continue; }
+        const size_t nt = trace.size();
+        const size_t steps_bytes = (size_t)(step_off[last] - step_off[first]) * sizeof(apd_path_step);
+        const size_t upload_bytes = up16(nt * sizeof(SpotRingWindow));
+        const size_t o_len = upload_bytes, o_found = o_len + up16(nt * 4), o_scores = o_found + up16(nt * 4), side_bytes = o_scores + up16(nt * 4);
+        int rc = reserve_ws(ctx, ctx->ws_spot_steps, steps_bytes + side_bytes + 16);
+        if (rc) return rc;
+        char *base = ctx->ws_spot_steps.as<char>(), *side = base + steps_bytes;
+        SpotRingTraceLaunch L{};
+        L.d_frames = t->d_frames.as<float>(); L.d_seq_off = t->d_seq_off; L.dim = t->dim; L.dpad = t->dpad;
+        L.ins = s->ins; L.del = s->del; L.mat = s->mat;
+        L.H = s->rings();
+        L.d_windows = (const SpotRingWindow *)side; L.n_windows = (uint32_t)nt;
+        L.d_steps = (apd_path_step *)base;
+        L.d_len = (uint32_t *)(side + o_len); L.d_found = (uint32_t *)(side + o_found); L.d_scores = (float *)(side + o_scores);
+        HIP_TRY(ctx, hipMemcpyAsync(side, trace.data(), nt * sizeof(SpotRingWindow), hipMemcpyHostToDevice, ctx->stream));
+        // an aged-out window between two traced ones leaves slots of the chunk no trace owns: the device copy is zeroed whole
+        HIP_TRY(ctx, hipMemsetAsync(base, 0, steps_bytes, ctx->stream));
+        if (ctx->timing && first_launch) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        first_launch = false;
+        HIP_TRY(ctx, launch_spot_stream_trace(L, ctx->stream));
+        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }   // the last chunk's record stands
+        h_len.resize(nt); h_found.resize(nt); h_scores.resize(nt);
+        HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), L.d_len, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_found.data(), L.d_found, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), L.d_scores, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `trace`)
+        for (size_t k = 0; k < nt; ++k) {
+            const uint64_t p = live[k];
+            path_len[p] = h_len[k];
+            if (found_start) found_start[p] = h_found[k];
+            if (scores) scores[p] = h_scores[k];
+        }
+        first = last;
+    }
     return APD_OK;
 }
 

@@ -319,7 +319,8 @@ size_t spot_lds_bytes(uint32_t rows_per_lane);
 // Under APD_DEBUG_PLAN, one stderr line per launch of a spotting kernel, printed where the template arguments are chosen:
 //   [apd] spot <kind> kernel <RT, D>: <n> pairs                                  (rows in registers)
 //   [apd] spot <kind> kernel <0, D>: <n> pairs, r_max <r>, lds <b> bytes         (lane columns in LDS; D = 0: any dimension)
-// kind: "sweep" (dtw_spot), "record" (dtw_spot_record) or "stream" (dtw_spot_stream).  The only report of which spotting kernel ran.
+// kind: "sweep" (dtw_spot), "record" (dtw_spot_record), "stream" (dtw_spot_stream) or "streamrec" (dtw_spot_stream_record).  The only
+// report of which spotting kernel ran.
 void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t r_max, size_t lds_bytes);
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
@@ -405,6 +406,49 @@ struct SpotPathLaunch {
 // The pairs of L all have row class `rt`, as for launch_spot.
 hipError_t launch_spot_record(const SpotPathLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
 hipError_t launch_spot_trace(const SpotPathLaunch &L, hipStream_t stream);
+
+// ---- streaming spotting with a history (dtw_spot_stream_rec.hip): a session that keeps the last `rows` = H pushed columns -- the
+// branches of every pair's cells, row n's value and start, and every channel's frames -- in rings on the device, and traces windows
+// that still lie inside them (include/apd.h, apd_spot_stream_keep / _paths).  The branch and curve rings are indexed by ABSOLUTE
+// macro-step (dtw_spot_sweep.h, SpotRing), the frame ring by absolute column.
+struct SpotHistory {
+    uint32_t rows;                   // H >= 1
+    uint32_t *d_dirs;                // pair p: rows x WPL_p x 64 words from word d_wpl_before[p] * rows * 64
+    const uint32_t *d_wpl_before;    // [n_pairs] by p: the sum of WPL = ceil(R / 16) over the pairs before p
+    float *d_curve_v;                // pair p: [p * rows ..), T[n][J] at row (J + lane of row n) mod rows
+    uint32_t *d_curve_s;             //         S[n][J], absolute
+    float *d_frames;                 // channel k: [k * rows * dpad ..), the resident frame of column J at row J mod rows
+};
+struct SpotStreamRecLaunch {
+    SpotStreamLaunch S;
+    SpotHistory H;
+};
+// As launch_spot_stream, and every live cell's branch and row n's curve go to the rings; kind "streamrec" on the APD_DEBUG_PLAN line.
+hipError_t launch_spot_stream_record(const SpotStreamRecLaunch &R, uint32_t rt, uint32_t r_max, hipStream_t stream);
+// The last min(m, H) staged frames of every channel's chunk go to its frame ring; total: staged frames of the push (> 0).
+hipError_t launch_spot_stream_frames(const SpotStreamRecLaunch &R, uint32_t total, hipStream_t stream);
+struct SpotRingWindow {
+    uint32_t px;           // resident position of the query
+    uint32_t channel;
+    uint32_t pair;         // p = channel n_queries + q
+    uint32_t end, start;   // the caller's window, absolute columns; end lies inside the kept columns
+    uint32_t first;        // the channel's first kept column: a start before it has aged out (no walk)
+    uint64_t step_off;     // first step slot of the window in d_steps
+};
+struct SpotRingTraceLaunch {
+    const float *d_frames;             // the templates
+    const uint32_t *d_seq_off;
+    uint32_t dim, dpad;
+    float ins, del, mat;
+    SpotHistory H;
+    const SpotRingWindow *d_windows;
+    uint32_t n_windows;
+    apd_path_step *d_steps;
+    uint32_t *d_len;                   // [n_windows] steps used
+    uint32_t *d_found;                 // [n_windows] S[n][end]
+    float *d_scores;                   // [n_windows]
+};
+hipError_t launch_spot_stream_trace(const SpotRingTraceLaunch &L, hipStream_t stream);
 
 // One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
 hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);

@@ -4,40 +4,19 @@
 // the other, are the bits of apd_spot on the whole stream (include/apd.h, "streaming spotting").
 //
 // The sweep is spot_sweep (dtw_spot_sweep.h) with CARRY = true -- one text with apd_spot for the lane mapping, the macro-step and
-// the arithmetic.  What a push adds around it is here: where the pair's chunk, carried column and curves lie.  The query rows come
-// from the templates' batch, the stream columns from the session's staging buffer (the chunk in the resident layout), the carried
-// column from one half of the state buffer and the new one goes to the other half (the per-channel parity word says which).
+// the arithmetic.  What a push adds around it -- where the pair's chunk, carried column and curves lie -- is spot_stream_pair
+// (dtw_spot_stream.h), shared with the recording kernels of a session that keeps a history (dtw_spot_stream_rec.hip).
 #include <cstdio>
 #include <cstdlib>
 
-#include "dtw_spot_sweep.h"
+#include "dtw_spot_stream.h"
 
 namespace apd {
 
 template <int RT, int D>
 __global__ __launch_bounds__(64) void dtw_spot_stream(const SpotStreamLaunch S)
 {
-    const SpotStreamPair Q = S.d_pairs[blockIdx.x];
-    const uint32_t first = S.d_push[Q.channel], m = S.d_push[Q.channel + 1] - first;
-    if (m == 0) return;                                                     // nothing pushed on this channel: state, best and parity stay
-    const uint32_t base = S.d_push[S.n_channels + 1 + Q.channel];
-    const uint32_t parity = S.d_push[2 * S.n_channels + 1 + Q.channel] & 1u;
-    SpotLaunch L{};
-    L.d_frames = S.d_frames; L.d_seq_off = S.d_seq_off; L.dim = S.dim; L.dpad = S.dpad;
-    L.ins = S.ins; L.del = S.del; L.mat = S.mat;
-    L.d_cost = S.d_cost; L.d_start = S.d_start; L.d_best = S.d_best;
-    SpotPair P{};
-    P.px = Q.px; P.out = Q.out;
-    // pair p = channel n_queries + q owns m entries behind those of the pairs before it
-    P.curve_off = (uint64_t)S.n_queries * first + (uint64_t)(Q.out - Q.channel * S.n_queries) * m;
-    const uint64_t column = (uint64_t)Q.rows * 64;                          // floats of a pair's values; its starts lie behind them
-    float *in = S.d_state + parity * S.state_half + Q.state_off, *out = S.d_state + (parity ^ 1u) * S.state_half + Q.state_off;
-    SpotCarry C;
-    C.y = S.d_stage + (uint64_t)first * S.dpad;
-    C.m = m; C.base = base;
-    C.in_v = in; C.in_s = reinterpret_cast<const uint32_t *>(in + column);
-    C.out_v = out; C.out_s = reinterpret_cast<uint32_t *>(out + column);
-    spot_sweep<RT, D, false, true>(L, P, SpotRecord{}, C);
+    spot_stream_pair<RT, D, false>(S, SpotHistory{});
 }
 
 // A fresh table for the pairs of `channel` (0xFFFFFFFF: every channel): column 0 (+INF / 0) in both halves of the state, best none.

@@ -4,7 +4,8 @@
 // instantiations (`if constexpr`): the same instruction mix, no scratch, registers within 2 of what they were and the same measured
 // speed as before this header existed.  The streaming session (dtw_spot_stream.hip, CARRY = true) enters the
 // same table behind any column and leaves it for the next chunk; what CARRY adds is compiled out of the other two likewise
-// (DESIGN.md section 4.13).
+// (DESIGN.md section 4.13).  A session that keeps a history (dtw_spot_stream_rec.hip, CARRY and RING) does all of CARRY and stores the
+// branches and row n's curve of every column into the pair's rings; what RING adds is compiled out of the other three (section 4.14).
 //
 // One wavefront per (query, stream) pair.  Rows go on lanes, the stream flows through: lane l owns the R = ceil(n / 64) query rows
 // l R + 1 .. l R + R, macro-step tau gives it stream column j = tau - l + 1, and m + (lane of row n) macro-steps cover the pair.
@@ -126,11 +127,27 @@ struct SpotCarry {
     uint32_t *out_s;
 };
 
-template <int RT, int D, bool REC, bool CARRY = false>
-__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec, const SpotCarry carry = SpotCarry{})
+// What the recording streaming sweep (RING, on top of CARRY) is given for its pair: rings of H rows indexed by ABSOLUTE macro-step.
+// The live cell of lane l at absolute column J belongs to macro-step J + l; its branch words (packed as SpotRecord's) go to
+// dirs[(((J + l) mod H) * WPL + w) * 64 + l], so the 64 lanes of a store write 64 consecutive words, and lane l's column J overwrites
+// lane l's column J - H and nothing else: every lane holds exactly its last H columns, whatever the chunking.  Row n's lane stores
+// T[n][J] and S[n][J] (absolute) at curve_v / curve_s[(J + lane_n) mod H].  The row is one wrapping counter, the same for every lane.
+// J + l < 2^32: kSpotMaxStream.  A waiting or drained lane and a lane without live rows store nothing.
+struct SpotRing {
+    uint32_t *dirs;
+    float *curve_v;
+    uint32_t *curve_s;
+    uint32_t rows;          // H >= 1
+};
+
+template <int RT, int D, bool REC, bool CARRY = false, bool RING = false>
+__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec, const SpotCarry carry = SpotCarry{},
+                                           const SpotRing ring = SpotRing{})
 {
     static_assert(RT == 0 || D > 0, "rows in registers need the frame dimension at compile time");
     static_assert(!(REC && CARRY), "a carried table has no column 1 to record from");
+    static_assert(!RING || CARRY, "the rings belong to a carried table: absolute columns, curves and best as CARRY keeps them");
+    constexpr bool OPS = REC || RING;                                       // the branch of a cell is wanted
     extern __shared__ __attribute__((aligned(16))) float spot_column[];   // RT == 0: [r][lane] values, then [r][lane] starts
     constexpr int DN = D > 0 ? ((D + 4) & ~3) : 4;                          // floats of a resident frame
     const int lane = threadIdx.x;
@@ -177,6 +194,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         if (rec.n_iv) { const SpotInterval v = rec.iv[0]; iv_a = v.a; iv_b = v.b; iv_off = v.off; }
         if (rec.n_ends) end_next = rec.ends[0];
     }
+    // RING: the ring row of the current macro-step; macro-step tau of this launch is absolute macro-step base + 1 + tau for every lane
+    [[maybe_unused]] uint32_t ring_row = 0;
+    if constexpr (RING) ring_row = (carry.base + 1u) % ring.rows;
 
     const int dp4 = (int)L.dpad / 4, dim = (int)L.dim;
     float y_even[DN], y_odd[DN];                                            // column j's frame and the next macro-step's, taking turns (D > 0)
@@ -220,6 +240,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 if ((rows_live > 0) & (j >= iv_a) & (j <= iv_b)) rec_words = rec.dirs + iv_off + ((uint64_t)(j - iv_a) + lane) * row_words + lane;
             }
         }
+        if constexpr (RING) {
+            if (column_live & (rows_live > 0)) rec_words = ring.dirs + (uint64_t)ring_row * row_words + lane;
+        }
         // T[row0][j] from the lower lane (lane 0: row 0 of the table, value 0, start j)
         float up = from_lower_lane(last, 0.0f);
         uint32_t up_s = from_lower_lane_u32(last_s, 0u);
@@ -251,7 +274,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
             for (int r = 0; r < RT; ++r) {
                 const float left = pv[r];
                 const uint32_t left_s = ps[r];
-                const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, d[r], del, ins, mat);
+                const SpotNode node = spot_select<OPS>(left, left_s, up, up_s, diag, diag_s, d[r], del, ins, mat);
                 const bool live = column_live & (r < rows_live);
                 float v = live ? node.value : APD_INF;
                 uint32_t s = live ? node.start : 0u;
@@ -260,9 +283,9 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 pv[r] = v; ps[r] = s;
                 up = v; up_s = s;
                 if (r == r_n) { cap_v = v; cap_s = s; }
-                if constexpr (REC) word |= node.op << (2 * r);
+                if constexpr (OPS) word |= node.op << (2 * r);
             }
-            if constexpr (REC) if (rec_words) rec_words[0] = word;
+            if constexpr (OPS) if (rec_words) rec_words[0] = word;
         } else {
             for (int r = 0; r < R; ++r) {
                 const float *xrow = X + (uint64_t)min(row0 + r, n - 1) * L.dpad;
@@ -276,7 +299,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 }
                 const float left = spot_column[r * 64 + lane];
                 const uint32_t left_s = col_start[r * 64 + lane];
-                const SpotNode node = spot_select<REC>(left, left_s, up, up_s, diag, diag_s, dist, del, ins, mat);
+                const SpotNode node = spot_select<OPS>(left, left_s, up, up_s, diag, diag_s, dist, del, ins, mat);
                 const bool live = column_live & (r < rows_live);
                 float v = live ? node.value : APD_INF;
                 uint32_t s = live ? node.start : 0u;
@@ -286,7 +309,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 col_start[r * 64 + lane] = s;
                 up = v; up_s = s;
                 if (r == r_n) { cap_v = v; cap_s = s; }
-                if constexpr (REC) {
+                if constexpr (OPS) {
                     word |= node.op << (2 * (r & 15));
                     if (((r & 15) == 15) | (r == R - 1)) {
                         if (rec_words) rec_words[(r >> 4) * 64] = word;
@@ -306,12 +329,14 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
                 }
             } else {
                 if (curves) { cost[jm1] = cap_v; start[jm1] = cap_s; }
+                if constexpr (RING) { ring.curve_v[ring_row] = cap_v; ring.curve_s[ring_row] = cap_s; }
                 const uint32_t window = ja - cap_s + 1u;                    // frames of y the alignment covers
                 const float score = cap_v / (float)((uint32_t)n + window);  // one f32 division (alignments.rs:121 with the window for m); < 2^32: kSpotMaxStream
                 if (score < best_score) { best_end = ja; best_start = cap_s; best_cost = cap_v; best_score = score; }
             }
         }
         ++jm1;
+        if constexpr (RING) { if (++ring_row == ring.rows) ring_row = 0u; }
     };
     // two macro-steps per turn, the frame buffers swapping roles; a step beyond `total` computes nothing that is live
     for (uint64_t tau = 0; tau < total; tau += 2) {

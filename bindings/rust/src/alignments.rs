@@ -215,6 +215,32 @@ impl SpotStream {
         unsafe { check(apd_spot_stream_columns(self.handle, channel, &mut c)); }
         c
     }
+    /// From now on the session keeps its last `history_columns` columns (0: none); windows inside them can be traced: paths().
+    pub fn keep(&mut self, history_columns: u32) {
+        unsafe { check(apd_spot_stream_keep(self.ctx, self.handle, history_columns)); }
+    }
+    /// (first, last) of the channel's kept columns; first == last + 1: none.
+    pub fn history(&self, channel: u32) -> (u64, u64) {
+        let (mut first, mut last) = (0u64, 0u64);
+        unsafe { check(apd_spot_stream_history(self.handle, channel, &mut first, &mut last)); }
+        (first, last)
+    }
+    /// windows[k]: x a template number, y a channel, end and start absolute columns as push() reported them.  Returns per window
+    /// (steps origin first, found_start, score); the steps are empty for a window that has aged out of the history, for a (0, 0)
+    /// window and for a start that is not the table's.
+    pub fn paths(&mut self, windows: &[apd_spot_window]) -> Vec<(Vec<apd_path_step>, u32, f32)> {
+        let k = windows.len();
+        let mut off = vec![0u64; k + 1];
+        let (mut len, mut found, mut scores) = (vec![0u32; k], vec![0u32; k], vec![0f32; k]);
+        unsafe {
+            check(apd_spot_stream_paths(self.ctx, self.handle, windows.as_ptr(), k as u64, std::ptr::null_mut(), 0, off.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()));
+        }
+        let mut steps = vec![apd_path_step::default(); (off[k] as usize).max(1)];
+        unsafe {
+            check(apd_spot_stream_paths(self.ctx, self.handle, windows.as_ptr(), k as u64, steps.as_mut_ptr(), steps.len() as u64, off.as_mut_ptr(), len.as_mut_ptr(), found.as_mut_ptr(), scores.as_mut_ptr()));
+        }
+        (0..k).map(|p| (steps[off[p] as usize..off[p] as usize + len[p] as usize].to_vec(), found[p], scores[p])).collect()
+    }
 }
 
 impl Drop for SpotStream {

@@ -217,6 +217,12 @@ extern "C" {
     pub fn apd_spot_stream_push(ctx: *mut apd_context, stream: *mut apd_spot_stream, frames: *const f32, chunk_off: *const u64, dim: u32,
                                 frames_on_device: c_int, cost: *mut f32, start: *mut u32, capacity: u64, curve_off: *mut u64,
                                 best: *mut apd_spot_best) -> c_int;
+    // streaming spotting, a kept history of columns
+    pub fn apd_spot_stream_keep(ctx: *mut apd_context, stream: *mut apd_spot_stream, history_columns: u32) -> c_int;
+    pub fn apd_spot_stream_history(stream: *const apd_spot_stream, channel: u32, first: *mut u64, last: *mut u64) -> c_int;
+    pub fn apd_spot_stream_paths(ctx: *mut apd_context, stream: *mut apd_spot_stream, windows: *const apd_spot_window, n_windows: u64,
+                                 steps: *mut apd_path_step, capacity: u64, step_off: *mut u64, path_len: *mut u32,
+                                 found_start: *mut u32, scores: *mut f32) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

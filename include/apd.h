@@ -500,8 +500,8 @@ int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const apd_align_con
  * Arithmetic: the literal one, always; apd_set_distance_mode is not read, no feature-range routing.  One wavefront per pair, as for
  * apd_spot: the parallelism is templates x channels.  A chunk of m columns costs m + (lane of row n) macro-steps, so chunks much
  * shorter than 64 columns pay mostly for filling the wavefront.
- * Not offered: warping paths of windows found while streaming.  apd_spot_paths needs the table from column 1; keep the recording
- * and ask it. */
+ * Warping paths of windows found while streaming: a session that keeps a history of its last columns traces them itself
+ * ("a kept history of columns" below).  apd_spot_paths needs the table from column 1, so it serves only a recording that was kept. */
 typedef struct apd_spot_stream apd_spot_stream;
 /* A query index >= the batch's sequence count, n_queries * n_channels == 0 or >= 2^24, or a batch of another context:
  * APD_ERR_INVALID_ARG; an empty query APD_ERR_EMPTY_SEQUENCE; one of more than 16 384 frames APD_ERR_UNSUPPORTED.  Blocking. */
@@ -532,6 +532,49 @@ int apd_spot_stream_columns(const apd_spot_stream *stream, uint32_t channel, uin
 int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, const float *frames, const uint64_t *chunk_off, uint32_t dim,
                          int frames_on_device, float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off,
                          apd_spot_best *best);
+
+/* ---- streaming spotting, a kept history of columns: warping paths of windows found while streaming ------------------------------
+ * A window [S, end] is walked back only through cells of columns S .. end, and the session sweeps those very cells of the very
+ * table once, as the chunks arrive.  A session that keeps, for its last H columns, the branch of every cell, row n's value and
+ * start and the stream's frames can trace every window that still lies inside those columns -- with the results of apd_spot_paths
+ * on the whole stream, at a cost that does not grow with the age of the stream and without the recording.
+ *
+ * apd_spot_stream_keep: from now on the session keeps the last history_columns pushed columns of every channel; 0 releases the
+ * history.  Legal at any time, in mid-stream and repeatedly.  The table is not touched: curves and bests of later pushes keep their
+ * bits.  The history starts EMPTY behind each channel's current column (its "origin"): windows that start at or before
+ * apd_spot_stream_columns at the time of the call are not traceable, whatever was kept before.  Blocking.  APD_ERR_OOM leaves the
+ * session exactly as before the call, its previous history included.  A foreign context: APD_ERR_INVALID_ARG.
+ * Device memory, H = history_columns, R = ceil(n / 64) rows per lane of a query of n frames:
+ *     per pair:     H * (ceil(R / 16) * 256 + 8) bytes    2 bits per cell in words of 16 rows per lane, 64 lanes; row n's value and start
+ *     per channel:  H * 4 * ceil4(dim + 1) bytes          one resident frame per column
+ * While a history is kept a push runs recording kernels (the same sweep, one more coalesced 256-byte store per macro-step and
+ * word); a session without one runs the kernels it always ran. */
+int apd_spot_stream_keep(apd_context *ctx, apd_spot_stream *stream, uint32_t history_columns);
+/* The absolute columns [*first, *last] of `channel` whose cells are kept: last = apd_spot_stream_columns, first = max(origin + 1,
+ * last - H + 1); nothing kept (no history, or nothing pushed since the origin): first = last + 1.  apd_spot_stream_reset of a
+ * channel empties its history, with the origin at the new first_column.  Host only. */
+int apd_spot_stream_history(const apd_spot_stream *stream, uint32_t channel, uint64_t *first, uint64_t *last);
+/* apd_spot_paths for the windows of a session.  windows[p]: x = index into the session's `queries`, y = channel, end and start
+ * absolute columns as a push reports them (a record of `best` can be handed over as it is).  Slots, step_off, sizes only (steps ==
+ * NULL, legal with or without a history), zeroed unused slots, results in input order, path_len / found_start / scores and the
+ * workspace cap (APD_SPOT_WORKSPACE_BYTES) exactly as for apd_spot_paths; a window owns apd_spot_path_bound(n, end, start) slots.
+ * The promise: for a window whose columns start .. end all lie in [first, last] of its channel (apd_spot_stream_history), steps (i,
+ * j, the bits of cost, op), path_len, found_start and scores are those of apd_spot_paths on the whole stream since the reset, in a
+ * joined batch -- j, found_start (unless 0) and the START step's column shifted by the channel's first_column -- and no bit of a
+ * cost or score differs, whatever the chunking of the pushes, zero-length chunks and pushes longer than H included.
+ * The caller's start is checked against the kept S[n][end], not trusted, as there.
+ *   end inside the history, start (or the start found) before `first`: found_start and scores as above, path_len = 0, the slots
+ *     zeroed, APD_OK: the window has aged out; found_start == start tells it from a wrong start.
+ *   end before `first`: path_len = 0, found_start = 0, score +INF, the slots zeroed, APD_OK.
+ *   end == 0 or start == 0: "no window", as for apd_spot_paths.
+ * Before anything is launched: x >= n_queries, y >= n_channels, start > end (with end >= 1) or end beyond the channel's pushed
+ * column: APD_ERR_INVALID_ARG; a foreign context: APD_ERR_INVALID_ARG; steps != NULL on a session that keeps no history:
+ * APD_ERR_UNSUPPORTED, with a text in apd_last_error.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the traces.
+ * The replay reads the templates' resident rows: after an apd_batch_refill the kept branches belong to the OLD rows; reset the
+ * channel, as for the table.  Workspace: the steps of a chunk of windows; nothing else is allocated. */
+int apd_spot_stream_paths(apd_context *ctx, apd_spot_stream *stream, const apd_spot_window *windows, uint64_t n_windows,
+                          apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len, uint32_t *found_start,
+                          float *scores);
 
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */

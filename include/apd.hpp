@@ -266,6 +266,33 @@ class SpotStream {
         check(apd_spot_stream_columns(handle_, channel, &c));
         return c;
     }
+    // From now on the session keeps its last history_columns columns (0: none); windows inside them can be traced: paths().
+    void keep(uint32_t history_columns) { check(apd_spot_stream_keep(ctx_.get(), handle_, history_columns), ctx_.get()); }
+    // [first, last] of the channel's kept columns; first == last + 1: none.
+    std::pair<uint64_t, uint64_t> history(uint32_t channel) const
+    {
+        uint64_t first = 0, last = 0;
+        check(apd_spot_stream_history(handle_, channel, &first, &last));
+        return {first, last};
+    }
+    // windows: x = index into the session's queries, y = channel, end / start absolute columns as push() reports them.  steps[p] is
+    // empty for a window that has aged out of the history, for a {0, 0} record and for a start that is not the table's.
+    struct Paths { std::vector<std::vector<apd_path_step>> steps; std::vector<uint32_t> found_start; std::vector<float> scores; };
+    Paths paths(const std::vector<apd_spot_window> &windows)
+    {
+        const std::size_t k = windows.size();
+        std::vector<uint64_t> off(k + 1, 0);
+        std::vector<uint32_t> len(k, 0);
+        Paths out;
+        out.found_start.assign(k, 0);
+        out.scores.assign(k, 0.0f);
+        check(apd_spot_stream_paths(ctx_.get(), handle_, windows.data(), k, nullptr, 0, off.data(), nullptr, nullptr, nullptr), ctx_.get());   // sizes
+        std::vector<apd_path_step> steps(std::max<uint64_t>(off.back(), 1));
+        check(apd_spot_stream_paths(ctx_.get(), handle_, windows.data(), k, steps.data(), steps.size(), off.data(), len.data(),
+                                    out.found_start.data(), out.scores.data()), ctx_.get());
+        for (std::size_t p = 0; p < k; ++p) out.steps.emplace_back(steps.begin() + off[p], steps.begin() + off[p] + len[p]);
+        return out;
+    }
   private:
     Context &ctx_;
     apd_spot_stream *handle_ = nullptr;
