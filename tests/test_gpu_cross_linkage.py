@@ -1,52 +1,14 @@
 """apd_cross_linkage: the reference's average linkage (clustering.rs:153-170) of every first-set sequence to sets of the second, and
-merge()'s choice among them (clustering.rs:178-187), bit for bit against a sequential numpy-f32 loop written here."""
+merge()'s choice among them (clustering.rs:178-187), bit for bit against the sequential numpy-f32 loop of tests/_linkage_reference.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from audio_pattern_discovery_amd import synth
+from _linkage_reference import F, NONE, assert_equal, reference, reference_over_q, same_bits, six_set_case
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-NONE = 0xFFFFFFFF
-
-
-def reference(fs, sf, sets, ascending=True):
-    """(link_fs, link_sf, nearest, nearest_linkage): one rounded f32 add per member, ascending sequence number (or, to show that the
-    order matters, the listed order), then one division; the scan keeps a value only if strictly below the best so far."""
-    n1 = fs.shape[0]
-    link_fs, link_sf = np.zeros((n1, len(sets)), F), np.zeros((n1, len(sets)), F)
-    with np.errstate(all="ignore"):
-        for k, s in enumerate(sets):
-            members = sorted(s) if ascending else list(s)
-            for q in range(n1):
-                a = b = F(0.0)
-                for y in members:
-                    a = F(a + fs[q, y])
-                    b = F(b + sf[y, q])
-                link_fs[q, k] = a / F(F(1.0) * F(len(members)))
-                link_sf[q, k] = b / F(F(len(members)) * F(1.0))
-    nearest, best = np.full(n1, NONE, np.uint32), np.full(n1, np.inf, F)
-    for q in range(n1):
-        for k in range(len(sets)):
-            for v in (link_fs[q, k], link_sf[q, k]):
-                if v < best[q]:
-                    best[q], nearest[q] = v, k
-    return link_fs, link_sf, nearest, best
-
-
-def same_bits(got, want):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    nan = np.isnan(want) if want.dtype == F else np.zeros(want.shape, bool)
-    if want.dtype == F and not np.array_equal(np.isnan(got), nan):
-        return False
-    return np.array_equal(got[~nan].view(np.uint32), want[~nan].view(np.uint32))
-
-
-def assert_equal(got, want, what):
-    for g, w, name in zip(got, want, ("link_fs", "link_sf", "nearest", "nearest_linkage")):
-        assert same_bits(g, w), "%s: %s differs from the sequential f32 loop" % (what, name)
 
 
 @pytest.fixture(scope="module")
@@ -58,15 +20,8 @@ def ctx(apd):
 
 def test_linkage_matches_the_sequential_loop_bitwise(ctx, apd):
     from audio_pattern_discovery_amd.clustering import cross_linkage
-    rng = np.random.default_rng(20240607)
-    n1, n2 = 37, 333
-    fs = (rng.random((n1, n2), dtype=F) * F(9.0) + F(0.01)).astype(F)
-    sf = (rng.random((n2, n1), dtype=F) * F(9.0) + F(0.01)).astype(F)
-    perm = rng.permutation(n2)
-    sizes, sets, at = (1, 2, 15, 64, 65, 186), [], 0
-    for sz in sizes:
-        sets.append([int(v) for v in perm[at:at + sz]])             # listed unsorted
-        at += sz
+    fs, sf, sets = six_set_case()
+    n1, n2 = fs.shape
     want = reference(fs, sf, sets)
     listed = reference(fs, sf, sets, ascending=False)
     n_link = n1 * len(sets)                                           # 222 linkages per direction
@@ -123,6 +78,41 @@ def test_linkage_matches_the_sequential_loop_bitwise(ctx, apd):
     assert_equal(dev, want, "device form")
     for b in (d_fs, d_sf, d_lf, d_ls, d_near, d_best):
         b.free()
+
+
+def test_three_query_blocks_and_more_sets_than_the_grid_has_rows(ctx, apd):
+    """cross_linkage_kernel / cross_nearest_kernel run one lane per first-set sequence q, 64 to a block, and stride the sets by
+    gridDim.y = min(n_sets, 16384).  n_first = 130: three blocks, the last with two lanes, rows of `link` at q >= 64;
+    n_sets = 16384 + 3: sets 16384 .. 16386 are a block's second trip.  Sets of 0, 1, 2 and 3 members in turn, drawn with repeats
+    across sets and listed unsorted; the host form and the device form, against the loop with q as the array axis."""
+    from audio_pattern_discovery_amd.clustering import cross_linkage
+    six = six_set_case()
+    assert_equal(reference_over_q(*six), reference(*six), "the loop over q as an array, on the six sets")
+    rng = np.random.default_rng(20240608)
+    n1, n2, n_sets = 130, 50, 16384 + 3
+    fs = (rng.random((n1, n2), dtype=F) * F(9.0) + F(0.01)).astype(F)
+    sf = (rng.random((n2, n1), dtype=F) * F(9.0) + F(0.01)).astype(F)
+    sets = [[int(v) for v in rng.choice(n2, size=k % 4, replace=False)] for k in range(n_sets)]
+    assert any(s != sorted(s) for s in sets) and [len(s) for s in sets[-3:]] == [0, 1, 2]
+    want = reference_over_q(fs, sf, sets)
+    assert len(set(want[2].tolist())) > 20 and NONE not in want[2]               # the scan's choice differs from lane to lane
+    assert_equal(cross_linkage(fs, sf, sets, ctx), want, "130 x 16387, host form")
+
+    members = np.array([m for s in sets for m in s], np.uint32)
+    set_off = np.zeros(n_sets + 1, np.uint32)
+    set_off[1:] = np.cumsum([len(s) for s in sets])
+    d_fs, d_sf = ctx.upload(fs), ctx.upload(sf)
+    d_lf, d_ls, d_near, d_best = (ctx.alloc(4 * n1 * n_sets), ctx.alloc(4 * n1 * n_sets), ctx.alloc(4 * n1), ctx.alloc(4 * n1))
+    u32p = C.POINTER(C.c_uint32)
+    try:
+        apd.check(apd.lib().apd_cross_linkage(ctx.handle, d_fs.at(), d_sf.at(), 1, n1, n2, members.ctypes.data_as(u32p),
+                                              set_off.ctypes.data_as(u32p), n_sets, d_lf.at(), d_ls.at(), d_near.at(), d_best.at()), ctx.handle)
+        ctx.synchronize()
+        dev = (d_lf.to_numpy(F).reshape(n1, -1), d_ls.to_numpy(F).reshape(n1, -1), d_near.to_numpy(np.uint32), d_best.to_numpy(F))
+    finally:
+        for b in (d_fs, d_sf, d_lf, d_ls, d_near, d_best):
+            b.free()
+    assert_equal(dev, want, "130 x 16387, device form")
 
 
 def test_queries_find_their_clusters_end_to_end(ctx, oracle, apd):

@@ -3,8 +3,8 @@
 Every comparison is bitwise: medoids and counts equal, cost, inertia and frames equal as uint32 (NaN payloads aside:
 _path_reference.bits says why).  Shapes are the smallest that reach each code path: barycenters longer than a wavefront, bands that
 bind and widen, structural ties, barycenters of 1 and 2 frames, singleton and empty sets, frame dimensions with and without padding
-slots, a NaN member, sets that straddle workspace chunks, joined batches, the device-resident result; medoid sets within one, two
-and three wavefronts."""
+slots, a NaN member, sets that straddle workspace chunks, joined batches, the device-resident result, 70 sets in one call; medoid
+sets within one, two and three wavefronts, and 130 sets with runs of empty ones."""
 import ctypes as C
 import os
 
@@ -175,6 +175,22 @@ def test_chunked_equals_unchunked(apd, ctx, several):
     assert_same((frames, inertia, used), want, "one pair per chunk")
 
 
+def test_seventy_sets_of_short_sequences(apd, ctx):
+    """bary_set_of (csrc/dtw_path.hip) finds the set of a pair, and of a barycenter frame, by the same search over set_off: 70 sets
+    of 0 to 4 sequences of 1 to 12 frames, empty ones at the front, at the end and in runs in between."""
+    rng = np.random.default_rng(82)
+    lengths = [1 + (5 * s) % 12 for s in range(40)]
+    seqs = gauss_seqs(lengths, 3, 82)
+    sizes = [int(v) for v in rng.integers(1, 5, 70)]
+    for k in (0, 1, 17, 33, 34, 35, 51, 68, 69):
+        sizes[k] = 0
+    sets = [[int(v) for v in rng.choice(len(seqs), size=sz, replace=False)] for sz in sizes]
+    init = [int(rng.integers(0, len(seqs))) for _ in sets]                                   # usually no member of its set
+    (frames, inertia, used), _ = check(apd, ctx, seqs, 0.25, UNIT, sets, init, 2, "70 sets")
+    assert [len(f) for f in frames] == [lengths[i] if s else 0 for i, s in zip(init, sets)]
+    assert (used[0] > 0).sum() >= 30 and np.all(used[:, [sz == 0 for sz in sizes]] == 0)
+
+
 @pytest.mark.parametrize("dim", [1, 5, 13, 26, 32])
 def test_dimensions(apd, ctx, dim):
     seqs = gauss_seqs((20, 23, 18, 21), dim, 80 + dim)
@@ -310,6 +326,26 @@ def test_medoids_of_sets_beyond_one_and_two_wavefronts(apd, ctx):
     assert np.array_equal(m2, want_m) and np.array_equal(ref.bits(c2), ref.bits(want_c))
     m3, _ = raw_medoids(apd, ctx, d, sets, want_cost=False)                                  # cost may be NULL
     assert np.array_equal(m3, want_m)
+
+
+def test_medoids_of_130_sets_with_runs_of_empty_ones(apd, ctx):
+    """medoid_pick_kernel's third, partial block (sets 128 and 129), and medoid_cost_kernel's search for `the largest k with
+    set_off[k] <= e` among runs of equal offsets: three empty sets at the front, four in the middle, three at the end, and single
+    empty sets in between."""
+    rng = np.random.default_rng(83)
+    n, n_sets = 200, 130
+    d = rng.random((n, n), dtype=np.float32)
+    sizes = [int(v) for v in rng.integers(1, 9, n_sets)]
+    for k in (0, 1, 2, 40, 63, 64, 65, 66, 97, 127, 128, 129):
+        sizes[k] = 0
+    sizes[126], sizes[3] = 70, 1                                                             # beyond a wavefront; a singleton
+    sets = [[int(v) for v in rng.choice(n, size=sz, replace=False)] for sz in sizes]        # unsorted, sequences shared between sets
+    assert sum(sizes) > 3 * 64 and any(s != sorted(s) for s in sets)
+    want_m, want_c = dba.medoids(d, sets)
+    got_m, got_c = raw_medoids(apd, ctx, d, sets)
+    assert np.array_equal(got_m, want_m) and np.array_equal(ref.bits(got_c), ref.bits(want_c))
+    empty = np.array([sz == 0 for sz in sizes])
+    assert np.all(got_m[empty] == dba.NONE) and np.isposinf(got_c[empty]).all() and np.all(got_m[~empty] != dba.NONE)
 
 
 def test_medoid_ties_and_nan(apd, ctx):
