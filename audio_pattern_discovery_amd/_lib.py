@@ -298,7 +298,10 @@ class Context:
     def set_distance_mode(self, mode, tau=0.0):
         """0 / "exact": difference form; 1 / "hybrid": norm expansion with exact recomputation below tau;
         2 / "strict": the reference's arithmetic operation for operation in every kernel family (bit-identical scores, ~2x slower);
-        0 already is that on the band-form kernels."""
+        0 already is that on the band-form kernels.
+        tau = 0 keeps the context's current threshold (1/64 in a fresh context).  A tau > 0 is sticky: it is stored whatever the mode,
+        survives later mode changes and stays until another value > 0 is set; exact and strict mode do not read it.  A negative or
+        NaN tau raises ApdError (APD_ERR_INVALID_ARG) and changes neither the mode nor the threshold."""
         mode = {"exact": 0, "hybrid": 1, "strict": 2}.get(mode, mode)
         check(lib().apd_set_distance_mode(self.handle, int(mode), float(tau)))
 

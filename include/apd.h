@@ -98,8 +98,11 @@ float apd_last_kernel_ms(apd_context *ctx);
 int apd_set_variant(apd_context *ctx, int variant);
 /* Local-distance form of the fast kernels with UNIT penalties (1.0, 1.0, 1.0 -- the shipped Discovery.toml).
  * mode 1 (default; D >= 8 in the band kernels, D >= 10 in the strip kernels): |x|^2 + |y|^2 - 2 x.y from precomputed frame
- * norms, recomputed in the difference form wherever the result is below tau * (|x|^2 + |y|^2) (cancellation region; tau <= 0
- * keeps the current value, default 1/64): ~3e-7 relative measured (tolerance asked: 1e-4); exact copies score exactly 0.
+ * norms, recomputed in the difference form wherever the result is below tau * (|x|^2 + |y|^2) (cancellation region; default
+ * tau 1/64): ~3e-7 relative measured (tolerance asked: 1e-4); exact copies score exactly 0.  tau = 0 (or -0.0) keeps the context's
+ * current value; a value > 0 is stored in the context whatever the mode and stays until the next value > 0 -- it survives mode
+ * changes, and modes 0 and 2 do not read it; tau < 0 or NaN is APD_ERR_INVALID_ARG and changes neither the mode nor the value.
+ * Since |x - y|^2 <= 2 (|x|^2 + |y|^2), tau = 4 recomputes every cell with a non-zero norm sum (tests/test_gpu_tau_gate.py).
  * mode 0: the difference form sqrt(sum (x_k-y_k)^2).  In the band-form kernels it is computed operation for operation as
  * numerics.rs:114-120 does (every difference, square and partial sum rounded on its own, correctly rounded sqrt), and with
  * unit penalties the fast select picks the reference's predecessor for every non-NaN input: scores are bit-identical to the CPU

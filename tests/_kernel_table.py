@@ -93,6 +93,24 @@ def capacity(family, first, second):
     return (64 if family == "wide" else 1) * first * second
 
 
+def default_tau(text=None):
+    """The hybrid form's recomputation threshold a fresh context holds: 'float tau = <a>f / <b>f;' of the header's context."""
+    text = header_text() if text is None else text
+    m = re.search(r"\bfloat\s+tau\s*=\s*([0-9.]+)f\s*/\s*([0-9.]+)f\s*;", text)
+    if m is None:
+        raise ValueError("no 'float tau = <a>f / <b>f;' in %s" % HEADER)
+    return float(np.float32(m.group(1)) / np.float32(m.group(2)))
+
+
+# literal mirror of launch_align's "part.hybrid = ..." (csrc/dtw_generic.hip) and of what admits the families that it asks for unit
+# penalties: launch_systolic's "unit && L.hybrid", the wide and strip kernels' "L.band.mat == 1.0f" under equal penalties
+def hybrid_live(family, dim, pens=(1.0, 1.0, 1.0), strict=False):
+    """True if hybrid mode launches the norm-expansion form (the one with the tau gate) of `family` at kernel dimension dim."""
+    if strict or tuple(float(p) for p in pens) != (1.0, 1.0, 1.0):
+        return False
+    return dim >= (8 if family in ("systolic", "shared") else 10)
+
+
 def pairs(table=None):
     """([(family, first, second, dim)] that exist, [...] that the dimension's clamp drops), in header order."""
     geoms, dims = parse_table() if table is None else table

@@ -1,5 +1,7 @@
 """The header parser behind tests/test_gpu_kernel_matrix.py, without a GPU: a refactor of csrc/apd_internal.h that the parser no
 longer reads, or a clamp that moved away from the Python mirror, fails here and not first on the GPU box."""
+import re
+
 import pytest
 
 import _kernel_table as kt
@@ -63,6 +65,27 @@ def test_plan_lines_are_read_per_geometry():
            "[apd] rank 0/1: geometry 0: 1 tiles, w_max 9, n_max 30\n[apd] rank 1/2: geometry 1609: 3 tiles, w_max 70, n_max 304\n")
     assert kt.read_plan(err) == {1609: 5, 0: 1}
     assert kt.read_plan("") == {}
+
+
+def test_default_tau_and_hybrid_live_at_hand_values():
+    """What tests/test_gpu_tau_gate.py builds its case list and its restore value from."""
+    assert kt.default_tau() == 0.015625
+    assert kt.default_tau("struct apd_context {\n    float tau = 1.0f / 32.0f;   // threshold\n};") == 0.03125
+    with pytest.raises(ValueError, match="tau"):
+        kt.default_tau("float tau;")
+    assert [kt.hybrid_live("systolic", d) for d in (5, 8, 10, 26)] == [False, True, True, True]
+    assert [kt.hybrid_live("shared", d) for d in (5, 8, 13)] == [False, True, True]
+    for fam in ("wide", "strip", "banded"):
+        assert [kt.hybrid_live(fam, d) for d in (8, 10, 13, 26)] == [False, True, True, True], fam
+    for fam in kt.FAMILIES:
+        assert not kt.hybrid_live(fam, 13, (0.7, 0.7, 0.7)) and not kt.hybrid_live(fam, 13, (0.6, 1.3, 1.0))
+        assert not kt.hybrid_live(fam, 13, strict=True)
+    # the two thresholds are launch_align's: the mirror is compared with the line it mirrors
+    src = open(kt.HEADER.replace("apd_internal.h", "dtw_generic.hip")).read()
+    m = re.search(r"part\.hybrid\s*=\s*L\.hybrid\s*&&\s*\((.*?)\);", src)
+    assert m is not None, "launch_align no longer has 'part.hybrid = L.hybrid && (...)'"
+    assert re.sub(r"\s+", " ", m.group(1)) == ("g.family == KernelGeom::Systolic || g.family == KernelGeom::SharedColumns ? "
+                                                "L.dim >= 8 && !L.strict : L.dim >= 10 && L.band.mat == 1.0f")
 
 
 # ---- the spotting kernels (tests/test_gpu_spot_matrix.py)
