@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <new>
 #include <tuple>
@@ -750,6 +751,13 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     const apd_batch::TilePlan *plan = nullptr;
     rc = tile_plan(ctx, batch, band, src, fast_ok, &plan);
     if (rc) return rc;
+    // A class of the literal kernel whose band does not fit its LDS rows: refused here, before the poison memset -- the call has
+    // enqueued nothing and written nothing when APD_ERR_BAND_TOO_WIDE comes back (launch_align keeps the same test)
+    for (const TileClass &tc : plan->classes)
+        if (tc.geom.family == KernelGeom::Generic && tc.count != 0 && !generic_band_fits(tc.w_max)) {
+            ctx->last_error = "band too wide for the generic kernel";
+            return APD_ERR_BAND_TOO_WIDE;
+        }
     // Poison: every score slot of the rank's slab starts as NaN, so a pair that no kernel writes (a launch cut short, a
     // skipped class) reaches the matrix as NaN and raises APD_ERR_INCOMPLETE in the unpack -- never a stale or zero distance.
     APD_AFFINITY(ctx, "alignment launches");
@@ -768,11 +776,17 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
     return APD_OK;
 }
 
+// Any f32 penalty is accepted (include/apd.h, "the domain of an alignment configuration").  A NaN penalty reaches the kernels as
+// THE canonical quiet NaN: its payload would otherwise travel into the scores, where the pattern 0xFFFFFFFF means "never written"
+// (is_poison, dtw_generic.hip).  Which scores are NaN does not depend on the payload.
+static float canonical_penalty(float p) { return p != p ? std::numeric_limits<float>::quiet_NaN() : p; }
+
 static BandSpec band_from_cfg(const apd_align_config *cfg)
 {
     BandSpec b{};
     b.pct = cfg->warping_band_percentage; b.use_explicit = 0; b.explicit_band = 0;
-    b.ins = cfg->insertion_penalty; b.del = cfg->deletion_penalty; b.mat = cfg->match_penalty;
+    b.ins = canonical_penalty(cfg->insertion_penalty); b.del = canonical_penalty(cfg->deletion_penalty);
+    b.mat = canonical_penalty(cfg->match_penalty);
     return b;
 }
 
@@ -970,7 +984,8 @@ static BandSpec band_from_params(const apd_alignment_params *params)
     BandSpec band{};
     band.use_explicit = 1;
     band.explicit_band = params->warping_band > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)params->warping_band;
-    band.ins = params->insertion_penalty; band.del = params->deletion_penalty; band.mat = params->match_penalty;
+    band.ins = canonical_penalty(params->insertion_penalty); band.del = canonical_penalty(params->deletion_penalty);
+    band.mat = canonical_penalty(params->match_penalty);
     return band;
 }
 

@@ -458,6 +458,9 @@ hipError_t launch_generic_fallback(const AlignLaunch &L, hipStream_t stream, boo
 // true if the literal kernel can hold a band of w_max in LDS AND the runtime grants it that much (the hipFuncSetAttribute is made
 // here, before anything is enqueued: a refusal sends the caller down the host-side choice instead of failing mid-call)
 bool generic_fallback_fits(uint32_t w_max);
+// true if the literal kernel's two DP rows of a band of w_max fit the 160 KB of LDS a workgroup can have: 2 * w_max + 1 <= 20480.
+// Host arithmetic only (launch_align's own test, asked before a call enqueues anything).
+bool generic_band_fits(uint32_t w_max);
 
 // One launch of the tile plan: the tiles [first, first + count) of its device tile list, all swept with geometry `geom`.
 struct TileClass { KernelGeom geom; uint32_t first, count, w_max, n_max; };

@@ -219,6 +219,12 @@ __global__ __launch_bounds__(256) void pad_frames_kernel(const float *__restrict
     if (__ballot(nonfinite) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flags, 1u);
 }
 
+// The poison of a score slot no kernel wrote: the 0xFF bytes the slabs are filled with before the alignment launches, compared by
+// its bits.  A score may be NaN in its own right -- an infinite penalty on a zero distance (INF * 0), a NaN penalty -- and is then
+// the NaN the arithmetic makes (0x7FC00000 on gfx950) or the canonical one the host puts in place of a NaN penalty
+// (canonical_penalty, apd_api.hip): never this pattern.
+__device__ __forceinline__ bool is_poison(float s) { return __builtin_bit_cast(uint32_t, s) == 0xFFFFFFFFu; }
+
 // gathered: `world` slabs of slab_floats each; slab r holds tiles r, r+world, ... in order.
 __global__ void unpack_tiles_kernel(const float *__restrict__ gathered, float *__restrict__ out,
                                     const uint32_t *__restrict__ order, uint32_t n_seq, uint32_t world, uint64_t slab_floats, uint32_t n_tiles_side,
@@ -238,13 +244,13 @@ __global__ void unpack_tiles_kernel(const float *__restrict__ gathered, float *_
         const float s1 = slab[sa * kTile + sb], s2 = slab[kSlotsPerTile + sa * kTile + sb];
         out[(uint64_t)a * n_seq + b] = s1;
         out[(uint64_t)b * n_seq + a] = s2;
-        poisoned = (s1 != s1) | (s2 != s2);
+        poisoned = is_poison(s1) | is_poison(s2);
     } else if (pa == pb && pb < n_seq) {
         const uint32_t a = order[pa];
         out[(uint64_t)a * n_seq + a] = 0.0f;                  // the diagonal is never aligned (alignments.rs:21-23, 51)
     }
-    // every slab is filled with NaN before the alignment launches: with finite frames no score is NaN, so a NaN here is a
-    // pair no kernel wrote (a launch cut short or skipped).  It stays NaN in the matrix and is reported, never a silent 0.
+    // every slab is filled with the poison NaN before the alignment launches: a slot that still holds it is a pair no kernel
+    // wrote (a launch cut short or skipped).  It stays NaN in the matrix and is reported, never a silent 0.
     if (__ballot(poisoned) != 0ull && (threadIdx.x & 63) == 0 && flags[0] == 0u) atomicOr(status, 1u);
 }
 
@@ -273,9 +279,9 @@ __global__ __launch_bounds__(256) void unpack_cross_kernel(const float *__restri
             if (out_sf) out_sf[(uint64_t)(a - n_first) * n_first + b] = s1;
             if (out_fs) out_fs[(uint64_t)b * n_second + (a - n_first)] = s2;
         }
-        poisoned = (s1 != s1) | (s2 != s2);
+        poisoned = is_poison(s1) | is_poison(s2);
     }
-    // as in unpack_tiles_kernel: with frames in range no score is NaN, so a NaN is the poison of a pair no kernel wrote
+    // as in unpack_tiles_kernel: a slot that still holds the poison pattern is a pair no kernel wrote
     if (__ballot(poisoned) != 0ull && (threadIdx.x & 63) == 0 && flags[0] == 0u) atomicOr(status, 1u);
 }
 
@@ -639,6 +645,8 @@ hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, 
     }
     return hipSuccess;
 }
+
+bool generic_band_fits(uint32_t w_max) { return generic_lds_bytes(w_max, nullptr) <= 160 * 1024; }
 
 bool generic_fallback_fits(uint32_t w_max)
 {

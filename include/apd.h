@@ -48,6 +48,33 @@ typedef struct apd_comm apd_comm;         /* this rank's end of an RCCL communic
 typedef struct apd_encoder apd_encoder;   /* AutoEncoder's w_encode / b_encode resident on a context's GPU (neural.rs:13-17) */
 typedef struct apd_cepstrum_plan apd_cepstrum_plan;   /* window, filterbank, DCT and twiddle tables + the offsets of a corpus, resident */
 
+/* THE DOMAIN OF AN ALIGNMENT CONFIGURATION (apd_align_config and apd_alignment_params; every entry point that takes one).
+ *
+ * Penalties.  Any f32 is accepted: zero, negative, +-INF, NaN, subnormal.  The arithmetic is the reference's, IEEE operation for
+ * operation (node = predecessor + (penalty * d), the product rounded on its own; a comparison with a NaN is false and takes the
+ * MATCH branch, alignments.rs:153-159), so 0 * d, INF * 0 = NaN on a duplicated frame and a NaN penalty come out as on the CPU,
+ * NaN payloads aside: a NaN penalty is read as the canonical quiet NaN, and a NaN score is a result, not APD_ERR_INCOMPLETE.
+ *   apd_align_all / _device_async, apd_align_tiles_async and what is built on them (apd_align_cross, apd_align_pair, the sharded,
+ *   multi-device and one-call forms): a call in which ANY penalty is <= 0 (-0.0 included), +INF or NaN runs the literal kernel
+ *   alone (the fast kernels need pen * INF = INF); apd_set_variant does not override that.  Positive finite penalties run the
+ *   fast kernels: equal ones within 1e-4 relative of the CPU code (bit-identical in distance mode 2), unequal ones bit-identical.
+ *   apd_align_paths, apd_align_pair_path, apd_spot, apd_spot_paths, the streaming session and apd_barycenters have one kernel
+ *   family each and route nothing: bit-identical for every penalty.
+ *
+ * The band.  warping_band_percentage: the band of a pair is (pct * (float)max(n, m)) as usize, ONE f32 product truncated with
+ * Rust's saturating cast (discovery.rs:40): NaN, negatives, -0.0 and products below 1 give 0; float32(0.7) * 10 is 7, not 6.
+ * warping_band: any u64.  Either way the window is w = max(min(band, max(n, m)), |n - m|) + 2 (alignments.rs:173 with the band
+ * clamped first): a band >= max(n, m) already spans the whole matrix, so 1.5, 1e10, 1e30, +INF, 2^32 - 1, 2^32 and UINT64_MAX
+ * all equal the full band.  DEVIATION, deliberate: for a band within 2 of usize::MAX the reference's `+ 2` overflows (a panic in
+ * a debug build, w = 1 in a release build); here, and in the checkers (oracle/apd_oracle.h), the band is the full matrix.
+ * apd_discovery_alignment_params saturates to UINT64_MAX as the cast does; an explicit band beyond 0xFFFFFFF0 is held as
+ * 0xFFFFFFF0 internally, which the clamp makes indistinguishable.  apd_spot and its family read no band.
+ *
+ * APD_ERR_BAND_TOO_WIDE.  The literal kernel keeps two DP rows of 2w + 1 offsets in LDS: 2w + 1 <= 20 480.  A call that must run
+ * it -- a non-positive, infinite or NaN penalty, or frames outside the fast kernels' feature range -- over a pair with a wider
+ * window (lengths beyond 10 237 under a full band) returns APD_ERR_BAND_TOO_WIDE before anything is enqueued or written.  The
+ * path and barycenter calls have the same limit for every penalty (below). */
+
 /* The four Discovery fields the path reads (src/discovery.rs:17-20, project/config/Discovery.toml:17-20). */
 typedef struct apd_align_config {
     float warping_band_percentage;

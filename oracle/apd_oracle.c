@@ -52,10 +52,18 @@ static uint64_t diff_usize(uint64_t n, uint64_t m) { return n > m ? n - m : 0; }
 static uint64_t max_u64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 static uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
+/* alignments.rs:173: w = max(band, |n-m|) + 2, with the band clamped to max(n, m) first (apd_oracle.h, "the band's domain"):
+ * a band >= max(n, m) already spans the whole matrix, so the clamp changes no cell set the reference defines, and w stays far
+ * from the usize overflow at which the reference itself is undefined.  w <= max(n, m) + 2, so i + w cannot wrap either. */
+static uint64_t dtw_w(uint64_t n, uint64_t m, uint64_t band)
+{
+    return max_u64(min_u64(band, max_u64(n, m)), abs_usize(n, m)) + 2;
+}
+
 /* alignments.rs:173-175: w = max(band, |n-m|) + 2; i in 1..=n; j in max(i-w,1)..min(i+w, m+1) */
 uint64_t orc_dtw_cells(uint64_t n, uint64_t m, uint64_t band)
 {
-    uint64_t w = max_u64(band, abs_usize(n, m)) + 2;
+    uint64_t w = dtw_w(n, m, band);
     uint64_t cells = 0;
     for (uint64_t i = 1; i <= n; i++) {
         uint64_t lo = max_u64(diff_usize(i, w), 1);
@@ -90,7 +98,7 @@ float orc_dtw_pair(const float *x, uint64_t n, const float *y, uint64_t m, uint3
 {
     if (n == 0 && m == 0) return ORC_INF;         /* alignments.rs:117-118 */
     if (n == 0 || m == 0) return NAN;             /* usize underflow at :120 -- undefined */
-    uint64_t w = max_u64(band, abs_usize(n, m)) + 2;   /* :173 */
+    uint64_t w = dtw_w(n, m, band);               /* :173 */
     float *buf = (float *)malloc(sizeof(float) * 2 * (m + 3));
     if (!buf) return NAN;
     float *prev = buf, *cur = buf + (m + 3);
@@ -189,7 +197,7 @@ float orc_dtw_pair_hashmap(const float *x, uint64_t n, const float *y, uint64_t 
     if (n == 0 || m == 0) return NAN;
     hm_map sparse; hm_init(&sparse);
     hm_insert(&sparse, 0, 0, 0.0f);                               /* :109 */
-    uint64_t w = max_u64(band, abs_usize(n, m)) + 2;              /* :173 */
+    uint64_t w = dtw_w(n, m, band);                               /* :173 */
     for (uint64_t i = 1; i <= n; i++) {
         uint64_t lo = max_u64(diff_usize(i, w), 1), hi = min_u64(i + w, m + 1);
         for (uint64_t j = lo; j < hi; j++) {

@@ -32,6 +32,22 @@ float orc_euclidean(const float *x, const float *y, uint32_t dim);
 /* discovery.rs:38-45 -- warping_band = (pct * n_size as f32) as usize (saturating cast). */
 uint64_t orc_warping_band(float pct, uint64_t n_size);
 
+/* THE BAND'S DOMAIN (a definition, not a restatement).  alignments.rs:173 computes
+ * w = usize::max(params.warping_band, |n-m|) + 2.  A percentage of 1e30 or +INF saturates the
+ * band to usize::MAX (discovery.rs:40, `as usize`), and the + 2 then overflows: a panic in a
+ * debug build of the reference, w = 1 in a release build -- the reference is undefined there.
+ * Every checker of this project (this file, oracle/np_reference.py, tests/_path_reference.py and
+ * what is built on it) and the product define instead:
+ *
+ *     w = max(min(band, max(n, m)), |n-m|) + 2
+ *
+ * A band >= max(n, m) already spans the whole matrix, so for every band at which the reference's
+ * arithmetic does not overflow the clamp changes no cell: where it does overflow, the band is the
+ * full matrix.  NaN and negative percentages give band 0 (Rust's saturating `as usize`); any f32
+ * penalty is taken as it is (0, negative, +-INF, NaN: the arithmetic is IEEE, the select of
+ * alignments.rs:153-159 sends every comparison with a NaN to MATCH).  No lo, hi or index below is
+ * derived from a wrapped value. */
+
 /* alignments.rs:165-180 loop bounds -- number of (i,j) cells construct_alignment visits. */
 uint64_t orc_dtw_cells(uint64_t n, uint64_t m, uint64_t band);
 

@@ -95,12 +95,15 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+_U64_MAX = (1 << 64) - 1                           # a band beyond usize::MAX is usize::MAX (ctypes would wrap it)
+
+
 def warping_band(pct, n_size):
     return int(lib().orc_warping_band(float(pct), int(n_size)))
 
 
 def dtw_cells(n, m, band):
-    return int(lib().orc_dtw_cells(int(n), int(m), int(band)))
+    return int(lib().orc_dtw_cells(int(n), int(m), min(int(band), _U64_MAX)))
 
 
 def dtw_pair(x, y, band, ins=1.0, dele=1.0, match=1.0, hashmap=False):
@@ -108,7 +111,7 @@ def dtw_pair(x, y, band, ins=1.0, dele=1.0, match=1.0, hashmap=False):
     x, y = _f32(x), _f32(y)
     dim = x.shape[1] if x.ndim == 2 else y.shape[1]
     fn = lib().orc_dtw_pair_hashmap if hashmap else lib().orc_dtw_pair
-    return float(fn(_p(x, C.c_float), x.shape[0], _p(y, C.c_float), y.shape[0], dim, int(band),
+    return float(fn(_p(x, C.c_float), x.shape[0], _p(y, C.c_float), y.shape[0], dim, min(int(band), _U64_MAX),
                     float(ins), float(dele), float(match)))
 
 

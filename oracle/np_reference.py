@@ -18,18 +18,32 @@ INF = F(np.inf)
 def euclidean(x, y):
     """numerics.rs:114-120"""
     d = F(0.0)
-    for a, b in zip(x, y):
-        t = F(a) - F(b)
-        d = F(d + F(t * t))
-    return F(np.sqrt(d))
+    with np.errstate(all="ignore"):
+        for a, b in zip(x, y):
+            t = F(a) - F(b)
+            d = F(d + F(t * t))
+        return F(np.sqrt(d))
+
+
+U64_MAX = (1 << 64) - 1
 
 
 def warping_band(pct, n_size):
-    """discovery.rs:38-45 -- f32 product, saturating truncation."""
-    v = F(pct) * F(n_size)
+    """discovery.rs:38-45 -- f32 product, saturating truncation (Rust `as usize`: NaN and negatives 0, anything at or beyond
+    2^64, +INF included, usize::MAX)."""
+    with np.errstate(all="ignore"):
+        v = F(pct) * F(n_size)
     if np.isnan(v) or v <= 0:
         return 0
+    if v >= F(2.0 ** 64):
+        return U64_MAX
     return int(v)
+
+
+def window(n, m, band):
+    """alignments.rs:173 with the band clamped to max(n, m) first (oracle/apd_oracle.h, "the band's domain"): where the reference's
+    usize arithmetic overflows, the band is the full matrix."""
+    return max(min(int(band), max(n, m)), abs(n - m)) + 2
 
 
 def dtw_pair(x, y, band, ins=1.0, dele=1.0, match=1.0):
@@ -41,24 +55,25 @@ def dtw_pair(x, y, band, ins=1.0, dele=1.0, match=1.0):
     sparse = {(0, 0): F(0.0)}                       # :109
     if n == 0 and m == 0:
         return INF                                  # :117-118
-    w = max(band, abs(n - m)) + 2                   # :173
-    for i in range(1, n + 1):                       # :174
-        for j in range(max(i - w, 1) if i > w else 1, min(i + w, m + 1)):   # :175
-            d = euclidean(x[i - 1], y[j - 1])       # :137
-            ms = sparse.get((i - 1, j - 1), INF)    # :139
-            is_ = sparse.get((i - 1, j), INF)       # :144
-            ds = sparse.get((i, j - 1), INF)        # :149
-            if ds < ms and ds < is_:                # :153
-                node = F(ds + F(dele * d))
-            elif is_ < ms and is_ < ds:             # :155
-                node = F(is_ + F(ins * d))
-            else:
-                node = F(ms + F(match * d))         # :158
-            sparse[(i, j)] = node                   # :177
-    cell = sparse.get((n - 1, m - 1))               # :120
-    if cell is None:
-        return INF
-    return F(cell / F(n + m))                       # :121
+    w = window(n, m, band)                          # :173
+    with np.errstate(all="ignore"):                 # 0 * INF, INF - INF, overflow: IEEE results, wanted as they are
+        for i in range(1, n + 1):                       # :174
+            for j in range(max(i - w, 1) if i > w else 1, min(i + w, m + 1)):   # :175
+                d = euclidean(x[i - 1], y[j - 1])       # :137
+                ms = sparse.get((i - 1, j - 1), INF)    # :139
+                is_ = sparse.get((i - 1, j), INF)       # :144
+                ds = sparse.get((i, j - 1), INF)        # :149
+                if ds < ms and ds < is_:                # :153
+                    node = F(ds + F(dele * d))
+                elif is_ < ms and is_ < ds:             # :155
+                    node = F(is_ + F(ins * d))
+                else:
+                    node = F(ms + F(match * d))         # :158
+                sparse[(i, j)] = node                   # :177
+        cell = sparse.get((n - 1, m - 1))               # :120
+        if cell is None:
+            return INF
+        return F(cell / F(n + m))                       # :121
 
 
 def align_all(seqs, band_pct, ins=1.0, dele=1.0, match=1.0):

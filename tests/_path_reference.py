@@ -14,13 +14,25 @@ MATCH, INSERT, DELETE, START = 0, 1, 2, 3
 STEP = np.dtype([("i", np.uint32), ("j", np.uint32), ("cost", np.float32), ("op", np.uint32)])
 
 
+U64_MAX = (1 << 64) - 1
+
+
 def band_from_pct(pct, length):
-    """discovery.rs:38-45: f32 product, saturating truncation."""
+    """discovery.rs:38-45: f32 product, saturating truncation (Rust `as usize`): NaN and negatives give 0, a product at or beyond
+    2^64 (+INF included) gives usize::MAX.  Never raises."""
     with np.errstate(all="ignore"):
         v = F(pct) * F(length)
     if np.isnan(v) or v <= 0:
         return 0
+    if v >= F(2.0 ** 64):
+        return U64_MAX
     return int(v)
+
+
+def window(n, m, band):
+    """alignments.rs:173, the band clamped to max(n, m) first (oracle/apd_oracle.h, "the band's domain"): where the reference's
+    usize arithmetic overflows, the band is the full matrix."""
+    return max(min(int(band), max(n, m)), abs(n - m)) + 2
 
 
 def sq_distances(x, y):
@@ -50,21 +62,21 @@ def table(x, y, band, ins=1.0, dele=1.0, match=1.0):
     d = distances(x, y)
     with np.errstate(all="ignore"):
         weighted = {MATCH: F(match) * d, INSERT: F(ins) * d, DELETE: F(dele) * d}      # pen * d, rounded on its own
-    w = max(band, abs(n - m)) + 2                                                      # :173
-    for i in range(1, n + 1):                                                          # :174
-        for j in range(max(i - w, 1), min(i + w, m + 1)):                              # :175
-            ms = sparse.get((i - 1, j - 1), INF)                                       # :139
-            is_ = sparse.get((i - 1, j), INF)                                          # :144
-            ds = sparse.get((i, j - 1), INF)                                           # :149
-            if ds < ms and ds < is_:                                                   # :153
-                op, pred = DELETE, ds
-            elif is_ < ms and is_ < ds:                                                # :155
-                op, pred = INSERT, is_
-            else:
-                op, pred = MATCH, ms                                                   # :158
-            with np.errstate(all="ignore"):
+    w = window(n, m, band)                                                             # :173
+    with np.errstate(all="ignore"):                                                    # comparisons with NaN included
+        for i in range(1, n + 1):                                                      # :174
+            for j in range(max(i - w, 1), min(i + w, m + 1)):                          # :175
+                ms = sparse.get((i - 1, j - 1), INF)                                   # :139
+                is_ = sparse.get((i - 1, j), INF)                                      # :144
+                ds = sparse.get((i, j - 1), INF)                                       # :149
+                if ds < ms and ds < is_:                                               # :153
+                    op, pred = DELETE, ds
+                elif is_ < ms and is_ < ds:                                            # :155
+                    op, pred = INSERT, is_
+                else:
+                    op, pred = MATCH, ms                                               # :158
                 sparse[(i, j)] = F(pred + weighted[op][i - 1, j - 1])                  # :177
-            branch[(i, j)] = op
+                branch[(i, j)] = op
     return sparse, branch
 
 

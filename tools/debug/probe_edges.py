@@ -1,4 +1,5 @@
-"""Edge-case probes of the C ABI through the Python mirror (run on the GPU box)."""
+"""Edge-case probes of the C ABI through the Python mirror (run on the GPU box).  Degenerate penalties and band percentages are
+not probed here: tests/test_gpu_config_edges.py pins them."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 from audio_pattern_discovery_amd import _lib, synth
@@ -30,8 +31,6 @@ g, w = run([rng.standard_normal((n, 13)).astype(np.float32) for n in [1, 1, 2, 2
 a = rng.standard_normal((200, 13)).astype(np.float32)
 g, w = run([a.copy() for _ in range(20)]); print("20 identical sequences all zero:", bool(np.all(g == 0)), same(g, w))
 g, w = run([rng.standard_normal((n, 300)).astype(np.float32) for n in (30, 41, 52, 17)], pct=0.3); print("dim 300 (generic):", same(g, w))
-g, w = run([rng.standard_normal((n, 13)).astype(np.float32) for n in (60, 70, 80)], pens=(0.0, 1.0, 1.0)); print("zero penalty (generic):", same(g, w))
-g, w = run([rng.standard_normal((n, 13)).astype(np.float32) for n in (60, 70, 80)], pens=(-0.5, 1.0, 1.0)); print("negative penalty (generic):", same(g, w))
 bad = [rng.standard_normal((n, 13)).astype(np.float32) for n in (60, 70, 300, 90)]
 bad[1][10, 3] = np.nan; bad[2][5, 0] = np.inf
 g, _ = run(bad); print("NaN / INF features: returned", g.shape, "finite entries", int(np.isfinite(g).sum()))
