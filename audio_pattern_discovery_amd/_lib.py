@@ -48,11 +48,18 @@ class PathStep(C.Structure):
 
 
 APD_PATH_MATCH, APD_PATH_INSERT, APD_PATH_DELETE, APD_PATH_START = 0, 1, 2, 3
+APD_DETECT_PER_PAIR, APD_DETECT_PER_STREAM = 0, 1
 
 
 class SpotBest(C.Structure):
     """apd_spot_best: a matched window of a stream -- 1-based columns of its last and first frame, the bits of T[n][end], the score."""
     _fields_ = [("end", C.c_uint32), ("start", C.c_uint32), ("cost", C.c_float), ("score", C.c_float)]
+
+
+class SpotHit(C.Structure):
+    """apd_spot_hit: a window apd_spot_detect accepted -- its pair, columns as in apd_spot_best, the curve's bits, the rank in its group."""
+    _fields_ = [("pair", C.c_uint32), ("end", C.c_uint32), ("start", C.c_uint32), ("cost", C.c_float), ("score", C.c_float),
+                ("rank", C.c_uint32)]
 
 
 class SpotWindow(C.Structure):
@@ -173,6 +180,8 @@ SYMBOLS = [
                                       C.POINTER(PathStep), C.c_uint64, _u64p, _f32p]),
     ("apd_spot", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, _f32p, _u32p, C.c_uint64, _u64p, C.POINTER(SpotBest)]),
     ("apd_spot_hits", C.c_int, [_f32p, _u32p, C.c_uint64, C.c_uint64, C.c_float, C.POINTER(SpotBest), C.c_uint64, _u64p]),
+    ("apd_spot_detect", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, _f32p, C.c_int, C.POINTER(SpotHit), C.c_uint64, _u64p,
+                                  _u64p, _u64p]),
     ("apd_spot_path_bound", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
     ("apd_spot_paths", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), C.POINTER(SpotWindow), C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p,
                                  _u32p, _u32p, _f32p]),

@@ -95,6 +95,10 @@ SPOT_BEST = np.dtype([("end", np.uint32), ("start", np.uint32), ("cost", np.floa
 # apd_spot_window as a numpy record: what AlignmentWorkers.spot_paths() hands to the library
 SPOT_WINDOW = np.dtype([("x", np.uint32), ("y", np.uint32), ("end", np.uint32), ("start", np.uint32)])
 
+# apd_spot_hit as a numpy record: what AlignmentWorkers.detect() returns
+SPOT_HIT = np.dtype([("pair", np.uint32), ("end", np.uint32), ("start", np.uint32), ("cost", np.float32), ("score", np.float32),
+                     ("rank", np.uint32)])
+
 
 class Alignment:
     """alignments.rs:99-181.  construct_alignment runs the HIP kernel.  The DP table `sparse` is not materialised as a whole; with
@@ -290,6 +294,42 @@ class AlignmentWorkers:
             if streams is not None:
                 batch.close()
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(n_pairs)], best
+
+    def detect(self, pairs, params, thresholds, per_stream=False, streams=None, capacity=None):
+        """Spot detection (include/apd.h, "spot detection"): spot() and spot_hits() in one call on the device.  pairs, params and
+        `streams` as for spot(); thresholds: one value for all pairs or one per pair.  per_stream=False: every pair picks its own
+        non-overlapping windows; True: the pairs of the list that share a stream compete for its columns.  capacity: hits to hold
+        (None: a bound that always suffices).  Returns (hits as a SPOT_HIT array, group-major; hit_off, groups + 1 entries; groups:
+        the stream number of every group with per_stream, else its pair index): apd_spot_detect.  With a capacity below the total
+        only the first `capacity` hits are returned; hit_off stays exact."""
+        if self._multi is not None or (streams is not None and streams._multi is not None):
+            raise ValueError("detect() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_pairs = len(pr)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (n_pairs,)))
+        if per_stream:
+            _, first = np.unique(pr[:, 1], return_index=True)
+            groups = pr[np.sort(first), 1].astype(np.uint32)              # distinct streams in order of first appearance
+        else:
+            groups = np.arange(n_pairs, dtype=np.uint32)
+        lens = [len(s.frames) for s in self.data] + ([len(s.frames) for s in streams.data] if streams is not None else [])
+        if capacity is None:
+            known = not n_pairs or int(pr.max()) < len(lens)             # a wrong index is the library's to refuse
+            capacity = int(sum(lens[int(y)] for y in (groups if per_stream else pr[:, 1]))) if known else 0
+        hits = np.zeros(max(int(capacity), 1), dtype=SPOT_HIT)
+        off = np.zeros(n_pairs + 1, dtype=np.uint64)
+        n_groups, n_hits = C.c_uint64(0), C.c_uint64(0)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
+        try:
+            _lib.check(_lib.lib().apd_spot_detect(self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs,
+                                                  thr.ctypes.data_as(f32p), int(bool(per_stream)), hits.ctypes.data_as(C.POINTER(_lib.SpotHit)),
+                                                  int(capacity), off.ctypes.data_as(u64p), C.byref(n_groups), C.byref(n_hits)), self.ctx.handle)
+        finally:
+            if streams is not None:
+                batch.close()
+        return hits[:min(int(n_hits.value), int(capacity))].copy(), off[:n_groups.value + 1].copy(), groups
 
     def spot_paths(self, pairs, windows, params, streams=None):
         """Warping paths of spotted windows (include/apd.h, "warping paths of spotted windows"): window k is columns windows[k]["start"]

@@ -1438,6 +1438,184 @@ extern "C" int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t 
     return APD_OK;
 }
 
+// ----------------------------------------------------------------------------------------- spot detection
+
+// apd_spot's sweep into the workspace, then candidates, greedy picking and the packed hits on the device (kernels:
+// dtw_spot_detect.hip).  A chunk is a run of whole groups; its pairs are numbered group by group.
+// ws_spot: [cost | start | candidates | accepted windows | sweep pairs, detect pairs, groups (uploaded) | best | candidate counts,
+// hit counts (zeroed) | hit bases]; ws_spot_hits: the chunk's packed hits, sized once its hit counts are known.
+extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+                               const float *thresholds, int compete, apd_spot_hit *hits, uint64_t capacity, uint64_t *hit_off,
+                               uint64_t *n_groups, uint64_t *n_hits)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
+    if ((compete != APD_DETECT_PER_PAIR && compete != APD_DETECT_PER_STREAM) || (n_pairs && !thresholds) || !hit_off || !n_groups || !n_hits ||
+        (capacity && !hits))
+        return APD_ERR_INVALID_ARG;
+    const uint32_t n_seq = batch->n_seq;
+    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
+    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
+    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    *n_groups = 0;
+    *n_hits = 0;
+    hit_off[0] = 0;
+    if (n_pairs == 0) return APD_OK;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (len_of(pairs[2 * p]) > kSpotMaxQuery || len_of(pairs[2 * p + 1]) >= kSpotMaxStream) {
+            ctx->last_error = "apd_spot_detect: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
+            return APD_ERR_UNSUPPORTED;
+        }
+    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // as apd_spot
+    // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
+    std::vector<uint64_t> group_of(n_pairs), member_first, members(n_pairs);
+    uint64_t ng = 0;
+    if (compete == APD_DETECT_PER_PAIR) {
+        ng = n_pairs;
+        for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
+    } else {
+        std::vector<uint64_t> group_of_stream(n_seq, ~0ull);
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            uint64_t &g = group_of_stream[pairs[2 * p + 1]];
+            if (g == ~0ull) g = ng++;
+            group_of[p] = g;
+        }
+    }
+    member_first.assign(ng + 1, 0);
+    for (uint64_t p = 0; p < n_pairs; ++p) ++member_first[group_of[p] + 1];
+    for (uint64_t g = 0; g < ng; ++g) {
+        if (member_first[g + 1] > kMaxPairsPerLaunch) {
+            ctx->last_error = "apd_spot_detect: a group of more than 2^24 pairs";
+            return APD_ERR_UNSUPPORTED;
+        }
+        member_first[g + 1] += member_first[g];
+    }
+    {
+        std::vector<uint64_t> fill(member_first.begin(), member_first.end() - 1);
+        for (uint64_t p = 0; p < n_pairs; ++p) members[fill[group_of[p]]++] = p;
+    }
+    auto stream_len = [&](uint64_t g) { return (uint64_t)len_of(pairs[2 * members[member_first[g]] + 1]); };
+    auto group_pairs = [&](uint64_t g) { return member_first[g + 1] - member_first[g]; };
+    *n_groups = ng;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot detect launch");
+    const uint64_t cap = spot_workspace_cap();
+    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
+    constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t) + sizeof(ulonglong2), kStageBytes = sizeof(uint2);
+    auto pad16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    std::vector<char> upload;
+    std::vector<uint32_t> counts;
+    bool first_chunk = true;
+    for (uint64_t g0 = 0; g0 < ng;) {
+        // the chunk of groups [g0, g1): at least one, then as many as keep the curves, the candidates and the windows under the cap
+        uint64_t g1 = g0, entries = 0, stage_slots = 0, np = 0;
+        while (g1 < ng) {
+            const uint64_t ne = entries + group_pairs(g1) * stream_len(g1), ns = stage_slots + stream_len(g1);
+            if (g1 > g0 && (ne * kEntryBytes + ns * kStageBytes > cap || np + group_pairs(g1) > kMaxPairsPerLaunch)) break;
+            entries = ne; stage_slots = ns; np += group_pairs(g1);
+            ++g1;
+        }
+        const uint64_t ngc = g1 - g0;
+        // what is uploaded: [sweep pairs by kernel class | detect pairs | groups]
+        const size_t desc_bytes = pad16((size_t)np * sizeof(SpotPair)), dp_bytes = (size_t)np * sizeof(SpotDetectPair);
+        const size_t grp_bytes = (size_t)ngc * sizeof(SpotDetectGroup);
+        upload.assign(desc_bytes + dp_bytes + grp_bytes, 0);
+        SpotPair *desc = (SpotPair *)upload.data();
+        SpotDetectPair *dp = (SpotDetectPair *)(upload.data() + desc_bytes);
+        SpotDetectGroup *grp = (SpotDetectGroup *)(upload.data() + desc_bytes + dp_bytes);
+        uint64_t class_count[kClasses] = {}, class_first[kClasses] = {};
+        uint32_t r_max = 1, m_max = 1;
+        uint64_t k = 0, off = 0, stage_off = 0;
+        for (uint64_t g = g0; g < g1; ++g) {
+            SpotDetectGroup &G = grp[g - g0];
+            const uint32_t m = (uint32_t)stream_len(g);
+            G.cand_off = off; G.cand_cap = group_pairs(g) * m; G.stage_off = stage_off; G.stage_cap = m;
+            stage_off += m;
+            m_max = std::max(m_max, m);
+            for (uint64_t t = member_first[g]; t < member_first[g + 1]; ++t, ++k) {
+                const uint64_t p = members[t];
+                SpotDetectPair &d = dp[k];
+                d.curve_off = off; d.m = m; d.n = len_of(pairs[2 * p]); d.threshold = thresholds[p];
+                d.group = (uint32_t)(g - g0); d.pair = (uint32_t)p;
+                off += m;
+                const uint32_t c = spot_row_class(batch->dim, d.n);
+                ++class_count[c];
+                if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(d.n));
+            }
+        }
+        for (uint32_t c = 1; c < kClasses; ++c) class_first[c] = class_first[c - 1] + class_count[c - 1];
+        uint64_t fill[kClasses];
+        std::copy(class_first, class_first + kClasses, fill);
+        for (k = 0; k < np; ++k) {
+            const uint64_t p = dp[k].pair;
+            SpotPair &d = desc[fill[spot_row_class(batch->dim, dp[k].n)]++];
+            d.px = pos[pairs[2 * p]];
+            d.py = pos[pairs[2 * p + 1]];
+            d.out = (uint32_t)k;
+            d.pad = 0;
+            d.curve_off = dp[k].curve_off;
+        }
+        const size_t curve_bytes = pad16((size_t)entries * 4), cand_bytes = (size_t)entries * sizeof(ulonglong2);
+        const size_t stage_bytes = pad16((size_t)stage_slots * sizeof(uint2)), best_bytes = (size_t)np * sizeof(apd_spot_best);
+        const size_t cc_bytes = (size_t)ngc * sizeof(unsigned long long), hc_bytes = pad16((size_t)ngc * sizeof(uint32_t));
+        const size_t hb_bytes = (size_t)(ngc + 1) * sizeof(unsigned long long);
+        rc = reserve_ws(ctx, ctx->ws_spot, 2 * curve_bytes + cand_bytes + stage_bytes + upload.size() + best_bytes + cc_bytes + hc_bytes + hb_bytes + 16);
+        if (rc) return rc;
+        char *base = ctx->ws_spot.as<char>();
+        char *d_upload = base + 2 * curve_bytes + cand_bytes + stage_bytes, *d_counts = d_upload + upload.size() + best_bytes;
+        SpotLaunch L{};
+        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
+        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
+        L.d_cost = (float *)base;
+        L.d_start = (uint32_t *)(base + curve_bytes);
+        const SpotPair *d_desc = (const SpotPair *)d_upload;
+        L.d_best = (apd_spot_best *)(d_upload + upload.size());
+        SpotDetectLaunch D{};
+        D.d_cost = L.d_cost; D.d_start = L.d_start;
+        D.d_pairs = (const SpotDetectPair *)(d_upload + desc_bytes); D.n_pairs = (uint32_t)np;
+        D.d_groups = (const SpotDetectGroup *)(d_upload + desc_bytes + dp_bytes); D.n_groups = (uint32_t)ngc;
+        D.d_cand = (ulonglong2 *)(base + 2 * curve_bytes);
+        D.d_stage = (uint2 *)(base + 2 * curve_bytes + cand_bytes);
+        D.d_cand_count = (unsigned long long *)d_counts;
+        D.d_hit_count = (uint32_t *)(d_counts + cc_bytes);
+        D.d_hit_base = (unsigned long long *)(d_counts + cc_bytes + hc_bytes);
+        HIP_TRY(ctx, hipMemcpyAsync(d_upload, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, cc_bytes + hc_bytes, ctx->stream));
+        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        for (uint32_t c = 0; c < kClasses; ++c) {
+            L.d_pairs = d_desc + class_first[c];
+            L.n_pairs = (uint32_t)class_count[c];
+            HIP_TRY(ctx, launch_spot(L, c, r_max, ctx->stream));
+        }
+        HIP_TRY(ctx, launch_spot_detect(D, m_max, ctx->stream));
+        counts.resize(ngc);
+        HIP_TRY(ctx, hipMemcpyAsync(counts.data(), D.d_hit_count, (size_t)ngc * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the packed buffer is sized by the counts
+        const uint64_t chunk_first = hit_off[g0];
+        for (uint64_t g = g0; g < g1; ++g) hit_off[g + 1] = hit_off[g] + counts[g - g0];
+        const uint64_t chunk_hits = hit_off[g1] - chunk_first;
+        const uint64_t n_write = capacity > chunk_first ? std::min(chunk_hits, capacity - chunk_first) : 0;
+        if (n_write) {
+            rc = reserve_ws(ctx, ctx->ws_spot_hits, (size_t)n_write * sizeof(apd_spot_hit));
+            if (rc) return rc;
+            HIP_TRY(ctx, launch_spot_detect_emit(D, ctx->ws_spot_hits.as<apd_spot_hit>(), n_write, ctx->stream));
+        }
+        if (ctx->timing && g1 == ng) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        if (n_write) {
+            HIP_TRY(ctx, hipMemcpyAsync(hits + chunk_first, ctx->ws_spot_hits.ptr, (size_t)n_write * sizeof(apd_spot_hit), hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `upload`)
+        g0 = g1;
+        first_chunk = false;
+    }
+    *n_hits = hit_off[ng];
+    return APD_OK;
+}
+
 // ------------------------------------------------------------------- warping paths of spotted windows
 
 extern "C" uint64_t apd_spot_path_bound(uint64_t n, uint64_t end, uint64_t start)

@@ -325,6 +325,42 @@ void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
 
+// ---- spot detection (dtw_spot_detect.hip): candidates and greedy non-overlapping picking on the curves launch_spot left in the
+// workspace.  A chunk holds whole groups; its pairs are numbered group by group (a group's pairs adjacent, in the caller's order), so
+// a group's curve entries are one stretch and its candidate list -- one 16-byte slot per entry at most -- lies at the same offset.
+struct SpotDetectPair {
+    uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
+    uint32_t m, n;         // frames of the stream and of the query
+    float threshold;
+    uint32_t group;        // of the chunk
+    uint32_t pair;         // the caller's index into `pairs`
+    uint32_t pad;
+};
+struct SpotDetectGroup {
+    uint64_t cand_off;     // first slot of the group's candidate list in d_cand = first curve entry of its first pair
+    uint64_t cand_cap;     // its slots: the group's curve entries
+    uint64_t stage_off;    // first slot of the group's accepted windows in d_stage
+    uint32_t stage_cap;    // its slots: frames of the group's stream (disjoint windows cover one column each at least)
+    uint32_t pad;
+};
+struct SpotDetectLaunch {
+    const float *d_cost;
+    const uint32_t *d_start;
+    const SpotDetectPair *d_pairs;
+    uint32_t n_pairs;
+    const SpotDetectGroup *d_groups;
+    uint32_t n_groups;
+    ulonglong2 *d_cand;                  // (sortable score << 32 | end, pair of the chunk << 32 | start)
+    unsigned long long *d_cand_count;    // [n_groups], zeroed by the caller
+    uint2 *d_stage;                      // (pair of the chunk, end) in acceptance order
+    uint32_t *d_hit_count;               // [n_groups]
+    unsigned long long *d_hit_base;      // [n_groups + 1] exclusive prefix of d_hit_count
+};
+// marking, picking and the prefix of the hit counts; m_max: the longest stream among the pairs
+hipError_t launch_spot_detect(const SpotDetectLaunch &L, uint32_t m_max, hipStream_t stream);
+// d_hits[0 .. n_write): the chunk's first n_write hits, group-major
+hipError_t launch_spot_detect_emit(const SpotDetectLaunch &L, apd_spot_hit *d_hits, uint64_t n_write, hipStream_t stream);
+
 // ---- streaming spotting (dtw_spot_stream.hip): the sweep above entered and left in mid-stream.  A session (apd_spot_stream) keeps,
 // per pair p = channel n_queries + q, the last pushed column of the table and the running best on the device; a push sweeps every
 // channel's chunk from there.  Query rows come from the templates' batch, stream columns from the session's staging buffer.
@@ -623,7 +659,8 @@ struct apd_context {
     apd::DeviceBuf ws_path_dirs;      // apd_align_paths: direction words of a chunk of pairs
     apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
     apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters in the resident layout, sums, counts, descriptors of every chunk
-    apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]
+    apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]; apd_spot_detect: see there
+    apd::DeviceBuf ws_spot_hits;      // apd_spot_detect: the packed hits of a chunk
     apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
     apd::DeviceBuf ws_spot_steps;     // ... its steps, then [pairs | intervals | ends | end cost | end start | windows | lengths | found | scores]
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score

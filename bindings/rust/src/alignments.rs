@@ -151,6 +151,55 @@ pub fn spot(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery
     best
 }
 
+/// Not in the reference: spot detection.  Every template against every stream on the first device of APD_DEVICES (apd_batch_join +
+/// apd_spot_detect), pair p = t * streams.len() + r as for spot(); thresholds: one per pair.  per_stream = false: every pair picks its
+/// own non-overlapping windows, group g = pair g; true: the templates compete for the columns of each stream, group g = stream g.
+/// Returns (hits, group-major and in acceptance order inside a group; hit_off, groups + 1 entries).
+pub fn detect(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery, thresholds: &[f32], per_stream: bool) -> (Vec<apd_spot_hit>, Vec<u64>) {
+    let (n1, n2) = (templates.len(), streams.len());
+    if n1 == 0 || n2 == 0 { return (Vec::new(), vec![0u64]); }
+    assert_eq!(thresholds.len(), n1 * n2, "one threshold per pair");
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let pack = |set: &[NDSequence]| {
+        let mut offsets = vec![0u64; set.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in set.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        (frames, offsets)
+    };
+    let dim = templates[0].n_bins as u32;
+    let ((fa, oa), (fb, ob)) = (pack(templates), pack(streams));
+    let mut pairs: Vec<u32> = Vec::with_capacity(2 * n1 * n2);
+    for t in 0..n1 { for r in 0..n2 { pairs.push(t as u32); pairs.push((n1 + r) as u32); } }
+    // a group has no more hits than its stream has frames
+    let frames_of = |r: usize| (ob[r + 1] - ob[r]) as usize;
+    let capacity: usize = if per_stream { (0..n2).map(frames_of).sum() } else { n1 * (0..n2).map(frames_of).sum::<usize>() };
+    let mut hits = vec![apd_spot_hit::default(); capacity.max(1)];
+    let mut hit_off = vec![0u64; n1 * n2 + 1];
+    let (mut n_groups, mut n_hits) = (0u64, 0u64);
+    let compete = if per_stream { APD_DETECT_PER_STREAM } else { APD_DETECT_PER_PAIR };
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let (mut a, mut b, mut j) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        check(apd_batch_create(ctx, fa.as_ptr(), oa.as_ptr(), n1 as u32, dim, 0, &mut a));
+        check(apd_batch_create(ctx, fb.as_ptr(), ob.as_ptr(), n2 as u32, dim, 0, &mut b));
+        check(apd_batch_join(ctx, a, b, &mut j));
+        let rc = apd_spot_detect(ctx, j, &cfg, pairs.as_ptr(), (n1 * n2) as u64, thresholds.as_ptr(), compete, hits.as_mut_ptr(), capacity as u64, hit_off.as_mut_ptr(), &mut n_groups, &mut n_hits);
+        apd_destroy(ctx);                                                 // releases the device side of the three batches
+        for h in [j, b, a] { apd_batch_destroy(h); }
+        check(rc);
+    }
+    hits.truncate(n_hits as usize);
+    hit_off.truncate(n_groups as usize + 1);
+    (hits, hit_off)
+}
+
 /// Not in the reference: a streaming spotting session on the first device of APD_DEVICES (apd_spot_stream_*): every template against
 /// `channels` streams that arrive in chunks.  Pair p = channel * templates.len() + t; the curves of the pushes, one after the other,
 /// are apd_spot's curves of the whole stream, bit for bit, whatever the chunking.  Owns its context and the templates' batch.

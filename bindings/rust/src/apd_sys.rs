@@ -66,6 +66,19 @@ pub struct apd_spot_best {
     pub score: f32,
 }
 
+/// A window apd_spot_detect accepted: its pair, columns as in apd_spot_best, the curve's bits, the acceptance rank in its group.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct apd_spot_hit {
+    pub pair: u32,
+    pub end: u32,
+    pub start: u32,
+    pub cost: f32,
+    pub score: f32,
+    pub rank: u32,
+}
+pub const APD_DETECT_PER_PAIR: c_int = 0;
+pub const APD_DETECT_PER_STREAM: c_int = 1;
+
 /// A window of stream y matched to query x (apd_spot_paths): end and start as in apd_spot_best.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct apd_spot_window {
@@ -203,6 +216,10 @@ extern "C" {
                     cost: *mut f32, start: *mut u32, capacity: u64, curve_off: *mut u64, best: *mut apd_spot_best) -> c_int;
     pub fn apd_spot_hits(cost: *const f32, start: *const u32, m: u64, n: u64, threshold: f32, hits: *mut apd_spot_best,
                          capacity: u64, n_hits: *mut u64) -> c_int;
+    // spot detection
+    pub fn apd_spot_detect(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, pairs: *const u32, n_pairs: u64,
+                           thresholds: *const f32, compete: c_int, hits: *mut apd_spot_hit, capacity: u64, hit_off: *mut u64,
+                           n_groups: *mut u64, n_hits: *mut u64) -> c_int;
     // warping paths of spotted windows
     pub fn apd_spot_path_bound(n: u64, end: u64, start: u64) -> u64;
     pub fn apd_spot_paths(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, windows: *const apd_spot_window,

@@ -58,8 +58,8 @@ typedef struct apd_cepstrum_plan apd_cepstrum_plan;   /* window, filterbank, DCT
  *   multi-device and one-call forms): a call in which ANY penalty is <= 0 (-0.0 included), +INF or NaN runs the literal kernel
  *   alone (the fast kernels need pen * INF = INF); apd_set_variant does not override that.  Positive finite penalties run the
  *   fast kernels: equal ones within 1e-4 relative of the CPU code (bit-identical in distance mode 2), unequal ones bit-identical.
- *   apd_align_paths, apd_align_pair_path, apd_spot, apd_spot_paths, the streaming session and apd_barycenters have one kernel
- *   family each and route nothing: bit-identical for every penalty.
+ *   apd_align_paths, apd_align_pair_path, apd_spot, apd_spot_detect, apd_spot_paths, the streaming session and apd_barycenters have
+ *   one kernel family each and route nothing: bit-identical for every penalty.
  *
  * The band.  warping_band_percentage: the band of a pair is (pct * (float)max(n, m)) as usize, ONE f32 product truncated with
  * Rust's saturating cast (discovery.rs:40): NaN, negatives, -0.0 and products below 1 give 0; float32(0.7) * 10 is 7, not 6.
@@ -470,6 +470,48 @@ int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *c
  * may exceed capacity.  n == 0: APD_ERR_INVALID_ARG. */
 int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t m, uint64_t n, float threshold, apd_spot_best *hits,
                   uint64_t capacity, uint64_t *n_hits);
+
+/* ---- spot detection: apd_spot and apd_spot_hits in one call on the device, per pair or with the templates of a stream competing --
+ * Table, curves, score: exactly apd_spot's -- free start, no band, ALWAYS the literal arithmetic (apd_set_distance_mode is not
+ * read); score(j) = cost / (float)(n + (j - start + 1)), one f32 division.  The curves never leave the device; only hits come back.
+ * Candidates: column j of pair p is a candidate if score(j) < thresholds[p] (strict, as apd_spot_hits; a NaN score is never a
+ * candidate, a NaN threshold gives none).  A column whose start is 0 is never a candidate: its alignment ran through column 0, so
+ * its cost is +INF or NaN whatever the penalties (T[i][0] = +INF, and +INF plus any pen * d is +INF or NaN).
+ * Groups.  APD_DETECT_PER_PAIR: group g is pair g -- apd_spot + apd_spot_hits, pair by pair.  APD_DETECT_PER_STREAM: group g is the
+ * g-th distinct stream number y in order of first appearance in `pairs`, and all pairs of the list with that y belong to it, adjacent
+ * in the list or not; a repeated pair is a member like any other.
+ * Order inside a group: ascending score by f32 < (so -0.0 and +0.0 tie), then the smaller end, then the smaller pair index.  A group
+ * holds one candidate per (pair, end), so this is a strict total order and the result depends on nothing else -- not on the
+ * workspace cap, not on scheduling.
+ * Greedy: candidates are taken in that order; one is accepted iff its window [start, end] shares no column with an accepted window
+ * of its group.
+ * Output: hits group-major, in acceptance order inside a group (rank 0, 1, ...); group g owns hits[hit_off[g] .. hit_off[g+1]).
+ * hit_off (*n_groups + 1 entries; n_pairs + 1 slots always suffice), *n_groups and *n_hits are exact whatever `capacity`; only hits
+ * whose global index is below `capacity` are written, nothing past it; hits == NULL with capacity == 0: counts only.  Disjoint windows
+ * cover one column each at least, so a group has no more hits than its stream has frames: the sum over the groups of the frames of
+ * the group's stream is a capacity that always suffices.
+ * Errors, each before anything is launched: whatever apd_spot refuses, with its code (a pair index >= the batch's sequence count or
+ * a batch of another context APD_ERR_INVALID_ARG, an empty sequence in the batch APD_ERR_EMPTY_SEQUENCE, a query of more than 16 384
+ * frames or a stream at apd_spot's limit APD_ERR_UNSUPPORTED); compete other than 0 or 1, thresholds == NULL with n_pairs > 0,
+ * hit_off, n_groups or n_hits NULL, capacity > 0 with hits == NULL: APD_ERR_INVALID_ARG; a group of more than 2^24 pairs:
+ * APD_ERR_UNSUPPORTED.  n_pairs == 0: zero groups, hit_off[0] = 0, APD_OK.
+ * Follows apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the sweep and the detection kernels of the
+ * call (all chunks).
+ * Workspace: per curve entry 8 bytes of curves and a 16-byte candidate slot, plus 8 bytes per group and frame of its stream (the
+ * accepted windows) -- 24 to 32 bytes per entry -- and 24 bytes per hit written.  A long list is cut into chunks of WHOLE groups
+ * that keep this under 1 GiB (APD_SPOT_WORKSPACE_BYTES overrides the cap: tests only); a chunk holds at least one group even if
+ * that group alone exceeds the cap; results identical whatever the cap. */
+typedef struct apd_spot_hit {
+    uint32_t pair;         /* index into `pairs` */
+    uint32_t end, start;   /* 1-based stream columns, as apd_spot_best */
+    float    cost, score;  /* the bits of apd_spot's curve at `end` and of its score there */
+    uint32_t rank;         /* acceptance rank inside the hit's group, 0 = first accepted */
+} apd_spot_hit;            /* 24 bytes */
+#define APD_DETECT_PER_PAIR   0   /* every pair is its own group: apd_spot + apd_spot_hits, pair by pair */
+#define APD_DETECT_PER_STREAM 1   /* all pairs of the list that share a stream y compete for its columns */
+int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+                    const float *thresholds, int compete, apd_spot_hit *hits, uint64_t capacity, uint64_t *hit_off,
+                    uint64_t *n_groups, uint64_t *n_hits);
 
 /* ---- warping paths of spotted windows: which query frame was matched to which stream frame inside a window ----------------------
  * Table: exactly apd_spot's T and S -- free start, no band, always the literal arithmetic -- with every cell also remembering the
