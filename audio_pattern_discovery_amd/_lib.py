@@ -194,6 +194,9 @@ SYMBOLS = [
     ("apd_spot_stream_history", C.c_int, [_vp, C.c_uint32, _u64p, _u64p]),
     ("apd_spot_stream_paths", C.c_int, [_vp, _vp, C.POINTER(SpotWindow), C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p, _u32p, _u32p,
                                         _f32p]),
+    ("apd_spot_stream_detect", C.c_int, [_vp, _vp, _f32p, C.c_int, C.c_uint32]),
+    ("apd_spot_stream_flush", C.c_int, [_vp, _vp, C.c_uint32]),
+    ("apd_spot_stream_hits", C.c_int, [_vp, _vp, C.POINTER(SpotHit), C.c_uint64, _u64p]),
     ("apd_percentile", C.c_int, [_vp, _vp, C.c_uint64, C.c_float, C.c_int, _f32p]),
     ("apd_clustering", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_float, C.POINTER(ClusterOp), _u32p, _u32p,
                                  _u32p, _f32p]),

@@ -527,6 +527,41 @@ class SpotStream:
         _lib.check(L.apd_spot_stream_push(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(self.n_pairs)], best
 
+    NEVER = 0xFFFFFFFF                                            # a holdoff whose timer never fires
+
+    def detect(self, thresholds, per_stream=False, holdoff=0):
+        """Arms the online detector (include/apd.h, "streaming spotting, online detection"), or arms it again: from the channels'
+        current columns on, every push also runs the hold-off machine on the device and queues its hits.  thresholds: one value, one
+        per query or the full (channels, queries) matrix; None disarms.  per_stream=False: every pair is its own group; True: the
+        queries of a channel compete for its columns.  holdoff: columns after a pending window's end at which it is final (NEVER:
+        only a later disjoint candidate or flush() emits it).  Arming again and disarming discard pending windows and hits not yet
+        drained: flush() and hits() first.  apd_spot_stream_detect."""
+        if thresholds is None:
+            _lib.check(_lib.lib().apd_spot_stream_detect(self.ctx.handle, self.handle, None, 0, 0), self.ctx.handle)
+            return
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (self.channels, len(self.queries))))
+        _lib.check(_lib.lib().apd_spot_stream_detect(self.ctx.handle, self.handle, thr.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     int(bool(per_stream)), int(holdoff)), self.ctx.handle)
+
+    def flush(self, channel=None):
+        """Emits the pending windows of `channel` (None: every channel) as if their timers had fired; the stream may go on:
+        apd_spot_stream_flush."""
+        _lib.check(_lib.lib().apd_spot_stream_flush(self.ctx.handle, self.handle, self.ALL if channel is None else int(channel)),
+                   self.ctx.handle)
+
+    def hits(self):
+        """Drains the queue: every hit emitted since the last drain as a SPOT_HIT array (what AlignmentWorkers.detect returns),
+        ascending group, then ascending rank, whatever the chunking of the pushes; empty on a session that is not armed:
+        apd_spot_stream_hits.  hits[k] as a window for paths(): x = pair % len(queries), y = pair // len(queries), end, start."""
+        L = _lib.lib()
+        n = C.c_uint64(0)
+        _lib.check(L.apd_spot_stream_hits(self.ctx.handle, self.handle, None, 0, C.byref(n)), self.ctx.handle)
+        out = np.zeros(int(n.value), dtype=SPOT_HIT)
+        if len(out):
+            _lib.check(L.apd_spot_stream_hits(self.ctx.handle, self.handle, out.ctypes.data_as(C.POINTER(_lib.SpotHit)), len(out), C.byref(n)),
+                       self.ctx.handle)
+        return out
+
     def reset(self, channel=None, first_column=0):
         """A fresh table for `channel` (None: every channel); its next frame is absolute column first_column + 1."""
         _lib.check(_lib.lib().apd_spot_stream_reset(self.ctx.handle, self.handle, self.ALL if channel is None else int(channel),

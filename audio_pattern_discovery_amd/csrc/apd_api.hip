@@ -1830,6 +1830,24 @@ struct apd_spot_stream : apd::ContextChild {
     std::vector<uint32_t> q_len, q_pos; // per query: frames, resident position
     std::vector<uint32_t> wpl_before;   // per pair p: the sum of ceil(R / 16) over the pairs before it (and the total behind the last)
     apd::DeviceBuf d_hist_dirs, d_hist_curves, d_hist_frames, d_hist_wpl;
+    // the online detector (apd_spot_stream_detect; kernels: dtw_spot_online.hip); a session that is not armed holds none of it and
+    // a push runs the kernels it ran before there was one
+    bool armed = false;
+    uint32_t det_per_stream = 0, det_holdoff = 0, det_groups = 0;
+    apd::DeviceBuf d_det_pairs, d_det_state, d_det_count;
+    apd::DeviceBuf d_det_queue;         // det_cap records, the first det_queued of them queued, in arrival order
+    uint64_t det_cap = 0, det_queued = 0;
+    unsigned long long h_det_count = 0; // where a push's copy of *d_det_count lands (alive as long as the session)
+    SpotOnlineLaunch online() const
+    {
+        SpotOnlineLaunch L{};
+        L.d_push = d_push.as<uint32_t>();
+        L.n_channels = n_channels; L.n_queries = n_queries;
+        L.per_stream = det_per_stream; L.holdoff = det_holdoff; L.n_groups = det_groups;
+        L.d_pairs = d_det_pairs.as<SpotOnlinePair>(); L.d_state = d_det_state.as<SpotOnlineState>();
+        L.d_queue = d_det_queue.as<apd_spot_hit>(); L.d_count = d_det_count.as<unsigned long long>(); L.queue_cap = det_cap;
+        return L;
+    }
     SpotHistory rings() const
     {
         SpotHistory H{};
@@ -1866,8 +1884,31 @@ struct apd_spot_stream : apd::ContextChild {
     {
         d_pairs.reset(); d_state.reset(); d_best.reset(); d_push.reset(); d_raw.reset(); d_stage.reset(); d_curves.reset();
         d_hist_dirs.reset(); d_hist_curves.reset(); d_hist_frames.reset(); d_hist_wpl.reset();
+        d_det_pairs.reset(); d_det_state.reset(); d_det_count.reset(); d_det_queue.reset();
     }
 };
+
+// Room for `extra` more hits behind the queued ones, made before the launch that may emit them: no hit is ever dropped.  Growth
+// allocates first -- a refusal is APD_ERR_OOM with nothing enqueued and the session untouched -- then moves the queued records over.
+static int spot_online_reserve(apd_context *ctx, apd_spot_stream *s, uint64_t extra)
+{
+    const uint64_t need = s->det_queued + extra;
+    if (need <= s->det_cap) return APD_OK;
+    const uint64_t cap = std::max(need, 2 * s->det_cap);
+    apd::DeviceBuf grown;
+    if (grown.alloc((size_t)cap * sizeof(apd_spot_hit)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->last_error = "apd_spot_stream: no device memory for a queue of " + std::to_string(cap) + " hits";
+        return APD_ERR_OOM;
+    }
+    if (s->det_queued) {
+        HIP_TRY(ctx, hipMemcpyAsync(grown.ptr, s->d_det_queue.ptr, (size_t)s->det_queued * sizeof(apd_spot_hit), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the old queue is released below
+    }
+    s->d_det_queue = std::move(grown);
+    s->det_cap = cap;
+    return APD_OK;
+}
 
 extern "C" int apd_spot_stream_create(apd_context *ctx, const apd_batch *templates, const apd_align_config *cfg, const uint32_t *queries,
                                       uint32_t n_queries, uint32_t n_channels, apd_spot_stream **stream)
@@ -1956,6 +1997,8 @@ extern "C" int apd_spot_stream_reset(apd_context *ctx, apd_spot_stream *stream, 
     HIP_TRY(ctx, bind_device(ctx));
     APD_AFFINITY(ctx, "spot stream reset");
     HIP_TRY(ctx, launch_spot_stream_reset(stream->launch(), channel, ctx->stream));
+    // an armed session: the channel's pending windows go, its floors move to the new origin; ranks and queued hits stay
+    if (stream->armed) HIP_TRY(ctx, launch_spot_online_touch(stream->online(), channel, false, (uint32_t)first_column, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t k = 0; k < stream->n_channels; ++k)
         if (all || k == channel) stream->columns[k] = stream->origin[k] = first_column;   // either half holds column 0 now: the parity stays; the history is empty
@@ -2005,14 +2048,23 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
     const size_t best_bytes = (size_t)s->n_pairs * sizeof(apd_spot_best);
     if (total > 0) {
         // buffers: grown to the largest push seen, then reused
-        const size_t curve_bytes = curves ? ((size_t)entries * 4 + 15) / 16 * 16 : 0;
+        // an armed session: the detector reads the curves on the device whether or not the caller asked for them on the host
+        const bool stored = curves || s->armed;
+        const size_t curve_bytes = stored ? ((size_t)entries * 4 + 15) / 16 * 16 : 0;
         HIP_TRY(ctx, s->d_stage.reserve((size_t)(total + 2) * t->dpad * sizeof(float)));
-        if (curves) HIP_TRY(ctx, s->d_curves.reserve(2 * curve_bytes));
+        if (stored) HIP_TRY(ctx, s->d_curves.reserve(2 * curve_bytes));
         const size_t raw_bytes = (size_t)total * dim * sizeof(float);
         if (!frames_on_device) HIP_TRY(ctx, s->d_raw.reserve(raw_bytes));
+        if (s->armed) {
+            // a group emits at most (chunk columns + 1) hits per push, and none on a channel without columns
+            uint64_t bound = 0;
+            for (uint32_t k = 0; k < n_ch; ++k)
+                if (chunk_off[k + 1] > chunk_off[k]) bound += (chunk_off[k + 1] - chunk_off[k] + 1) * (s->det_per_stream ? 1u : n_q);
+            if (const int rc = spot_online_reserve(ctx, s, bound)) return rc;
+        }
         S = s->launch();
-        S.d_cost = curves ? s->d_curves.as<float>() : nullptr;
-        S.d_start = curves ? (uint32_t *)(s->d_curves.as<char>() + curve_bytes) : nullptr;
+        S.d_cost = stored ? s->d_curves.as<float>() : nullptr;
+        S.d_start = stored ? (uint32_t *)(s->d_curves.as<char>() + curve_bytes) : nullptr;
         // the words of this push
         uint32_t *w = s->h_push.data(), *pad = w + 3 * (size_t)n_ch + 1;
         for (uint32_t k = 0; k <= n_ch; ++k) w[k] = (uint32_t)chunk_off[k];
@@ -2040,6 +2092,14 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
             if (s->history) HIP_TRY(ctx, launch_spot_stream_record(A, c, s->r_max, ctx->stream));
             else HIP_TRY(ctx, launch_spot_stream(S, c, s->r_max, ctx->stream));
         }
+        if (s->armed) {
+            SpotOnlineLaunch O = s->online();
+            O.d_cost = S.d_cost; O.d_start = S.d_start;
+            uint64_t m_max = 0;
+            for (uint32_t k = 0; k < n_ch; ++k) m_max = std::max(m_max, chunk_off[k + 1] - chunk_off[k]);
+            HIP_TRY(ctx, launch_spot_online_scan(O, m_max, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&s->h_det_count, O.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        }
         if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
         // the table has moved on, whatever the copies below do
         for (uint32_t k = 0; k < n_ch; ++k) {
@@ -2053,6 +2113,94 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
     }
     if (best) HIP_TRY(ctx, hipMemcpyAsync(best, S.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's, `frames` is free again
+    if (s->armed && total > 0) s->det_queued = s->h_det_count;            // the queued count came back with that synchronisation
+    return APD_OK;
+}
+
+// ---- the online detector of a session: apd_spot_stream_detect / _flush / _hits (include/apd.h; kernels: dtw_spot_online.hip)
+
+extern "C" int apd_spot_stream_detect(apd_context *ctx, apd_spot_stream *stream, const float *thresholds, int compete, uint32_t holdoff)
+{
+    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
+    if (compete != APD_DETECT_PER_PAIR && compete != APD_DETECT_PER_STREAM) return APD_ERR_INVALID_ARG;
+    apd_spot_stream *s = stream;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream detector");
+    if (!thresholds) {
+        s->d_det_pairs.reset(); s->d_det_state.reset(); s->d_det_count.reset(); s->d_det_queue.reset();
+        s->armed = false;
+        s->det_groups = 0; s->det_cap = s->det_queued = 0;
+        return APD_OK;
+    }
+    const uint32_t n_q = s->n_queries, groups = compete == APD_DETECT_PER_STREAM ? s->n_channels : s->n_pairs;
+    std::vector<SpotOnlinePair> pairs(s->n_pairs);
+    for (uint32_t p = 0; p < s->n_pairs; ++p) { pairs[p].n = s->q_len[p % n_q]; pairs[p].threshold = thresholds[p]; }
+    // every group: no pending window, rank 0, the floor at its channel's current column (the detector's origin)
+    std::vector<SpotOnlineState> state(groups, SpotOnlineState{});
+    for (uint32_t g = 0; g < groups; ++g) state[g].floor = (uint32_t)s->columns[compete == APD_DETECT_PER_STREAM ? g : g / n_q];
+    // the new buffers first: a refusal leaves the session as it was, armed or not
+    apd::DeviceBuf d_pairs, d_state, d_count, d_queue;
+    const uint64_t cap = s->d_det_queue ? s->det_cap : std::max<uint64_t>(groups, 64);
+    if (d_pairs.alloc(pairs.size() * sizeof(SpotOnlinePair)) != hipSuccess || d_state.alloc(state.size() * sizeof(SpotOnlineState)) != hipSuccess ||
+        d_count.alloc(sizeof(unsigned long long)) != hipSuccess ||
+        (!s->d_det_queue && d_queue.alloc((size_t)cap * sizeof(apd_spot_hit)) != hipSuccess)) {
+        (void)hipGetLastError();
+        ctx->last_error = "apd_spot_stream_detect: no device memory for " + std::to_string(groups) + " groups";
+        return APD_ERR_OOM;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_pairs.ptr, pairs.data(), pairs.size() * sizeof(SpotOnlinePair), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_state.ptr, state.data(), state.size() * sizeof(SpotOnlineState), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_count.ptr, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    s->d_det_pairs = std::move(d_pairs); s->d_det_state = std::move(d_state); s->d_det_count = std::move(d_count);
+    if (!s->d_det_queue) s->d_det_queue = std::move(d_queue);             // arming again keeps the queue's memory and discards its hits
+    s->det_cap = cap; s->det_queued = 0;
+    s->det_per_stream = (uint32_t)compete; s->det_holdoff = holdoff; s->det_groups = groups;
+    s->armed = true;
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_flush(apd_context *ctx, apd_spot_stream *stream, uint32_t channel)
+{
+    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
+    apd_spot_stream *s = stream;
+    if (channel != 0xFFFFFFFFu && channel >= s->n_channels) return APD_ERR_INVALID_ARG;
+    if (!s->armed) {
+        ctx->last_error = "apd_spot_stream_flush: the session is not armed (apd_spot_stream_detect)";
+        return APD_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream flush");
+    if (const int rc = spot_online_reserve(ctx, s, s->det_groups)) return rc;   // one pending window per group at most
+    const SpotOnlineLaunch O = s->online();
+    HIP_TRY(ctx, launch_spot_online_touch(O, channel, true, 0u, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&s->h_det_count, O.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    s->det_queued = s->h_det_count;
+    return APD_OK;
+}
+
+extern "C" int apd_spot_stream_hits(apd_context *ctx, apd_spot_stream *stream, apd_spot_hit *hits, uint64_t capacity, uint64_t *n_hits)
+{
+    if (!ctx || !stream || stream->ctx != ctx || !n_hits) return APD_ERR_INVALID_ARG;
+    apd_spot_stream *s = stream;
+    *n_hits = s->armed ? s->det_queued : 0;
+    if (*n_hits == 0 || capacity < *n_hits) return APD_OK;                // too small: nothing written, nothing consumed
+    if (!hits) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot stream hits");
+    std::vector<apd_spot_hit> h((size_t)*n_hits);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), s->d_det_queue.ptr, h.size() * sizeof(apd_spot_hit), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->d_det_count.ptr, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    s->det_queued = 0;
+    // the queue holds arrival order, which depends on scheduling; (group, rank) is unique and does not
+    const uint32_t per_group = s->det_per_stream ? s->n_queries : 1u;
+    std::sort(h.begin(), h.end(), [&](const apd_spot_hit &a, const apd_spot_hit &b) {
+        const uint32_t ga = a.pair / per_group, gb = b.pair / per_group;
+        return ga != gb ? ga < gb : a.rank < b.rank;
+    });
+    std::copy(h.begin(), h.end(), hits);
     return APD_OK;
 }
 

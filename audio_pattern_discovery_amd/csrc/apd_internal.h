@@ -486,6 +486,43 @@ struct SpotRingTraceLaunch {
 };
 hipError_t launch_spot_stream_trace(const SpotRingTraceLaunch &L, hipStream_t stream);
 
+// ---- online spot detection (dtw_spot_online.hip): the hold-off machine of an armed session (include/apd.h, "streaming spotting,
+// online detection").  It reads the curves a push's sweeps have just left in the session's buffer -- pair p = channel n_queries + q
+// owns the m entries of its channel's chunk behind those of the pairs before it, so a channel's pairs are adjacent -- and keeps 32
+// bytes of state per group.  Group g is pair g, or (per_stream) channel g with its n_queries pairs.
+struct SpotOnlinePair {
+    uint32_t n;            // frames of the pair's query
+    float threshold;
+};
+struct SpotOnlineState {
+    uint32_t pair, end, start;   // the pending window P; end == 0: none (an absolute column is >= 1)
+    float cost, score;           // the curve's bits at `end` and the score taken from them
+    uint32_t floor;              // F: the end of the group's last emitted hit, or its origin
+    uint32_t rank;               // emissions since arming
+    uint32_t pad;
+};
+struct SpotOnlineLaunch {
+    const float *d_cost;             // the push's curves (scan only)
+    const uint32_t *d_start;
+    const uint32_t *d_push;          // SpotStreamLaunch::d_push of the same push (scan only)
+    uint32_t n_channels, n_queries;
+    uint32_t per_stream;             // 0: a group per pair, 1: a group per channel
+    uint32_t holdoff;                // 0xFFFFFFFF: the timer never fires
+    uint32_t n_groups;
+    const SpotOnlinePair *d_pairs;   // [n_channels n_queries] by p
+    SpotOnlineState *d_state;        // [n_groups]
+    apd_spot_hit *d_queue;           // emitted hits in arrival order (the drain orders them); queue_cap slots
+    unsigned long long *d_count;     // hits queued
+    uint64_t queue_cap;
+};
+// One workgroup per group walks its channel's chunk; a group of a channel whose chunk is empty does nothing.  Appends at most
+// (chunk columns + 1) hits per group: the caller has sized the queue for that.  m_max: the longest chunk of the push (it sizes the
+// workgroup: one wavefront per 64 columns, 16 at most and no more than fill the chip once; the hits do not depend on it).
+hipError_t launch_spot_online_scan(const SpotOnlineLaunch &L, uint64_t m_max, hipStream_t stream);
+// The groups of `channel` (0xFFFFFFFF: all).  flush: a pending window is emitted and becomes the floor.  Otherwise (a reset): the
+// pending window is dropped and the floor becomes first_column; the rank stays.  Appends at most one hit per group.
+hipError_t launch_spot_online_touch(const SpotOnlineLaunch &L, uint32_t channel, bool flush, uint32_t first_column, hipStream_t stream);
+
 // One launch of the alignment kernel that geometry g names, cut into launches below 2^31 work-items.
 hipError_t launch_align(const AlignLaunch &L, KernelGeom g, hipStream_t stream, std::string &err, int *status);
 // The generic kernel over ALL tiles of L as a small persistent grid that does nothing unless *L.d_nonfinite is set.

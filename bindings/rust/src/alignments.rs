@@ -290,6 +290,31 @@ impl SpotStream {
         }
         (0..k).map(|p| (steps[off[p] as usize..off[p] as usize + len[p] as usize].to_vec(), found[p], scores[p])).collect()
     }
+    /// Arms the online detector, or arms it again (pending windows and undrained hits are discarded: flush() and hits() first).
+    /// thresholds: [channels][templates], None disarms.  per_stream = false: every pair is its own group; true: the templates of a
+    /// channel compete.  holdoff: columns after a pending window's end at which it is final; u32::MAX: the timer never fires.
+    pub fn detect(&mut self, thresholds: Option<&[f32]>, per_stream: bool, holdoff: u32) {
+        let compete = if per_stream { APD_DETECT_PER_STREAM } else { APD_DETECT_PER_PAIR };
+        let ptr = match thresholds {
+            Some(t) => { assert_eq!(t.len(), self.n_pairs); t.as_ptr() }
+            None => std::ptr::null(),
+        };
+        unsafe { check(apd_spot_stream_detect(self.ctx, self.handle, ptr, compete, holdoff)); }
+    }
+    /// Emits the pending windows of `channel` (None: every channel) as if their timers had fired; the stream may go on.
+    pub fn flush(&mut self, channel: Option<u32>) {
+        unsafe { check(apd_spot_stream_flush(self.ctx, self.handle, channel.unwrap_or(0xFFFF_FFFF))); }
+    }
+    /// Drains the queue: the hits emitted since the last drain, ascending group, then ascending rank.
+    pub fn hits(&mut self) -> Vec<apd_spot_hit> {
+        let mut n: u64 = 0;
+        unsafe { check(apd_spot_stream_hits(self.ctx, self.handle, std::ptr::null_mut(), 0, &mut n)); }
+        let mut hits = vec![apd_spot_hit::default(); n as usize];
+        if n > 0 {
+            unsafe { check(apd_spot_stream_hits(self.ctx, self.handle, hits.as_mut_ptr(), n, &mut n)); }
+        }
+        hits
+    }
 }
 
 impl Drop for SpotStream {

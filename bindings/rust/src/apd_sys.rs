@@ -240,6 +240,12 @@ extern "C" {
     pub fn apd_spot_stream_paths(ctx: *mut apd_context, stream: *mut apd_spot_stream, windows: *const apd_spot_window, n_windows: u64,
                                  steps: *mut apd_path_step, capacity: u64, step_off: *mut u64, path_len: *mut u32,
                                  found_start: *mut u32, scores: *mut f32) -> c_int;
+    // streaming spotting, online detection
+    pub fn apd_spot_stream_detect(ctx: *mut apd_context, stream: *mut apd_spot_stream, thresholds: *const f32, compete: c_int,
+                                  holdoff: u32) -> c_int;
+    pub fn apd_spot_stream_flush(ctx: *mut apd_context, stream: *mut apd_spot_stream, channel: u32) -> c_int;
+    pub fn apd_spot_stream_hits(ctx: *mut apd_context, stream: *mut apd_spot_stream, hits: *mut apd_spot_hit, capacity: u64,
+                                n_hits: *mut u64) -> c_int;
     // numerics::percentile, AgglomerativeClustering
     pub fn apd_percentile(ctx: *mut apd_context, x: *const f32, len: u64, perc: f32, x_on_device: c_int, value: *mut f32) -> c_int;
     pub fn apd_clustering(ctx: *mut apd_context, distances: *const f32, distances_on_device: c_int, n: u32, perc: f32,

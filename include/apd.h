@@ -648,6 +648,63 @@ int apd_spot_stream_paths(apd_context *ctx, apd_spot_stream *stream, const apd_s
                           apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len, uint32_t *found_start,
                           float *scores);
 
+/* ---- streaming spotting, online detection: hold-off hits from a session, the curves never leaving the device ---------------------
+ * apd_spot_detect takes candidates in global score order, so on a stream a hit would be final only when the stream ends.  An armed
+ * session runs another contract: a causal machine per group, a function of the curves alone -- so the chunking of the pushes
+ * changes nothing -- that reports a hit at most holdoff + 1 columns after the hit's end.
+ * Candidates: column j (absolute, as a push reports it) of session pair p = channel * n_queries + q is a candidate iff
+ * score(j) < thresholds[p] and start(j) != 0, with score(j) = cost / (float)(n + (j - start + 1)) on the bits a push would put in
+ * its curves: the sweep's own expression, one f32 division.  The test is strict; a NaN on either side gives no candidate, a NaN
+ * threshold none at all (apd_spot_detect's rules).
+ * Groups.  APD_DETECT_PER_PAIR: group g is pair g.  APD_DETECT_PER_STREAM: group g is channel g and its n_queries pairs compete: at
+ * column j the group has at most ONE candidate, the one among its pairs with the smallest score by f32 < (-0.0 and +0.0 tie), the
+ * smaller p among equal scores.  This reduction is part of the definition: the column's other candidates do not exist below.
+ * The machine, per group, over the columns in ascending order.  State: a pending window P or none; a floor F, the end of the
+ * group's last emitted hit; a rank counter.  With c the group's candidate at column j, in this order:
+ *   1. timer: if P exists and j - P.end > holdoff: emit P, F = P.end, no P.
+ *   2. no c: the column is done.
+ *   3. c.start <= F: discard c (it shares a column with an emitted hit).
+ *   4. else no P: P = c.
+ *   5. else c.start <= P.end (overlap; c.end = j > P.end): P = c if c.score < P.score by f32 <, else discard c -- an equal score
+ *      keeps the earlier end.
+ *   6. else (disjoint): emit P, F = P.end, P = c.
+ * Emitting writes an apd_spot_hit: pair = p; end and start absolute; cost and score the curve's bits (a zero score keeps its
+ * sign); rank = the group's emissions since arming, from 0.  holdoff == 0xFFFFFFFF never fires the timer.
+ * Consequences: a group's emitted windows are pairwise disjoint and their ends ascend; a hit is emitted by the push that contains
+ * column end + holdoff + 1, or earlier.
+ * The promise: after any sequence of pushes the hits emitted so far are exactly what the machine emits up to each channel's current
+ * column, the records bit for bit, whatever the chunking -- zero-length chunks and pushes longer or shorter than holdoff included.
+ * A session that is not armed runs the kernels it always ran and returns the bits it always returned.
+ *
+ * apd_spot_stream_detect arms the session, or arms it again; thresholds ([n_channels][n_queries], host) == NULL disarms it and
+ * releases the detector's device memory.  Legal at any time; the table, the curves and the bests of later pushes keep their bits.
+ * Every group starts with no pending window, rank 0 and F = its channel's current column (apd_spot_stream_columns), the detector's
+ * origin as apd_spot_stream_keep's: a window that starts at or before the origin is never reported.  Arming again and disarming
+ * DISCARD pending windows and hits not yet drained: drain first (apd_spot_stream_flush, apd_spot_stream_hits).  compete other than
+ * 0 or 1 (read even when disarming) or a foreign context: APD_ERR_INVALID_ARG.  APD_ERR_OOM leaves the session as it was.
+ * Blocking.  Device memory: 8 bytes per pair, 32 bytes per group, 24 bytes per slot of the hit queue.
+ *
+ * apd_spot_stream_push on an armed session keeps its signature and every rule above ("all three NULL: sizes only, the state is not
+ * advanced" included).  Any other push also runs the machine over the chunk's columns of every group: the sweeps write their
+ * curves to the session's device buffer whether or not the caller asked for them on the host (8 bytes per curve entry of the
+ * largest push seen), one more kernel on the same stream reads them, and emitted hits are appended to a queue on the device.  Still
+ * one synchronisation per push; the count of queued hits comes back with it.  No hit is ever dropped: a group emits at most
+ * (chunk columns + 1) hits per push, and the queue is grown to the queued count plus that bound BEFORE anything is launched; if it
+ * cannot grow: APD_ERR_OOM with nothing enqueued and the state untouched. */
+int apd_spot_stream_detect(apd_context *ctx, apd_spot_stream *stream, const float *thresholds, int compete, uint32_t holdoff);
+/* Emits every pending window of the groups of `channel` (0xFFFFFFFF: every channel) as if its timer had fired, F = the emitted
+ * window's end.  The stream may go on afterwards.  Not armed: APD_ERR_UNSUPPORTED, with a text in apd_last_error; channel >=
+ * n_channels or a foreign context: APD_ERR_INVALID_ARG.  Blocking. */
+int apd_spot_stream_flush(apd_context *ctx, apd_spot_stream *stream, uint32_t channel);
+/* *n_hits = the hits queued.  capacity >= *n_hits: all are written and the queue is emptied.  Otherwise (hits == NULL with
+ * capacity 0 included): nothing is written, nothing is consumed, APD_OK.  Order: ascending group, then ascending rank -- so it does
+ * not depend on how the pushes were cut; a hit's group is its pair (per pair) or pair / n_queries (per stream).  Not armed: *n_hits
+ * = 0, APD_OK.  n_hits == NULL, hits == NULL with hits to write, or a foreign context: APD_ERR_INVALID_ARG.  Blocking.
+ * apd_spot_stream_reset of a channel also clears the pending windows of the channel's groups and sets their F to the new
+ * first_column; the rank is NOT restarted, so (group, rank) stays unique in the queue, and hits already emitted stay queued.
+ * A hit can be handed to apd_spot_stream_paths as the window {x = pair % n_queries, y = pair / n_queries, end, start}. */
+int apd_spot_stream_hits(apd_context *ctx, apd_spot_stream *stream, apd_spot_hit *hits, uint64_t capacity, uint64_t *n_hits);
+
 /* ---- numerics::percentile (src/numerics.rs:125-133) ----------------------------------- */
 /* x: len floats, host or (x_on_device != 0) device. */
 int apd_percentile(apd_context *ctx, const float *x, uint64_t len, float perc, int x_on_device, float *value);
