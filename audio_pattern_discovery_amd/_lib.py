@@ -208,6 +208,13 @@ SYMBOLS = [
     ("apd_cepstrum_plan_create", C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u32p, C.POINTER(_vp)]),
     ("apd_cepstrum_plan_destroy", C.c_int, [_vp]),
     ("apd_cepstrum_batch_async", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("apd_cepstrum_frames", C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    ("apd_feed_create", C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _u32p, C.POINTER(_vp)]),
+    ("apd_feed_destroy", C.c_int, [_vp]),
+    ("apd_feed_reset", C.c_int, [_vp, _vp, C.c_uint32]),
+    ("apd_feed_totals", C.c_int, [_vp, C.c_uint32, _u64p, _u64p]),
+    ("apd_feed_push", C.c_int, [_vp, _vp, _vp, _u64p, C.c_int, _vp, C.c_int, C.c_uint64, _u64p]),
+    ("apd_spot_stream_push_audio", C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_int, _f32p, _u32p, C.c_uint64, _u64p, C.POINTER(SpotBest)]),
     ("apd_stream_busy", C.c_int, [_vp, C.POINTER(C.c_int)]),
     ("apd_debug_affinity_probe", C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     ("apd_encode", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_int, _vp]),

@@ -527,6 +527,25 @@ class SpotStream:
         _lib.check(L.apd_spot_stream_push(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(self.n_pairs)], best
 
+    def push_audio(self, feed, chunks, curves=True, on_device=False):
+        """push() with an AudioFeed in front: `chunks` is what AudioFeed.push takes (int16 samples per channel), the result what
+        push() returns for the frames the feed makes of them; the frames never leave the device: apd_spot_stream_push_audio."""
+        L = _lib.lib()
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        samples, sample_off, _keep = feed._samples(chunks, on_device)
+        off = np.zeros(self.n_pairs + 1, dtype=np.uint64)
+        best = np.zeros(self.n_pairs, dtype=SPOT_BEST)
+        head = (self.ctx.handle, self.handle, feed.handle, samples, sample_off.ctypes.data_as(u64p), int(bool(on_device)))
+        tail = (off.ctypes.data_as(u64p), best.ctypes.data_as(C.POINTER(_lib.SpotBest)))
+        if not curves:
+            _lib.check(L.apd_spot_stream_push_audio(*head, None, None, 0, *tail), self.ctx.handle)
+            return [], best
+        _lib.check(L.apd_spot_stream_push_audio(*head, None, None, 0, off.ctypes.data_as(u64p), None), self.ctx.handle)      # sizes
+        cost = np.zeros(max(int(off[-1]), 1), dtype=np.float32)
+        start = np.zeros(len(cost), dtype=np.uint32)
+        _lib.check(L.apd_spot_stream_push_audio(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
+        return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(self.n_pairs)], best
+
     NEVER = 0xFFFFFFFF                                            # a holdoff whose timer never fires
 
     def detect(self, thresholds, per_stream=False, holdoff=0):
@@ -576,6 +595,94 @@ class SpotStream:
     def close(self):
         if getattr(self, "handle", None):
             _lib.lib().apd_spot_stream_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cepstrum_frames(n_samples, fft_size, fft_step):
+    """apd_cepstrum_frames: the frames NDSequence::new yields for a recording of n_samples (spectrogram.rs:51).  Host only."""
+    return int(_lib.lib().apd_cepstrum_frames(int(n_samples), int(fft_size), int(fft_step)))
+
+
+class AudioFeed:
+    """apd_feed: int16 samples of `channels` live recordings in, in chunks of any length; cepstrum frames (or, with an encoder,
+    their encodings) out.  The frames of the pushes, one after the other, are the bits of apd_cepstrum (+ apd_encode) on the whole
+    recording, whatever the chunking.  encoder: None, a (w_encode [n_bins][latent], b_encode [latent]) pair, or the handle of an
+    apd_encoder of the same context (its weights are copied: it may be destroyed afterwards)."""
+
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, ctx, channels, fft_size, fft_step, filter_size, encoder=None):
+        self.ctx = ctx
+        self.channels = int(channels)
+        self.handle = C.c_void_p()
+        L = _lib.lib()
+        dim = C.c_uint32(0)
+        made = None
+        if isinstance(encoder, tuple):
+            w = np.ascontiguousarray(encoder[0], dtype=np.float32)
+            b = np.ascontiguousarray(encoder[1], dtype=np.float32).ravel()
+            made = C.c_void_p()
+            f32p = C.POINTER(C.c_float)
+            _lib.check(L.apd_encoder_create(ctx.handle, w.ctypes.data_as(f32p), b.ctypes.data_as(f32p), w.shape[0], w.shape[1], C.byref(made)),
+                       ctx.handle)
+            encoder = made
+        try:
+            _lib.check(L.apd_feed_create(ctx.handle, self.channels, int(fft_size), int(fft_step), int(filter_size), encoder, C.byref(dim),
+                                         C.byref(self.handle)), ctx.handle)
+        finally:
+            if made is not None:
+                L.apd_encoder_destroy(made)
+        self.dim = int(dim.value)
+
+    def _samples(self, chunks, on_device):
+        """(samples pointer, sample_off, what must stay alive during the call) of a push."""
+        if on_device:
+            ptr, sample_off = chunks
+            sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+            if len(sample_off) != self.channels + 1:
+                raise ValueError("sample_off needs channels + 1 entries")
+            return C.c_void_p(int(ptr)), sample_off, None
+        if len(chunks) != self.channels:
+            raise ValueError("one chunk per channel")
+        arrays = [np.ascontiguousarray(c, dtype=np.int16).ravel() for c in chunks]
+        sample_off = np.zeros(self.channels + 1, dtype=np.uint64)
+        sample_off[1:] = np.cumsum([len(a) for a in arrays])
+        host = np.ascontiguousarray(np.concatenate(arrays)) if arrays else np.zeros(0, np.int16)
+        return C.c_void_p(host.ctypes.data), sample_off, host
+
+    def push(self, chunks, on_device=False):
+        """One chunk per channel: a list of int16 arrays, any lengths, empty ones allowed; with on_device=True the pair (device
+        pointer of the packed samples, sample_off array of channels + 1 entries).  Returns the new frames, one (frames, dim) float32
+        array per channel: apd_feed_push."""
+        L = _lib.lib()
+        u64p = C.POINTER(C.c_uint64)
+        samples, sample_off, _keep = self._samples(chunks, on_device)
+        off = np.zeros(self.channels + 1, dtype=np.uint64)
+        head = (self.ctx.handle, self.handle, samples, sample_off.ctypes.data_as(u64p), int(bool(on_device)))
+        _lib.check(L.apd_feed_push(*head, None, 0, 0, off.ctypes.data_as(u64p)), self.ctx.handle)                         # sizes
+        rows = np.zeros((max(int(off[-1]), 1), self.dim), dtype=np.float32)
+        _lib.check(L.apd_feed_push(*head, C.c_void_p(rows.ctypes.data), 0, len(rows), off.ctypes.data_as(u64p)), self.ctx.handle)
+        return [rows[int(off[k]):int(off[k + 1])].copy() for k in range(self.channels)]
+
+    def reset(self, channel=None):
+        """The channel (None: every channel) starts a new recording: apd_feed_reset."""
+        _lib.check(_lib.lib().apd_feed_reset(self.ctx.handle, self.handle, self.ALL if channel is None else int(channel)), self.ctx.handle)
+
+    def totals(self, channel):
+        """(samples received, frames emitted) of the channel since its reset: apd_feed_totals."""
+        s, f = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().apd_feed_totals(self.handle, int(channel), C.byref(s), C.byref(f)))
+        return int(s.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.lib().apd_feed_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

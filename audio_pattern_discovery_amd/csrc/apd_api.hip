@@ -2117,6 +2117,32 @@ extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, c
     return APD_OK;
 }
 
+// Raw audio into a session: the feed's push into its own device buffer, then the push above on those rows.  Everything either
+// would refuse is refused before the feed moves on.
+extern "C" int apd_spot_stream_push_audio(apd_context *ctx, apd_spot_stream *stream, apd_feed *feed, const int16_t *samples,
+                                          const uint64_t *sample_off, int samples_on_device, float *cost, uint32_t *start,
+                                          uint64_t capacity, uint64_t *curve_off, apd_spot_best *best)
+{
+    if (!ctx || !stream || stream->ctx != ctx || !feed || !sample_off || !curve_off) return APD_ERR_INVALID_ARG;
+    const apd_context *feed_ctx = nullptr;
+    uint32_t feed_channels = 0, dim = 0;
+    feed_info(feed, &feed_ctx, &feed_channels, &dim);
+    if (feed_ctx != ctx || feed_channels != stream->n_channels || dim != stream->templates->src_dim) return APD_ERR_INVALID_ARG;
+    std::vector<uint64_t> chunk_off((size_t)feed_channels + 1);
+    if (const int rc = feed_sizes(feed, sample_off, chunk_off.data())) return rc;
+    // the session's own checks and curve_off: its sizes-only form
+    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
+    static const float unread = 0.0f;                                     // the sizes-only form wants a frame pointer and does not follow it
+    if (const int rc = apd_spot_stream_push(ctx, stream, &unread, chunk_off.data(), dim, 1, nullptr, nullptr, 0, curve_off, nullptr)) return rc;
+    if (!cost && !best) return APD_OK;                                    // sizes only: neither state is advanced
+    if (cost && capacity < curve_off[stream->n_pairs]) return APD_ERR_INVALID_ARG;
+    if (sample_off[feed_channels] > sample_off[0] && !samples) return APD_ERR_INVALID_ARG;
+    HIP_TRY(ctx, bind_device(ctx));
+    const float *d_rows = nullptr;
+    if (const int rc = feed_enqueue(ctx, feed, samples, sample_off, samples_on_device, chunk_off.data(), &d_rows)) return rc;
+    return apd_spot_stream_push(ctx, stream, d_rows, chunk_off.data(), dim, 1, cost, start, capacity, curve_off, best);
+}
+
 // ---- the online detector of a session: apd_spot_stream_detect / _flush / _hits (include/apd.h; kernels: dtw_spot_online.hip)
 
 extern "C" int apd_spot_stream_detect(apd_context *ctx, apd_spot_stream *stream, const float *thresholds, int compete, uint32_t holdoff)

@@ -621,6 +621,14 @@ struct ContextChild {
 };
 int destroy_child(ContextChild *child);   // the shared body of apd_batch_destroy, apd_comm_destroy, ... (apd_api.hip)
 
+// companions.hip: what apd_spot_stream_push_audio needs of an apd_feed.  feed_sizes: the rows a push would add per channel
+// (frame_off: n_channels + 1, always written; APD_ERR_INVALID_ARG for descending offsets), host only.  feed_enqueue: that push into
+// the feed's own device buffer (*d_rows), enqueued on the context's stream without a synchronisation.
+void feed_info(const apd_feed *feed, const apd_context **ctx, uint32_t *n_channels, uint32_t *dim);
+int feed_sizes(const apd_feed *feed, const uint64_t *sample_off, uint64_t *frame_off);
+int feed_enqueue(apd_context *ctx, apd_feed *feed, const int16_t *samples, const uint64_t *sample_off, int samples_on_device,
+                 const uint64_t *frame_off, const float **d_rows);
+
 // numerics.rs:125-133 on a device array (clustering.hip): radix select of the k-th smallest non-NaN value.
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value);
 uint64_t percentile_index(uint64_t len, float perc);

@@ -2,7 +2,8 @@
 //! 77-93, 99-125, 165), bodies on the MI355X through libapd_hip.so.  UNCOMPILED (no Rust toolchain in the build image).
 use crate::apd_sys::*;
 use crate::discovery::Discovery;
-use crate::spectrogram::NDSequence;
+use crate::neural::AutoEncoder;
+use crate::spectrogram::{AudioFeed, NDSequence};
 use std::collections::HashMap;
 use std::os::raw::c_int;
 use std::sync::{Arc, Mutex};
@@ -252,6 +253,31 @@ impl SpotStream {
         let mut best = vec![apd_spot_best::default(); self.n_pairs];
         unsafe {
             check(apd_spot_stream_push(self.ctx, self.handle, frames.as_ptr(), chunk_off.as_ptr(), self.dim, 0, cost.as_mut_ptr(), start.as_mut_ptr(), entries as u64, curve_off.as_mut_ptr(), best.as_mut_ptr()));
+        }
+        (cost, start, curve_off, best)
+    }
+    /// An AudioFeed on this session's context, one channel per channel of the session; its rows must have the templates' dimension.
+    pub fn audio_feed(&self, fft_size: usize, fft_step: usize, filter_size: usize, nn: Option<&AutoEncoder>) -> AudioFeed {
+        AudioFeed::on(self.ctx, self.channels, fft_size, fft_step, filter_size, nn)
+    }
+    /// push() with the feed in front: chunks[k] is channel k's new int16 samples; the frames never leave the device.
+    pub fn push_audio(&mut self, feed: &mut AudioFeed, chunks: &[&[i16]]) -> (Vec<f32>, Vec<u32>, Vec<u64>, Vec<apd_spot_best>) {
+        assert_eq!(chunks.len(), self.channels);
+        let mut sample_off = vec![0u64; self.channels + 1];
+        let mut samples: Vec<i16> = Vec::new();
+        for (k, c) in chunks.iter().enumerate() {
+            sample_off[k + 1] = sample_off[k] + c.len() as u64;
+            samples.extend_from_slice(c);
+        }
+        let mut curve_off = vec![0u64; self.n_pairs + 1];
+        let mut best = vec![apd_spot_best::default(); self.n_pairs];
+        unsafe {
+            check(apd_spot_stream_push_audio(self.ctx, self.handle, feed.handle, samples.as_ptr(), sample_off.as_ptr(), 0, std::ptr::null_mut(), std::ptr::null_mut(), 0, curve_off.as_mut_ptr(), std::ptr::null_mut()));   // sizes first
+        }
+        let entries = (curve_off[self.n_pairs] as usize).max(1);
+        let (mut cost, mut start) = (vec![0f32; entries], vec![0u32; entries]);
+        unsafe {
+            check(apd_spot_stream_push_audio(self.ctx, self.handle, feed.handle, samples.as_ptr(), sample_off.as_ptr(), 0, cost.as_mut_ptr(), start.as_mut_ptr(), entries as u64, curve_off.as_mut_ptr(), best.as_mut_ptr()));
         }
         (cost, start, curve_off, best)
     }

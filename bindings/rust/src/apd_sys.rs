@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct apd_multi_batch { _p: [u8; 0] }
 #[repr(C)] pub struct apd_encoder { _p: [u8; 0] }
 #[repr(C)] pub struct apd_cepstrum_plan { _p: [u8; 0] }
+#[repr(C)] pub struct apd_feed { _p: [u8; 0] }
 
 pub const APD_OK: c_int = 0;
 pub const APD_ERR_INVALID_ARG: c_int = -1;
@@ -277,6 +278,18 @@ extern "C" {
                                     filter_size: u32, frame_offsets: *mut u64, n_bins: *mut u32, plan: *mut *mut apd_cepstrum_plan) -> c_int;
     pub fn apd_cepstrum_plan_destroy(plan: *mut apd_cepstrum_plan) -> c_int;
     pub fn apd_cepstrum_batch_async(ctx: *mut apd_context, plan: *const apd_cepstrum_plan, d_samples: *const i16, d_out: *mut f32) -> c_int;
+    // raw audio in chunks: a resident front end for a live feed
+    pub fn apd_cepstrum_frames(n_samples: u64, fft_size: u32, fft_step: u32) -> u64;
+    pub fn apd_feed_create(ctx: *mut apd_context, n_channels: u32, fft_size: u32, fft_step: u32, filter_size: u32, encoder: *const apd_encoder,
+                           dim: *mut u32, feed: *mut *mut apd_feed) -> c_int;
+    pub fn apd_feed_destroy(feed: *mut apd_feed) -> c_int;
+    pub fn apd_feed_reset(ctx: *mut apd_context, feed: *mut apd_feed, channel: u32) -> c_int;
+    pub fn apd_feed_totals(feed: *const apd_feed, channel: u32, samples: *mut u64, frames: *mut u64) -> c_int;
+    pub fn apd_feed_push(ctx: *mut apd_context, feed: *mut apd_feed, samples: *const i16, sample_off: *const u64, samples_on_device: c_int,
+                         frames: *mut f32, frames_on_device: c_int, capacity: u64, frame_off: *mut u64) -> c_int;
+    pub fn apd_spot_stream_push_audio(ctx: *mut apd_context, stream: *mut apd_spot_stream, feed: *mut apd_feed, samples: *const i16,
+                                      sample_off: *const u64, samples_on_device: c_int, cost: *mut f32, start: *mut u32, capacity: u64,
+                                      curve_off: *mut u64, best: *mut apd_spot_best) -> c_int;
     pub fn apd_interesting_ranges(ctx: *mut apd_context, frames: *const f32, t: u64, n_bins: u32, moving_average: u32, perc: f32,
                                   min_len: u64, on_device: c_int, ranges: *mut u64, capacity: u64, n_ranges: *mut u64) -> c_int;
     // formats either side of the path (host only)

@@ -118,3 +118,81 @@ impl<'a> Slice<'a> {
         Slice { start, stop, sequence }
     }
 }
+
+/// The frames `NDSequence::new` yields for a recording of n_samples (spectrogram.rs:51): the window that ends exactly at sample n is
+/// not produced.  Host only.
+pub fn cepstrum_frames(n_samples: usize, fft_size: usize, fft_step: usize) -> usize {
+    unsafe { apd_cepstrum_frames(n_samples as u64, fft_size as u32, fft_step as u32) as usize }
+}
+
+/// apd_feed: the int16 samples of `channels` live recordings in, in chunks of any length; cepstrum frames (with an encoder: their
+/// encodings) out.  The frames of the pushes, one after the other, are the bits of `NDSequence::new` (+ `encoded`) on the whole
+/// recording, whatever the chunking.  Lives on the feature context, or on the context of the session it feeds (`on`).
+pub struct AudioFeed {
+    pub(crate) ctx: *mut apd_context,
+    pub(crate) handle: *mut apd_feed,
+    pub channels: usize,
+    pub n_bins: usize,
+}
+
+impl AudioFeed {
+    pub fn new(channels: usize, fft_size: usize, fft_step: usize, filter_size: usize, nn: Option<&AutoEncoder>) -> AudioFeed {
+        AudioFeed::on(feature_context(), channels, fft_size, fft_step, filter_size, nn)
+    }
+    pub(crate) fn on(ctx: *mut apd_context, channels: usize, fft_size: usize, fft_step: usize, filter_size: usize, nn: Option<&AutoEncoder>) -> AudioFeed {
+        let mut feed = AudioFeed { ctx, handle: std::ptr::null_mut(), channels, n_bins: 0 };
+        let mut dim = 0u32;
+        unsafe {
+            let mut encoder: *mut apd_encoder = std::ptr::null_mut();
+            if let Some(nn) = nn {
+                let d_in = (nn.w_encode.flat.len() / nn.n_latent()) as u32;
+                check(apd_encoder_create(ctx, nn.w_encode.flat.as_ptr(), nn.b_encode.flat.as_ptr(), d_in, nn.n_latent() as u32, &mut encoder));
+            }
+            let rc = apd_feed_create(ctx, channels as u32, fft_size as u32, fft_step as u32, filter_size as u32, encoder, &mut dim, &mut feed.handle);
+            if !encoder.is_null() {
+                apd_encoder_destroy(encoder);                               // the feed holds a copy of the weights
+            }
+            check(rc);
+        }
+        feed.n_bins = dim as usize;
+        feed
+    }
+    /// chunks[k]: channel k's new samples, any number of them.  Returns (frames, frame_off): channel k owns the packed rows
+    /// frames[frame_off[k] * n_bins .. frame_off[k + 1] * n_bins).
+    pub fn push(&mut self, chunks: &[&[i16]]) -> (Vec<f32>, Vec<u64>) {
+        assert_eq!(chunks.len(), self.channels);
+        let mut sample_off = vec![0u64; self.channels + 1];
+        let mut samples: Vec<i16> = Vec::new();
+        for (k, c) in chunks.iter().enumerate() {
+            sample_off[k + 1] = sample_off[k] + c.len() as u64;
+            samples.extend_from_slice(c);
+        }
+        let mut frame_off = vec![0u64; self.channels + 1];
+        unsafe {
+            check(apd_feed_push(self.ctx, self.handle, samples.as_ptr(), sample_off.as_ptr(), 0, std::ptr::null_mut(), 0, 0, frame_off.as_mut_ptr()));   // sizes first
+        }
+        let total = frame_off[self.channels] as usize;
+        let mut frames = vec![0f32; total.max(1) * self.n_bins];
+        unsafe {
+            check(apd_feed_push(self.ctx, self.handle, samples.as_ptr(), sample_off.as_ptr(), 0, frames.as_mut_ptr(), 0, total.max(1) as u64, frame_off.as_mut_ptr()));
+        }
+        frames.truncate(total * self.n_bins);
+        (frames, frame_off)
+    }
+    /// channel None: every channel starts a new recording.
+    pub fn reset(&mut self, channel: Option<u32>) {
+        unsafe { check(apd_feed_reset(self.ctx, self.handle, channel.unwrap_or(0xFFFF_FFFF))); }
+    }
+    /// (samples received, frames emitted) of the channel since its reset.
+    pub fn totals(&self, channel: u32) -> (u64, u64) {
+        let (mut samples, mut frames) = (0u64, 0u64);
+        unsafe { check(apd_feed_totals(self.handle, channel, &mut samples, &mut frames)); }
+        (samples, frames)
+    }
+}
+
+impl Drop for AudioFeed {
+    fn drop(&mut self) {
+        unsafe { apd_feed_destroy(self.handle); }
+    }
+}

@@ -839,6 +839,45 @@ int apd_cepstrum_plan_create(apd_context *ctx, const uint64_t *sample_offsets, u
 int apd_cepstrum_plan_destroy(apd_cepstrum_plan *plan);
 int apd_cepstrum_batch_async(apd_context *ctx, const apd_cepstrum_plan *plan, const int16_t *d_samples, float *d_out);
 
+/* ---- raw audio in chunks: a resident front end for a live feed -------------------------- */
+/* The frames NDSequence::new yields for a recording of n_samples: n > fft ? ceil((n - fft) / step) : 0.  The loop is
+ * `for i in (fft_size..n).step_by(fft_step)` (spectrogram.rs:51): the window that ends exactly at sample n is not produced, a frame
+ * appears one sample after its window is complete.  Host only; 0 for fft_step == 0. */
+uint64_t apd_cepstrum_frames(uint64_t n_samples, uint32_t fft_size, uint32_t fft_step);
+
+/* An apd_feed turns the int16 samples of n_channels live recordings, delivered in chunks of any length, into the rows a streaming
+ * session takes: cepstrum frames, or with an encoder (NULL: cepstra as they are) their encodings.  THE FRAMES OF THE PUSHES, ONE
+ * AFTER THE OTHER, ARE THE BITS OF apd_cepstrum (+ apd_encode) ON THE WHOLE RECORDING, WHATEVER THE CHUNKING: a frame depends on its
+ * own fft_size samples and nothing else, and the encoder is per frame.  The feed carries what a push leaves for the next: per
+ * channel the samples from the start of the next window on (at most fft_size, in HBM), or how many samples are still to be skipped
+ * when fft_step > fft_size.  A push is one kernel launch; buffers grow to the largest push seen and are then reused.
+ *   create: limits and error codes are apd_cepstrum's; *dim is the row width -- the cepstrum's n_bins, or the encoder's latent.
+ *     n_channels == 0, an encoder of another context or one whose d_in is not n_bins: APD_ERR_INVALID_ARG; a plan with the encoder's
+ *     weights that does not fit the 160 KiB of LDS: APD_ERR_UNSUPPORTED.  The encoder's weights are copied: it may be destroyed.
+ *     The feed is a child of its context, like plans and sessions.
+ *   reset: the channel (0xFFFFFFFF: all) starts a new recording; totals: samples received and frames emitted since (host only).
+ *   push: channel k's chunk is samples[sample_off[k] .. sample_off[k+1]) (0, 1 or any number of samples).  A push that takes a channel
+ *     from N0 to N1 samples emits frames apd_cepstrum_frames(N0) .. apd_cepstrum_frames(N1) - 1 of its recording; the output is packed
+ *     [frame_off[n_channels]][dim] -- the `frames` / `chunk_off` pair of apd_spot_stream_push.  frame_off (n_channels + 1, host) is
+ *     always written.  frames == NULL: sizes only, the state does not move.  Descending sample_off or capacity (in frames) below
+ *     frame_off[n_channels]: APD_ERR_INVALID_ARG, the state untouched; every error is raised before anything is launched.  Blocking. */
+typedef struct apd_feed apd_feed;
+int apd_feed_create(apd_context *ctx, uint32_t n_channels, uint32_t fft_size, uint32_t fft_step, uint32_t filter_size,
+                    const apd_encoder *encoder, uint32_t *dim, apd_feed **feed);
+int apd_feed_destroy(apd_feed *feed);
+int apd_feed_reset(apd_context *ctx, apd_feed *feed, uint32_t channel);
+int apd_feed_totals(const apd_feed *feed, uint32_t channel, uint64_t *samples, uint64_t *frames);
+int apd_feed_push(apd_context *ctx, apd_feed *feed, const int16_t *samples, const uint64_t *sample_off, int samples_on_device,
+                  float *frames, int frames_on_device, uint64_t capacity, uint64_t *frame_off);
+/* apd_feed_push into a device buffer the feed owns, then apd_spot_stream_push on those rows: raw audio in, curves, bests, queued hits
+ * and kept history out, exactly what apd_spot_stream_push produces for the same frames (it is that code).  The feed's dim must be
+ * the templates' dimension and its channel count the session's (else APD_ERR_INVALID_ARG before anything runs); the remaining
+ * arguments and the sizes-only form (cost, start and best all NULL: neither state moves) are apd_spot_stream_push's.  The session
+ * and the feed are reset separately. */
+int apd_spot_stream_push_audio(apd_context *ctx, apd_spot_stream *stream, apd_feed *feed, const int16_t *samples,
+                               const uint64_t *sample_off, int samples_on_device, float *cost, uint32_t *start,
+                               uint64_t capacity, uint64_t *curve_off, apd_spot_best *best);
+
 /* NDSequence::interesting_ranges (src/spectrogram.rs:174-216), the "VAT" pre-segmentation that precedes the path:
  * per-frame std, mean of the `moving_average` previous values, percentile threshold, runs longer than min_len.
  * frames: [t][n_bins] (device if on_device).  ranges: (start, stop) frame pairs, host; *n_ranges may exceed capacity. */
