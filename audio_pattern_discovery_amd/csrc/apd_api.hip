@@ -6,9 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <map>
 #include <new>
-#include <tuple>
 
 #include "apd_internal.h"
 
@@ -580,7 +578,7 @@ extern "C" int apd_unpack_tiles_host(const uint64_t *offsets, uint32_t n_seq, ui
     return APD_OK;
 }
 
-static int check_lengths(const apd_batch *b)
+int check_lengths(const apd_batch *b)
 {
     if (b->n_seq > 0 && b->min_len == 0) return APD_ERR_EMPTY_SEQUENCE;
     return APD_OK;
@@ -781,7 +779,7 @@ static int align_tiles_impl(apd_context *ctx, const apd_batch *batch, const Band
 // (is_poison, dtw_generic.hip).  Which scores are NaN does not depend on the payload.
 static float canonical_penalty(float p) { return p != p ? std::numeric_limits<float>::quiet_NaN() : p; }
 
-static BandSpec band_from_cfg(const apd_align_config *cfg)
+BandSpec band_from_cfg(const apd_align_config *cfg)
 {
     BandSpec b{};
     b.pct = cfg->warping_band_percentage; b.use_explicit = 0; b.explicit_band = 0;
@@ -956,8 +954,7 @@ extern "C" int apd_cross_linkage(apd_context *ctx, const float *fs, const float 
     return APD_OK;
 }
 
-// The context's two-sequence batch holding (x, y): sequence 0 = x, sequence 1 = y.
-static int prepare_pair_batch(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim)
+int prepare_pair_batch(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim)
 {
     std::vector<float> frames((n + m) * (size_t)dim);
     std::memcpy(frames.data(), x, n * (size_t)dim * sizeof(float));
@@ -979,7 +976,7 @@ static int prepare_pair_batch(apd_context *ctx, const float *x, uint64_t n, cons
     return APD_OK;
 }
 
-static BandSpec band_from_params(const apd_alignment_params *params)
+BandSpec band_from_params(const apd_alignment_params *params)
 {
     BandSpec band{};
     band.use_explicit = 1;
@@ -1007,1367 +1004,6 @@ extern "C" int apd_align_pair(apd_context *ctx, const float *x, uint64_t n, cons
     rc = read_back(ctx, align_all_device_impl(ctx, b, band, d_out), {{host, d_out, sizeof(host)}});
     if (rc == APD_OK) *score = host[1];                                   // out[0*2+1] = score(x, y)
     return rc;
-}
-
-// --------------------------------------------------------------------------------- warping paths
-
-extern "C" uint64_t apd_path_bound(uint64_t n, uint64_t m) { return (n == 0 || m == 0) ? 0 : n + m - 1; }
-
-// Cap of the direction workspace of one chunk of pairs (bytes); also bounds the chunk's step buffer.
-static uint64_t path_workspace_cap()
-{
-    if (const char *v = std::getenv("APD_PATH_WORKSPACE_BYTES")) {
-        const unsigned long long b = std::strtoull(v, nullptr, 10);
-        if (b > 0) return b;
-    }
-    return 1ull << 30;
-}
-
-// The sweep and the trace (dtw_path.hip) over `pairs`, in chunks whose direction words stay under the cap.
-static int align_paths_impl(apd_context *ctx, const apd_batch *batch, const BandSpec &band, const uint32_t *pairs, uint64_t n_pairs,
-                            apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len, float *scores)
-{
-    if (!ctx || !batch || batch->ctx != ctx || !step_off || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    step_off[0] = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) step_off[p + 1] = step_off[p] + apd_path_bound(len_of(pairs[2 * p]), len_of(pairs[2 * p + 1]));
-    if (!steps) return APD_OK;                                            // sizes only
-    if (capacity < step_off[n_pairs] || (n_pairs && !path_len)) return APD_ERR_INVALID_ARG;
-    if (n_pairs == 0) return APD_OK;
-    std::vector<PathPair> desc(n_pairs);
-    std::vector<uint64_t> dir_words(n_pairs);
-    std::vector<uint32_t> cells(n_pairs);
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint32_t n = len_of(pairs[2 * p]), m = len_of(pairs[2 * p + 1]);
-        const uint32_t w = host_w(band, n, m);
-        if (2ull * w + 1 > kPathMaxOffsets) { ctx->last_error = "band too wide for the path sweep"; return APD_ERR_BAND_TOO_WIDE; }
-        desc[p].px = pos[pairs[2 * p]];
-        desc[p].py = pos[pairs[2 * p + 1]];
-        dir_words[p] = path_dir_words(n, m, w);
-        cells[p] = path_cells_per_lane(w);
-    }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "path launch");
-    const uint64_t cap = path_workspace_cap();
-    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // 64 work-items per pair, launches stay below 2^31
-    std::vector<float> score_sink;
-    if (!scores) score_sink.resize(n_pairs);
-    float *h_scores = scores ? scores : score_sink.data();
-    bool first_chunk = true;
-    for (uint64_t first = 0; first < n_pairs;) {
-        // the chunk [first, last): at least one pair, then as many as keep the direction words and the steps under the cap
-        uint64_t last = first, words = 0, slots = 0;
-        uint32_t c_max = 2;
-        while (last < n_pairs && last - first < kMaxPairsPerLaunch) {
-            const uint64_t nw = words + dir_words[last], ns = slots + (step_off[last + 1] - step_off[last]);
-            if (last > first && (nw * sizeof(uint32_t) > cap || ns * sizeof(apd_path_step) > cap)) break;
-            desc[last].dir_off = words;
-            desc[last].step_off = slots;
-            words = nw; slots = ns;
-            c_max = std::max(c_max, cells[last]);
-            ++last;
-        }
-        const uint64_t np = last - first;
-        // steps workspace: [steps | pair descriptors | lengths | scores]
-        const size_t steps_bytes = (size_t)slots * sizeof(apd_path_step), desc_bytes = (size_t)np * sizeof(PathPair);
-        rc = reserve_ws(ctx, ctx->ws_path_dirs, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
-        if (rc) return rc;
-        rc = reserve_ws(ctx, ctx->ws_path_steps, steps_bytes + desc_bytes + (size_t)np * 8 + 16);
-        if (rc) return rc;
-        char *base = ctx->ws_path_steps.as<char>();
-        PathLaunch L{};
-        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
-        L.d_pairs = (const PathPair *)(base + steps_bytes);
-        L.n_pairs = (uint32_t)np;
-        L.d_dirs = ctx->ws_path_dirs.as<uint32_t>();
-        L.d_steps = (apd_path_step *)base;
-        L.d_len = (uint32_t *)(base + steps_bytes + desc_bytes);
-        L.d_scores = (float *)(base + steps_bytes + desc_bytes + (size_t)np * 4);
-        HIP_TRY(ctx, hipMemcpyAsync((void *)L.d_pairs, desc.data() + first, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        HIP_TRY(ctx, launch_path_sweep(L, c_max, ctx->stream));
-        HIP_TRY(ctx, launch_path_trace(L, ctx->stream));
-        if (ctx->timing && last == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-        if (slots) HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(path_len + first, L.d_len, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_scores + first, L.d_scores, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspaces
-        first = last;
-        first_chunk = false;
-    }
-    return APD_OK;
-}
-
-extern "C" int apd_align_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs,
-                               uint64_t n_pairs, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
-                               float *scores)
-{
-    if (!ctx || !batch || !cfg) return APD_ERR_INVALID_ARG;
-    return align_paths_impl(ctx, batch, band_from_cfg(cfg), pairs, n_pairs, steps, capacity, step_off, path_len, scores);
-}
-
-extern "C" int apd_align_pair_path(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim,
-                                   const apd_alignment_params *params, apd_path_step *steps, uint64_t capacity, uint64_t *n_steps,
-                                   float *score)
-{
-    if (!ctx || !params || !n_steps || !score || dim == 0) return APD_ERR_INVALID_ARG;
-    if (n == 0 && m == 0) { *n_steps = 0; *score = INFINITY; return APD_OK; }   // alignments.rs:117-118
-    if (n == 0 || m == 0) return APD_ERR_EMPTY_SEQUENCE;                  // usize underflow at :120
-    if (!x || !y) return APD_ERR_INVALID_ARG;
-    if (!steps) { *n_steps = apd_path_bound(n, m); return APD_OK; }
-    if (capacity < apd_path_bound(n, m)) return APD_ERR_INVALID_ARG;
-    int rc = prepare_pair_batch(ctx, x, n, y, m, dim);
-    if (rc) return rc;
-    const uint32_t pair[2] = {0, 1};
-    uint64_t off[2] = {0, 0};
-    uint32_t len = 0;
-    rc = align_paths_impl(ctx, ctx->pair_batch, band_from_params(params), pair, 1, steps, capacity, off, &len, score);
-    if (rc == APD_OK) *n_steps = len;
-    return rc;
-}
-
-// ------------------------------------------------------------------------------ DTW barycenters
-
-// DBA over sets of a resident batch (kernels: dtw_path.hip).  The pairs (set, member ascending) are cut into chunks under the path
-// workspace cap once; every iteration runs sweep, trace and accumulate per chunk, then one finalize.  ws_bary, uploaded once:
-// [barycenters | sums | counts | score sums | used | bary_off | init positions | pair descriptors | per chunk: pairs of every set |
-//  contributes | inertia, used of every iteration].
-extern "C" int apd_barycenters(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *members,
-                               const uint32_t *set_off, uint32_t n_sets, const uint32_t *init, uint32_t iterations, float *frames,
-                               int frames_on_device, uint64_t capacity, uint64_t *frame_off, float *inertia, uint32_t *used)
-{
-    if (!ctx || !batch || !cfg || batch->ctx != ctx || !frame_off || (n_sets && (!set_off || !init))) return APD_ERR_INVALID_ARG;
-    if (n_sets && set_off[0] != 0) return APD_ERR_INVALID_ARG;
-    for (uint32_t k = 0; k < n_sets; ++k) if (set_off[k + 1] < set_off[k]) return APD_ERR_INVALID_ARG;
-    const uint32_t n_pairs = n_sets ? set_off[n_sets] : 0u, n_seq = batch->n_seq;
-    if (n_pairs && !members) return APD_ERR_INVALID_ARG;
-    // ascending sequence number inside every set: the order of the contract's sums
-    std::vector<uint32_t> sorted(members, members + n_pairs);
-    for (uint32_t k = 0; k < n_sets; ++k) {
-        if (init[k] >= n_seq) return APD_ERR_INVALID_ARG;
-        std::sort(sorted.begin() + set_off[k], sorted.begin() + set_off[k + 1]);
-        for (uint32_t t = set_off[k]; t < set_off[k + 1]; ++t)
-            if (sorted[t] >= n_seq || (t > set_off[k] && sorted[t] == sorted[t - 1])) return APD_ERR_INVALID_ARG;
-    }
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
-    auto frames_of = [&](uint32_t k) { return set_off[k + 1] > set_off[k] ? len_of(init[k]) : 0u; };   // an empty set has no barycenter
-    frame_off[0] = 0;
-    for (uint32_t k = 0; k < n_sets; ++k) frame_off[k + 1] = frame_off[k] + frames_of(k);
-    if (!frames) return APD_OK;                                           // sizes only
-    if (capacity < frame_off[n_sets]) return APD_ERR_INVALID_ARG;
-    const BandSpec band = band_from_cfg(cfg);
-    const uint64_t n_padded = frame_off[n_sets] + 2ull * n_sets;
-    if (n_padded >= (1ull << 32) || n_padded * batch->dpad >= (1ull << 39)) return APD_ERR_INVALID_ARG;   // one work-item per float, below 2^31 workgroups
-
-    // ---- the plan: pair descriptors, chunks, and per chunk the pairs of every set
-    struct Chunk { uint32_t first, last, c_max; uint64_t words, slots; };
-    std::vector<PathPair> desc(n_pairs);
-    std::vector<Chunk> chunks;
-    const uint64_t cap = path_workspace_cap();
-    constexpr uint32_t kMaxPairsPerLaunch = 1u << 24;                     // 64 work-items per pair, launches stay below 2^31
-    {
-        std::vector<uint32_t> set_of(n_pairs);
-        for (uint32_t k = 0; k < n_sets; ++k) for (uint32_t t = set_off[k]; t < set_off[k + 1]; ++t) set_of[t] = k;
-        Chunk c{0, 0, 2, 0, 0};
-        for (uint32_t p = 0; p < n_pairs; ++p) {
-            const uint32_t n = frames_of(set_of[p]), m = len_of(sorted[p]);
-            const uint32_t w = host_w(band, n, m);
-            if (2ull * w + 1 > kPathMaxOffsets) { ctx->last_error = "band too wide for the path sweep"; return APD_ERR_BAND_TOO_WIDE; }
-            const uint64_t words = path_dir_words(n, m, w), slots = apd_path_bound(n, m);
-            if (p > c.first && ((c.words + words) * sizeof(uint32_t) > cap || (c.slots + slots) * sizeof(apd_path_step) > cap ||
-                                p - c.first >= kMaxPairsPerLaunch)) {
-                c.last = p;
-                chunks.push_back(c);
-                c = Chunk{p, 0, 2, 0, 0};
-            }
-            desc[p] = PathPair{set_of[p], pos[sorted[p]], c.words, c.slots};   // px: the set, whose barycenter is x
-            c.words += words; c.slots += slots;
-            c.c_max = std::max(c.c_max, path_cells_per_lane(w));
-        }
-        if (n_pairs) { c.last = n_pairs; chunks.push_back(c); }
-    }
-    std::vector<uint2> set_pairs(chunks.size() * n_sets);                 // per chunk and set: its pairs [x, y), relative to the chunk
-    uint64_t max_words = 0, max_slots = 0;
-    uint32_t max_np = 0;
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const Chunk &c = chunks[ci];
-        for (uint32_t k = 0; k < n_sets; ++k) {
-            const uint32_t lo = std::min(std::max(set_off[k], c.first), c.last), hi = std::min(std::max(set_off[k + 1], c.first), c.last);
-            set_pairs[ci * n_sets + k] = make_uint2(lo - c.first, hi - c.first);
-        }
-        max_words = std::max(max_words, c.words); max_slots = std::max(max_slots, c.slots); max_np = std::max(max_np, c.last - c.first);
-    }
-    if (n_sets == 0) return APD_OK;
-
-    // ---- device state
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "barycenter launch");
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t bary_bytes = up((size_t)n_padded * batch->dpad * sizeof(float)), cnt_bytes = up((size_t)n_padded * 4);
-    const size_t set_bytes = up((size_t)n_sets * 4), off_bytes = up(((size_t)n_sets + 1) * 4);
-    const size_t desc_bytes = up(desc.size() * sizeof(PathPair)), ranges_bytes = up(set_pairs.size() * sizeof(uint2));
-    const size_t contrib_bytes = up((size_t)max_np * 4), result_bytes = up((size_t)iterations * n_sets * 4);
-    // [bary | sum | cnt | score_sum | used] then the uploaded block [bary_off | init_pos | desc | ranges] then [contrib | inertia | used_out]
-    const size_t o_sum = bary_bytes, o_cnt = o_sum + bary_bytes, o_score = o_cnt + cnt_bytes, o_used = o_score + set_bytes;
-    const size_t o_off = o_used + set_bytes, o_init = o_off + off_bytes, o_desc = o_init + set_bytes, o_ranges = o_desc + desc_bytes;
-    const size_t o_contrib = o_ranges + ranges_bytes, o_inertia = o_contrib + contrib_bytes, o_usedout = o_inertia + result_bytes;
-    rc = reserve_ws(ctx, ctx->ws_bary, o_usedout + result_bytes);
-    if (rc) return rc;
-    rc = reserve_ws(ctx, ctx->ws_path_dirs, std::max<size_t>((size_t)max_words * sizeof(uint32_t), 16));
-    if (rc) return rc;
-    // steps workspace, as apd_align_paths lays it out: [steps | lengths | scores] (the descriptors live in ws_bary)
-    const size_t steps_bytes = (size_t)max_slots * sizeof(apd_path_step);
-    rc = reserve_ws(ctx, ctx->ws_path_steps, steps_bytes + (size_t)max_np * 8 + 16);
-    if (rc) return rc;
-    DeviceBuf d_packed;                                                   // the host form's result on its way out
-    const size_t out_bytes = (size_t)frame_off[n_sets] * batch->src_dim * sizeof(float);
-    if (!frames_on_device && out_bytes) HIP_TRY(ctx, d_packed.alloc(out_bytes));
-    char *base = ctx->ws_bary.as<char>();
-    std::vector<char> upload(o_contrib - o_off, 0);
-    {
-        uint32_t *h_off = (uint32_t *)upload.data(), *h_init = (uint32_t *)(upload.data() + (o_init - o_off));
-        for (uint32_t k = 0; k <= n_sets; ++k) h_off[k] = (uint32_t)(frame_off[k] + 2ull * k);
-        for (uint32_t k = 0; k < n_sets; ++k) h_init[k] = pos[init[k]];
-        if (!desc.empty()) std::memcpy(upload.data() + (o_desc - o_off), desc.data(), desc.size() * sizeof(PathPair));
-        if (!set_pairs.empty()) std::memcpy(upload.data() + (o_ranges - o_off), set_pairs.data(), set_pairs.size() * sizeof(uint2));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // `upload` is a local: it must have left the host
-    BaryLaunch B{};
-    B.d_frames = batch->d_frames.as<float>(); B.d_seq_off = batch->d_seq_off;
-    B.d_bary = (float *)base; B.d_bary_off = (const uint32_t *)(base + o_off);
-    B.n_sets = n_sets; B.n_padded = (uint32_t)n_padded;
-    B.dim = batch->dim; B.src_dim = batch->src_dim; B.dpad = batch->dpad;
-    B.d_sum = (float *)(base + o_sum); B.d_cnt = (uint32_t *)(base + o_cnt);
-    B.d_score_sum = (float *)(base + o_score); B.d_used = (uint32_t *)(base + o_used);
-    B.d_contrib = (uint32_t *)(base + o_contrib);
-    float *d_inertia = (float *)(base + o_inertia);
-    uint32_t *d_used_out = (uint32_t *)(base + o_usedout);
-    char *steps_base = ctx->ws_path_steps.as<char>();
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(ctx, launch_bary_init(B, (const uint32_t *)(base + o_init), ctx->stream));
-    for (uint32_t it = 0; it < iterations; ++it) {
-        HIP_TRY(ctx, hipMemsetAsync(base + o_sum, 0, o_off - o_sum, ctx->stream));   // sums, counts, score sums, used
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            const Chunk &c = chunks[ci];
-            const uint32_t np = c.last - c.first;
-            PathLaunch L{};
-            L.d_frames = B.d_frames; L.d_seq_off = B.d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad; L.band = band;
-            L.d_x_frames = B.d_bary; L.d_x_seq_off = B.d_bary_off;
-            L.d_pairs = (const PathPair *)(base + o_desc) + c.first;
-            L.n_pairs = np;
-            L.d_dirs = ctx->ws_path_dirs.as<uint32_t>();
-            L.d_steps = (apd_path_step *)steps_base;
-            L.d_len = (uint32_t *)(steps_base + steps_bytes);
-            L.d_scores = (float *)(steps_base + steps_bytes + (size_t)max_np * 4);
-            HIP_TRY(ctx, launch_path_sweep(L, c.c_max, ctx->stream));
-            HIP_TRY(ctx, launch_path_trace(L, ctx->stream));
-            B.d_pairs = L.d_pairs; B.d_set_pairs = (const uint2 *)(base + o_ranges) + ci * n_sets;
-            B.d_steps = L.d_steps; B.d_len = L.d_len; B.d_scores = L.d_scores;
-            HIP_TRY(ctx, launch_bary_accumulate(B, ctx->stream));
-        }
-        HIP_TRY(ctx, launch_bary_finalize(B, d_inertia + (size_t)it * n_sets, d_used_out + (size_t)it * n_sets, ctx->stream));
-    }
-    float *d_out = frames_on_device ? frames : d_packed.as<float>();
-    if (out_bytes) HIP_TRY(ctx, launch_bary_pack(B, d_out, ctx->stream));
-    if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-    const size_t res = (size_t)iterations * n_sets * 4;
-    if (!frames_on_device && out_bytes) HIP_TRY(ctx, hipMemcpyAsync(frames, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (inertia && res) HIP_TRY(ctx, hipMemcpyAsync(inertia, d_inertia, res, hipMemcpyDeviceToHost, ctx->stream));
-    if (used && res) HIP_TRY(ctx, hipMemcpyAsync(used, d_used_out, res, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's now
-    return APD_OK;
-}
-
-// ------------------------------------------------------------------------- subsequence alignment
-
-// Cap of the device curves of one chunk of pairs (bytes).
-static uint64_t spot_workspace_cap()
-{
-    if (const char *v = std::getenv("APD_SPOT_WORKSPACE_BYTES")) {
-        const unsigned long long b = std::strtoull(v, nullptr, 10);
-        if (b > 0) return b;
-    }
-    return 1ull << 30;
-}
-
-extern "C" int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
-                        float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off, apd_spot_best *best)
-{
-    if (!ctx || !batch || !cfg || batch->ctx != ctx || !curve_off || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
-    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    curve_off[0] = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) curve_off[p + 1] = curve_off[p] + len_of(pairs[2 * p + 1]);
-    const bool curves = cost != nullptr;
-    if (!curves && !best) return APD_OK;                                  // sizes only
-    if (curves && capacity < curve_off[n_pairs]) return APD_ERR_INVALID_ARG;
-    if (n_pairs == 0) return APD_OK;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (len_of(pairs[2 * p]) > kSpotMaxQuery || len_of(pairs[2 * p + 1]) >= kSpotMaxStream) {
-            ctx->last_error = "apd_spot: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
-            return APD_ERR_UNSUPPORTED;
-        }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot launch");
-    const uint64_t cap = spot_workspace_cap();
-    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // 64 work-items per pair, launches stay below 2^31
-    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
-    std::vector<apd_spot_best> best_sink;
-    if (!best) best_sink.resize(n_pairs);
-    apd_spot_best *h_best = best ? best : best_sink.data();
-    std::vector<SpotPair> desc;
-    bool first_chunk = true;
-    for (uint64_t first = 0; first < n_pairs;) {
-        // the chunk [first, last): at least one pair, then as many as keep the curves under the cap
-        uint64_t last = first, entries = 0;
-        while (last < n_pairs && last - first < kMaxPairsPerLaunch) {
-            const uint64_t ne = entries + (curve_off[last + 1] - curve_off[last]);
-            if (curves && last > first && ne * (sizeof(float) + sizeof(uint32_t)) > cap) break;
-            entries = ne;
-            ++last;
-        }
-        const uint64_t np = last - first;
-        // the chunk's descriptors, grouped by kernel class (one launch each); `out` keeps the input order
-        uint64_t class_count[kClasses] = {}, class_first[kClasses] = {};
-        uint32_t r_max = 1;
-        for (uint64_t p = first; p < last; ++p) {
-            const uint32_t n = len_of(pairs[2 * p]);
-            const uint32_t c = spot_row_class(batch->dim, n);
-            ++class_count[c];
-            if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(n));
-        }
-        for (uint32_t c = 1; c < kClasses; ++c) class_first[c] = class_first[c - 1] + class_count[c - 1];
-        desc.resize(np);
-        uint64_t fill[kClasses];
-        std::copy(class_first, class_first + kClasses, fill);
-        for (uint64_t p = first; p < last; ++p) {
-            SpotPair &d = desc[fill[spot_row_class(batch->dim, len_of(pairs[2 * p]))]++];
-            d.px = pos[pairs[2 * p]];
-            d.py = pos[pairs[2 * p + 1]];
-            d.out = (uint32_t)(p - first);
-            d.pad = 0;
-            d.curve_off = curve_off[p] - curve_off[first];
-        }
-        // workspace: [cost | start | pair descriptors | best]
-        const size_t curve_floats = curves ? (size_t)entries : 0;
-        const size_t curve_bytes = (curve_floats * 4 + 15) / 16 * 16;
-        const size_t desc_bytes = (size_t)np * sizeof(SpotPair), best_bytes = (size_t)np * sizeof(apd_spot_best);
-        rc = reserve_ws(ctx, ctx->ws_spot, 2 * curve_bytes + desc_bytes + best_bytes + 16);
-        if (rc) return rc;
-        char *base = ctx->ws_spot.as<char>();
-        SpotLaunch L{};
-        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
-        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
-        L.d_cost = curves ? (float *)base : nullptr;
-        L.d_start = curves ? (uint32_t *)(base + curve_bytes) : nullptr;
-        const SpotPair *d_desc = (const SpotPair *)(base + 2 * curve_bytes);
-        L.d_best = (apd_spot_best *)(base + 2 * curve_bytes + desc_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync((void *)d_desc, desc.data(), desc_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (uint32_t c = 0; c < kClasses; ++c) {
-            L.d_pairs = d_desc + class_first[c];
-            L.n_pairs = (uint32_t)class_count[c];
-            HIP_TRY(ctx, launch_spot(L, c, r_max, ctx->stream));
-        }
-        if (ctx->timing && last == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-        if (curve_floats) {
-            HIP_TRY(ctx, hipMemcpyAsync(cost + curve_off[first], L.d_cost, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(start + curve_off[first], L.d_start, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(h_best + first, L.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `desc`)
-        first = last;
-        first_chunk = false;
-    }
-    return APD_OK;
-}
-
-// score(j) of the spotting contract: one f32 division, the window's length in place of m (alignments.rs:121)
-static float spot_score(float cost, uint64_t j, uint32_t start, uint64_t n)
-{
-    return cost / (float)(n + (j - start + 1));
-}
-
-extern "C" int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t m, uint64_t n, float threshold, apd_spot_best *hits,
-                             uint64_t capacity, uint64_t *n_hits)
-{
-    if (!n_hits || n == 0 || (m && (!cost || !start)) || (capacity && !hits)) return APD_ERR_INVALID_ARG;
-    *n_hits = 0;
-    try {
-        std::vector<std::pair<float, uint64_t>> cand;                     // (score, end), ends ascending
-        for (uint64_t j = 1; j <= m; ++j) {
-            if (start[j - 1] > j) return APD_ERR_INVALID_ARG;             // not a curve of apd_spot
-            const float s = spot_score(cost[j - 1], j, start[j - 1], n);
-            if (s < threshold) cand.emplace_back(s, j);                   // strict; NaN compares false
-        }
-        std::stable_sort(cand.begin(), cand.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
-        std::map<uint64_t, uint64_t> taken;                               // accepted windows, first column -> last column (disjoint)
-        for (const auto &c : cand) {
-            const uint64_t hi = c.second, lo = start[hi - 1];
-            auto next = taken.upper_bound(hi);                            // the first accepted window that begins after `hi`
-            if (next != taken.begin() && std::prev(next)->second >= lo) continue;   // the one before it reaches into [lo, hi]
-            taken.emplace(lo, hi);
-            if (*n_hits < capacity) {
-                apd_spot_best &h = hits[*n_hits];
-                h.end = (uint32_t)hi; h.start = (uint32_t)lo; h.cost = cost[hi - 1]; h.score = c.first;
-            }
-            ++*n_hits;
-        }
-    } catch (const std::bad_alloc &) {
-        return APD_ERR_OOM;
-    }
-    return APD_OK;
-}
-
-// ----------------------------------------------------------------------------------------- spot detection
-
-// apd_spot's sweep into the workspace, then candidates, greedy picking and the packed hits on the device (kernels:
-// dtw_spot_detect.hip).  A chunk is a run of whole groups; its pairs are numbered group by group.
-// ws_spot: [cost | start | candidates | accepted windows | sweep pairs, detect pairs, groups (uploaded) | best | candidate counts,
-// hit counts (zeroed) | hit bases]; ws_spot_hits: the chunk's packed hits, sized once its hit counts are known.
-extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
-                               const float *thresholds, int compete, apd_spot_hit *hits, uint64_t capacity, uint64_t *hit_off,
-                               uint64_t *n_groups, uint64_t *n_hits)
-{
-    if (!ctx || !batch || !cfg || batch->ctx != ctx || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
-    if ((compete != APD_DETECT_PER_PAIR && compete != APD_DETECT_PER_STREAM) || (n_pairs && !thresholds) || !hit_off || !n_groups || !n_hits ||
-        (capacity && !hits))
-        return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    *n_groups = 0;
-    *n_hits = 0;
-    hit_off[0] = 0;
-    if (n_pairs == 0) return APD_OK;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (len_of(pairs[2 * p]) > kSpotMaxQuery || len_of(pairs[2 * p + 1]) >= kSpotMaxStream) {
-            ctx->last_error = "apd_spot_detect: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
-            return APD_ERR_UNSUPPORTED;
-        }
-    constexpr uint64_t kMaxPairsPerLaunch = 1ull << 24;                   // as apd_spot
-    // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
-    std::vector<uint64_t> group_of(n_pairs), member_first, members(n_pairs);
-    uint64_t ng = 0;
-    if (compete == APD_DETECT_PER_PAIR) {
-        ng = n_pairs;
-        for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
-    } else {
-        std::vector<uint64_t> group_of_stream(n_seq, ~0ull);
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            uint64_t &g = group_of_stream[pairs[2 * p + 1]];
-            if (g == ~0ull) g = ng++;
-            group_of[p] = g;
-        }
-    }
-    member_first.assign(ng + 1, 0);
-    for (uint64_t p = 0; p < n_pairs; ++p) ++member_first[group_of[p] + 1];
-    for (uint64_t g = 0; g < ng; ++g) {
-        if (member_first[g + 1] > kMaxPairsPerLaunch) {
-            ctx->last_error = "apd_spot_detect: a group of more than 2^24 pairs";
-            return APD_ERR_UNSUPPORTED;
-        }
-        member_first[g + 1] += member_first[g];
-    }
-    {
-        std::vector<uint64_t> fill(member_first.begin(), member_first.end() - 1);
-        for (uint64_t p = 0; p < n_pairs; ++p) members[fill[group_of[p]]++] = p;
-    }
-    auto stream_len = [&](uint64_t g) { return (uint64_t)len_of(pairs[2 * members[member_first[g]] + 1]); };
-    auto group_pairs = [&](uint64_t g) { return member_first[g + 1] - member_first[g]; };
-    *n_groups = ng;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot detect launch");
-    const uint64_t cap = spot_workspace_cap();
-    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
-    constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t) + sizeof(ulonglong2), kStageBytes = sizeof(uint2);
-    auto pad16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    std::vector<char> upload;
-    std::vector<uint32_t> counts;
-    bool first_chunk = true;
-    for (uint64_t g0 = 0; g0 < ng;) {
-        // the chunk of groups [g0, g1): at least one, then as many as keep the curves, the candidates and the windows under the cap
-        uint64_t g1 = g0, entries = 0, stage_slots = 0, np = 0;
-        while (g1 < ng) {
-            const uint64_t ne = entries + group_pairs(g1) * stream_len(g1), ns = stage_slots + stream_len(g1);
-            if (g1 > g0 && (ne * kEntryBytes + ns * kStageBytes > cap || np + group_pairs(g1) > kMaxPairsPerLaunch)) break;
-            entries = ne; stage_slots = ns; np += group_pairs(g1);
-            ++g1;
-        }
-        const uint64_t ngc = g1 - g0;
-        // what is uploaded: [sweep pairs by kernel class | detect pairs | groups]
-        const size_t desc_bytes = pad16((size_t)np * sizeof(SpotPair)), dp_bytes = (size_t)np * sizeof(SpotDetectPair);
-        const size_t grp_bytes = (size_t)ngc * sizeof(SpotDetectGroup);
-        upload.assign(desc_bytes + dp_bytes + grp_bytes, 0);
-        SpotPair *desc = (SpotPair *)upload.data();
-        SpotDetectPair *dp = (SpotDetectPair *)(upload.data() + desc_bytes);
-        SpotDetectGroup *grp = (SpotDetectGroup *)(upload.data() + desc_bytes + dp_bytes);
-        uint64_t class_count[kClasses] = {}, class_first[kClasses] = {};
-        uint32_t r_max = 1, m_max = 1;
-        uint64_t k = 0, off = 0, stage_off = 0;
-        for (uint64_t g = g0; g < g1; ++g) {
-            SpotDetectGroup &G = grp[g - g0];
-            const uint32_t m = (uint32_t)stream_len(g);
-            G.cand_off = off; G.cand_cap = group_pairs(g) * m; G.stage_off = stage_off; G.stage_cap = m;
-            stage_off += m;
-            m_max = std::max(m_max, m);
-            for (uint64_t t = member_first[g]; t < member_first[g + 1]; ++t, ++k) {
-                const uint64_t p = members[t];
-                SpotDetectPair &d = dp[k];
-                d.curve_off = off; d.m = m; d.n = len_of(pairs[2 * p]); d.threshold = thresholds[p];
-                d.group = (uint32_t)(g - g0); d.pair = (uint32_t)p;
-                off += m;
-                const uint32_t c = spot_row_class(batch->dim, d.n);
-                ++class_count[c];
-                if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(d.n));
-            }
-        }
-        for (uint32_t c = 1; c < kClasses; ++c) class_first[c] = class_first[c - 1] + class_count[c - 1];
-        uint64_t fill[kClasses];
-        std::copy(class_first, class_first + kClasses, fill);
-        for (k = 0; k < np; ++k) {
-            const uint64_t p = dp[k].pair;
-            SpotPair &d = desc[fill[spot_row_class(batch->dim, dp[k].n)]++];
-            d.px = pos[pairs[2 * p]];
-            d.py = pos[pairs[2 * p + 1]];
-            d.out = (uint32_t)k;
-            d.pad = 0;
-            d.curve_off = dp[k].curve_off;
-        }
-        const size_t curve_bytes = pad16((size_t)entries * 4), cand_bytes = (size_t)entries * sizeof(ulonglong2);
-        const size_t stage_bytes = pad16((size_t)stage_slots * sizeof(uint2)), best_bytes = (size_t)np * sizeof(apd_spot_best);
-        const size_t cc_bytes = (size_t)ngc * sizeof(unsigned long long), hc_bytes = pad16((size_t)ngc * sizeof(uint32_t));
-        const size_t hb_bytes = (size_t)(ngc + 1) * sizeof(unsigned long long);
-        rc = reserve_ws(ctx, ctx->ws_spot, 2 * curve_bytes + cand_bytes + stage_bytes + upload.size() + best_bytes + cc_bytes + hc_bytes + hb_bytes + 16);
-        if (rc) return rc;
-        char *base = ctx->ws_spot.as<char>();
-        char *d_upload = base + 2 * curve_bytes + cand_bytes + stage_bytes, *d_counts = d_upload + upload.size() + best_bytes;
-        SpotLaunch L{};
-        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
-        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
-        L.d_cost = (float *)base;
-        L.d_start = (uint32_t *)(base + curve_bytes);
-        const SpotPair *d_desc = (const SpotPair *)d_upload;
-        L.d_best = (apd_spot_best *)(d_upload + upload.size());
-        SpotDetectLaunch D{};
-        D.d_cost = L.d_cost; D.d_start = L.d_start;
-        D.d_pairs = (const SpotDetectPair *)(d_upload + desc_bytes); D.n_pairs = (uint32_t)np;
-        D.d_groups = (const SpotDetectGroup *)(d_upload + desc_bytes + dp_bytes); D.n_groups = (uint32_t)ngc;
-        D.d_cand = (ulonglong2 *)(base + 2 * curve_bytes);
-        D.d_stage = (uint2 *)(base + 2 * curve_bytes + cand_bytes);
-        D.d_cand_count = (unsigned long long *)d_counts;
-        D.d_hit_count = (uint32_t *)(d_counts + cc_bytes);
-        D.d_hit_base = (unsigned long long *)(d_counts + cc_bytes + hc_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(d_upload, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, cc_bytes + hc_bytes, ctx->stream));
-        if (ctx->timing && first_chunk) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (uint32_t c = 0; c < kClasses; ++c) {
-            L.d_pairs = d_desc + class_first[c];
-            L.n_pairs = (uint32_t)class_count[c];
-            HIP_TRY(ctx, launch_spot(L, c, r_max, ctx->stream));
-        }
-        HIP_TRY(ctx, launch_spot_detect(D, m_max, ctx->stream));
-        counts.resize(ngc);
-        HIP_TRY(ctx, hipMemcpyAsync(counts.data(), D.d_hit_count, (size_t)ngc * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the packed buffer is sized by the counts
-        const uint64_t chunk_first = hit_off[g0];
-        for (uint64_t g = g0; g < g1; ++g) hit_off[g + 1] = hit_off[g] + counts[g - g0];
-        const uint64_t chunk_hits = hit_off[g1] - chunk_first;
-        const uint64_t n_write = capacity > chunk_first ? std::min(chunk_hits, capacity - chunk_first) : 0;
-        if (n_write) {
-            rc = reserve_ws(ctx, ctx->ws_spot_hits, (size_t)n_write * sizeof(apd_spot_hit));
-            if (rc) return rc;
-            HIP_TRY(ctx, launch_spot_detect_emit(D, ctx->ws_spot_hits.as<apd_spot_hit>(), n_write, ctx->stream));
-        }
-        if (ctx->timing && g1 == ng) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-        if (n_write) {
-            HIP_TRY(ctx, hipMemcpyAsync(hits + chunk_first, ctx->ws_spot_hits.ptr, (size_t)n_write * sizeof(apd_spot_hit), hipMemcpyDeviceToHost,
-                                        ctx->stream));
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `upload`)
-        g0 = g1;
-        first_chunk = false;
-    }
-    *n_hits = hit_off[ng];
-    return APD_OK;
-}
-
-// ------------------------------------------------------------------- warping paths of spotted windows
-
-extern "C" uint64_t apd_spot_path_bound(uint64_t n, uint64_t end, uint64_t start)
-{
-    return (n == 0 || start == 0 || start > end) ? 0 : n + (end - start + 1);
-}
-
-// The windows are taken in input order, a chunk at a time: as many as keep the direction words (counted per window, before the
-// merge makes them fewer) and the steps under the workspace cap, at least one.  Inside a chunk the windows are grouped by (query,
-// stream) pair: one sweep per pair over the union of its windows' columns, one trace per window (kernels: dtw_spot_path.hip).
-// ws_spot_steps: [steps | pairs | intervals | windows | ends] (all but the steps uploaded), then [end cost | end start | lengths |
-// found | scores]; ws_spot_dirs: the intervals' words.
-extern "C" int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const apd_spot_window *windows,
-                              uint64_t n_windows, apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
-                              uint32_t *found_start, float *scores)
-{
-    if (!ctx || !batch || !cfg || batch->ctx != ctx || !step_off || (n_windows && !windows)) return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[batch->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(batch->offsets[pos[s] + 1] - batch->offsets[pos[s]]); };
-    for (uint64_t p = 0; p < n_windows; ++p)
-        if (windows[p].x >= n_seq || windows[p].y >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
-    if (rc) return rc;
-    for (uint64_t p = 0; p < n_windows; ++p) {
-        const apd_spot_window &w = windows[p];
-        if (w.end > len_of(w.y) || (w.end && w.start > w.end)) return APD_ERR_INVALID_ARG;
-    }
-    auto slots_of = [&](uint64_t p) { return apd_spot_path_bound(len_of(windows[p].x), windows[p].end, windows[p].start); };
-    step_off[0] = 0;
-    for (uint64_t p = 0; p < n_windows; ++p) step_off[p + 1] = step_off[p] + slots_of(p);
-    if (!steps) return APD_OK;                                            // sizes only
-    if (capacity < step_off[n_windows] || (n_windows && !path_len)) return APD_ERR_INVALID_ARG;
-    if (n_windows == 0) return APD_OK;
-    for (uint64_t p = 0; p < n_windows; ++p)
-        if (len_of(windows[p].x) > kSpotMaxQuery || len_of(windows[p].y) >= kSpotMaxStream) {
-            ctx->last_error = "apd_spot_paths: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
-            return APD_ERR_UNSUPPORTED;
-        }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot path launch");
-    const uint64_t cap = spot_workspace_cap();
-    constexpr uint64_t kMaxWindowsPerLaunch = 1ull << 24;                 // 64 work-items per window, launches stay below 2^31
-    constexpr uint32_t kClasses = kSpotRegisterRows + 1;                  // spot_row_class
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    std::vector<uint64_t> live;                                           // the chunk's windows that own slots, input order
-    std::vector<uint64_t> by_pair;                                        // the same, grouped by pair, starts ascending
-    std::vector<SpotRecPair> rec_pairs[kClasses];
-    std::vector<SpotInterval> intervals;
-    std::vector<uint32_t> ends;
-    std::vector<SpotTraceWindow> trace;
-    std::vector<char> upload;
-    std::vector<uint32_t> h_len, h_found;
-    std::vector<float> h_scores;
-    bool first_launch = true;
-    for (uint64_t first = 0; first < n_windows;) {
-        uint64_t last = first, est_words = 0;
-        while (last < n_windows && last - first < kMaxWindowsPerLaunch) {
-            const apd_spot_window &w = windows[last];
-            const uint64_t slots = step_off[last + 1] - step_off[last];
-            const uint64_t nw = est_words + (slots ? spot_dir_words(len_of(w.x), (uint64_t)w.end - w.start + 1) : 0);
-            if (last > first && (nw * sizeof(uint32_t) > cap || (step_off[last + 1] - step_off[first]) * sizeof(apd_path_step) > cap)) break;
-            est_words = nw;
-            ++last;
-        }
-        live.clear();
-        for (uint64_t p = first; p < last; ++p) {
-            if (step_off[p + 1] > step_off[p]) { live.push_back(p); continue; }
-            path_len[p] = 0;                                              // no window: nothing to sweep
-            if (found_start) found_start[p] = 0;
-            if (scores) scores[p] = INFINITY;
-        }
-        if (live.empty()) { first = last; continue; }
-        // ---- the plan: per pair its merged intervals and its distinct ends; per window its interval and its end's slot
-        by_pair = live;
-        std::sort(by_pair.begin(), by_pair.end(), [&](uint64_t a, uint64_t b) {
-            const apd_spot_window &u = windows[a], &v = windows[b];
-            return std::make_tuple(u.x, u.y, u.start, u.end, a) < std::make_tuple(v.x, v.y, v.start, v.end, b);
-        });
-        for (auto &v : rec_pairs) v.clear();
-        intervals.clear(); ends.clear();
-        trace.assign(live.size(), SpotTraceWindow{});
-        uint64_t words = 0;
-        uint32_t r_max = 1;
-        for (size_t g = 0; g < by_pair.size();) {
-            size_t g_end = g;
-            const apd_spot_window &head = windows[by_pair[g]];
-            while (g_end < by_pair.size() && windows[by_pair[g_end]].x == head.x && windows[by_pair[g_end]].y == head.y) ++g_end;
-            const uint32_t n = len_of(head.x), c = spot_row_class(batch->dim, n);
-            if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(n));
-            SpotRecPair rp{};
-            rp.px = pos[head.x]; rp.py = pos[head.y];
-            rp.iv_first = (uint32_t)intervals.size(); rp.end_first = (uint32_t)ends.size();
-            for (size_t t = g; t < g_end; ++t) {
-                const apd_spot_window &w = windows[by_pair[t]];
-                if (intervals.size() > rp.iv_first && (uint64_t)w.start <= (uint64_t)intervals.back().b + 1)
-                    intervals.back().b = std::max(intervals.back().b, w.end);   // overlapping or touching: one interval
-                else
-                    intervals.push_back(SpotInterval{w.start, w.end, 0});
-                ends.push_back(w.end);
-                rp.max_end = std::max(rp.max_end, w.end);
-            }
-            std::sort(ends.begin() + rp.end_first, ends.end());
-            ends.erase(std::unique(ends.begin() + rp.end_first, ends.end()), ends.end());
-            rp.n_iv = (uint32_t)intervals.size() - rp.iv_first; rp.n_ends = (uint32_t)ends.size() - rp.end_first;
-            for (uint32_t k = rp.iv_first; k < intervals.size(); ++k) {
-                intervals[k].off = words;
-                words += spot_dir_words(n, (uint64_t)intervals[k].b - intervals[k].a + 1);
-            }
-            for (size_t t = g; t < g_end; ++t) {
-                const uint64_t p = by_pair[t];
-                const apd_spot_window &w = windows[p];
-                SpotTraceWindow &tw = trace[std::lower_bound(live.begin(), live.end(), p) - live.begin()];
-                uint32_t k = rp.iv_first;
-                while (intervals[k].b < w.end) ++k;                       // the interval that holds [start, end]
-                tw.px = rp.px; tw.py = rp.py; tw.end = w.end; tw.start = w.start;
-                tw.a = intervals[k].a; tw.dir_off = intervals[k].off;
-                tw.end_slot = (uint32_t)(std::lower_bound(ends.begin() + rp.end_first, ends.end(), w.end) - ends.begin());
-                tw.step_off = step_off[p] - step_off[first];
-            }
-            rec_pairs[c].push_back(rp);
-            g = g_end;
-        }
-        // ---- workspaces
-        const size_t nt = trace.size(), ne = ends.size();
-        size_t np = 0;
-        for (auto &v : rec_pairs) np += v.size();
-        const size_t steps_bytes = (size_t)(step_off[last] - step_off[first]) * sizeof(apd_path_step);
-        const size_t o_pairs = 0, o_iv = o_pairs + np * sizeof(SpotRecPair), o_win = o_iv + intervals.size() * sizeof(SpotInterval);
-        const size_t o_ends = o_win + nt * sizeof(SpotTraceWindow), upload_bytes = up16(o_ends + ne * 4);
-        const size_t o_end_cost = upload_bytes, o_end_start = o_end_cost + up16(ne * 4), o_len = o_end_start + up16(ne * 4);
-        const size_t o_found = o_len + up16(nt * 4), o_scores = o_found + up16(nt * 4), side_bytes = o_scores + up16(nt * 4);
-        rc = reserve_ws(ctx, ctx->ws_spot_dirs, std::max<size_t>((size_t)words * sizeof(uint32_t), 16));
-        if (rc) return rc;
-        rc = reserve_ws(ctx, ctx->ws_spot_steps, steps_bytes + side_bytes + 16);
-        if (rc) return rc;
-        upload.assign(upload_bytes, 0);
-        size_t class_first[kClasses], at = 0;
-        for (uint32_t c = 0; c < kClasses; ++c) {
-            class_first[c] = at;
-            if (!rec_pairs[c].empty()) std::memcpy(upload.data() + o_pairs + at * sizeof(SpotRecPair), rec_pairs[c].data(), rec_pairs[c].size() * sizeof(SpotRecPair));
-            at += rec_pairs[c].size();
-        }
-        std::memcpy(upload.data() + o_iv, intervals.data(), intervals.size() * sizeof(SpotInterval));
-        std::memcpy(upload.data() + o_win, trace.data(), nt * sizeof(SpotTraceWindow));
-        std::memcpy(upload.data() + o_ends, ends.data(), ne * 4);
-        char *base = ctx->ws_spot_steps.as<char>(), *side = base + steps_bytes;
-        SpotPathLaunch L{};
-        L.d_frames = batch->d_frames.as<float>(); L.d_seq_off = batch->d_seq_off; L.dim = batch->dim; L.dpad = batch->dpad;
-        L.ins = cfg->insertion_penalty; L.del = cfg->deletion_penalty; L.mat = cfg->match_penalty;
-        L.d_intervals = (const SpotInterval *)(side + o_iv);
-        L.d_ends = (const uint32_t *)(side + o_ends);
-        L.d_end_cost = (float *)(side + o_end_cost); L.d_end_start = (uint32_t *)(side + o_end_start);
-        L.d_dirs = ctx->ws_spot_dirs.as<uint32_t>();
-        L.d_windows = (const SpotTraceWindow *)(side + o_win); L.n_windows = (uint32_t)nt;
-        L.d_steps = (apd_path_step *)base;
-        L.d_len = (uint32_t *)(side + o_len); L.d_found = (uint32_t *)(side + o_found); L.d_scores = (float *)(side + o_scores);
-        HIP_TRY(ctx, hipMemcpyAsync(side, upload.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->timing && first_launch) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        first_launch = false;
-        for (uint32_t c = 0; c < kClasses; ++c) {
-            L.d_pairs = (const SpotRecPair *)(side + o_pairs) + class_first[c];
-            L.n_pairs = (uint32_t)rec_pairs[c].size();
-            HIP_TRY(ctx, launch_spot_record(L, c, r_max, ctx->stream));
-        }
-        HIP_TRY(ctx, launch_spot_trace(L, ctx->stream));
-        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }   // the last chunk's record stands
-        h_len.resize(nt); h_found.resize(nt); h_scores.resize(nt);
-        HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), L.d_len, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_found.data(), L.d_found, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), L.d_scores, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspaces (and `upload`)
-        for (size_t t = 0; t < nt; ++t) {
-            const uint64_t p = live[t];
-            path_len[p] = h_len[t];
-            if (found_start) found_start[p] = h_found[t];
-            if (scores) scores[p] = h_scores[t];
-        }
-        first = last;
-    }
-    return APD_OK;
-}
-
-// ------------------------------------------------------------------------------------ streaming spotting
-
-// A resident spotting session (include/apd.h, "streaming spotting"; kernels: dtw_spot_stream.hip).  Everything a push needs lives
-// here and grows only: the pair descriptors (grouped by kernel class once, at create), the two halves of the carried columns, the
-// running bests, the words a push uploads, the staged chunk and the curves.
-struct apd_spot_stream : apd::ContextChild {
-    static constexpr uint32_t kClasses = kSpotRegisterRows + 1;             // spot_row_class
-    const apd_batch *templates = nullptr;
-    uint32_t n_queries = 0, n_channels = 0, n_pairs = 0;
-    float ins = 0.0f, del = 0.0f, mat = 0.0f;
-    std::vector<uint64_t> columns;      // per channel: absolute column of the last frame pushed (first_column after a reset)
-    std::vector<uint32_t> parity;       // per channel: the half of d_state that holds its column
-    std::vector<SpotStreamPair> h_pairs;
-    std::vector<uint32_t> h_push;       // host image of d_push, alive as long as the session (the upload is asynchronous)
-    uint32_t class_first[kClasses] = {}, class_count[kClasses] = {};
-    uint32_t r_max = 1;
-    uint64_t state_half = 0;            // floats
-    apd::DeviceBuf d_pairs, d_state, d_best;
-    apd::DeviceBuf d_push;              // [chunk first n_channels + 1 | base n_channels | parity n_channels | the repack's words, kPadWords]
-    apd::DeviceBuf d_raw;               // host chunks on their way to the repack kernel
-    apd::DeviceBuf d_stage;             // the chunks in the resident layout, two sentinel frames behind them
-    apd::DeviceBuf d_curves;            // [cost | start]
-    // the history (apd_spot_stream_keep; kernels: dtw_spot_stream_rec.hip): the last `history` columns of every pair's branches and
-    // row-n curve and of every channel's frames, in rings; 0: none kept, and a push runs the kernels it ran before there was one
-    uint32_t history = 0;
-    std::vector<uint64_t> origin;       // per channel: the column behind which the history starts (cells of columns > origin are kept)
-    std::vector<uint32_t> q_len, q_pos; // per query: frames, resident position
-    std::vector<uint32_t> wpl_before;   // per pair p: the sum of ceil(R / 16) over the pairs before it (and the total behind the last)
-    apd::DeviceBuf d_hist_dirs, d_hist_curves, d_hist_frames, d_hist_wpl;
-    // the online detector (apd_spot_stream_detect; kernels: dtw_spot_online.hip); a session that is not armed holds none of it and
-    // a push runs the kernels it ran before there was one
-    bool armed = false;
-    uint32_t det_per_stream = 0, det_holdoff = 0, det_groups = 0;
-    apd::DeviceBuf d_det_pairs, d_det_state, d_det_count;
-    apd::DeviceBuf d_det_queue;         // det_cap records, the first det_queued of them queued, in arrival order
-    uint64_t det_cap = 0, det_queued = 0;
-    unsigned long long h_det_count = 0; // where a push's copy of *d_det_count lands (alive as long as the session)
-    SpotOnlineLaunch online() const
-    {
-        SpotOnlineLaunch L{};
-        L.d_push = d_push.as<uint32_t>();
-        L.n_channels = n_channels; L.n_queries = n_queries;
-        L.per_stream = det_per_stream; L.holdoff = det_holdoff; L.n_groups = det_groups;
-        L.d_pairs = d_det_pairs.as<SpotOnlinePair>(); L.d_state = d_det_state.as<SpotOnlineState>();
-        L.d_queue = d_det_queue.as<apd_spot_hit>(); L.d_count = d_det_count.as<unsigned long long>(); L.queue_cap = det_cap;
-        return L;
-    }
-    SpotHistory rings() const
-    {
-        SpotHistory H{};
-        H.rows = history;
-        H.d_dirs = d_hist_dirs.as<uint32_t>(); H.d_wpl_before = d_hist_wpl.as<uint32_t>();
-        H.d_curve_v = d_hist_curves.as<float>();
-        H.d_curve_s = d_hist_curves.as<uint32_t>() + (size_t)n_pairs * history;
-        H.d_frames = d_hist_frames.as<float>();
-        return H;
-    }
-    // [first, last] of the channel's kept columns; first = last + 1: none
-    void kept(uint32_t channel, uint64_t *first, uint64_t *last) const
-    {
-        const uint64_t end = columns[channel], from_ring = end + 1 > history ? end + 1 - history : 0;
-        *last = end;
-        *first = history ? std::max(origin[channel] + 1, from_ring) : end + 1;
-    }
-    // the staged chunks are ONE sequence to the repack kernel: [seq_off 2 | src_off 1 | unused 1 | flags 4 | norm maximum 1 | unused 3]
-    static constexpr uint32_t kPadWords = 12;
-    size_t push_words() const { return 3 * (size_t)n_channels + 1 + kPadWords; }
-    SpotStreamLaunch launch() const
-    {
-        SpotStreamLaunch S{};
-        S.d_frames = templates->d_frames.as<float>(); S.d_seq_off = templates->d_seq_off;
-        S.d_stage = d_stage.as<float>(); S.d_push = d_push.as<uint32_t>();
-        S.n_channels = n_channels; S.n_queries = n_queries; S.dim = templates->dim; S.dpad = templates->dpad;
-        S.ins = ins; S.del = del; S.mat = mat;
-        S.d_pairs = d_pairs.as<SpotStreamPair>(); S.n_pairs = n_pairs;
-        S.d_state = d_state.as<float>(); S.state_half = state_half;
-        S.d_best = d_best.as<apd_spot_best>();
-        return S;
-    }
-    void release_device() override
-    {
-        d_pairs.reset(); d_state.reset(); d_best.reset(); d_push.reset(); d_raw.reset(); d_stage.reset(); d_curves.reset();
-        d_hist_dirs.reset(); d_hist_curves.reset(); d_hist_frames.reset(); d_hist_wpl.reset();
-        d_det_pairs.reset(); d_det_state.reset(); d_det_count.reset(); d_det_queue.reset();
-    }
-};
-
-// Room for `extra` more hits behind the queued ones, made before the launch that may emit them: no hit is ever dropped.  Growth
-// allocates first -- a refusal is APD_ERR_OOM with nothing enqueued and the session untouched -- then moves the queued records over.
-static int spot_online_reserve(apd_context *ctx, apd_spot_stream *s, uint64_t extra)
-{
-    const uint64_t need = s->det_queued + extra;
-    if (need <= s->det_cap) return APD_OK;
-    const uint64_t cap = std::max(need, 2 * s->det_cap);
-    apd::DeviceBuf grown;
-    if (grown.alloc((size_t)cap * sizeof(apd_spot_hit)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->last_error = "apd_spot_stream: no device memory for a queue of " + std::to_string(cap) + " hits";
-        return APD_ERR_OOM;
-    }
-    if (s->det_queued) {
-        HIP_TRY(ctx, hipMemcpyAsync(grown.ptr, s->d_det_queue.ptr, (size_t)s->det_queued * sizeof(apd_spot_hit), hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the old queue is released below
-    }
-    s->d_det_queue = std::move(grown);
-    s->det_cap = cap;
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_create(apd_context *ctx, const apd_batch *templates, const apd_align_config *cfg, const uint32_t *queries,
-                                      uint32_t n_queries, uint32_t n_channels, apd_spot_stream **stream)
-{
-    if (!ctx || !templates || !cfg || !stream || !queries || templates->ctx != ctx) return APD_ERR_INVALID_ARG;
-    *stream = nullptr;
-    const uint64_t n_pairs = (uint64_t)n_queries * n_channels;
-    if (n_pairs == 0 || n_pairs >= (1ull << 24)) return APD_ERR_INVALID_ARG;   // 64 work-items per pair: a launch stays below 2^31
-    const uint32_t n_seq = templates->n_seq;
-    for (uint32_t q = 0; q < n_queries; ++q)
-        if (queries[q] >= n_seq) return APD_ERR_INVALID_ARG;
-    std::vector<uint32_t> pos(n_seq);                                     // caller's sequence number -> resident position
-    for (uint32_t p = 0; p < n_seq; ++p) pos[templates->order[p]] = p;
-    auto len_of = [&](uint32_t s) { return (uint32_t)(templates->offsets[pos[s] + 1] - templates->offsets[pos[s]]); };
-    for (uint32_t q = 0; q < n_queries; ++q)
-        if (len_of(queries[q]) == 0) return APD_ERR_EMPTY_SEQUENCE;
-    for (uint32_t q = 0; q < n_queries; ++q)
-        if (len_of(queries[q]) > kSpotMaxQuery) {
-            ctx->last_error = "apd_spot_stream_create: a query of more than " + std::to_string(kSpotMaxQuery) + " frames";
-            return APD_ERR_UNSUPPORTED;
-        }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream allocation");
-    apd_spot_stream *s = new (std::nothrow) apd_spot_stream();
-    if (!s) return APD_ERR_OOM;
-    s->templates = templates; s->n_queries = n_queries; s->n_channels = n_channels; s->n_pairs = (uint32_t)n_pairs;
-    s->ins = cfg->insertion_penalty; s->del = cfg->deletion_penalty; s->mat = cfg->match_penalty;
-    s->columns.assign(n_channels, 0);
-    s->parity.assign(n_channels, 0u);
-    s->origin.assign(n_channels, 0);
-    s->h_push.assign(s->push_words(), 0u);
-    for (uint32_t q = 0; q < n_queries; ++q) { s->q_len.push_back(len_of(queries[q])); s->q_pos.push_back(pos[queries[q]]); }
-    s->wpl_before.assign(n_pairs + 1, 0u);
-    for (uint64_t p = 0; p < n_pairs; ++p) s->wpl_before[p + 1] = s->wpl_before[p] + (spot_rows_per_lane(s->q_len[p % n_queries]) + 15) / 16;
-    // the descriptors, grouped by kernel class (one launch each per push); `out` keeps p = channel n_queries + q
-    constexpr uint32_t kClasses = apd_spot_stream::kClasses;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        const uint32_t n = len_of(queries[q]), c = spot_row_class(templates->dim, n);
-        s->class_count[c] += n_channels;
-        if (c == 0) s->r_max = std::max(s->r_max, spot_rows_per_lane(n));
-    }
-    for (uint32_t c = 1; c < kClasses; ++c) s->class_first[c] = s->class_first[c - 1] + s->class_count[c - 1];
-    uint32_t fill[kClasses];
-    std::copy(s->class_first, s->class_first + kClasses, fill);
-    s->h_pairs.resize(n_pairs);
-    uint64_t state_floats = 0;
-    for (uint32_t k = 0; k < n_channels; ++k)
-        for (uint32_t q = 0; q < n_queries; ++q) {
-            const uint32_t n = len_of(queries[q]);
-            SpotStreamPair &d = s->h_pairs[fill[spot_row_class(templates->dim, n)]++];
-            d.px = pos[queries[q]];
-            d.channel = k;
-            d.out = k * n_queries + q;
-            d.rows = spot_rows_per_lane(n);
-            d.state_off = state_floats;
-            state_floats += 2ull * d.rows * 64;                           // values, then starts
-        }
-    s->state_half = state_floats;
-    s->ctx = ctx;
-    ctx->children.insert(s);                                              // from here on apd_spot_stream_destroy undoes everything
-    auto fail = [&](int rc) { apd_spot_stream_destroy(s); return rc; };
-    const size_t pair_bytes = (size_t)n_pairs * sizeof(SpotStreamPair);
-    if (s->d_pairs.alloc(pair_bytes) != hipSuccess || s->d_state.alloc((size_t)state_floats * 2 * sizeof(float)) != hipSuccess ||
-        s->d_best.alloc((size_t)n_pairs * sizeof(apd_spot_best)) != hipSuccess ||
-        s->d_push.alloc(s->push_words() * sizeof(uint32_t)) != hipSuccess)
-        return fail(APD_ERR_OOM);
-    hipError_t e = hipMemcpyAsync(s->d_pairs.ptr, s->h_pairs.data(), pair_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_spot_stream_reset(s->launch(), 0xFFFFFFFFu, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = std::string("apd_spot_stream_create: ") + hipGetErrorString(e); return fail(APD_ERR_HIP); }
-    *stream = s;
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_destroy(apd_spot_stream *stream) { return destroy_child(stream); }
-
-extern "C" int apd_spot_stream_reset(apd_context *ctx, apd_spot_stream *stream, uint32_t channel, uint64_t first_column)
-{
-    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
-    const bool all = channel == 0xFFFFFFFFu;
-    if (!all && channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
-    if (first_column >= kSpotMaxStream) {
-        ctx->last_error = "apd_spot_stream_reset: first_column at or beyond " + std::to_string(kSpotMaxStream);
-        return APD_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream reset");
-    HIP_TRY(ctx, launch_spot_stream_reset(stream->launch(), channel, ctx->stream));
-    // an armed session: the channel's pending windows go, its floors move to the new origin; ranks and queued hits stay
-    if (stream->armed) HIP_TRY(ctx, launch_spot_online_touch(stream->online(), channel, false, (uint32_t)first_column, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t k = 0; k < stream->n_channels; ++k)
-        if (all || k == channel) stream->columns[k] = stream->origin[k] = first_column;   // either half holds column 0 now: the parity stays; the history is empty
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_columns(const apd_spot_stream *stream, uint32_t channel, uint64_t *columns)
-{
-    if (!stream || !columns || channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
-    *columns = stream->columns[channel];
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_push(apd_context *ctx, apd_spot_stream *stream, const float *frames, const uint64_t *chunk_off, uint32_t dim,
-                                    int frames_on_device, float *cost, uint32_t *start, uint64_t capacity, uint64_t *curve_off,
-                                    apd_spot_best *best)
-{
-    if (!ctx || !stream || stream->ctx != ctx || !chunk_off || !curve_off) return APD_ERR_INVALID_ARG;
-    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
-    apd_spot_stream *s = stream;
-    const apd_batch *t = s->templates;
-    if (t->ctx != ctx || dim != t->src_dim) return APD_ERR_INVALID_ARG;
-    const uint32_t n_ch = s->n_channels, n_q = s->n_queries;
-    if (chunk_off[0] != 0) return APD_ERR_INVALID_ARG;
-    for (uint32_t k = 0; k < n_ch; ++k)
-        if (chunk_off[k + 1] < chunk_off[k]) return APD_ERR_INVALID_ARG;
-    const uint64_t total = chunk_off[n_ch];
-    if (total + 2 >= (1ull << 32) || (total > 0 && !frames)) return APD_ERR_INVALID_ARG;   // one resident "sequence", as a batch's limit
-    for (uint32_t k = 0; k < n_ch; ++k)
-        if (s->columns[k] + (chunk_off[k + 1] - chunk_off[k]) >= kSpotMaxStream) {
-            ctx->last_error = "apd_spot_stream_push: channel " + std::to_string(k) + " would reach column " + std::to_string(kSpotMaxStream);
-            return APD_ERR_UNSUPPORTED;
-        }
-    curve_off[0] = 0;
-    for (uint32_t k = 0; k < n_ch; ++k)
-        for (uint32_t q = 0; q < n_q; ++q) {
-            const uint64_t p = (uint64_t)k * n_q + q;
-            curve_off[p + 1] = curve_off[p] + (chunk_off[k + 1] - chunk_off[k]);
-        }
-    const bool curves = cost != nullptr;
-    if (!curves && !best) return APD_OK;                                  // sizes only: the state is not advanced
-    const uint64_t entries = curve_off[s->n_pairs];
-    if (curves && capacity < entries) return APD_ERR_INVALID_ARG;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream launch");
-    SpotStreamLaunch S = s->launch();
-    const size_t best_bytes = (size_t)s->n_pairs * sizeof(apd_spot_best);
-    if (total > 0) {
-        // buffers: grown to the largest push seen, then reused
-        // an armed session: the detector reads the curves on the device whether or not the caller asked for them on the host
-        const bool stored = curves || s->armed;
-        const size_t curve_bytes = stored ? ((size_t)entries * 4 + 15) / 16 * 16 : 0;
-        HIP_TRY(ctx, s->d_stage.reserve((size_t)(total + 2) * t->dpad * sizeof(float)));
-        if (stored) HIP_TRY(ctx, s->d_curves.reserve(2 * curve_bytes));
-        const size_t raw_bytes = (size_t)total * dim * sizeof(float);
-        if (!frames_on_device) HIP_TRY(ctx, s->d_raw.reserve(raw_bytes));
-        if (s->armed) {
-            // a group emits at most (chunk columns + 1) hits per push, and none on a channel without columns
-            uint64_t bound = 0;
-            for (uint32_t k = 0; k < n_ch; ++k)
-                if (chunk_off[k + 1] > chunk_off[k]) bound += (chunk_off[k + 1] - chunk_off[k] + 1) * (s->det_per_stream ? 1u : n_q);
-            if (const int rc = spot_online_reserve(ctx, s, bound)) return rc;
-        }
-        S = s->launch();
-        S.d_cost = stored ? s->d_curves.as<float>() : nullptr;
-        S.d_start = stored ? (uint32_t *)(s->d_curves.as<char>() + curve_bytes) : nullptr;
-        // the words of this push
-        uint32_t *w = s->h_push.data(), *pad = w + 3 * (size_t)n_ch + 1;
-        for (uint32_t k = 0; k <= n_ch; ++k) w[k] = (uint32_t)chunk_off[k];
-        for (uint32_t k = 0; k < n_ch; ++k) {
-            w[n_ch + 1 + k] = (uint32_t)s->columns[k];
-            w[2 * n_ch + 1 + k] = s->parity[k];
-        }
-        std::fill(pad, pad + apd_spot_stream::kPadWords, 0u);
-        pad[1] = (uint32_t)total + 2;                                     // seq_off = {0, total + 2}, src_off = {0}, flags and norm maximum zeroed
-        uint32_t *d_w = s->d_push.as<uint32_t>(), *d_pad = d_w + 3 * (size_t)n_ch + 1;
-        HIP_TRY(ctx, hipMemcpyAsync(d_w, w, s->push_words() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        const float *d_src = frames;
-        if (!frames_on_device) {
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_raw.ptr, frames, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
-            d_src = s->d_raw.as<float>();
-        }
-        if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        HIP_TRY(ctx, launch_pad(d_src, s->d_stage.as<float>(), d_pad, d_pad + 2, 1, total + 2, dim, t->dim, t->dpad, d_pad + 4,
-                                reinterpret_cast<float *>(d_pad + 8), ctx->stream));
-        SpotStreamRecLaunch A{S, s->rings()};
-        if (s->history) HIP_TRY(ctx, launch_spot_stream_frames(A, (uint32_t)total, ctx->stream));
-        for (uint32_t c = 0; c < apd_spot_stream::kClasses; ++c) {
-            A.S.d_pairs = S.d_pairs = s->d_pairs.as<SpotStreamPair>() + s->class_first[c];
-            A.S.n_pairs = S.n_pairs = s->class_count[c];
-            if (s->history) HIP_TRY(ctx, launch_spot_stream_record(A, c, s->r_max, ctx->stream));
-            else HIP_TRY(ctx, launch_spot_stream(S, c, s->r_max, ctx->stream));
-        }
-        if (s->armed) {
-            SpotOnlineLaunch O = s->online();
-            O.d_cost = S.d_cost; O.d_start = S.d_start;
-            uint64_t m_max = 0;
-            for (uint32_t k = 0; k < n_ch; ++k) m_max = std::max(m_max, chunk_off[k + 1] - chunk_off[k]);
-            HIP_TRY(ctx, launch_spot_online_scan(O, m_max, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(&s->h_det_count, O.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-        // the table has moved on, whatever the copies below do
-        for (uint32_t k = 0; k < n_ch; ++k) {
-            const uint64_t m = chunk_off[k + 1] - chunk_off[k];
-            if (m) { s->columns[k] += m; s->parity[k] ^= 1u; }
-        }
-        if (curves) {
-            HIP_TRY(ctx, hipMemcpyAsync(cost, S.d_cost, (size_t)entries * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(start, S.d_start, (size_t)entries * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    if (best) HIP_TRY(ctx, hipMemcpyAsync(best, S.d_best, best_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                      // blocking: the results are the caller's, `frames` is free again
-    if (s->armed && total > 0) s->det_queued = s->h_det_count;            // the queued count came back with that synchronisation
-    return APD_OK;
-}
-
-// Raw audio into a session: the feed's push into its own device buffer, then the push above on those rows.  Everything either
-// would refuse is refused before the feed moves on.
-extern "C" int apd_spot_stream_push_audio(apd_context *ctx, apd_spot_stream *stream, apd_feed *feed, const int16_t *samples,
-                                          const uint64_t *sample_off, int samples_on_device, float *cost, uint32_t *start,
-                                          uint64_t capacity, uint64_t *curve_off, apd_spot_best *best)
-{
-    if (!ctx || !stream || stream->ctx != ctx || !feed || !sample_off || !curve_off) return APD_ERR_INVALID_ARG;
-    const apd_context *feed_ctx = nullptr;
-    uint32_t feed_channels = 0, dim = 0;
-    feed_info(feed, &feed_ctx, &feed_channels, &dim);
-    if (feed_ctx != ctx || feed_channels != stream->n_channels || dim != stream->templates->src_dim) return APD_ERR_INVALID_ARG;
-    std::vector<uint64_t> chunk_off((size_t)feed_channels + 1);
-    if (const int rc = feed_sizes(feed, sample_off, chunk_off.data())) return rc;
-    // the session's own checks and curve_off: its sizes-only form
-    if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
-    static const float unread = 0.0f;                                     // the sizes-only form wants a frame pointer and does not follow it
-    if (const int rc = apd_spot_stream_push(ctx, stream, &unread, chunk_off.data(), dim, 1, nullptr, nullptr, 0, curve_off, nullptr)) return rc;
-    if (!cost && !best) return APD_OK;                                    // sizes only: neither state is advanced
-    if (cost && capacity < curve_off[stream->n_pairs]) return APD_ERR_INVALID_ARG;
-    if (sample_off[feed_channels] > sample_off[0] && !samples) return APD_ERR_INVALID_ARG;
-    HIP_TRY(ctx, bind_device(ctx));
-    const float *d_rows = nullptr;
-    if (const int rc = feed_enqueue(ctx, feed, samples, sample_off, samples_on_device, chunk_off.data(), &d_rows)) return rc;
-    return apd_spot_stream_push(ctx, stream, d_rows, chunk_off.data(), dim, 1, cost, start, capacity, curve_off, best);
-}
-
-// ---- the online detector of a session: apd_spot_stream_detect / _flush / _hits (include/apd.h; kernels: dtw_spot_online.hip)
-
-extern "C" int apd_spot_stream_detect(apd_context *ctx, apd_spot_stream *stream, const float *thresholds, int compete, uint32_t holdoff)
-{
-    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
-    if (compete != APD_DETECT_PER_PAIR && compete != APD_DETECT_PER_STREAM) return APD_ERR_INVALID_ARG;
-    apd_spot_stream *s = stream;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream detector");
-    if (!thresholds) {
-        s->d_det_pairs.reset(); s->d_det_state.reset(); s->d_det_count.reset(); s->d_det_queue.reset();
-        s->armed = false;
-        s->det_groups = 0; s->det_cap = s->det_queued = 0;
-        return APD_OK;
-    }
-    const uint32_t n_q = s->n_queries, groups = compete == APD_DETECT_PER_STREAM ? s->n_channels : s->n_pairs;
-    std::vector<SpotOnlinePair> pairs(s->n_pairs);
-    for (uint32_t p = 0; p < s->n_pairs; ++p) { pairs[p].n = s->q_len[p % n_q]; pairs[p].threshold = thresholds[p]; }
-    // every group: no pending window, rank 0, the floor at its channel's current column (the detector's origin)
-    std::vector<SpotOnlineState> state(groups, SpotOnlineState{});
-    for (uint32_t g = 0; g < groups; ++g) state[g].floor = (uint32_t)s->columns[compete == APD_DETECT_PER_STREAM ? g : g / n_q];
-    // the new buffers first: a refusal leaves the session as it was, armed or not
-    apd::DeviceBuf d_pairs, d_state, d_count, d_queue;
-    const uint64_t cap = s->d_det_queue ? s->det_cap : std::max<uint64_t>(groups, 64);
-    if (d_pairs.alloc(pairs.size() * sizeof(SpotOnlinePair)) != hipSuccess || d_state.alloc(state.size() * sizeof(SpotOnlineState)) != hipSuccess ||
-        d_count.alloc(sizeof(unsigned long long)) != hipSuccess ||
-        (!s->d_det_queue && d_queue.alloc((size_t)cap * sizeof(apd_spot_hit)) != hipSuccess)) {
-        (void)hipGetLastError();
-        ctx->last_error = "apd_spot_stream_detect: no device memory for " + std::to_string(groups) + " groups";
-        return APD_ERR_OOM;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_pairs.ptr, pairs.data(), pairs.size() * sizeof(SpotOnlinePair), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_state.ptr, state.data(), state.size() * sizeof(SpotOnlineState), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(d_count.ptr, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->d_det_pairs = std::move(d_pairs); s->d_det_state = std::move(d_state); s->d_det_count = std::move(d_count);
-    if (!s->d_det_queue) s->d_det_queue = std::move(d_queue);             // arming again keeps the queue's memory and discards its hits
-    s->det_cap = cap; s->det_queued = 0;
-    s->det_per_stream = (uint32_t)compete; s->det_holdoff = holdoff; s->det_groups = groups;
-    s->armed = true;
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_flush(apd_context *ctx, apd_spot_stream *stream, uint32_t channel)
-{
-    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
-    apd_spot_stream *s = stream;
-    if (channel != 0xFFFFFFFFu && channel >= s->n_channels) return APD_ERR_INVALID_ARG;
-    if (!s->armed) {
-        ctx->last_error = "apd_spot_stream_flush: the session is not armed (apd_spot_stream_detect)";
-        return APD_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream flush");
-    if (const int rc = spot_online_reserve(ctx, s, s->det_groups)) return rc;   // one pending window per group at most
-    const SpotOnlineLaunch O = s->online();
-    HIP_TRY(ctx, launch_spot_online_touch(O, channel, true, 0u, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&s->h_det_count, O.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->det_queued = s->h_det_count;
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_hits(apd_context *ctx, apd_spot_stream *stream, apd_spot_hit *hits, uint64_t capacity, uint64_t *n_hits)
-{
-    if (!ctx || !stream || stream->ctx != ctx || !n_hits) return APD_ERR_INVALID_ARG;
-    apd_spot_stream *s = stream;
-    *n_hits = s->armed ? s->det_queued : 0;
-    if (*n_hits == 0 || capacity < *n_hits) return APD_OK;                // too small: nothing written, nothing consumed
-    if (!hits) return APD_ERR_INVALID_ARG;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream hits");
-    std::vector<apd_spot_hit> h((size_t)*n_hits);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), s->d_det_queue.ptr, h.size() * sizeof(apd_spot_hit), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->d_det_count.ptr, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->det_queued = 0;
-    // the queue holds arrival order, which depends on scheduling; (group, rank) is unique and does not
-    const uint32_t per_group = s->det_per_stream ? s->n_queries : 1u;
-    std::sort(h.begin(), h.end(), [&](const apd_spot_hit &a, const apd_spot_hit &b) {
-        const uint32_t ga = a.pair / per_group, gb = b.pair / per_group;
-        return ga != gb ? ga < gb : a.rank < b.rank;
-    });
-    std::copy(h.begin(), h.end(), hits);
-    return APD_OK;
-}
-
-// ---- the history of a session: apd_spot_stream_keep / _history / _paths (include/apd.h; kernels: dtw_spot_stream_rec.hip)
-
-extern "C" int apd_spot_stream_keep(apd_context *ctx, apd_spot_stream *stream, uint32_t history_columns)
-{
-    if (!ctx || !stream || stream->ctx != ctx) return APD_ERR_INVALID_ARG;
-    apd_spot_stream *s = stream;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream history");
-    const uint64_t H = history_columns;
-    apd::DeviceBuf dirs, curves, frames;
-    if (H) {
-        // the new rings first: a refusal leaves the session with the ones it has
-        const uint64_t dir_bytes = (uint64_t)s->wpl_before[s->n_pairs] * H * 64 * sizeof(uint32_t);
-        const uint64_t curve_bytes = (uint64_t)s->n_pairs * H * 8, frame_bytes = (uint64_t)s->n_channels * H * s->templates->dpad * sizeof(float);
-        if (dirs.alloc((size_t)dir_bytes) != hipSuccess || curves.alloc((size_t)curve_bytes) != hipSuccess ||
-            frames.alloc((size_t)frame_bytes) != hipSuccess || (!s->d_hist_wpl.ptr && s->d_hist_wpl.alloc((size_t)s->n_pairs * sizeof(uint32_t)) != hipSuccess)) {
-            (void)hipGetLastError();
-            ctx->last_error = "apd_spot_stream_keep: no device memory for " + std::to_string(H) + " columns of history";
-            return APD_ERR_OOM;
-        }
-        // nothing reads a row before a push has written it; zeros all the same, so that no run depends on what the memory held
-        HIP_TRY(ctx, hipMemsetAsync(dirs.ptr, 0, (size_t)dir_bytes, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(curves.ptr, 0, (size_t)curve_bytes, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(frames.ptr, 0, (size_t)frame_bytes, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(s->d_hist_wpl.ptr, s->wpl_before.data(), (size_t)s->n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    s->d_hist_dirs = std::move(dirs); s->d_hist_curves = std::move(curves); s->d_hist_frames = std::move(frames);
-    s->history = history_columns;
-    s->origin = s->columns;                                               // the history starts empty, behind every channel's current column
-    return APD_OK;
-}
-
-extern "C" int apd_spot_stream_history(const apd_spot_stream *stream, uint32_t channel, uint64_t *first, uint64_t *last)
-{
-    if (!stream || !first || !last || channel >= stream->n_channels) return APD_ERR_INVALID_ARG;
-    stream->kept(channel, first, last);
-    return APD_OK;
-}
-
-// The windows are taken in input order, a chunk at a time: as many as keep the steps under the workspace cap, at least one.  What
-// the rings no longer hold is decided here: a window whose end lies before the channel's first kept column never reaches the
-// device; one whose end is kept is given to the trace, which reads S[n][end] and walks only if that start is kept as well.
-// ws_spot_steps: [steps | windows (uploaded) | lengths | found | scores].
-extern "C" int apd_spot_stream_paths(apd_context *ctx, apd_spot_stream *stream, const apd_spot_window *windows, uint64_t n_windows,
-                                     apd_path_step *steps, uint64_t capacity, uint64_t *step_off, uint32_t *path_len,
-                                     uint32_t *found_start, float *scores)
-{
-    if (!ctx || !stream || stream->ctx != ctx || !step_off || (n_windows && !windows)) return APD_ERR_INVALID_ARG;
-    const apd_spot_stream *s = stream;
-    const apd_batch *t = s->templates;
-    if (t->ctx != ctx) return APD_ERR_INVALID_ARG;
-    for (uint64_t p = 0; p < n_windows; ++p) {
-        const apd_spot_window &w = windows[p];
-        if (w.x >= s->n_queries || w.y >= s->n_channels) return APD_ERR_INVALID_ARG;
-        if (w.end > s->columns[w.y] || (w.end && w.start > w.end)) return APD_ERR_INVALID_ARG;
-    }
-    step_off[0] = 0;
-    for (uint64_t p = 0; p < n_windows; ++p)
-        step_off[p + 1] = step_off[p] + apd_spot_path_bound(s->q_len[windows[p].x], windows[p].end, windows[p].start);
-    if (!steps) return APD_OK;                                            // sizes only
-    if (capacity < step_off[n_windows] || (n_windows && !path_len)) return APD_ERR_INVALID_ARG;
-    if (!s->history) {
-        ctx->last_error = "apd_spot_stream_paths: the session keeps no history (apd_spot_stream_keep)";
-        return APD_ERR_UNSUPPORTED;
-    }
-    if (n_windows == 0) return APD_OK;
-    HIP_TRY(ctx, bind_device(ctx));
-    APD_AFFINITY(ctx, "spot stream path launch");
-    const uint64_t cap = spot_workspace_cap();
-    constexpr uint64_t kMaxWindowsPerLaunch = 1ull << 24;                 // 64 work-items per window, launches stay below 2^31
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    std::vector<uint64_t> live;                                           // the chunk's windows that reach the trace, input order
-    std::vector<SpotRingWindow> trace;
-    std::vector<uint32_t> h_len, h_found;
-    std::vector<float> h_scores;
-    bool first_launch = true;
-    for (uint64_t first = 0; first < n_windows;) {
-        uint64_t last = first;
-        while (last < n_windows && last - first < kMaxWindowsPerLaunch) {
-            if (last > first && (step_off[last + 1] - step_off[first]) * sizeof(apd_path_step) > cap) break;
-            ++last;
-        }
-        live.clear(); trace.clear();
-        for (uint64_t p = first; p < last; ++p) {
-            const apd_spot_window &w = windows[p];
-            uint64_t kept_first, kept_last;
-            s->kept(w.y, &kept_first, &kept_last);
-            if (step_off[p + 1] > step_off[p] && w.end >= kept_first) {
-                SpotRingWindow r{};
-                r.px = s->q_pos[w.x]; r.channel = w.y; r.pair = w.y * s->n_queries + w.x;
-                r.end = w.end; r.start = w.start; r.first = (uint32_t)kept_first;
-                r.step_off = step_off[p] - step_off[first];
-                live.push_back(p); trace.push_back(r);
-                continue;
-            }
-            path_len[p] = 0;                                              // no window, or its end has aged out: nothing to read
-            if (found_start) found_start[p] = 0;
-            if (scores) scores[p] = INFINITY;
-            std::memset(steps + step_off[p], 0, (size_t)(step_off[p + 1] - step_off[p]) * sizeof(apd_path_step));
-        }
-        if (live.empty()) { first = last; continue; }
-        const size_t nt = trace.size();
-        const size_t steps_bytes = (size_t)(step_off[last] - step_off[first]) * sizeof(apd_path_step);
-        const size_t upload_bytes = up16(nt * sizeof(SpotRingWindow));
-        const size_t o_len = upload_bytes, o_found = o_len + up16(nt * 4), o_scores = o_found + up16(nt * 4), side_bytes = o_scores + up16(nt * 4);
-        int rc = reserve_ws(ctx, ctx->ws_spot_steps, steps_bytes + side_bytes + 16);
-        if (rc) return rc;
-        char *base = ctx->ws_spot_steps.as<char>(), *side = base + steps_bytes;
-        SpotRingTraceLaunch L{};
-        L.d_frames = t->d_frames.as<float>(); L.d_seq_off = t->d_seq_off; L.dim = t->dim; L.dpad = t->dpad;
-        L.ins = s->ins; L.del = s->del; L.mat = s->mat;
-        L.H = s->rings();
-        L.d_windows = (const SpotRingWindow *)side; L.n_windows = (uint32_t)nt;
-        L.d_steps = (apd_path_step *)base;
-        L.d_len = (uint32_t *)(side + o_len); L.d_found = (uint32_t *)(side + o_found); L.d_scores = (float *)(side + o_scores);
-        HIP_TRY(ctx, hipMemcpyAsync(side, trace.data(), nt * sizeof(SpotRingWindow), hipMemcpyHostToDevice, ctx->stream));
-        // an aged-out window between two traced ones leaves slots of the chunk no trace owns: the device copy is zeroed whole
-        HIP_TRY(ctx, hipMemsetAsync(base, 0, steps_bytes, ctx->stream));
-        if (ctx->timing && first_launch) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        first_launch = false;
-        HIP_TRY(ctx, launch_spot_stream_trace(L, ctx->stream));
-        if (ctx->timing) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }   // the last chunk's record stands
-        h_len.resize(nt); h_found.resize(nt); h_scores.resize(nt);
-        HIP_TRY(ctx, hipMemcpyAsync(steps + step_off[first], L.d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), L.d_len, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_found.data(), L.d_found, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), L.d_scores, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `trace`)
-        for (size_t k = 0; k < nt; ++k) {
-            const uint64_t p = live[k];
-            path_len[p] = h_len[k];
-            if (found_start) found_start[p] = h_found[k];
-            if (scores) scores[p] = h_scores[k];
-        }
-        first = last;
-    }
-    return APD_OK;
 }
 
 // ------------------------------------------------------------------------------- work accounting

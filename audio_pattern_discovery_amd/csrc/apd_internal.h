@@ -701,13 +701,13 @@ struct apd_context {
     apd::DeviceBuf ws_slab;
     apd::DeviceBuf ws_misc;
     apd::DeviceBuf ws_gather;         // gathered slabs of apd_align_all_sharded_async
-    apd::DeviceBuf ws_path_dirs;      // apd_align_paths: direction words of a chunk of pairs
-    apd::DeviceBuf ws_path_steps;     // ... its steps, then [pairs | lengths | scores]
-    apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters in the resident layout, sums, counts, descriptors of every chunk
-    apd::DeviceBuf ws_spot;           // apd_spot: [cost | start] curves of a chunk of pairs, then [pairs | best]; apd_spot_detect: see there
+    apd::DeviceBuf ws_path_dirs;      // apd_align_paths, apd_barycenters: direction words of a chunk of pairs
+    apd::DeviceBuf ws_path_steps;     // ... its steps, descriptors and results
+    apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters, their sums and counts, the plan of every chunk
+    apd::DeviceBuf ws_spot;           // apd_spot, apd_spot_detect: curves, descriptors and results of a chunk of pairs
     apd::DeviceBuf ws_spot_hits;      // apd_spot_detect: the packed hits of a chunk
     apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
-    apd::DeviceBuf ws_spot_steps;     // ... its steps, then [pairs | intervals | ends | end cost | end start | windows | lengths | found | scores]
+    apd::DeviceBuf ws_spot_steps;     // apd_spot_paths, apd_spot_stream_paths: steps, descriptors and results of a chunk of windows
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat
@@ -749,3 +749,12 @@ struct apd_batch : apd::ContextChild {
     mutable std::map<std::string, TilePlan> tile_cache;   // keyed by tile source/band/variant (tile_plan, apd_api.hip)
     void release_device() override;
 };
+
+// ---- what the API units share (defined in apd_api.hip; hidden: not among the exported symbols of libapd_hip.so)
+#pragma GCC visibility push(hidden)
+int check_lengths(const apd_batch *b);                                   // APD_ERR_EMPTY_SEQUENCE for a batch with an empty sequence
+apd::BandSpec band_from_cfg(const apd_align_config *cfg);
+apd::BandSpec band_from_params(const apd_alignment_params *params);
+// The context's two-sequence batch (ctx->pair_batch) holding (x, y): sequence 0 = x, sequence 1 = y.
+int prepare_pair_batch(apd_context *ctx, const float *x, uint64_t n, const float *y, uint64_t m, uint32_t dim);
+#pragma GCC visibility pop

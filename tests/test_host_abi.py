@@ -277,6 +277,21 @@ def test_formats_survive_the_sanitizer_fuzz(tmp_path):
     assert out.returncode == 0 and "no sanitizer report" in out.stdout, out.stdout[-1000:] + out.stderr[-3000:]
 
 
+def test_plan_helpers_match_their_slow_definitions(tmp_path):
+    """csrc/apd_plan.h (workspace layouts, chunk cuts, class buckets of the pair-list host drivers) is plain C++: tests/cpp/plan_check.cpp
+    checks each helper against its definition on seeded random inputs, built under AddressSanitizer + UBSan (CPU build, own process)."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(root, "tests", "cpp", "plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe, "3000", "20261"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "plan ok: 3000 rounds, no sanitizer report" in out.stdout, out.stdout[-1000:] + out.stderr[-3000:]
+
+
 def test_rust_binding_declares_every_symbol_with_the_headers_arity():
     """bindings/rust/src/apd_sys.rs cannot be compiled here (no rustc), so it is at least kept in step with include/apd.h
     mechanically: the same set of functions, each with as many parameters as the C declaration."""
