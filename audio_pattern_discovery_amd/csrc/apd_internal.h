@@ -629,6 +629,9 @@ int feed_sizes(const apd_feed *feed, const uint64_t *sample_off, uint64_t *frame
 int feed_enqueue(apd_context *ctx, apd_feed *feed, const int16_t *samples, const uint64_t *sample_off, int samples_on_device,
                  const uint64_t *frame_off, const float **d_rows);
 
+// companions.hip: an apd_encoder of this context whose weights ([d_in][latent]) and bias ([latent]) are copied from device memory
+int encoder_from_device(apd_context *ctx, const float *d_w_encode, const float *d_b_encode, uint32_t d_in, uint32_t latent, apd_encoder **out);
+
 // numerics.rs:125-133 on a device array (clustering.hip): radix select of the k-th smallest non-NaN value.
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value);
 uint64_t percentile_index(uint64_t len, float perc);

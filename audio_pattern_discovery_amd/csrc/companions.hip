@@ -588,6 +588,31 @@ extern "C" int apd_encoder_create(apd_context *ctx, const float *w_encode, const
 
 extern "C" int apd_encoder_destroy(apd_encoder *e) { return apd::destroy_child(e); }
 
+// An encoder whose weights already lie in this context's HBM (apd_trainer_encoder, train.hip): copied device to device, so the
+// source may change or go afterwards.
+int apd::encoder_from_device(apd_context *ctx, const float *d_w_encode, const float *d_b_encode, uint32_t d_in, uint32_t latent, apd_encoder **out)
+{
+    *out = nullptr;
+    const size_t w_bytes = (size_t)d_in * latent * sizeof(float), b_bytes = latent * sizeof(float);
+    if (w_bytes + b_bytes > 64 * 1024) return APD_ERR_UNSUPPORTED;
+    HIP_TRY(ctx, apd::bind_device(ctx));
+    apd_encoder *e = new (std::nothrow) apd_encoder();
+    if (!e) return APD_ERR_OOM;
+    e->ctx = ctx; e->d_in = d_in; e->latent = latent;
+    hipError_t err = e->d_w.alloc(w_bytes + b_bytes);
+    if (err == hipSuccess) err = hipMemcpyAsync(e->d_w.ptr, d_w_encode, w_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(e->d_w.as<char>() + w_bytes, d_b_encode, b_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (err != hipSuccess) {
+        ctx->last_error = std::string("apd_trainer_encoder: ") + hipGetErrorString(err);
+        delete e;
+        return err == hipErrorOutOfMemory ? APD_ERR_OOM : APD_ERR_HIP;
+    }
+    ctx->children.insert(e);
+    *out = e;
+    return APD_OK;
+}
+
 extern "C" int apd_encode_async(apd_context *ctx, const apd_encoder *e, const float *d_x, uint64_t t, float *d_out)
 {
     if (!ctx || !e || e->ctx != ctx || (t && (!d_x || !d_out))) return APD_ERR_INVALID_ARG;

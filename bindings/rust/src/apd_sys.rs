@@ -13,6 +13,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct apd_encoder { _p: [u8; 0] }
 #[repr(C)] pub struct apd_cepstrum_plan { _p: [u8; 0] }
 #[repr(C)] pub struct apd_feed { _p: [u8; 0] }
+#[repr(C)] pub struct apd_trainer { _p: [u8; 0] }
 
 pub const APD_OK: c_int = 0;
 pub const APD_ERR_INVALID_ARG: c_int = -1;
@@ -300,6 +301,18 @@ extern "C" {
     pub fn apd_discovery_parse_toml(text: *const c_char, out: *mut apd_discovery) -> c_int;
     pub fn apd_dendrograms(ops: *const apd_cluster_op, n_ops: u32, roots: *const u32, n_roots: u32, labels: *const *const c_char,
                            n_labels: u32, out: *mut c_char, capacity: u64, n_bytes: *mut u64, which_root: *mut u32, n_strings: *mut u32) -> c_int;
+    // autoencoder training (neural.rs:74-94, main.rs:115-135): n_models models resident, one launch per run
+    pub fn apd_trainer_create(ctx: *mut apd_context, d_in: u32, latent: u32, n_models: u32, w_encode: *const f32, w_decode: *const f32,
+                              b_encode: *const f32, b_decode: *const f32, trainer: *mut *mut apd_trainer) -> c_int;
+    pub fn apd_trainer_destroy(trainer: *mut apd_trainer) -> c_int;
+    pub fn apd_trainer_run(ctx: *mut apd_context, trainer: *mut apd_trainer, frames: *const f32, n_frames: u64, frames_on_device: c_int,
+                           order: *const u32, n_steps: u64, order_per_model: c_int, alpha: *const f32) -> c_int;
+    pub fn apd_trainer_totals(trainer: *mut apd_trainer, total_err: *mut f32, steps: *mut u64, first_nonfinite: *mut u64, reset: c_int) -> c_int;
+    pub fn apd_trainer_weights(trainer: *mut apd_trainer, model: u32, w_encode: *mut f32, w_decode: *mut f32, b_encode: *mut f32,
+                               b_decode: *mut f32) -> c_int;
+    pub fn apd_trainer_encoder(ctx: *mut apd_context, trainer: *mut apd_trainer, model: u32, encoder: *mut *mut apd_encoder) -> c_int;
+    pub fn apd_step_decay(learning_rate: f32, drop: f32, epoch_drop: f32, epoch: f32) -> f32;
+    pub fn apd_train_order(seed: u64, epoch: u64, offsets: *const u64, n_seq: u32, order: *mut u32) -> c_int;
 }
 
 /// A negative status becomes a panic carrying the library's text: the reference panics in the same places (poisoned mutex

@@ -926,6 +926,48 @@ int apd_dendrograms(const apd_cluster_op *ops, uint32_t n_ops, const uint32_t *r
                     const char *const *labels, uint32_t n_labels, char *out, uint64_t capacity, uint64_t *n_bytes,
                     uint32_t *which_root, uint32_t *n_strings);
 
+/* ---- autoencoder training (src/neural.rs:74-94, src/main.rs:115-135) ----------------------------------------------------------
+ * The reference's SGD: batch size 1, one AutoEncoder::take_step per frame, in the order given.  A trainer holds n_models
+ * independent models of one shape on the context's GPU; apd_trainer_run advances every one of them by n_steps steps in ONE launch,
+ * one wavefront per model, the model on chip throughout.  A step is neural.rs:74-94 operation for operation in f32 (Mat::norm's
+ * inverted condition, the decoder fed the pre-activation latent, Mat::mul from 0.0 with k ascending and no fused multiply-add),
+ * with ONE stated deviation: the sigmoid's exponential is the defined sequence of f32 operations of DESIGN.md section 4.18 instead
+ * of the platform's expf (at most 2 ulp from it).  WHAT A RUN LEAVES IS THEREFORE DEFINED BIT FOR BIT, whatever n_models and however
+ * an order is split into runs; tests/_train_reference.py is the literal restatement.
+ *   apd_trainer_create: host arrays [n_models][...] in the reference's Mat layouts: w_encode [d_in][latent], w_decode
+ *     [latent][d_in], b_encode [latent], b_decode [d_in].  d_in or latent above 64: APD_ERR_UNSUPPORTED; 0, n_models == 0 or a NULL:
+ *     APD_ERR_INVALID_ARG.
+ *   apd_trainer_run: frames [n_frames][d_in] (host, or device with frames_on_device); order: HOST array of frame numbers, [n_steps]
+ *     shared by all models or [n_models][n_steps] with order_per_model; alpha [n_models] (host).  Continues from the state the
+ *     previous run left.  An index >= n_frames: APD_ERR_INVALID_ARG before anything is enqueued, the state untouched.  n_steps == 0
+ *     changes nothing.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the training kernel.
+ *   apd_trainer_totals: per model, the running total_err (main.rs:130: one f32 add of 0.5 * euclidean per step), the steps since the
+ *     last reset, and the step -- counted from the trainer's creation, resets notwithstanding -- at which a weight first became
+ *     non-finite (UINT64_MAX while the model is finite; non-finite weights never recover).  Any of the three may be NULL.  reset:
+ *     total_err and steps go back to 0 afterwards (an epoch boundary); the weights and first_nonfinite stay.
+ *   apd_trainer_weights: one model's four matrices, downloaded.
+ *   apd_trainer_encoder: an apd_encoder made from the model's CURRENT w_encode / b_encode, device to device: what apd_encode_async
+ *     and apd_feed_create take.  It owns a copy: later runs do not change it, and the trainer may be destroyed before it.
+ * A trainer or context of another context, a NULL where data is due, model >= n_models: APD_ERR_INVALID_ARG.  After APD_ERR_HIP the
+ * trainer's state is undefined. */
+typedef struct apd_trainer apd_trainer;
+int apd_trainer_create(apd_context *ctx, uint32_t d_in, uint32_t latent, uint32_t n_models, const float *w_encode,
+                       const float *w_decode, const float *b_encode, const float *b_decode, apd_trainer **trainer);
+int apd_trainer_destroy(apd_trainer *trainer);
+int apd_trainer_run(apd_context *ctx, apd_trainer *trainer, const float *frames, uint64_t n_frames, int frames_on_device,
+                    const uint32_t *order, uint64_t n_steps, int order_per_model, const float *alpha);
+int apd_trainer_totals(apd_trainer *trainer, float *total_err, uint64_t *steps, uint64_t *first_nonfinite, int reset);
+int apd_trainer_weights(apd_trainer *trainer, uint32_t model, float *w_encode, float *w_decode, float *b_encode, float *b_decode);
+int apd_trainer_encoder(apd_context *ctx, apd_trainer *trainer, uint32_t model, apd_encoder **encoder);
+/* AutoEncoder::step_decay (neural.rs:26-28): learning_rate * drop ^ floor((1 + epoch) / epoch_drop) in f32.  Host only. */
+float apd_step_decay(float learning_rate, float drop, float epoch_drop, float epoch);
+/* The order of one epoch (main.rs:120-124): the signals in order (signal s owns frames offsets[s] .. offsets[s + 1]), each signal's
+ * frames in a fresh Fisher-Yates shuffle.  order: offsets[n_seq] - offsets[0] frame numbers.  The reference draws from thread_rng;
+ * here the draws come from a counter-based generator (SplitMix64's finaliser over a key of (seed, epoch, signal) and the position:
+ * csrc/train_math.h), so (seed, epoch) fixes the order on every machine.  Descending offsets or 2^32 frames or more:
+ * APD_ERR_INVALID_ARG.  n_seq == 0: nothing written.  Host only. */
+int apd_train_order(uint64_t seed, uint64_t epoch, const uint64_t *offsets, uint32_t n_seq, uint32_t *order);
+
 #ifdef __cplusplus
 }
 #endif
