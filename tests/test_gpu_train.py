@@ -3,7 +3,9 @@ step count and the first non-finite step, bit for bit (NaN signs and payloads as
 shapes at which the kernel's loops change their trip counts (rows in blocks of 8, steps in blocks of 8, 64 lanes), over any split
 of an order into runs, over models side by side, with non-finite frames, through the hand-off to the resident encoder and through
 train().  The SGD is chaotic (at 2000 steps of 13 -> 8 the checker is O(1) away from its float64 twin), so only identical
-arithmetic passes."""
+arithmetic passes.  The step counts here (0, 1, 2, 63, 257) lie beside the multiples of the prefetch block: run lengths 7 .. 25 and
+64, shared and per-model orders and continuations around a block edge are in tests/test_gpu_train_edges.py, with the inputs that
+are not ordinary (its case table: tests/_train_cases.py)."""
 import ctypes as C
 
 import numpy as np
