@@ -220,6 +220,10 @@ SYMBOLS = [
     ("apd_encode", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _f32p, _f32p, C.c_uint32, C.c_int, _vp]),
     ("apd_interesting_ranges", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint64, C.c_int, _u64p,
                                          C.c_uint64, _u64p]),
+    ("apd_interesting_ranges_batch", C.c_int, [_vp, _vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint64, C.c_int,
+                                               _u64p, _u64p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("apd_slice_offsets", C.c_int, [_u64p, _u64p, _u64p, C.c_uint32, C.c_uint32, _u64p, _u32p]),
+    ("apd_slice_samples", C.c_int, [_vp, _vp, _u64p, C.c_uint32, _u64p, _u64p, C.c_uint32, C.c_int, _vp, C.c_uint64]),
     ("apd_cepstrum_batch", C.c_int, [_vp, _vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, _u64p,
                                      _u32p]),
     ("apd_cepstrum", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, _u64p,

@@ -75,6 +75,98 @@ class Slice:
         return NDSequence(self.sequence.frames[self.start:self.stop], self.sequence.n_bins, self.sequence.audio_id)
 
 
+_U64P = C.POINTER(C.c_uint64)
+
+
+def _ptr(x):
+    """The address of a numpy array, or of a DeviceBuffer's first byte."""
+    return x.at() if isinstance(x, _lib.DeviceBuffer) else C.c_void_p(x.ctypes.data if x.size else None)
+
+
+def interesting_ranges_batch(frames, offsets, moving_average, perc, min_len, ctx=None, on_device=False, strict=True, n_bins=None):
+    """NDSequence.interesting_ranges for every recording of a packed corpus (apd_interesting_ranges_batch): `frames` [offsets[-1]][n_bins]
+    and `offsets` as apd_cepstrum_batch leaves them; frames a DeviceBuffer (n_bins given) with on_device.  Returns a list, per
+    recording, of (start, stop) frame pairs.  strict: a recording for which the reference panics raises ApdError(APD_ERR_INDEX);
+    strict=False: (ranges, status), that recording's status APD_ERR_INDEX and its list empty."""
+    ctx = ctx or _lib.default_context()
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    if not on_device:
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n_bins = int(frames.shape[1]) if frames.ndim == 2 else int(n_bins)
+    L = _lib.lib()
+    range_off = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    st = None if strict else status.ctypes.data_as(C.POINTER(C.c_int32))
+    head = (ctx.handle, _ptr(frames), offsets.ctypes.data_as(_U64P), n, int(n_bins), int(moving_average), float(perc), int(min_len), int(bool(on_device)))
+    # the bound of a recording's ranges: each takes more than min_len frames and the frame that closes it
+    capacity = int(sum(int(offsets[s + 1] - offsets[s]) // (int(min_len) + 2) for s in range(n)))
+    ranges = np.zeros(2 * max(capacity, 1), dtype=np.uint64)
+    _lib.check(L.apd_interesting_ranges_batch(*head, range_off.ctypes.data_as(_U64P), ranges.ctypes.data_as(_U64P), capacity, st), ctx.handle)
+    out = [[(int(ranges[2 * r]), int(ranges[2 * r + 1])) for r in range(int(range_off[s]), int(range_off[s + 1]))] for s in range(n)]
+    return out if strict else (out, [int(v) for v in status[:n]])
+
+
+def _flat_ranges(ranges):
+    """A list of lists of (start, stop) -> (range_off [n + 1], flat pairs), both uint64."""
+    range_off = np.zeros(len(ranges) + 1, dtype=np.uint64)
+    range_off[1:] = np.cumsum([len(r) for r in ranges], dtype=np.uint64)
+    flat = np.array([v for rec in ranges for pair in rec for v in pair], dtype=np.uint64)
+    return range_off, flat
+
+
+def slice_offsets(sample_offsets, ranges, fft_step):
+    """apd_slice_offsets: (slice_offsets [n_slices + 1], slice_seq [n_slices]) of the ranges a list per recording holds -- the sample
+    offsets of the sliced corpus (main.rs:81-88) and, per slice, the recording it came from."""
+    sample_offsets = np.ascontiguousarray(sample_offsets, dtype=np.uint64)
+    range_off, flat = _flat_ranges(ranges)
+    n_slices = int(range_off[-1])
+    out, seq = np.zeros(n_slices + 1, dtype=np.uint64), np.zeros(max(n_slices, 1), dtype=np.uint32)
+    _lib.check(_lib.lib().apd_slice_offsets(sample_offsets.ctypes.data_as(_U64P), range_off.ctypes.data_as(_U64P),
+                                            flat.ctypes.data_as(_U64P) if n_slices else None, len(ranges), int(fft_step),
+                                            out.ctypes.data_as(_U64P), seq.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out, seq[:n_slices]
+
+
+def slice_samples(samples, sample_offsets, ranges, fft_step, ctx=None, on_device=False):
+    """apd_slice_samples: the slices packed back to back -- an int16 array, or with on_device (samples a DeviceBuffer) a DeviceBuffer
+    of slice_offsets[-1] samples."""
+    ctx = ctx or _lib.default_context()
+    sample_offsets = np.ascontiguousarray(sample_offsets, dtype=np.uint64)
+    range_off, flat = _flat_ranges(ranges)
+    total = int(slice_offsets(sample_offsets, ranges, fft_step)[0][-1])
+    if on_device:
+        out = ctx.alloc(max(2 * total, 16))
+    else:
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        out = np.zeros(total, dtype=np.int16)
+    _lib.check(_lib.lib().apd_slice_samples(ctx.handle, _ptr(samples), sample_offsets.ctypes.data_as(_U64P), len(ranges),
+                                            range_off.ctypes.data_as(_U64P), flat.ctypes.data_as(_U64P) if len(flat) else None,
+                                            int(fft_step), int(bool(on_device)), _ptr(out), total), ctx.handle)
+    return out
+
+
+def segment(samples, sample_offsets, discovery, ctx=None):
+    """Stage 1 of the reference (main.rs:58-92) for a whole corpus, resident: apd_cepstrum_batch on the device, the batched VAT
+    ranges with discovery.vat_*, the gather of the raw audio.  samples: int16 array or DeviceBuffer.  Returns (d_slices, slice_offsets,
+    slice_seq, ranges): a DeviceBuffer holding the sliced corpus, ready for apd_cepstrum_batch with slice_offsets."""
+    ctx = ctx or _lib.default_context()
+    L = _lib.lib()
+    sample_offsets = np.ascontiguousarray(sample_offsets, dtype=np.uint64)
+    n = len(sample_offsets) - 1
+    d_samples = samples if isinstance(samples, _lib.DeviceBuffer) else ctx.upload(np.ascontiguousarray(samples, dtype=np.int16))
+    frame_off, nb = np.zeros(n + 1, dtype=np.uint64), C.c_uint32(0)
+    head = (ctx.handle, d_samples.at(), sample_offsets.ctypes.data_as(_U64P), n, int(discovery.dft_win), int(discovery.dft_step),
+            int(discovery.ceps_filter), 1)
+    _lib.check(L.apd_cepstrum_batch(*head, None, frame_off.ctypes.data_as(_U64P), C.byref(nb)), ctx.handle)
+    d_frames = ctx.alloc(max(int(frame_off[-1]) * nb.value * 4, 16))
+    _lib.check(L.apd_cepstrum_batch(*head, d_frames.at(), frame_off.ctypes.data_as(_U64P), C.byref(nb)), ctx.handle)
+    ranges = interesting_ranges_batch(d_frames, frame_off, discovery.vat_moving, discovery.vat_percentile, discovery.vat_min_len, ctx,
+                                      on_device=True, n_bins=nb.value)
+    offs, seq = slice_offsets(sample_offsets, ranges, discovery.dft_step)
+    return slice_samples(d_samples, sample_offsets, ranges, discovery.dft_step, ctx, on_device=True), offs, seq, ranges
+
+
 @dataclass
 class AlignmentParams:
     """alignments.rs:77-83"""

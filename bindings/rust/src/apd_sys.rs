@@ -293,6 +293,14 @@ extern "C" {
                                       curve_off: *mut u64, best: *mut apd_spot_best) -> c_int;
     pub fn apd_interesting_ranges(ctx: *mut apd_context, frames: *const f32, t: u64, n_bins: u32, moving_average: u32, perc: f32,
                                   min_len: u64, on_device: c_int, ranges: *mut u64, capacity: u64, n_ranges: *mut u64) -> c_int;
+    // stage 1 for a whole corpus: batched VAT ranges and the slices they name
+    pub fn apd_interesting_ranges_batch(ctx: *mut apd_context, frames: *const f32, frame_offsets: *const u64, n_seq: u32, n_bins: u32,
+                                        moving_average: u32, perc: f32, min_len: u64, on_device: c_int, range_off: *mut u64,
+                                        ranges: *mut u64, capacity: u64, status: *mut i32) -> c_int;
+    pub fn apd_slice_offsets(sample_offsets: *const u64, range_off: *const u64, ranges: *const u64, n_seq: u32, fft_step: u32,
+                             slice_offsets: *mut u64, slice_seq: *mut u32) -> c_int;
+    pub fn apd_slice_samples(ctx: *mut apd_context, samples: *const i16, sample_offsets: *const u64, n_seq: u32, range_off: *const u64,
+                             ranges: *const u64, fft_step: u32, on_device: c_int, out: *mut i16, capacity: u64) -> c_int;
     // formats either side of the path (host only)
     pub fn apd_autoencoder_parse(bytes: *const c_void, n_bytes: u64, view: *mut apd_autoencoder_view) -> c_int;
     pub fn apd_autoencoder_copy(bytes: *const c_void, mat: *const apd_mat_view, out: *mut f32) -> c_int;

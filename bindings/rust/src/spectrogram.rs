@@ -106,6 +106,36 @@ impl NDSequence {
     }
 }
 
+/// `interesting_ranges` of every sequence of a corpus (main.rs:58-92) in a number of launches that does not depend on the corpus:
+/// the sequences' frames packed back to back, ONE apd_interesting_ranges_batch.  Sequence s gets, in order, exactly what
+/// `sequences[s].interesting_ranges(..)` returns.  All sequences share n_bins.  A sequence for which the reference panics (no
+/// frames, numerics.rs:132) panics here, as one call per sequence would; so does a moving_average beyond u32.
+pub fn interesting_ranges_batch<'a>(sequences: &[&'a NDSequence], moving_average: usize, perc: f32, min_len: usize) -> Vec<Vec<Slice<'a>>> {
+    if sequences.is_empty() {
+        return Vec::new();
+    }
+    let moving = u32::try_from(moving_average).expect("moving_average beyond u32");
+    let n_bins = sequences[0].n_bins;
+    let mut offsets = vec![0u64; sequences.len() + 1];
+    let mut frames: Vec<f32> = Vec::new();
+    let mut capacity = 0usize;                      // a range takes more than min_len frames and the frame that closes it
+    for (s, seq) in sequences.iter().enumerate() {
+        assert_eq!(seq.n_bins, n_bins);
+        frames.extend_from_slice(&seq.frames);
+        offsets[s + 1] = offsets[s] + seq.len() as u64;
+        capacity += seq.len() / (min_len.saturating_add(2));
+    }
+    let mut range_off = vec![0u64; sequences.len() + 1];
+    let mut ranges = vec![0u64; 2 * capacity.max(1)];
+    unsafe {
+        check(apd_interesting_ranges_batch(feature_context(), frames.as_ptr(), offsets.as_ptr(), sequences.len() as u32, n_bins as u32, moving, perc,
+                                           min_len as u64, 0, range_off.as_mut_ptr(), ranges.as_mut_ptr(), capacity as u64, std::ptr::null_mut()));
+    }
+    sequences.iter().enumerate().map(|(s, seq)| {
+        (range_off[s] as usize..range_off[s + 1] as usize).map(|r| Slice::new(ranges[2 * r] as usize, ranges[2 * r + 1] as usize, seq)).collect()
+    }).collect()
+}
+
 /// spectrogram.rs:223-233 (the rest of `impl Slice` is unchanged reference code)
 pub struct Slice<'a> {
     pub start: usize,

@@ -885,6 +885,37 @@ int apd_interesting_ranges(apd_context *ctx, const float *frames, uint64_t t, ui
                            float perc, uint64_t min_len, int on_device, uint64_t *ranges, uint64_t capacity,
                            uint64_t *n_ranges);
 
+/* ---- stage 1 for a whole corpus: batched VAT ranges and the slices they name (src/main.rs:58-92) ------------------------------
+ * apd_interesting_ranges for n_seq recordings in a number of launches and synchronisations that depends on neither n_seq nor any
+ * length: frames / frame_offsets are what apd_cepstrum_batch writes and apd_batch_create takes (packed [frame_offsets[n_seq]][n_bins],
+ * the offsets a HOST array; frames in HBM with on_device).  RECORDING s GETS, IN ORDER, EXACTLY THE RANGES apd_interesting_ranges
+ * GIVES FOR ITS FRAMES, whatever its neighbours are: ranges[range_off[s] .. range_off[s + 1]) as (start, stop) frame pairs counted
+ * within the recording.  range_off (n_seq + 1, host) is always written and exact whatever the capacity (in ranges); ranges past the
+ * capacity are not written; ranges == NULL with capacity == 0 only counts, with capacity > 0 it is APD_ERR_INVALID_ARG.
+ * Where the reference panics for one recording (no frames, moving_average == 0, a percentile index at or beyond its non-NaN
+ * variances): with status (n_seq, host) that recording gets APD_ERR_INDEX there and no ranges, the others APD_OK, and the call returns
+ * APD_OK; with status == NULL the call returns APD_ERR_INDEX, apd_last_error names the first such recording and range_off is all zero.
+ * n_seq == 0: APD_OK, range_off[0] = 0.  Descending offsets: APD_ERR_INVALID_ARG; a recording of 2^32 frames or more:
+ * APD_ERR_UNSUPPORTED; both before anything is launched.  Blocking: one read-back of verdicts and counts, one of the ranges; no
+ * variance leaves the device.  Kernels: csrc/vat_batch.hip, DESIGN.md section 4.19. */
+int apd_interesting_ranges_batch(apd_context *ctx, const float *frames, const uint64_t *frame_offsets, uint32_t n_seq,
+                                 uint32_t n_bins, uint32_t moving_average, float perc, uint64_t min_len, int on_device,
+                                 uint64_t *range_off, uint64_t *ranges, uint64_t capacity, int32_t *status);
+/* The slices of the raw audio (main.rs:76-89, audio.rs:54-60) as a new packed corpus: slice r of recording s is
+ * samples[sample_offsets[s] + start * fft_step .. sample_offsets[s] + stop * fft_step), the slices back to back in range order.
+ * apd_slice_offsets (host only): slice_offsets (range_off[n_seq] + 1) is the sample_offsets argument of apd_cepstrum_batch /
+ * apd_cepstrum_plan_create for the sliced corpus; slice_seq[r] (or NULL) is the recording slice r came from, the reference's
+ * audio_id.  apd_slice_samples: the gather, one launch; on_device covers both samples and out; capacity (in samples) below
+ * slice_offsets[range_off[n_seq]] is APD_ERR_INVALID_ARG.  From both calls APD_ERR_INVALID_ARG for descending offsets, a range with
+ * stop < start, ranges of a recording that are not ascending (a start before the previous stop), and a range whose stop * fft_step
+ * runs past its recording (ranges of a cepstrum with the same fft_step never do); range_off must start at 0, and both offset arrays
+ * are checked as a whole before anything is sized from them or written.  No ranges: APD_OK, nothing written. */
+int apd_slice_offsets(const uint64_t *sample_offsets, const uint64_t *range_off, const uint64_t *ranges, uint32_t n_seq,
+                      uint32_t fft_step, uint64_t *slice_offsets, uint32_t *slice_seq);
+int apd_slice_samples(apd_context *ctx, const int16_t *samples, const uint64_t *sample_offsets, uint32_t n_seq,
+                      const uint64_t *range_off, const uint64_t *ranges, uint32_t fft_step, int on_device, int16_t *out,
+                      uint64_t capacity);
+
 /* ---- formats either side of the path (host only, no context needed) ------------------------------------------------ */
 /* AutoEncoder::from_file / save_file (src/neural.rs:30-44): the bincode 1.x image of
  *   struct AutoEncoder { w_encode, w_decode, b_encode, b_decode: Mat }  (neural.rs:13-19)
