@@ -632,9 +632,16 @@ int feed_enqueue(apd_context *ctx, apd_feed *feed, const int16_t *samples, const
 // companions.hip: an apd_encoder of this context whose weights ([d_in][latent]) and bias ([latent]) are copied from device memory
 int encoder_from_device(apd_context *ctx, const float *d_w_encode, const float *d_b_encode, uint32_t d_in, uint32_t latent, apd_encoder **out);
 
-// numerics.rs:125-133 on a device array (clustering.hip): radix select of the k-th smallest non-NaN value.
+// numerics.rs:125-133 on a device array (clustering.hip): radix select of the k-th smallest non-NaN value, a launch and a read-back
+// per digit, for inputs of any size (apd_percentile, apd_clustering).  vat.hip selects per recording inside one workgroup instead.
 int device_select(apd_context *ctx, const float *d_x, uint64_t len, uint64_t k, float *value);
 uint64_t percentile_index(uint64_t len, float perc);
+// The digits both selects (clustering.hip, vat.hip) walk: ascending key order == ascending float order.
+__device__ __forceinline__ uint32_t order_key(float v)
+{
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 
 // Host-side mirrors of the device band arithmetic (bit-identical f32 product).
 inline uint32_t host_band_from_pct(float pct, uint32_t len)

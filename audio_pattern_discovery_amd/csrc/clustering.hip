@@ -52,12 +52,6 @@ struct Owned {
 
 // ---------------------------------------------------------------------------------- radix select
 
-__device__ __forceinline__ uint32_t order_key(float v)
-{
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // ascending key order == ascending float order
-}
-
 // hist[d] = #{non-NaN x : key(x) has `prefix` in the bits above shift+8 and digit d at `shift`}; hist[256] = #NaN
 __global__ void select_hist_kernel(const float *__restrict__ x, uint64_t len, uint32_t prefix, uint32_t prefix_mask, int shift,
                                    unsigned long long *__restrict__ hist)

@@ -1,14 +1,14 @@
-// Stage 1 of the reference (main.rs:58-92, dump_interesting) for a whole corpus at once: NDSequence::interesting_ranges
-// (spectrogram.rs:174-216) of every recording in a number of launches that does not depend on the corpus, and the gather of
-// the raw audio the ranges name (main.rs:76-89, audio.rs:54-60) into a new packed corpus.  DESIGN.md section 4.19.
+// The VAT pre-segmentation, NDSequence::interesting_ranges (spectrogram.rs:174-216), and stage 1 of the reference (main.rs:58-92,
+// dump_interesting) built on it: the ranges of every recording of a corpus in a number of launches that does not depend on the
+// corpus, and the gather of the raw audio the ranges name (main.rs:76-89, audio.rs:54-60) into a new packed corpus.  DESIGN.md
+// section 4.19.
 //
 //   vat_variance_kernel   per-frame std + moving mean, a tile of one recording per workgroup, the halo's stds in LDS
 //   vat_select_kernel     numerics.rs:125-133 per recording: four 8-bit digit passes, histogram, prefix and rank on chip
 //   vat_scan_kernel       the run scan, 64 columns per wavefront step through ballots; counts, then the ranges in order
 //   slice_gather_kernel   one work-item per 16 bytes of output
 //
-// apd_interesting_ranges (companions.hip) is not touched and shares nothing with this unit but percentile_index: a recording's
-// answer here must equal that call's, which the tests compare.
+// This is the library's one implementation: apd_interesting_ranges is apd_interesting_ranges_batch for a batch of one.
 #include <algorithm>
 #include <cstring>
 #include <exception>
@@ -50,8 +50,8 @@ struct VatParams {
     float *var;                    // [T]
 };
 
-// NDSequence::variance (spectrogram.rs:174-187), the arithmetic of frame_std_kernel and moving_mean_kernel (companions.hip)
-// operation for operation.
+// NDSequence::variance (spectrogram.rs:174-187): per-frame population std (numerics.rs:12-29), then the mean of the k PREVIOUS
+// values, summed in order.
 __device__ __forceinline__ float frame_std(const float *v, uint32_t n_bins)
 {
     float mean = 0.0f;
@@ -122,12 +122,6 @@ __global__ __launch_bounds__(kVatTile) void vat_variance_kernel(const VatParams 
     if (MODE == 1) return;
     __syncthreads();
     if (i < b) P.var[q.off + i] = i >= k ? moving_mean(sstd + (i - k - row_lo), k) : 0.0f;
-}
-
-__device__ __forceinline__ uint32_t order_key(float v)
-{
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);              // ascending key order == ascending float order
 }
 
 // One workgroup per recording: the k-th smallest non-NaN variance, by four passes over the digits of order_key.  The histogram
@@ -345,11 +339,10 @@ int slice_plan(const uint64_t *sample_offsets, const uint64_t *range_off, const 
     return APD_OK;
 }
 
-}  // namespace
-
-extern "C" int apd_interesting_ranges_batch(apd_context *ctx, const float *frames, const uint64_t *frame_offsets, uint32_t n_seq,
-                                            uint32_t n_bins, uint32_t moving_average, float perc, uint64_t min_len, int on_device,
-                                            uint64_t *range_off, uint64_t *ranges, uint64_t capacity, int32_t *status)
+// Both entry points; `who` is the one called, for the texts of apd_last_error.
+int interesting_ranges(const char *who, apd_context *ctx, const float *frames, const uint64_t *frame_offsets, uint32_t n_seq,
+                       uint32_t n_bins, uint32_t moving_average, float perc, uint64_t min_len, int on_device, uint64_t *range_off,
+                       uint64_t *ranges, uint64_t capacity, int32_t *status)
 {
     if (!ctx || !range_off || n_bins == 0 || (n_seq && !frame_offsets) || (capacity && !ranges)) return APD_ERR_INVALID_ARG;
     for (uint32_t s = 0; s < n_seq; ++s)
@@ -367,13 +360,13 @@ extern "C" int apd_interesting_ranges_batch(apd_context *ctx, const float *frame
     uint32_t t_max = 0;
     for (uint32_t s = 0; s < n_seq; ++s) {
         const uint64_t t = frame_offsets[s + 1] - frame_offsets[s];
-        if (t > 0xFFFFFFFFull) { ctx->last_error = "apd_interesting_ranges_batch: a recording of 2^32 frames or more"; return APD_ERR_UNSUPPORTED; }
+        if (t > 0xFFFFFFFFull) { ctx->last_error = std::string(who) + ": a recording of 2^32 frames or more"; return APD_ERR_UNSUPPORTED; }
         const uint64_t kidx = percentile_index(t, perc);
         h_seq[s] = VatSeq{frame_offsets[s] - base, (uint32_t)t, (uint32_t)std::min<uint64_t>(kidx, 0xFFFFFFFFull)};   // >= t either way: a panic
         h_tile[s] = (uint32_t)tiles;
         tiles += (t + kVatTile - 1) / kVatTile;
         t_max = std::max(t_max, (uint32_t)t);
-        if (tiles >= (1ull << 31)) { ctx->last_error = "apd_interesting_ranges_batch: 2^39 frames or more"; return APD_ERR_UNSUPPORTED; }
+        if (tiles >= (1ull << 31)) { ctx->last_error = std::string(who) + ": 2^39 frames or more"; return APD_ERR_UNSUPPORTED; }
     }
     h_tile[n_seq] = (uint32_t)tiles;
     HIP_TRY(ctx, bind_device(ctx));
@@ -425,7 +418,7 @@ extern "C" int apd_interesting_ranges_batch(apd_context *ctx, const float *frame
     std::vector<uint64_t> h_roff((size_t)n_seq + 1, 0);
     for (uint32_t s = 0; s < n_seq; ++s) {
         if (h_res[s].status != APD_OK && !status) {
-            ctx->last_error = "apd_interesting_ranges_batch: recording " + std::to_string(s) + ": the percentile's index is beyond its " +
+            ctx->last_error = std::string(who) + ": recording " + std::to_string(s) + ": the percentile's index is beyond its " +
                               std::to_string((uint64_t)h_seq[s].t - h_res[s].nan) + " non-NaN variances (numerics.rs:132)";
             return APD_ERR_INDEX;                                    // range_off is all zero
         }
@@ -442,6 +435,31 @@ extern "C" int apd_interesting_ranges_batch(apd_context *ctx, const float *frame
     HIP_TRY(ctx, hipMemcpyAsync(ranges, d_ranges, n_write * sizeof(ulonglong2), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
+}
+
+}  // namespace
+
+extern "C" int apd_interesting_ranges_batch(apd_context *ctx, const float *frames, const uint64_t *frame_offsets, uint32_t n_seq,
+                                            uint32_t n_bins, uint32_t moving_average, float perc, uint64_t min_len, int on_device,
+                                            uint64_t *range_off, uint64_t *ranges, uint64_t capacity, int32_t *status)
+{
+    return interesting_ranges("apd_interesting_ranges_batch", ctx, frames, frame_offsets, n_seq, n_bins, moving_average, perc, min_len,
+                              on_device, range_off, ranges, capacity, status);
+}
+
+// A batch of one.  Where the reference panics, APD_ERR_INDEX is the batch's verdict for its only recording.
+extern "C" int apd_interesting_ranges(apd_context *ctx, const float *frames, uint64_t t, uint32_t n_bins, uint32_t moving_average,
+                                      float perc, uint64_t min_len, int on_device, uint64_t *ranges, uint64_t capacity,
+                                      uint64_t *n_ranges)
+{
+    if (!ctx || !n_ranges || n_bins == 0 || (t && !frames) || (capacity && !ranges)) return APD_ERR_INVALID_ARG;
+    *n_ranges = 0;
+    const uint64_t frame_offsets[2] = {0, t};
+    uint64_t range_off[2] = {0, 0};
+    const int rc = interesting_ranges("apd_interesting_ranges", ctx, frames, frame_offsets, 1, n_bins, moving_average, perc, min_len,
+                                      on_device, range_off, ranges, capacity, nullptr);
+    *n_ranges = range_off[1];
+    return rc;
 }
 
 extern "C" int apd_slice_offsets(const uint64_t *sample_offsets, const uint64_t *range_off, const uint64_t *ranges, uint32_t n_seq,

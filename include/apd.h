@@ -880,15 +880,21 @@ int apd_spot_stream_push_audio(apd_context *ctx, apd_spot_stream *stream, apd_fe
 
 /* NDSequence::interesting_ranges (src/spectrogram.rs:174-216), the "VAT" pre-segmentation that precedes the path:
  * per-frame std, mean of the `moving_average` previous values, percentile threshold, runs longer than min_len.
- * frames: [t][n_bins] (device if on_device).  ranges: (start, stop) frame pairs, host; *n_ranges may exceed capacity. */
+ * frames: [t][n_bins] (device if on_device).  ranges: (start, stop) frame pairs, host; *n_ranges may exceed capacity; ranges == NULL
+ * with capacity == 0 only counts, with capacity > 0 it is APD_ERR_INVALID_ARG.
+ * This is apd_interesting_ranges_batch (below) for a batch of one: frame_offsets = {0, t}, no status array, *n_ranges = range_off[1].
+ * So where the reference panics (t == 0, moving_average == 0, a percentile index at or beyond the non-NaN variances) the call returns
+ * APD_ERR_INDEX with *n_ranges == 0, and apd_last_error carries the batch's text under this call's name; t >= 2^32 is
+ * APD_ERR_UNSUPPORTED before anything is launched (*n_ranges == 0, nothing read or written); the host form's input and the variances
+ * live in the context's grow-only workspace, nothing is allocated per call once it has grown.  Kernels: csrc/vat.hip. */
 int apd_interesting_ranges(apd_context *ctx, const float *frames, uint64_t t, uint32_t n_bins, uint32_t moving_average,
                            float perc, uint64_t min_len, int on_device, uint64_t *ranges, uint64_t capacity,
                            uint64_t *n_ranges);
 
 /* ---- stage 1 for a whole corpus: batched VAT ranges and the slices they name (src/main.rs:58-92) ------------------------------
- * apd_interesting_ranges for n_seq recordings in a number of launches and synchronisations that depends on neither n_seq nor any
- * length: frames / frame_offsets are what apd_cepstrum_batch writes and apd_batch_create takes (packed [frame_offsets[n_seq]][n_bins],
- * the offsets a HOST array; frames in HBM with on_device).  RECORDING s GETS, IN ORDER, EXACTLY THE RANGES apd_interesting_ranges
+ * NDSequence::interesting_ranges (src/spectrogram.rs:174-216) for n_seq recordings in a number of launches and synchronisations that
+ * depends on neither n_seq nor any length: frames / frame_offsets are what apd_cepstrum_batch writes and apd_batch_create takes (packed [frame_offsets[n_seq]][n_bins],
+ * the offsets a HOST array; frames in HBM with on_device).  RECORDING s GETS, IN ORDER, EXACTLY THE RANGES spectrogram.rs:174-216
  * GIVES FOR ITS FRAMES, whatever its neighbours are: ranges[range_off[s] .. range_off[s + 1]) as (start, stop) frame pairs counted
  * within the recording.  range_off (n_seq + 1, host) is always written and exact whatever the capacity (in ranges); ranges past the
  * capacity are not written; ranges == NULL with capacity == 0 only counts, with capacity > 0 it is APD_ERR_INVALID_ARG.
@@ -897,7 +903,7 @@ int apd_interesting_ranges(apd_context *ctx, const float *frames, uint64_t t, ui
  * APD_OK; with status == NULL the call returns APD_ERR_INDEX, apd_last_error names the first such recording and range_off is all zero.
  * n_seq == 0: APD_OK, range_off[0] = 0.  Descending offsets: APD_ERR_INVALID_ARG; a recording of 2^32 frames or more:
  * APD_ERR_UNSUPPORTED; both before anything is launched.  Blocking: one read-back of verdicts and counts, one of the ranges; no
- * variance leaves the device.  Kernels: csrc/vat_batch.hip, DESIGN.md section 4.19. */
+ * variance leaves the device.  Kernels: csrc/vat.hip, DESIGN.md section 4.19. */
 int apd_interesting_ranges_batch(apd_context *ctx, const float *frames, const uint64_t *frame_offsets, uint32_t n_seq,
                                  uint32_t n_bins, uint32_t moving_average, float perc, uint64_t min_len, int on_device,
                                  uint64_t *range_off, uint64_t *ranges, uint64_t capacity, int32_t *status);

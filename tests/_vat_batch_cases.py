@@ -1,5 +1,5 @@
 """The case table of the batched VAT edge tests ("Tests"): batches at which vat_variance_kernel,
-vat_select_kernel and vat_scan_kernel (csrc/vat_batch.hip) could leave the reference without tests/test_gpu_vat_batch.py noticing --
+vat_select_kernel and vat_scan_kernel (csrc/vat.hip) could leave the reference without tests/test_gpu_vat_batch.py noticing --
 stretches of unclassified (NaN) columns laid on the scan's 64-column and workgroup-wide edges with a run open or idle across them,
 recordings that emit as many ranges as the device buffer is sized for, the percentile's index on the last non-NaN variance and one
 past it, and random frames at the lengths and widths where the kernels change path.  tests/test_vat_batch_cases.py shows on the CPU

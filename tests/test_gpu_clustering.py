@@ -115,6 +115,25 @@ def test_percentile_select_matches_sort(ctx, oracle, apd):
     # the index is computed in f32 from the UNFILTERED length (numerics.rs:126)
     y = np.arange(4096 * 4096 // 64, dtype=np.float32)
     assert percentile(y, 0.05, ctx) == oracle.percentile(y, 0.05)
+    # 4096 * 256 + 300 elements: the second grid-stride iteration of select_hist_kernel (4096 blocks of 256) reads the last 300.
+    # One value that occurs only there is placed between two neighbours of the sorted input, so that it is the selected element
+    # at 0.73: a select that drops the wrapped tail returns the neighbour above it instead.
+    wrap = 4096 * 256
+    z = rng.standard_normal(wrap + 300).astype(np.float32) * 100
+    z[::97] = np.nan
+    z[5::1013] = np.inf
+    z[7::1013] = -np.inf
+    z[11::501] = 0.0
+    z[12::501] = -0.0
+    k = int(np.float32(z.size) * np.float32(0.73))
+    s = np.sort(z[~np.isnan(z)])
+    at = wrap + int(np.flatnonzero(z[wrap:] > s[k])[0])
+    planted = np.float32((np.float64(s[k - 1]) + np.float64(s[k])) / 2)
+    assert z[at] > s[k] and s[k - 1] < planted < s[k]                # taking z[at] out moves nothing at or below rank k
+    z[at] = planted
+    assert list(np.flatnonzero(z == planted)) == [at] and oracle.percentile(z, 0.73) == planted
+    for perc in (0.05, 0.5, 0.73):
+        assert percentile(z, perc, ctx) == oracle.percentile(z, perc)
 
 
 def test_end_to_end_align_then_cluster(ctx, oracle):

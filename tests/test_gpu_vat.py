@@ -1,6 +1,6 @@
-"""The VAT pre-segmentation on the GPU (apd_interesting_ranges: frame_std_kernel, moving_mean_kernel, the radix select and the
-host scan; reference spectrogram.rs:174-216) against the C oracle, its numpy twin (oracle/np_reference.py) and, where the
-arithmetic is exact, plain integers.
+"""The VAT pre-segmentation on the GPU through its single call (apd_interesting_ranges, a batch of one recording through
+vat_variance_kernel, vat_select_kernel and vat_scan_kernel of csrc/vat.hip; reference spectrogram.rs:174-216) against the C
+oracle, its numpy twin (oracle/np_reference.py) and, where the arithmetic is exact, plain integers.
 
 The call returns integer ranges only.  Random frames rarely put a boundary where an off-by-one window or comparison would
 move it, so the known answers use frames [a, -a, a, -a] with small integers a and a power-of-two window: every mean, std
@@ -194,9 +194,9 @@ def test_random_sweep(ctx, apd, oracle, n_bins):
 
 
 def test_grid_wrap(ctx, apd, oracle):
-    """8192 * 256 + 300 frames: the second iteration of the grid-stride loops of frame_std_kernel and moving_mean_kernel
-    (8192 blocks of 256) and of select_hist_kernel (4096 blocks of 256).  Exact arithmetic: frames [a, -a], a constant over
-    256 frames, window 8."""
+    """One recording of 8192 * 256 + 300 frames: 8193 tiles of vat_variance_kernel, the last one partial, and 2049 steps of
+    the 1024-wide vat_select_kernel and vat_scan_kernel.  Exact arithmetic: frames [a, -a], a constant over 256 frames,
+    window 8."""
     a = cc.wrap_a()
     f = cc.alternating(a, 2)
     assert f.shape == (cc.GRID_WRAP_FRAMES, 2) and cc.GRID_WRAP_FRAMES > 8192 * 256 > 4096 * 256

@@ -1,9 +1,10 @@
-"""Stage 1 for a whole corpus (csrc/vat_batch.hip): apd_interesting_ranges_batch against apd_interesting_ranges per recording, the C
-oracle, its numpy twin and -- where the arithmetic is exact -- plain integers (_companion_cases.py); apd_slice_samples against
-numpy slicing; `segment` against the reference's order of operations done with the single-recording calls.
+"""Stage 1 for a whole corpus (csrc/vat.hip): apd_interesting_ranges_batch against the C oracle, its numpy twin and -- where the
+arithmetic is exact -- plain integers (_companion_cases.py); apd_slice_samples against numpy slicing; `segment` against the
+reference's order of operations done with the single-recording calls and the oracle.
 
 A recording's answer must not depend on the batch around it: every comparison below is per recording, and the same recordings are
-run in several batches (in order, reversed, alone)."""
+run in several batches (in order, reversed, alone, and alone through apd_interesting_ranges, which is a batch of one: the same
+kernels, so no witness of its own -- every such comparison stands beside one with the oracle or the integers)."""
 import ctypes as C
 
 import numpy as np
@@ -15,7 +16,7 @@ from audio_pattern_discovery_amd import synth
 from oracle import np_reference as npr
 
 pytestmark = pytest.mark.gpu
-TILE = 256            # kVatTile (csrc/vat_batch.hip): frames per workgroup of the variance kernel; windows up to it keep their halo in LDS
+TILE = 256            # kVatTile (csrc/vat.hip): frames per workgroup of the variance kernel; windows up to it keep their halo in LDS
 FORMS = ["host", "device", "device+4"]
 
 
@@ -59,7 +60,7 @@ def test_known_answers_in_a_batch(ctx, apd, form):
         assert batch_result(apd, ctx, recs[::-1], k, perc, min_len, form) == want[::-1]
 
 
-# ------------------------------------------------------------------------- batch == per-recording call == oracle
+# -------------------------------------------------------------- among neighbours == alone (a batch of one) == oracle
 
 def planted(rng, t, n_bins):
     """Random f32 frames with louder stretches, so that runs open and close at every length."""
@@ -139,6 +140,15 @@ def test_argument_errors_and_empty_batches(ctx, apd):
     huge = np.array([0, 2 ** 32], np.uint64)
     assert L.apd_interesting_ranges_batch(ctx.handle, C.c_void_p(f.ctypes.data), huge.ctypes.data_as(U64P), 1, 4, 4, 0.5, 3, 0, range_off.ctypes.data_as(U64P),
                                           ranges.ctypes.data_as(U64P), 32, None) == apd.APD_ERR_UNSUPPORTED
+    # the same through the single call, device form: the limit comes before any launch or allocation, so the pointer is never read
+    # (it is no device address), *n_ranges is 0 and the caller's array is untouched
+    ranges[:] = SENTINEL
+    n = C.c_uint64(12345)
+    assert L.apd_interesting_ranges(ctx.handle, C.c_void_p(f.ctypes.data), 2 ** 32, 4, 4, 0.5, 3, 1, ranges.ctypes.data_as(U64P), 32,
+                                    C.byref(n)) == apd.APD_ERR_UNSUPPORTED
+    assert n.value == 0 and np.all(ranges == SENTINEL)
+    assert b"apd_interesting_ranges:" in L.apd_last_error(ctx.handle)
+    ranges[:] = 0
     # n_bins == 0, no range_off
     ok = np.array([0, 64], np.uint64)
     assert L.apd_interesting_ranges_batch(ctx.handle, C.c_void_p(f.ctypes.data), ok.ctypes.data_as(U64P), 1, 0, 4, 0.5, 3, 0, range_off.ctypes.data_as(U64P),
@@ -346,7 +356,9 @@ def test_cepstra_of_gathered_slices_are_the_cepstra_of_host_slices(ctx, apd):
     assert int(f_off[-1]) > 100
 
 
-def test_segment_equals_the_single_recording_calls(ctx, apd):
+def test_segment_equals_the_single_recording_calls(ctx, apd, oracle):
+    """`segment` over the corpus against main.rs:58-92 done per recording; the ranges of a recording also against the oracle on the
+    GPU's own cepstrum frames of it, since the single call runs the batch's kernels."""
     from audio_pattern_discovery_amd.alignments import NDSequence, segment
     from audio_pattern_discovery_amd.discovery import Discovery
     cfg = Discovery(dft_win=256, dft_step=128, ceps_filter=18, vat_moving=15, vat_percentile=0.6, vat_min_len=10)
@@ -361,6 +373,7 @@ def test_segment_equals_the_single_recording_calls(ctx, apd):
     for s, rec in enumerate(recs):                                  # main.rs:58-92 per recording
         seq = NDSequence.new(cfg.dft_win, cfg.dft_step, cfg.ceps_filter, rec, ctx)
         found = [(sl.start, sl.stop) for sl in seq.interesting_ranges(cfg.vat_moving, cfg.vat_percentile, cfg.vat_min_len, ctx)]
+        assert found == oracle.interesting_ranges(seq.frames, cfg.vat_moving, cfg.vat_percentile, cfg.vat_min_len)
         want_ranges.append(found)
         want_slices += [rec[a * cfg.dft_step:b * cfg.dft_step] for a, b in found]
         want_seq += [s] * len(found)

@@ -1,4 +1,4 @@
-"""The batched VAT kernels (csrc/vat_batch.hip) at the edges tests/test_gpu_vat_batch.py leaves out: every case of
+"""The VAT kernels (csrc/vat.hip) at the edges tests/test_gpu_vat_batch.py leaves out: every case of
 tests/_vat_batch_cases.py -- NaN stretches on the scan's wavefront and step edges, recordings that emit as many ranges as the device
 buffer holds, the percentile's index on the last classified variance, random frames at the lengths and widths where the kernels
 change path -- through apd_interesting_ranges_batch in the host and the device form, in order and reversed, against the integer
@@ -34,8 +34,8 @@ def assert_every_way(apd, ctx, c, want):
 
 @pytest.mark.parametrize("name", cases.names("stretch") + cases.names("verdict"))
 def test_hole_cases_equal_the_model_and_the_single_call(ctx, apd, name):
-    """NaN stretches on the scan's edges and the verdict boundary: the batch equals the integer model, and the single-recording call
-    (whose scan runs on the host) equals it too -- section 4.19's contract is the equality of the two calls."""
+    """NaN stretches on the scan's edges and the verdict boundary: the batch equals the integer model, and so does every recording
+    alone through the single call, a batch of one (its workgroup size then follows that recording's own length)."""
     entry = cases.get(name)
     c, want = entry.case, entry.expected()
     assert_every_way(apd, ctx, c, want)

@@ -3,7 +3,8 @@
 frames and samples that are already resident, D = 13, vat_moving = 15, vat_percentile = 0.95, vat_min_len = 150, dft_step = 128.
 Two corpora: many short recordings (4096 x 1024 frames) and few long ones (16 x 2^20 frames).  Two routes, taking turns in one
 process, wall clock around the blocking calls, best of --repeats with the spread:
-  (a) what a caller had before: apd_interesting_ranges(on_device=1) per recording, the slices cut on the host and uploaded;
+  (a) the single call per recording: apd_interesting_ranges(on_device=1), a batch of one each time, the slices cut on the host and
+      uploaded;
   (b) apd_interesting_ranges_batch + apd_slice_samples(on_device=1).
 Both must give the same ranges and the same slices before anything is timed.
 
