@@ -240,6 +240,7 @@ SYMBOLS = [
     ("apd_trainer_totals", C.c_int, [_vp, _f32p, _u64p, _u64p, C.c_int]),
     ("apd_trainer_weights", C.c_int, [_vp, C.c_uint32, _f32p, _f32p, _f32p, _f32p]),
     ("apd_trainer_encoder", C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    ("apd_trainer_evaluate", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _u32p, C.c_uint64, C.c_int, _vp, C.c_int, _f32p, _u64p]),
     ("apd_step_decay", C.c_float, [C.c_float, C.c_float, C.c_float, C.c_float]),
     ("apd_train_order", C.c_int, [C.c_uint64, C.c_uint64, _u64p, C.c_uint32, _u32p]),
 ]

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "apd_internal.h"
+#include "apd_plan.h"
 #include "train_math.h"
 
 namespace {
@@ -215,6 +216,139 @@ __global__ void __launch_bounds__(64) train_kernel(TrainLaunch T)
 
 size_t train_lds_bytes(uint32_t d_in, uint32_t latent) { return ((size_t)(2 * d_in + latent) * 64 + kTrainBlock * 64) * sizeof(float); }
 
+// ---- evaluation (apd_trainer_evaluate): the forward half of the step above under frozen weights, one lane
+// per position.  Nothing below writes the trainer.
+struct EvalCarry {
+    float total_err;                 // main.rs:130 with the weights frozen: one add per position, in position order
+    uint32_t pad;
+    unsigned long long first_nonfinite;   // the first position whose error is not finite
+};
+
+struct EvalLaunch {
+    const float *d_frames;           // [n_frames][d_in]
+    const uint32_t *d_order;         // the chunk's first entry of row 0; nullptr: position p names frame first + p
+    const float *d_weights;          // the trainer's
+    float *d_err;                    // model m, position p of the chunk: d_err[m * err_stride + p]
+    EvalCarry *d_carry;              // [n_models]
+    uint64_t first;                  // the chunk's first position
+    uint64_t n_pos;                  // positions of the chunk
+    uint64_t order_stride;           // 0: one order for all models
+    uint64_t err_stride;
+    uint64_t model_floats;
+    uint32_t d_in, latent, n_models;
+    uint32_t groups;                 // workgroups per model
+};
+
+constexpr uint32_t kEvalBlockOutputs = 4;   // units whose sums run side by side: one read of x[k] (latent[j]) feeds four of them
+constexpr size_t kEvalLdsTarget = 64 * 1024;
+
+// A workgroup owns model blockIdx.x / groups and every `groups`-th tile of blockDim.x positions; the model is staged once.
+// LDS (floats): wenc [D][L] | wdec [L][D] | benc [L] | bdec [D] in the reference's flat layouts (every lane reads the same word: a
+// broadcast) | xs [D][T] the tile's frames | lat [L][T] its pre-activation latents (lane t's accesses fall into bank t mod 64).
+// Every (model, position) chain is private to a lane, in the order of train_kernel: the bits do not depend on T, groups or the grid.
+__global__ void __launch_bounds__(256) train_eval_kernel(EvalLaunch E)
+{
+    extern __shared__ float lds[];
+    const uint32_t D = E.d_in, L = E.latent, T = blockDim.x, t = threadIdx.x;
+    const uint32_t m = blockIdx.x / E.groups, g = blockIdx.x % E.groups;
+    float *wenc = lds, *wdec = wenc + D * L, *benc = wdec + L * D, *bdec = benc + L, *xs = bdec + D, *lat = xs + D * T;
+    const float *gw = E.d_weights + m * E.model_floats;
+    for (uint32_t i = t; i < (uint32_t)E.model_floats; i += T) lds[i] = gw[i];
+    const uint32_t *order = E.d_order ? E.d_order + m * E.order_stride : nullptr;
+    float *err = E.d_err + m * E.err_stride;
+    const uint64_t n_tiles = (E.n_pos + T - 1) / T;
+    __syncthreads();
+
+    for (uint64_t tile = g; tile < n_tiles; tile += E.groups) {
+        const uint64_t p = tile * T + t;
+        if (p >= E.n_pos) continue;                 // no barrier below: xs and lat columns are the lane's own
+        const float *x = E.d_frames + (order ? (uint64_t)order[p] : E.first + p) * D;
+        // the frame, and Mat::norm's decision as train_norm_kernel takes it
+        float mn = INFINITY, mx = -INFINITY;
+        for (uint32_t k = 0; k < D; ++k) {
+            const float v = x[k];
+            xs[k * T + t] = v;
+            const bool finite = (__float_as_uint(v) & kNonFiniteBits) != kNonFiniteBits;
+            if (v < mn && finite) mn = v;
+            if (v > mx && finite) mx = v;
+        }
+        const bool rescale = fabsf(mn - mx) < 1e-8f;
+        const float scaler = mx - mn;
+        // latent = x . W_enc + b_enc (from 0.0, k ascending, multiply then add)
+        for (uint32_t j0 = 0; j0 < L; j0 += kEvalBlockOutputs) {
+            float acc[kEvalBlockOutputs];
+            uint32_t col[kEvalBlockOutputs];
+#pragma unroll
+            for (uint32_t u = 0; u < kEvalBlockOutputs; ++u) { acc[u] = 0.0f; col[u] = min(j0 + u, L - 1); }
+            for (uint32_t k = 0; k < D; ++k) {
+                const float xk = xs[k * T + t];
+#pragma unroll
+                for (uint32_t u = 0; u < kEvalBlockOutputs; ++u) acc[u] = acc[u] + xk * wenc[k * L + col[u]];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < kEvalBlockOutputs; ++u)
+                if (j0 + u < L) lat[(j0 + u) * T + t] = acc[u] + benc[j0 + u];
+        }
+        // output = latent . W_dec + b_dec from the pre-activation latent; the output units are streamed into the distance, i ascending
+        float dist = 0.0f;
+        for (uint32_t i0 = 0; i0 < D; i0 += kEvalBlockOutputs) {
+            float acc[kEvalBlockOutputs];
+            uint32_t col[kEvalBlockOutputs];
+#pragma unroll
+            for (uint32_t u = 0; u < kEvalBlockOutputs; ++u) { acc[u] = 0.0f; col[u] = min(i0 + u, D - 1); }
+            for (uint32_t j = 0; j < L; ++j) {
+                const float lj = lat[j * T + t];
+#pragma unroll
+                for (uint32_t u = 0; u < kEvalBlockOutputs; ++u) acc[u] = acc[u] + lj * wdec[j * D + col[u]];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < kEvalBlockOutputs; ++u) {
+                if (i0 + u < D) {
+                    const float act = apd::train_sigmoid(acc[u] + bdec[i0 + u]);
+                    const float xi = xs[(i0 + u) * T + t];
+                    float y = xi;
+                    if (rescale) y = (xi - mn) / scaler;
+                    const float diff = act - y, sq = diff * diff;
+                    dist = dist + sq;
+                }
+            }
+        }
+        err[p] = 0.5f * __builtin_sqrtf(dist);
+    }
+}
+
+// blockIdx.x: the model; one wavefront.  The chunk's errors 64 per load, added in position order on one chain.
+__global__ void __launch_bounds__(64) train_eval_total_kernel(EvalLaunch E)
+{
+    const uint32_t lane = threadIdx.x, m = blockIdx.x;
+    const float *err = E.d_err + m * E.err_stride;
+    EvalCarry c = E.d_carry[m];
+    float next = lane < E.n_pos ? err[lane] : 0.0f;
+    for (uint64_t s = 0; s < E.n_pos; s += 64) {
+        const float v = next;
+        if (s + 64 + lane < E.n_pos) next = err[s + 64 + lane];
+        const uint32_t n = (uint32_t)min((uint64_t)64, E.n_pos - s);
+        const bool bad = lane < n && (__float_as_uint(v) & kNonFiniteBits) == kNonFiniteBits;
+        const unsigned long long b = __ballot(bad);
+        if (b != 0 && c.first_nonfinite == ~0ull) c.first_nonfinite = E.first + s + (uint64_t)__builtin_ctzll(b);
+        if (n == 64) {
+#pragma unroll
+            for (uint32_t l = 0; l < 64; ++l) c.total_err = c.total_err + lane_value(v, l);
+        } else {
+            for (uint32_t l = 0; l < n; ++l) c.total_err = c.total_err + lane_value(v, l);
+        }
+    }
+    if (lane == 0) E.d_carry[m] = c;
+}
+
+// positions per workgroup of train_eval_kernel: the most of 256, 128, 64 whose tile keeps the workgroup's LDS within kEvalLdsTarget
+uint32_t eval_tile(uint32_t d_in, uint32_t latent, uint64_t model_floats)
+{
+    for (uint32_t tile : {256u, 128u})
+        if ((model_floats + (size_t)(d_in + latent) * tile) * sizeof(float) <= kEvalLdsTarget) return tile;
+    return 64;
+}
+
 }  // namespace
 
 struct apd_trainer : apd::ContextChild {
@@ -355,4 +489,104 @@ extern "C" int apd_trainer_encoder(apd_context *ctx, apd_trainer *t, uint32_t mo
     if (!ctx || !t || t->ctx != ctx || model >= t->n_models || !encoder) return APD_ERR_INVALID_ARG;
     const float *p = t->d_weights.as<float>() + model * t->model_floats;
     return apd::encoder_from_device(ctx, p, p + 2 * (uint64_t)t->d_in * t->latent, t->d_in, t->latent, encoder);
+}
+
+// Evaluation: every model's current weights on frames[order[e]], no update.  Nothing here writes t->d_weights or t->d_totals, so the
+// trainer keeps its bits whatever this call returns.  The positions are cut into chunks whose per-frame errors stay within the cap
+// (APD_EVAL_WORKSPACE_BYTES, 1 GiB); the running total and the first non-finite position travel between chunks in d_carry.
+extern "C" int apd_trainer_evaluate(apd_context *ctx, apd_trainer *t, const float *frames, uint64_t n_frames, int frames_on_device,
+                                    const uint32_t *order, uint64_t n_eval, int order_per_model, float *errors, int errors_on_device,
+                                    float *total_err, uint64_t *first_nonfinite)
+{
+    if (!ctx) return APD_ERR_INVALID_ARG;
+    auto refuse = [ctx](const char *why) { ctx->last_error = std::string("apd_trainer_evaluate: ") + why; return APD_ERR_INVALID_ARG; };
+    if (!t || t->ctx != ctx) return refuse("the trainer is not one of this context");
+    if (!errors && !total_err && !first_nonfinite) return refuse("errors, total_err and first_nonfinite are all NULL");
+    if (n_frames >= (1ull << 32)) return refuse("2^32 frames or more");
+    if (!order && order_per_model) return refuse("order_per_model without an order");
+    if (!order && n_eval != n_frames) return refuse("order == NULL needs n_eval == n_frames");
+    if (n_eval && !frames) return refuse("frames is NULL");
+    const uint64_t rows = order_per_model ? t->n_models : 1;
+    if (n_eval >= (1ull << 40) / t->n_models) return refuse("n_models * n_eval is 2^40 or more");
+    const uint64_t n_entries = order ? rows * n_eval : 0;
+    for (uint64_t e = 0; e < n_entries; ++e)
+        if (order[e] >= n_frames) return refuse("an order entry is not below n_frames");      // before anything is enqueued
+    const uint32_t n_models = t->n_models;
+    if (n_eval == 0) {
+        for (uint32_t m = 0; m < n_models; ++m) {
+            if (total_err) total_err[m] = 0.0f;
+            if (first_nonfinite) first_nonfinite[m] = ~0ull;
+        }
+        return APD_OK;
+    }
+    HIP_TRY(ctx, apd::bind_device(ctx));
+    APD_AFFINITY(ctx, "trainer evaluation");
+    const bool want_totals = total_err || first_nonfinite;
+    const uint64_t cap = apd::workspace_cap("APD_EVAL_WORKSPACE_BYTES");
+    const uint64_t chunk = std::min<uint64_t>(n_eval, std::max<uint64_t>(cap / ((uint64_t)n_models * sizeof(float)), 1));
+    apd::DeviceBuf d_order, d_host_frames;
+    std::vector<EvalCarry> carry;
+    try {
+        carry.assign(n_models, EvalCarry{0.0f, 0u, ~0ull});
+    } catch (const std::bad_alloc &) {
+        return APD_ERR_OOM;
+    }
+    // the context's workspace: [carry | the chunk's errors, unless they go to the caller's device buffer]
+    apd::Carve ws;
+    const size_t o_carry = ws.take<EvalCarry>(n_models);
+    const size_t o_err = ws.take<float>(errors_on_device && errors ? 0 : (size_t)n_models * chunk);
+    if (const int rc = reserve_ws(ctx, ctx->ws_misc, ws.size)) return rc;
+    EvalCarry *d_carry = (EvalCarry *)(ctx->ws_misc.as<char>() + o_carry);
+    float *d_ws_err = (float *)(ctx->ws_misc.as<char>() + o_err);
+    HIP_TRY(ctx, hipMemcpyAsync(d_carry, carry.data(), n_models * sizeof(EvalCarry), hipMemcpyHostToDevice, ctx->stream));
+    if (order) {
+        HIP_TRY(ctx, d_order.alloc(n_entries * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMemcpyAsync(d_order.ptr, order, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const float *d_frames = frames;
+    if (!frames_on_device) {
+        const size_t bytes = (size_t)n_frames * t->d_in * sizeof(float);
+        HIP_TRY(ctx, d_host_frames.alloc(bytes));
+        HIP_TRY(ctx, hipMemcpyAsync(d_host_frames.ptr, frames, bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_frames = d_host_frames.as<float>();
+    }
+    const uint32_t tile = eval_tile(t->d_in, t->latent, t->model_floats);
+    const size_t lds_bytes = (t->model_floats + (size_t)(t->d_in + t->latent) * tile) * sizeof(float);
+    if (lds_bytes > 64 * 1024)
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(train_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    EvalLaunch E{};
+    E.d_frames = d_frames; E.d_weights = t->d_weights.as<float>(); E.d_carry = d_carry;
+    E.order_stride = order_per_model ? n_eval : 0; E.model_floats = t->model_floats;
+    E.d_in = t->d_in; E.latent = t->latent; E.n_models = n_models;
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (uint64_t first = 0; first < n_eval; first += chunk) {
+        const uint64_t n_pos = std::min(chunk, n_eval - first);
+        E.first = first; E.n_pos = n_pos;
+        E.d_order = order ? d_order.as<uint32_t>() + first : nullptr;
+        if (errors_on_device && errors) { E.d_err = errors + first; E.err_stride = n_eval; }
+        else { E.d_err = d_ws_err; E.err_stride = n_pos; }
+        // workgroups per model: enough to fill the chip a few times over, and several tiles per staged model beyond that
+        const uint64_t n_tiles = (n_pos + tile - 1) / tile;
+        E.groups = (uint32_t)std::min<uint64_t>(n_tiles, std::max<uint32_t>(2048 / n_models, 1));
+        hipLaunchKernelGGL(train_eval_kernel, dim3(n_models * E.groups), dim3(tile), lds_bytes, ctx->stream, E);
+        HIP_TRY(ctx, hipGetLastError());
+        if (want_totals) {
+            hipLaunchKernelGGL(train_eval_total_kernel, dim3(n_models), dim3(64), 0, ctx->stream, E);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (ctx->timing && first + n_pos == n_eval) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        if (errors && !errors_on_device)
+            HIP_TRY(ctx, hipMemcpy2DAsync(errors + first, n_eval * sizeof(float), d_ws_err, n_pos * sizeof(float), n_pos * sizeof(float), n_models,
+                                          hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace
+    }
+    if (want_totals) {
+        HIP_TRY(ctx, hipMemcpyAsync(carry.data(), d_carry, n_models * sizeof(EvalCarry), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t m = 0; m < n_models; ++m) {
+            if (total_err) total_err[m] = carry[m].total_err;
+            if (first_nonfinite) first_nonfinite[m] = carry[m].first_nonfinite;
+        }
+    }
+    return APD_OK;
 }

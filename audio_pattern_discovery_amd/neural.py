@@ -118,6 +118,12 @@ class AutoEncoder:
                                          latent, 0, C.c_void_p(out.ctypes.data)), ctx.handle)
         return out
 
+    def reconstruction_errors(self, frames, ctx=None):
+        """The error take_step would return for every row of `frames` under these weights (0.5 * euclidean(activation, x.norm())),
+        nothing updated: Trainer.evaluate over a one-model trainer made and dropped.  A novelty curve of the frames under this model."""
+        with Trainer(ctx or _lib.default_context(), [self]) as t:
+            return t.evaluate(frames, errors=True)[0][0]
+
     def predict(self, x, ctx=None):           # neural.rs:55-71, x: Mat 1 x D
         flat = x.flat if isinstance(x, Mat) else np.asarray(x, np.float32)
         return Mat(self.predict_frames(np.asarray(flat, np.float32).reshape(1, -1), ctx).ravel(), self.n_latent())
@@ -191,6 +197,44 @@ class Trainer:
                                                  first.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset))), self.ctx.handle)
         none = np.uint64(0xFFFFFFFFFFFFFFFF)
         return [(err[m], int(steps[m]), None if first[m] == none else int(first[m])) for m in range(self.n_models)]
+
+    def evaluate(self, frames, order=None, on_device=False, errors=False):
+        """apd_trainer_evaluate: every model's current weights on frames[order[e]], nothing updated.  frames as in run(); order: None
+        (every frame, in order), [n_eval] shared by all models, or [n_models][n_eval].  Returns (total_err [n_models] f32,
+        first_nonfinite [n_models]: a position or None); with errors=True (errors [n_models][n_eval] f32, total_err, first_nonfinite).
+        errors may also be a device pointer (a DeviceBuffer.at()): the per-frame errors are left there and the pointer is returned."""
+        if on_device:
+            ptr, n_frames = frames
+            ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+        else:
+            x = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, self.d_in)
+            ptr, n_frames = C.c_void_p(x.ctypes.data), x.shape[0]
+        per_model, order_ptr, n_eval = False, None, int(n_frames)
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            per_model = order.ndim == 2
+            if per_model and order.shape[0] != self.n_models:
+                raise ValueError("a per-model order has one row per model")
+            order_ptr, n_eval = order.ctypes.data_as(C.POINTER(C.c_uint32)), order.shape[-1]
+        out, out_ptr, out_on_device = None, None, 0
+        if errors is True:
+            out = np.empty((self.n_models, n_eval), np.float32)
+            out_ptr = C.c_void_p(out.ctypes.data)
+        elif errors is not False and errors is not None:
+            out, out_on_device = errors, 1
+            out_ptr = errors if isinstance(errors, C.c_void_p) else C.c_void_p(int(errors))
+        total, first = np.empty(self.n_models, np.float32), np.empty(self.n_models, np.uint64)
+        _lib.check(_lib.lib().apd_trainer_evaluate(self.ctx.handle, self.handle, ptr, int(n_frames), int(bool(on_device)), order_ptr, n_eval,
+                                                   int(per_model), out_ptr, out_on_device, total.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   first.ctypes.data_as(C.POINTER(C.c_uint64))), self.ctx.handle)
+        none = np.uint64(0xFFFFFFFFFFFFFFFF)
+        first = [None if f == none else int(f) for f in first]
+        return (total, first) if out is None else (out, total, first)
+
+    def best(self, frames, order=None, on_device=False):
+        """The model evaluate() scores lowest on these frames (a NaN total never wins), and the totals: (index or None, total_err)."""
+        total, _ = self.evaluate(frames, order, on_device)
+        return (None if np.isnan(total).all() else int(np.nanargmin(total))), total
 
     def weights(self, model):
         d, l = self.d_in, self.latent

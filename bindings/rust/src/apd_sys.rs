@@ -319,6 +319,9 @@ extern "C" {
     pub fn apd_trainer_weights(trainer: *mut apd_trainer, model: u32, w_encode: *mut f32, w_decode: *mut f32, b_encode: *mut f32,
                                b_decode: *mut f32) -> c_int;
     pub fn apd_trainer_encoder(ctx: *mut apd_context, trainer: *mut apd_trainer, model: u32, encoder: *mut *mut apd_encoder) -> c_int;
+    pub fn apd_trainer_evaluate(ctx: *mut apd_context, trainer: *mut apd_trainer, frames: *const f32, n_frames: u64, frames_on_device: c_int,
+                                order: *const u32, n_eval: u64, order_per_model: c_int, errors: *mut f32, errors_on_device: c_int,
+                                total_err: *mut f32, first_nonfinite: *mut u64) -> c_int;
     pub fn apd_step_decay(learning_rate: f32, drop: f32, epoch_drop: f32, epoch: f32) -> f32;
     pub fn apd_train_order(seed: u64, epoch: u64, offsets: *const u64, n_seq: u32, order: *mut u32) -> c_int;
 }

@@ -144,3 +144,37 @@ impl AutoEncoder {
         Mat { flat, cols: latent }
     }
 }
+
+/// apd_trainer: models of one shape resident on the GPU, side by side.  The reference has no such item (it trains one model); this
+/// is what restarts and learning-rate sweeps are made of, and `evaluate` is what picks one of them.
+pub struct Trainer {
+    handle: *mut apd_trainer,
+    n_models: usize,
+    d_in: usize,
+}
+
+impl Trainer {
+    pub fn new(models: &[AutoEncoder]) -> Trainer {
+        Trainer { handle: AutoEncoder::trainer(models), n_models: models.len(), d_in: models[0].b_decode.cols }
+    }
+
+    /// The error of every model's current weights on `frames[order[e]]` (order: one list shared by the models; None: every frame in
+    /// order), nothing updated: (total_err per model -- one f32 add per position in position order, first position whose error is not
+    /// finite per model).  Bit for bit what take_step would return for each frame under frozen weights.
+    pub fn evaluate(&self, frames: &[f32], order: Option<&[u32]>) -> (Vec<f32>, Vec<Option<u64>>) {
+        let n_frames = (frames.len() / self.d_in) as u64;
+        let (order_ptr, n_eval) = match order { Some(o) => (o.as_ptr(), o.len() as u64), None => (std::ptr::null(), n_frames) };
+        let (mut total, mut first) = (vec![0f32; self.n_models], vec![0u64; self.n_models]);
+        unsafe {
+            check(apd_trainer_evaluate(feature_context(), self.handle, frames.as_ptr(), n_frames, 0, order_ptr, n_eval, 0, std::ptr::null_mut(), 0,
+                                       total.as_mut_ptr(), first.as_mut_ptr()));
+        }
+        (total, first.into_iter().map(|f| if f == u64::MAX { None } else { Some(f) }).collect())
+    }
+}
+
+impl Drop for Trainer {
+    fn drop(&mut self) {
+        unsafe { apd_trainer_destroy(self.handle); }
+    }
+}

@@ -996,6 +996,27 @@ int apd_trainer_run(apd_context *ctx, apd_trainer *trainer, const float *frames,
 int apd_trainer_totals(apd_trainer *trainer, float *total_err, uint64_t *steps, uint64_t *first_nonfinite, int reset);
 int apd_trainer_weights(apd_trainer *trainer, uint32_t model, float *w_encode, float *w_decode, float *b_encode, float *b_decode);
 int apd_trainer_encoder(apd_context *ctx, apd_trainer *trainer, uint32_t model, apd_encoder **encoder);
+/* Evaluation: the error of every model's CURRENT weights on chosen frames, and no update -- what picks one of many trained models
+ * on held-out frames.  For model m and position e < n_eval, with x = frames[order[e]] (order [n_eval] shared by the models, or
+ * [n_models][n_eval] with order_per_model; HOST array), error[m][e] is what AutoEncoder::take_step (neural.rs:74-94) would return for
+ * x: the arithmetic of apd_trainer_run operation for operation (x.norm() with its inverted condition, Mat::mul from 0.0 with k
+ * ascending and no fused multiply-add, the decoder fed the pre-activation latent, the defined sigmoid, 0.5 * sqrt of the squares
+ * added in ascending i).  Every (model, position) is independent: DEFINED BIT FOR BIT whatever n_models, the grid or the chunking.
+ *   errors: [n_models][n_eval] f32, host, or device with errors_on_device; may be NULL.
+ *   total_err [n_models] (host, may be NULL): main.rs:130 with the weights frozen -- from +0.0, one f32 add per position in position
+ *     order (no tree, no f64): the bits of apd_trainer_run with alpha = 0 wherever that route is defined.
+ *   first_nonfinite [n_models] (host, may be NULL): the first position whose error is not finite, UINT64_MAX if there is none.
+ * The trainer is not changed: weights, total_err, steps, the lifetime count and its own first_nonfinite keep their bits, also after
+ * APD_ERR_HIP.  A constant, NaN or infinite frame gives a NaN or inf error at its own position (and from there on in the sequential
+ * total) and touches nothing else -- apd_trainer_run with alpha = 0 turns every weight NaN on the first constant frame.
+ * order == NULL: positions 0 .. n_frames - 1; n_eval must equal n_frames and order_per_model be 0.  An index >= n_frames, n_frames
+ * >= 2^32, all three outputs NULL, a trainer of another context, a NULL where data is due: APD_ERR_INVALID_ARG before anything is
+ * enqueued, apd_last_error naming the call.  n_eval == 0 launches nothing: totals +0.0, first_nonfinite UINT64_MAX.  Blocking.  A call
+ * whose n_models * n_eval * 4 bytes exceed 1 GiB (APD_EVAL_WORKSPACE_BYTES overrides, for tests) is cut into chunks of positions, the
+ * results identical whatever the cut.  With apd_set_timing on, apd_last_kernel_ms covers the evaluation's kernels. */
+int apd_trainer_evaluate(apd_context *ctx, apd_trainer *trainer, const float *frames, uint64_t n_frames, int frames_on_device,
+                         const uint32_t *order, uint64_t n_eval, int order_per_model, float *errors, int errors_on_device,
+                         float *total_err, uint64_t *first_nonfinite);
 /* AutoEncoder::step_decay (neural.rs:26-28): learning_rate * drop ^ floor((1 + epoch) / epoch_drop) in f32.  Host only. */
 float apd_step_decay(float learning_rate, float drop, float epoch_drop, float epoch);
 /* The order of one epoch (main.rs:120-124): the signals in order (signal s owns frames offsets[s] .. offsets[s + 1]), each signal's
