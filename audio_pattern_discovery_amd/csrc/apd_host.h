@@ -22,10 +22,9 @@ struct ResidentIndex {
 };
 
 // The head every spotting launch struct begins with: the batch the query rows come from, and the penalties.
-template <class L> void spot_source(L &l, const apd_batch *b, float ins, float del, float mat)
+inline SpotSource spot_source(const apd_batch *b, float ins, float del, float mat)
 {
-    l.d_frames = b->d_frames.as<float>(); l.d_seq_off = b->d_seq_off; l.dim = b->dim; l.dpad = b->dpad;
-    l.ins = ins; l.del = del; l.mat = mat;
+    return {b->d_frames.as<float>(), b->d_seq_off, b->dim, b->dpad, ins, del, mat};
 }
 
 // A query of n frames against a stream of m: APD_ERR_UNSUPPORTED beyond what the spotting kernels hold, in `entry`'s name.
@@ -37,7 +36,6 @@ inline int spot_check_lengths(apd_context *ctx, const char *entry, uint32_t n, u
 }
 
 // The descriptors of a spotting launch, grouped by kernel class (spot_row_class): one launch per class.
-constexpr uint32_t kSpotClasses = kSpotRegisterRows + 1;
 struct SpotClasses : ClassBuckets<kSpotClasses> {
     uint32_t r_max = 1;             // the most rows per lane among the queries of class 0: it sizes their LDS
     uint32_t add(uint32_t dim, uint32_t n, uint64_t items = 1)   // counts `items` descriptors of a query of n frames; its class

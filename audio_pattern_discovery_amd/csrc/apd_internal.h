@@ -291,12 +291,45 @@ hipError_t launch_bary_pack(const BaryLaunch &L, float *d_out, hipStream_t strea
 constexpr uint32_t kSpotMaxQuery = 16384;     // frames of a query: 256 rows per lane, 128 KB of LDS for the lane columns
 constexpr uint32_t kSpotMaxStream = 0xFFFF0000u;   // frames of a stream: query + window + 1 stays below 2^32
 constexpr uint32_t kSpotRegisterRows = 4;     // rows per lane the kernels hold in registers
+constexpr uint32_t kSpotClasses = kSpotRegisterRows + 1;   // kernel classes: the host's buckets and the launcher's fold (dtw_spot_sweep.h)
 constexpr uint32_t spot_rows_per_lane(uint32_t n) { return (n + 63) / 64; }
 // The kernel class of a query of n frames at resident dimension dim: R = 1 .. kSpotRegisterRows rows per lane in registers (frame
 // dimensions with instantiated kernels only), 0: the lane columns in LDS.
 constexpr uint32_t spot_row_class(uint32_t dim, uint32_t n)
 {
     return is_kernel_dim(dim) && spot_rows_per_lane(n) <= kSpotRegisterRows ? spot_rows_per_lane(n) : 0u;
+}
+constexpr bool spot_row_classes_hold()
+{
+    for (int d : kKernelDims) {
+        for (uint32_t r = 1; r < kSpotClasses; ++r)
+            if (spot_row_class(d, 64 * (r - 1) + 1) != r || spot_row_class(d, 64 * r) != r) return false;
+        if (spot_row_class(d, 64 * kSpotRegisterRows + 1) != 0 || spot_row_class(d, kSpotMaxQuery) != 0) return false;
+    }
+    return true;
+}
+static_assert(spot_row_classes_hold(), "spot_row_class names the classes 0 .. kSpotClasses - 1, r rows per lane as class r, and no other");
+// Where the query rows and the penalties of a spotting launch are: the head of every spotting launch struct (spot_source, apd_host.h).
+struct SpotSource {
+    const float *d_frames;
+    const uint32_t *d_seq_off;
+    uint32_t dim, dpad;
+    float ins, del, mat;
+};
+// The score of a spotted window [start, end] of cost `cost` under a query of n frames, for the sweep's running best, the traces,
+// detection and online detection alike: the window and the sum in u32 (< 2^32: kSpotMaxStream), one conversion, one f32 division
+// (alignments.rs:121 with the window for m).
+__device__ __forceinline__ float spot_score(float cost, uint32_t end, uint32_t start, uint32_t n)
+{
+    const uint32_t window = end - start + 1u;                     // frames of the stream the alignment covers
+    return cost / (float)(n + window);
+}
+// The sort key of a score in both detections: the usual monotone map of f32 onto u32 (the sign bit flipped for a non-negative score,
+// every bit for a negative one) after both zeros were made +0.0, so that -0.0 and +0.0 tie as f32 < says they do.
+__device__ __forceinline__ uint32_t spot_score_key(float score)
+{
+    const uint32_t b = score == 0.0f ? 0u : __float_as_uint(score);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 struct SpotPair {
     uint32_t px, py;       // resident positions of the query x and the stream y
@@ -305,10 +338,7 @@ struct SpotPair {
     uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
 };
 struct SpotLaunch {
-    const float *d_frames;
-    const uint32_t *d_seq_off;
-    uint32_t dim, dpad;
-    float ins, del, mat;
+    SpotSource src;
     const SpotPair *d_pairs;
     uint32_t n_pairs;
     float *d_cost;         // both null: best only
@@ -319,8 +349,8 @@ size_t spot_lds_bytes(uint32_t rows_per_lane);
 // Under APD_DEBUG_PLAN, one stderr line per launch of a spotting kernel, printed where the template arguments are chosen:
 //   [apd] spot <kind> kernel <RT, D>: <n> pairs                                  (rows in registers)
 //   [apd] spot <kind> kernel <0, D>: <n> pairs, r_max <r>, lds <b> bytes         (lane columns in LDS; D = 0: any dimension)
-// kind: "sweep" (dtw_spot), "record" (dtw_spot_record), "stream" (dtw_spot_stream) or "streamrec" (dtw_spot_stream_record).  The only
-// report of which spotting kernel ran.
+// kind: the word of the kind type whose spot_kernel<Kind, RT, D> is launched (dtw_spot_sweep.h): "sweep" (SpotSweep), "record"
+// (SpotRecordSweep), "stream" (SpotStreamSweep) or "streamrec" (SpotStreamRecordSweep).  The only report of which spotting kernel ran.
 void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t r_max, size_t lds_bytes);
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
@@ -372,15 +402,12 @@ struct SpotStreamPair {
     uint64_t state_off;    // first float of the pair's state in either half of d_state
 };
 struct SpotStreamLaunch {
-    const float *d_frames;           // the templates
-    const uint32_t *d_seq_off;
+    SpotSource src;                  // the templates
     const float *d_stage;            // the chunks of this push, packed, in the resident layout (dpad floats per frame)
     // what a push uploads, n_channels + 1 | n_channels | n_channels words: first staged frame of every channel's chunk (and the
     // total); absolute column of the channel's last frame before this push; which half of d_state holds the channel's column
     const uint32_t *d_push;
     uint32_t n_channels, n_queries;
-    uint32_t dim, dpad;
-    float ins, del, mat;
     const SpotStreamPair *d_pairs;
     uint32_t n_pairs;
     float *d_state;                  // two halves of state_half floats: a sweep reads one and writes the other
@@ -421,10 +448,7 @@ struct SpotTraceWindow {
     uint64_t step_off;     // first step slot of the window in d_steps
 };
 struct SpotPathLaunch {
-    const float *d_frames;
-    const uint32_t *d_seq_off;
-    uint32_t dim, dpad;
-    float ins, del, mat;
+    SpotSource src;
     const SpotRecPair *d_pairs;        // the sweep's grid
     uint32_t n_pairs;
     const SpotInterval *d_intervals;
@@ -472,10 +496,7 @@ struct SpotRingWindow {
     uint64_t step_off;     // first step slot of the window in d_steps
 };
 struct SpotRingTraceLaunch {
-    const float *d_frames;             // the templates
-    const uint32_t *d_seq_off;
-    uint32_t dim, dpad;
-    float ins, del, mat;
+    SpotSource src;                    // the templates
     SpotHistory H;
     const SpotRingWindow *d_windows;
     uint32_t n_windows;

@@ -57,7 +57,7 @@ extern "C" int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_alig
         if (rc) return rc;
         char *base = ctx->ws_spot.as<char>();
         SpotLaunch L{};
-        spot_source(L, batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
+        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
         L.d_cost = curves ? (float *)(base + o_cost) : nullptr;
         L.d_start = curves ? (uint32_t *)(base + o_start) : nullptr;
         const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
@@ -227,7 +227,7 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
         if (rc) return rc;
         char *base = ctx->ws_spot.as<char>();
         SpotLaunch L{};
-        spot_source(L, batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
+        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
         L.d_cost = (float *)(base + o_cost);
         L.d_start = (uint32_t *)(base + o_start);
         const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
@@ -408,7 +408,7 @@ extern "C" int apd_spot_paths(apd_context *ctx, const apd_batch *batch, const ap
         std::memcpy(upload.data() + (o_ends - o_pairs), ends.data(), ne * 4);
         char *base = ctx->ws_spot_steps.as<char>();
         SpotPathLaunch L{};
-        spot_source(L, batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
+        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
         L.d_intervals = (const SpotInterval *)(base + o_iv);
         L.d_ends = (const uint32_t *)(base + o_ends);
         L.d_end_cost = (float *)(base + o_end_cost); L.d_end_start = (uint32_t *)(base + o_end_start);

@@ -73,7 +73,7 @@ struct apd_spot_stream : apd::ContextChild {
     SpotStreamLaunch launch() const
     {
         SpotStreamLaunch S{};
-        spot_source(S, templates, ins, del, mat);
+        S.src = spot_source(templates, ins, del, mat);
         S.d_stage = d_stage.as<float>(); S.d_push = d_push.as<uint32_t>();
         S.n_channels = n_channels; S.n_queries = n_queries;
         S.d_pairs = d_pairs.as<SpotStreamPair>(); S.n_pairs = n_pairs;
@@ -516,7 +516,7 @@ extern "C" int apd_spot_stream_paths(apd_context *ctx, apd_spot_stream *stream, 
         if (rc) return rc;
         char *base = ctx->ws_spot_steps.as<char>();
         SpotRingTraceLaunch L{};
-        spot_source(L, t, s->ins, s->del, s->mat);
+        L.src = spot_source(t, s->ins, s->del, s->mat);
         L.H = s->rings();
         L.d_windows = (const SpotRingWindow *)(base + o_win);
         L.d_steps = (apd_path_step *)(base + o_steps);

@@ -7,9 +7,10 @@
 // of reading the score one row and one column short, at (n-1, m-1) (alignments.rs:120): the curves are row n's, or a one-frame query
 // would have no row at all.
 //
-// The sweep itself -- lane mapping, macro-step, arithmetic -- is spot_sweep (dtw_spot_sweep.h), which apd_spot_paths' recording
-// sweep shares; here it runs with REC = false: the lane that owns row n stores the curves (when the caller asked for them) and keeps
-// the running best -- the scan over j is serial there already, no atomics, no reduction.
+// The sweep itself -- lane mapping, macro-step, arithmetic -- is spot_sweep (dtw_spot_sweep.h), which the other three sweep kinds
+// share, as they share the kernel template and the launcher; the kind SpotSweep runs it with REC = false: the lane that owns row n
+// stores the curves (when the caller asked for them) and keeps the running best -- the scan over j is serial there already, no
+// atomics, no reduction.  spot_lds_bytes and spot_debug_line, which the launcher calls for every kind, live here.
 #include <cstdio>
 #include <cstdlib>
 
@@ -17,12 +18,15 @@
 
 namespace apd {
 
-template <int RT, int D>
-__global__ __launch_bounds__(64) void dtw_spot(const SpotLaunch L)
-{
-    const SpotPair P = L.d_pairs[blockIdx.x];
-    spot_sweep<RT, D, false>(L, P, SpotRecord{});
-}
+struct SpotSweep {
+    using Launch = SpotLaunch;
+    static constexpr const char *word = "sweep";
+    template <int RT, int D>
+    static __device__ __forceinline__ void pair(const Launch &L)
+    {
+        spot_sweep<RT, D, false>(L.src, SpotOut{L.d_cost, L.d_start, L.d_best}, L.d_pairs[blockIdx.x], SpotRecord{});
+    }
+};
 
 size_t spot_lds_bytes(uint32_t rows_per_lane) { return (size_t)rows_per_lane * 64 * (sizeof(float) + sizeof(uint32_t)); }
 
@@ -35,44 +39,9 @@ void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t
         std::fprintf(stderr, "[apd] spot %s kernel <0, %d>: %u pairs, r_max %u, lds %zu bytes\n", kind, d, n_pairs, r_max, lds_bytes);
 }
 
-namespace {
-
-template <int RT, int D>
-hipError_t launch_spot_as(const SpotLaunch &L, uint32_t r_max, hipStream_t stream)
-{
-    const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
-    spot_debug_line("sweep", RT, D, L.n_pairs, r_max, lds_bytes);
-    if (lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_spot<RT, D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((dtw_spot<RT, D>), dim3(L.n_pairs), dim3(64), lds_bytes, stream, L);
-    return hipGetLastError();
-}
-
-template <int D>
-hipError_t launch_spot_rows(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream)
-{
-    switch (rt) {
-        case 1: return launch_spot_as<1, D>(L, r_max, stream);
-        case 2: return launch_spot_as<2, D>(L, r_max, stream);
-        case 3: return launch_spot_as<3, D>(L, r_max, stream);
-        case 4: return launch_spot_as<4, D>(L, r_max, stream);
-        default: return launch_spot_as<0, D>(L, r_max, stream);
-    }
-}
-
-}  // namespace
-
-// The pairs of L all belong to one class (spot_row_class): rt = 1 .. 4 rows per lane in registers, or 0 with at most r_max rows in LDS.
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream)
 {
-    if (L.n_pairs == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
-    const bool typed = with_kernel_dim(L.dim, [&](auto d) { e = launch_spot_rows<decltype(d)::value>(L, rt, r_max, stream); });
-    if (!typed) e = launch_spot_as<0, 0>(L, r_max, stream);              // any other dimension: frames re-read per cell, column in LDS
-    return e;
+    return spot_launch<SpotSweep>(L, L.n_pairs, L.src.dim, rt, r_max, stream);
 }
 
 }  // namespace apd

@@ -1,10 +1,10 @@
 // Spot detection (gfx950): apd_spot_detect.  What stands between the curves of apd_spot and the windows a caller wants -- score every
 // column, keep those below the pair's threshold, pick non-overlapping windows greedily in ascending (score, end, pair) -- done where
-// the curves already are.  The sweep is dtw_spot<RT, D> (dtw_spot.hip), launched by the host exactly as apd_spot launches it with
-// curves on; the kernels here read its curves and never touch the table (include/apd.h, "spot detection").
+// the curves already are.  The sweep is spot_kernel<SpotSweep, RT, D> (dtw_spot.hip), launched by the host exactly as apd_spot
+// launches it with curves on; the kernels here read its curves and never touch the table (include/apd.h, "spot detection").
 //
 // Four kernels on the call's stream, per chunk of whole groups:
-//   spot_detect_mark     over the chunk's curve entries, coalesced: the score (the sweep's own expression: one IEEE division), the
+//   spot_detect_mark     over the chunk's curve entries, coalesced: the score (spot_score, the sweep's own: one IEEE division), the
 //                        threshold test, and for every candidate a 16-byte key in its GROUP's list.  A wavefront compacts with one
 //                        ballot and one atomic on the group's counter; the order of a list therefore depends on scheduling, and
 //                        nothing downstream reads it: every choice below is a minimum over the full key.
@@ -13,12 +13,12 @@
 //   spot_detect_offsets  one workgroup: the exclusive prefix of the groups' hit counts.
 //   spot_detect_emit     after the host has sized the packed buffer: the apd_spot_hit records, group-major, acceptance order inside.
 //
-// The key.  hi = sortable(score) << 32 | end, lo = pair << 32 | start, compared (hi, lo): ascending score by f32 <, then the smaller
-// end, then the smaller pair (a group holds one candidate per (pair, end), so `start` below the pair never decides).  sortable():
-// the sign bit flipped for a non-negative score, every bit for a negative one -- the usual monotone map of f32 onto u32 -- after
-// both zeros were made +0.0, so that -0.0 and +0.0 tie as f32 < says they do.  A candidate's score is below its threshold and so
-// below +INF: its sortable form is below 0xFF800000, and hi = 2^64 - 1 is free to mean "dead".  The record's score is computed
-// again from the curves at emit (the same expression, the same bits, and the sign of a zero survives).
+// The key.  hi = spot_score_key(score) << 32 | end, lo = pair << 32 | start, compared (hi, lo): ascending score by f32 <, then the
+// smaller end, then the smaller pair (a group holds one candidate per (pair, end), so `start` below the pair never decides).
+// spot_score_key() (apd_internal.h): the sign bit flipped for a non-negative score, every bit for a negative one -- the usual monotone
+// map of f32 onto u32 -- after both zeros were made +0.0, so that -0.0 and +0.0 tie as f32 < says they do.  A candidate's score is
+// below its threshold and so below +INF: its key is below 0xFF800000, and hi = 2^64 - 1 is free to mean "dead".  The record's score
+// is computed again from the curves at emit (spot_score again: the same bits, and the sign of a zero survives).
 #include "apd_internal.h"
 
 namespace apd {
@@ -28,19 +28,6 @@ namespace {
 constexpr unsigned long long kDead = ~0ull;
 constexpr int kPickThreads = 1024;             // 16 wavefronts per group
 constexpr int kMarkThreads = 256;
-
-// the sweep's expression (dtw_spot_sweep.h): cost / (float)(n + window), window = end - start + 1 in u32
-__device__ __forceinline__ float detect_score(float cost, uint32_t end, uint32_t start, uint32_t n)
-{
-    const uint32_t window = end - start + 1u;
-    return cost / (float)(n + window);
-}
-
-__device__ __forceinline__ uint32_t sortable(float score)
-{
-    const uint32_t b = score == 0.0f ? 0u : __float_as_uint(score);       // -0.0 and +0.0: one key
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 __device__ __forceinline__ bool key_less(unsigned long long ah, unsigned long long al, unsigned long long bh, unsigned long long bl)
 {
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(kMarkThreads) void spot_detect_mark(const SpotDetec
         if (j < P.m) {
             const float c = cost[j];
             s = start[j];
-            score = detect_score(c, (uint32_t)j + 1u, s, P.n);
+            score = spot_score(c, (uint32_t)j + 1u, s, P.n);
             cand = s != 0u && score < P.threshold;                        // strict; a NaN on either side compares false
         }
         const unsigned long long vote = __ballot(cand);
@@ -88,7 +75,7 @@ __global__ __launch_bounds__(kMarkThreads) void spot_detect_mark(const SpotDetec
         if (cand) {
             const uint64_t slot = (((uint64_t)base_hi << 32) | base_lo) + (uint64_t)__popcll(vote & ((1ull << lane) - 1ull));
             ulonglong2 k;
-            k.x = ((unsigned long long)sortable(score) << 32) | (uint32_t)(j + 1u);
+            k.x = ((unsigned long long)spot_score_key(score) << 32) | (uint32_t)(j + 1u);
             k.y = ((unsigned long long)p << 32) | s;
             if (slot < G.cand_cap) list[slot] = k;                        // one candidate per entry at most: always true
         }
@@ -183,7 +170,7 @@ __global__ __launch_bounds__(64) void spot_detect_emit(const SpotDetectLaunch L,
         h.end = w.y;
         h.start = L.d_start[P.curve_off + w.y - 1u];
         h.cost = L.d_cost[P.curve_off + w.y - 1u];
-        h.score = detect_score(h.cost, h.end, h.start, P.n);
+        h.score = spot_score(h.cost, h.end, h.start, P.n);
         h.rank = r;
         d_hits[at] = h;
     }

@@ -1,11 +1,11 @@
 // Online spot detection (gfx950): the hold-off machine of an armed streaming session (include/apd.h, "streaming spotting, online
-// detection").  A push's sweeps (dtw_spot_stream / dtw_spot_stream_record) leave the chunk's curves in the
-// session's buffer; spot_online_scan, launched behind them on the same stream, turns them into hits without the curves ever
+// detection").  A push's sweeps (the kinds SpotStreamSweep / SpotStreamRecordSweep) leave the chunk's curves in
+// the session's buffer; spot_online_scan, launched behind them on the same stream, turns them into hits without the curves ever
 // leaving the device.
 //
 //   spot_online_scan   one workgroup of 16 wavefronts per group.  It walks the chunk in tiles of 16 x 64 columns.  Wavefront w takes
-//                      the tile's w-th block of 64 columns, lanes as columns: the score (the sweep's own expression: one IEEE
-//                      division), the strict threshold test, and per channel the smallest (sortable(score), pair) key over the
+//                      the tile's w-th block of 64 columns, lanes as columns: the score (spot_score, the sweep's own: one IEEE
+//                      division), the strict threshold test, and per channel the smallest (spot_score_key(score), pair) key over the
 //                      channel's pairs -- a lane loop over the pairs, every load coalesced (a pair's chunk entries are contiguous,
 //                      a channel's pairs adjacent).  A column belongs to ONE lane, which sees all of the group's pairs, so there
 //                      is no order of partial results for the outcome to depend on.  The block's candidates and their ballot go
@@ -18,27 +18,11 @@
 // A hit goes to the session's queue through one atomic on its counter; the order of the queue therefore depends on scheduling, and
 // nothing reads it: a record carries (pair, rank), and the drain orders by (group, rank) on the host.  The host has sized the queue
 // for the most a launch can emit (chunk columns + 1 per group; one per group for a flush) before the launch.
-//
-// detect_score() and sortable() restate dtw_spot_detect.hip's helpers of the same names: the same expressions, the same bits.
 #include "apd_internal.h"
 
 namespace apd {
 
 namespace {
-
-// the sweep's expression (dtw_spot_sweep.h): cost / (float)(n + window), window = end - start + 1 in u32
-__device__ __forceinline__ float detect_score(float cost, uint32_t end, uint32_t start, uint32_t n)
-{
-    const uint32_t window = end - start + 1u;
-    return cost / (float)(n + window);
-}
-
-// the usual monotone map of f32 onto u32, after both zeros were made +0.0: -0.0 and +0.0 tie as f32 < says they do
-__device__ __forceinline__ uint32_t sortable(float score)
-{
-    const uint32_t b = score == 0.0f ? 0u : __float_as_uint(score);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 // every lane holds the same state; lane 0 writes the record
 __device__ __forceinline__ void online_emit(const SpotOnlineLaunch &L, SpotOnlineState &st, bool writer)
@@ -88,9 +72,9 @@ __global__ __launch_bounds__(64 * kScanWaves) void spot_online_scan(const SpotOn
                 const uint64_t e = off0 + (uint64_t)q * m + i;
                 const float c = L.d_cost[e];
                 const uint32_t s = L.d_start[e];
-                const float score = detect_score(c, end, s, Q.n);
+                const float score = spot_score(c, end, s, Q.n);
                 if (s != 0u && score < Q.threshold) {                         // strict; a NaN on either side compares false
-                    const unsigned long long key = ((unsigned long long)sortable(score) << 32) | (p0 + q);
+                    const unsigned long long key = ((unsigned long long)spot_score_key(score) << 32) | (p0 + q);
                     if (key < c_key) { c_key = key; cand = true; c_start = s; c_cost = c; c_score = score; }
                 }
             }

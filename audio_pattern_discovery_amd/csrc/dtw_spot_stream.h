@@ -1,4 +1,4 @@
-// One pair of a streaming push (gfx950), shared by dtw_spot_stream (dtw_spot_stream.hip) and dtw_spot_stream_record
+// One pair of a streaming push (gfx950), shared by the kinds SpotStreamSweep (dtw_spot_stream.hip) and SpotStreamRecordSweep
 // (dtw_spot_stream_rec.hip): where the pair's chunk, carried column, curves and -- with RING -- rings lie, then spot_sweep
 // (dtw_spot_sweep.h).  The query rows come from the templates' batch, the stream columns from the session's staging buffer (the
 // chunk in the resident layout), the carried column from one half of the state buffer and the new one goes to the other half (the
@@ -16,10 +16,7 @@ __device__ __forceinline__ void spot_stream_pair(const SpotStreamLaunch &S, cons
     if (m == 0) return;                                                     // nothing pushed on this channel: state, best, parity and rings stay
     const uint32_t base = S.d_push[S.n_channels + 1 + Q.channel];
     const uint32_t parity = S.d_push[2 * S.n_channels + 1 + Q.channel] & 1u;
-    SpotLaunch L{};
-    L.d_frames = S.d_frames; L.d_seq_off = S.d_seq_off; L.dim = S.dim; L.dpad = S.dpad;
-    L.ins = S.ins; L.del = S.del; L.mat = S.mat;
-    L.d_cost = S.d_cost; L.d_start = S.d_start; L.d_best = S.d_best;
+    const SpotOut O{S.d_cost, S.d_start, S.d_best};
     SpotPair P{};
     P.px = Q.px; P.out = Q.out;
     // pair p = channel n_queries + q owns m entries behind those of the pairs before it
@@ -27,7 +24,7 @@ __device__ __forceinline__ void spot_stream_pair(const SpotStreamLaunch &S, cons
     const uint64_t column = (uint64_t)Q.rows * 64;                          // floats of a pair's values; its starts lie behind them
     float *in = S.d_state + parity * S.state_half + Q.state_off, *out = S.d_state + (parity ^ 1u) * S.state_half + Q.state_off;
     SpotCarry C;
-    C.y = S.d_stage + (uint64_t)first * S.dpad;
+    C.y = S.d_stage + (uint64_t)first * S.src.dpad;
     C.m = m; C.base = base;
     C.in_v = in; C.in_s = reinterpret_cast<const uint32_t *>(in + column);
     C.out_v = out; C.out_s = reinterpret_cast<uint32_t *>(out + column);
@@ -37,9 +34,9 @@ __device__ __forceinline__ void spot_stream_pair(const SpotStreamLaunch &S, cons
         G.curve_v = H.d_curve_v + (uint64_t)Q.out * H.rows;
         G.curve_s = H.d_curve_s + (uint64_t)Q.out * H.rows;
         G.rows = H.rows;
-        spot_sweep<RT, D, false, true, true>(L, P, SpotRecord{}, C, G);
+        spot_sweep<RT, D, false, true, true>(S.src, O, P, SpotRecord{}, C, G);
     } else {
-        spot_sweep<RT, D, false, true>(L, P, SpotRecord{}, C);
+        spot_sweep<RT, D, false, true>(S.src, O, P, SpotRecord{}, C);
     }
 }
 

@@ -4,8 +4,9 @@
 // the other, are the bits of apd_spot on the whole stream (include/apd.h, "streaming spotting").
 //
 // The sweep is spot_sweep (dtw_spot_sweep.h) with CARRY = true -- one text with apd_spot for the lane mapping, the macro-step and
-// the arithmetic.  What a push adds around it -- where the pair's chunk, carried column and curves lie -- is spot_stream_pair
-// (dtw_spot_stream.h), shared with the recording kernels of a session that keeps a history (dtw_spot_stream_rec.hip).
+// the arithmetic, under the one kernel template and launcher of that header.  What a push adds around it -- where the pair's chunk,
+// carried column and curves lie -- is spot_stream_pair (dtw_spot_stream.h), which the kind SpotStreamSweep shares with the recording
+// kind of a session that keeps a history (dtw_spot_stream_rec.hip).
 #include <cstdio>
 #include <cstdlib>
 
@@ -13,11 +14,12 @@
 
 namespace apd {
 
-template <int RT, int D>
-__global__ __launch_bounds__(64) void dtw_spot_stream(const SpotStreamLaunch S)
-{
-    spot_stream_pair<RT, D, false>(S, SpotHistory{});
-}
+struct SpotStreamSweep {
+    using Launch = SpotStreamLaunch;
+    static constexpr const char *word = "stream";
+    template <int RT, int D>
+    static __device__ __forceinline__ void pair(const Launch &S) { spot_stream_pair<RT, D, false>(S, SpotHistory{}); }
+};
 
 // A fresh table for the pairs of `channel` (0xFFFFFFFF: every channel): column 0 (+INF / 0) in both halves of the state, best none.
 __global__ __launch_bounds__(64) void spot_stream_reset_kernel(const SpotStreamLaunch S, uint32_t channel)
@@ -37,44 +39,9 @@ __global__ __launch_bounds__(64) void spot_stream_reset_kernel(const SpotStreamL
     }
 }
 
-namespace {
-
-template <int RT, int D>
-hipError_t launch_spot_stream_as(const SpotStreamLaunch &S, uint32_t r_max, hipStream_t stream)
-{
-    const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
-    spot_debug_line("stream", RT, D, S.n_pairs, r_max, lds_bytes);
-    if (lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dtw_spot_stream<RT, D>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((dtw_spot_stream<RT, D>), dim3(S.n_pairs), dim3(64), lds_bytes, stream, S);
-    return hipGetLastError();
-}
-
-template <int D>
-hipError_t launch_spot_stream_rows(const SpotStreamLaunch &S, uint32_t rt, uint32_t r_max, hipStream_t stream)
-{
-    switch (rt) {
-        case 1: return launch_spot_stream_as<1, D>(S, r_max, stream);
-        case 2: return launch_spot_stream_as<2, D>(S, r_max, stream);
-        case 3: return launch_spot_stream_as<3, D>(S, r_max, stream);
-        case 4: return launch_spot_stream_as<4, D>(S, r_max, stream);
-        default: return launch_spot_stream_as<0, D>(S, r_max, stream);
-    }
-}
-
-}  // namespace
-
-// The pairs of S all belong to one class (spot_row_class), as for launch_spot.
 hipError_t launch_spot_stream(const SpotStreamLaunch &S, uint32_t rt, uint32_t r_max, hipStream_t stream)
 {
-    if (S.n_pairs == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
-    const bool typed = with_kernel_dim(S.dim, [&](auto d) { e = launch_spot_stream_rows<decltype(d)::value>(S, rt, r_max, stream); });
-    if (!typed) e = launch_spot_stream_as<0, 0>(S, r_max, stream);       // any other dimension: frames re-read per cell, column in LDS
-    return e;
+    return spot_launch<SpotStreamSweep>(S, S.n_pairs, S.src.dim, rt, r_max, stream);
 }
 
 hipError_t launch_spot_stream_reset(const SpotStreamLaunch &S, uint32_t channel, hipStream_t stream)

@@ -111,12 +111,12 @@ struct SpotRecord {
 };
 
 // What the streaming sweep (CARRY) is given for its pair: the table is entered behind absolute column `base` and left behind column
-// base + m.  The stream side is the chunk alone -- m >= 1 frames at y in the resident layout, L's frames and offsets serve the
+// base + m.  The stream side is the chunk alone -- m >= 1 frames at y in the resident layout, src's frames and offsets serve the
 // query only and P.py is not read -- and the column the table was left in last time comes from in_v / in_s, laid out [r][lane] like
 // the LDS column: T[i][base] and S[i][base] of the lane's rows, +INF / 0 for column 0 and for rows beyond n.  Every lane with a
 // live row stores its column base + m to out_v / out_s behind the loop.  The session keeps in and out apart (two buffers taking
 // turns), so that nothing depends on the order in which the lanes of a wavefront read the old column and write the new one.
-// The running best starts from L.d_best[P.out] instead of +INF, and starts and ends are absolute columns.
+// The running best starts from out.d_best[P.out] instead of +INF, and starts and ends are absolute columns.
 struct SpotCarry {
     const float *y;
     uint32_t m;
@@ -140,9 +140,16 @@ struct SpotRing {
     uint32_t rows;          // H >= 1
 };
 
+// Where a sweep that is not REC leaves its results: row n's curves at P.curve_off (both null: best only) and the best at P.out.
+struct SpotOut {
+    float *d_cost;
+    uint32_t *d_start;
+    apd_spot_best *d_best;
+};
+
 template <int RT, int D, bool REC, bool CARRY = false, bool RING = false>
-__device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P, const SpotRecord rec, const SpotCarry carry = SpotCarry{},
-                                           const SpotRing ring = SpotRing{})
+__device__ __forceinline__ void spot_sweep(const SpotSource src, const SpotOut out, const SpotPair P, const SpotRecord rec,
+                                           const SpotCarry carry = SpotCarry{}, const SpotRing ring = SpotRing{})
 {
     static_assert(RT == 0 || D > 0, "rows in registers need the frame dimension at compile time");
     static_assert(!(REC && CARRY), "a carried table has no column 1 to record from");
@@ -151,22 +158,22 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
     extern __shared__ __attribute__((aligned(16))) float spot_column[];   // RT == 0: [r][lane] values, then [r][lane] starts
     constexpr int DN = D > 0 ? ((D + 4) & ~3) : 4;                          // floats of a resident frame
     const int lane = threadIdx.x;
-    uint32_t ox = L.d_seq_off[P.px], oy = 0u;
-    if constexpr (!CARRY) oy = L.d_seq_off[P.py];
-    const int n = (int)(L.d_seq_off[P.px + 1] - ox) - 2;                    // <= kSpotMaxQuery
+    uint32_t ox = src.d_seq_off[P.px], oy = 0u;
+    if constexpr (!CARRY) oy = src.d_seq_off[P.py];
+    const int n = (int)(src.d_seq_off[P.px + 1] - ox) - 2;                    // <= kSpotMaxQuery
     uint32_t m;
     if constexpr (CARRY) m = carry.m;
-    else m = REC ? rec.max_end : L.d_seq_off[P.py + 1] - oy - 2;            // REC: column j depends on columns <= j only
-    const float *X = L.d_frames + (uint64_t)ox * L.dpad;
-    const float *Y = CARRY ? carry.y : L.d_frames + (uint64_t)oy * L.dpad;
-    const float ins = L.ins, del = L.del, mat = L.mat;
+    else m = REC ? rec.max_end : src.d_seq_off[P.py + 1] - oy - 2;            // REC: column j depends on columns <= j only
+    const float *X = src.d_frames + (uint64_t)ox * src.dpad;
+    const float *Y = CARRY ? carry.y : src.d_frames + (uint64_t)oy * src.dpad;
+    const float ins = src.ins, del = src.del, mat = src.mat;
     const int R = RT > 0 ? RT : (n + 63) / 64;
     const int row0 = lane * R;                                              // 0-based first query row of the lane
     const int rows_live = min(max(n - row0, 0), R);
     const int lane_n = (n - 1) / R, r_n = (n - 1) - lane_n * R;             // where row n lives
-    const bool curves = !REC && L.d_cost != nullptr;
-    float *cost = curves ? L.d_cost + P.curve_off : nullptr;
-    uint32_t *start = curves ? L.d_start + P.curve_off : nullptr;
+    const bool curves = !REC && out.d_cost != nullptr;
+    float *cost = curves ? out.d_cost + P.curve_off : nullptr;
+    uint32_t *start = curves ? out.d_start + P.curve_off : nullptr;
     uint32_t *col_start = reinterpret_cast<uint32_t *>(spot_column) + (size_t)R * 64;
 
     float pv[RT > 0 ? RT : 1];                                              // the lane's previous column
@@ -177,7 +184,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         for (int r = 0; r < RT; ++r) {
             pv[r] = CARRY ? carry.in_v[r * 64 + lane] : APD_INF;
             ps[r] = CARRY ? carry.in_s[r * 64 + lane] : 0u;
-            spot_load_frame<DN>(xr[r], X + (uint64_t)min(row0 + r, n - 1) * L.dpad);
+            spot_load_frame<DN>(xr[r], X + (uint64_t)min(row0 + r, n - 1) * src.dpad);
         }
     } else {
         for (int r = 0; r < R; ++r) {
@@ -198,10 +205,10 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
     [[maybe_unused]] uint32_t ring_row = 0;
     if constexpr (RING) ring_row = (carry.base + 1u) % ring.rows;
 
-    const int dp4 = (int)L.dpad / 4, dim = (int)L.dim;
+    const int dp4 = (int)src.dpad / 4, dim = (int)src.dim;
     float y_even[DN], y_odd[DN];                                            // column j's frame and the next macro-step's, taking turns (D > 0)
     uint32_t jm1 = 0u - (uint32_t)lane;                                     // j - 1; wraps above m while the lane waits for column 1
-    if constexpr (D > 0) spot_load_frame<DN>(y_even, Y + (uint64_t)min(jm1, m - 1) * L.dpad);
+    if constexpr (D > 0) spot_load_frame<DN>(y_even, Y + (uint64_t)min(jm1, m - 1) * src.dpad);
     float in_prev = lane == 0 ? 0.0f : APD_INF;                             // T[row0][j-1]: row 0 reads 0, column 0 below it +INF
     uint32_t in_prev_s = 0u;
     float last = APD_INF;
@@ -213,7 +220,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         // A waiting lane hands it on unchanged (below); lane 0 never waits, so it starts out with it.
         if constexpr (RT > 0) { last = pv[RT - 1]; last_s = ps[RT - 1]; }
         else { last = spot_column[(R - 1) * 64 + lane]; last_s = col_start[(R - 1) * 64 + lane]; }
-        const apd_spot_best b = L.d_best[P.out];
+        const apd_spot_best b = out.d_best[P.out];
         best_end = b.end; best_start = b.start; best_cost = b.cost; best_score = b.score;
     }
     const uint64_t total = (uint64_t)m + (uint64_t)lane_n;
@@ -227,8 +234,8 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         // predecessors from this lane's live steps only.
         uint32_t ja = j;
         if constexpr (CARRY) ja = carry.base + j;
-        if constexpr (D > 0) spot_load_frame<DN>(yn, Y + (uint64_t)min(jm1 + 1u, m - 1) * L.dpad);
-        const float4 *yb = reinterpret_cast<const float4 *>(Y + (uint64_t)min(jm1, m - 1) * L.dpad);
+        if constexpr (D > 0) spot_load_frame<DN>(yn, Y + (uint64_t)min(jm1 + 1u, m - 1) * src.dpad);
+        const float4 *yb = reinterpret_cast<const float4 *>(Y + (uint64_t)min(jm1, m - 1) * src.dpad);
         // REC: where this column's branch words go, if it lies in an interval
         [[maybe_unused]] uint32_t *rec_words = nullptr;
         [[maybe_unused]] uint32_t word = 0;
@@ -288,7 +295,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
             if constexpr (OPS) if (rec_words) rec_words[0] = word;
         } else {
             for (int r = 0; r < R; ++r) {
-                const float *xrow = X + (uint64_t)min(row0 + r, n - 1) * L.dpad;
+                const float *xrow = X + (uint64_t)min(row0 + r, n - 1) * src.dpad;
                 float dist;
                 if constexpr (D > 0) {
                     float xf[DN];
@@ -330,8 +337,7 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
             } else {
                 if (curves) { cost[jm1] = cap_v; start[jm1] = cap_s; }
                 if constexpr (RING) { ring.curve_v[ring_row] = cap_v; ring.curve_s[ring_row] = cap_s; }
-                const uint32_t window = ja - cap_s + 1u;                    // frames of y the alignment covers
-                const float score = cap_v / (float)((uint32_t)n + window);  // one f32 division (alignments.rs:121 with the window for m); < 2^32: kSpotMaxStream
+                const float score = spot_score(cap_v, ja, cap_s, (uint32_t)n);
                 if (score < best_score) { best_end = ja; best_start = cap_s; best_cost = cap_v; best_score = score; }
             }
         }
@@ -362,9 +368,59 @@ __device__ __forceinline__ void spot_sweep(const SpotLaunch L, const SpotPair P,
         if (lane == lane_n) {
             apd_spot_best b;
             b.end = best_end; b.start = best_start; b.cost = best_cost; b.score = best_score;
-            L.d_best[P.out] = b;
+            out.d_best[P.out] = b;
         }
     }
+}
+
+// ---- the one kernel and the one launcher of the four sweep kinds.  A kind is a type with
+//   Launch:         its launch struct, the kernel's only argument;
+//   word:           its name on the APD_DEBUG_PLAN line (spot_debug_line);
+//   pair<RT, D>(L): what the wavefront of pair blockIdx.x does -- spot_sweep with the kind's REC / CARRY / RING.
+// SpotSweep (dtw_spot.hip), SpotRecordSweep (dtw_spot_path.hip), SpotStreamSweep (dtw_spot_stream.hip) and SpotStreamRecordSweep
+// (dtw_spot_stream_rec.hip) are the kinds; each unit instantiates its own kind's kernels through its launch_*.
+template <class Kind, int RT, int D>
+__global__ __launch_bounds__(64) void spot_kernel(const typename Kind::Launch L)
+{
+    Kind::template pair<RT, D>(L);
+}
+
+template <class Kind, int RT, int D>
+hipError_t spot_launch_as(const typename Kind::Launch &L, uint32_t n_pairs, uint32_t r_max, hipStream_t stream)
+{
+    const size_t lds_bytes = RT > 0 ? 0 : spot_lds_bytes(r_max);
+    spot_debug_line(Kind::word, RT, D, n_pairs, r_max, lds_bytes);
+    if (lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spot_kernel<Kind, RT, D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((spot_kernel<Kind, RT, D>), dim3(n_pairs), dim3(64), lds_bytes, stream, L);
+    return hipGetLastError();
+}
+
+// class C of kSpotClasses is kernel <C, D>; an rt that names no class runs as class 0
+template <class Kind, int D, size_t... C>
+hipError_t spot_launch_class(const typename Kind::Launch &L, uint32_t n_pairs, uint32_t rt, uint32_t r_max, hipStream_t stream,
+                             std::index_sequence<C...>)
+{
+    hipError_t e = hipSuccess;
+    const bool named = ((rt == C ? (e = spot_launch_as<Kind, (int)C, D>(L, n_pairs, r_max, stream), true) : false) || ...);
+    return named ? e : spot_launch_as<Kind, 0, D>(L, n_pairs, r_max, stream);
+}
+
+// The n_pairs pairs of L all belong to one class (spot_row_class): rt = 1 .. kSpotRegisterRows rows per lane in registers, or 0 with
+// at most r_max rows in LDS.  dim: the resident dimension of L's source.
+template <class Kind>
+hipError_t spot_launch(const typename Kind::Launch &L, uint32_t n_pairs, uint32_t dim, uint32_t rt, uint32_t r_max, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    const bool typed = with_kernel_dim(dim, [&](auto d) {
+        e = spot_launch_class<Kind, decltype(d)::value>(L, n_pairs, rt, r_max, stream, std::make_index_sequence<kSpotClasses>{});
+    });
+    if (!typed) e = spot_launch_as<Kind, 0, 0>(L, n_pairs, r_max, stream);   // any other dimension: frames re-read per cell, column in LDS
+    return e;
 }
 
 }  // namespace apd

@@ -22,16 +22,24 @@ static_assert(kSpotTraceStageWords / 64 >= (int)((kSpotMaxQuery / 64 + 15) / 16)
 
 // What both forms know of their window.  slot: the window's index in d_len / d_found / d_scores.
 struct SpotTraceJob {
+    SpotSource src;
     const float *X;        // the query's resident frames
     int n;
-    uint32_t dim, dpad;
-    float ins, del, mat;
     uint32_t end, start;
     uint4 *out;            // the window's slots: {i, j, bits of cost, op}
     uint32_t *d_len, *d_found;
     float *d_scores;
     uint32_t slot;
 };
+// The job of window blockIdx.x of either trace launch L: the query at resident position px, the caller's window [start, end], the
+// window's first step slot in L.d_steps.
+template <class L>
+__device__ __forceinline__ SpotTraceJob spot_trace_job(const L &l, uint32_t px, uint32_t end, uint32_t start, uint64_t step_off)
+{
+    const uint32_t ox = l.src.d_seq_off[px];
+    return {l.src, l.src.d_frames + (uint64_t)ox * l.src.dpad, (int)(l.src.d_seq_off[px + 1] - ox) - 2, end, start,
+            reinterpret_cast<uint4 *>(l.d_steps + step_off), l.d_len, l.d_found, l.d_scores, blockIdx.x};
+}
 
 template <class Src>
 __device__ __forceinline__ void spot_trace_window(const SpotTraceJob W, const Src src)
@@ -88,7 +96,7 @@ __device__ __forceinline__ void spot_trace_window(const SpotTraceJob W, const Sr
     __syncthreads();
 
     // ---- replay forward: slot bound - len + s holds path step s; step s goes to slot s (never ahead of what is still unread)
-    const int dp4 = (int)W.dpad / 4, dim = (int)W.dim;
+    const int dp4 = (int)W.src.dpad / 4, dim = (int)W.src.dim;
     float carry = APD_INF;
     for (uint32_t s = 0; s < len; s += 64) {
         const uint32_t idx = s + lane;
@@ -98,10 +106,10 @@ __device__ __forceinline__ void spot_trace_window(const SpotTraceJob W, const Sr
         if (live) {
             st = out[bound - len + idx];
             if (st.w != APD_PATH_START) {
-                const float4 *xa = reinterpret_cast<const float4 *>(X + (uint64_t)(st.x - 1) * W.dpad);
+                const float4 *xa = reinterpret_cast<const float4 *>(X + (uint64_t)(st.x - 1) * W.src.dpad);
                 const float4 *yb = src.y(st.y);
                 const float d = __builtin_sqrtf(spot_sq_distance_any(xa, yb, dp4, dim));
-                const float pen = st.w == APD_PATH_DELETE ? W.del : st.w == APD_PATH_INSERT ? W.ins : W.mat;
+                const float pen = st.w == APD_PATH_DELETE ? W.src.del : st.w == APD_PATH_INSERT ? W.src.ins : W.src.mat;
                 wd = pen * d;                                        // rounded on its own, then added
             }
         }
@@ -123,8 +131,7 @@ __device__ __forceinline__ void spot_trace_window(const SpotTraceJob W, const Sr
     if (lane == 0) {
         W.d_len[W.slot] = len;
         W.d_found[W.slot] = found;
-        const uint32_t covered = W.end - found + 1u;                 // frames of y the alignment covers, as dtw_spot counts them
-        W.d_scores[W.slot] = end_cost / (float)((uint32_t)n + covered);
+        W.d_scores[W.slot] = spot_score(end_cost, W.end, found, (uint32_t)n);   // as the sweep scores its running best
     }
 }
 

@@ -197,7 +197,7 @@ def read_plan(stderr_text):
     return plan
 
 
-# ---- the spotting kernels: dtw_spot<RT, D> and dtw_spot_record<RT, D> (csrc/dtw_spot.hip, csrc/dtw_spot_path.hip)
+# ---- the spotting kernels: spot_kernel<SpotSweep, RT, D> and spot_kernel<SpotRecordSweep, RT, D> (csrc/dtw_spot.hip, csrc/dtw_spot_path.hip)
 SPOT_KINDS = ("sweep", "record")
 
 

@@ -1,7 +1,7 @@
 """The inputs of tests/test_gpu_spot_matrix.py, and the conditions they must meet, without a GPU: TEST INFRASTRUCTURE.
 
-One case per spotting kernel <RT, D> that tests/_kernel_table.py reads from csrc/apd_internal.h (the sweep dtw_spot and the recording
-sweep dtw_spot_record run the same case), and one per frame dimension of the <0, 0> group.  A case is a list of sequences of one
+One case per spotting kernel <RT, D> that tests/_kernel_table.py reads from csrc/apd_internal.h (the sweep kind SpotSweep and the recording
+kind SpotRecordSweep run the same case), and one per frame dimension of the <0, 0> group.  A case is a list of sequences of one
 frame dimension, the (query, stream) pairs swept with unit penalties, the pairs swept with skewed ones, and -- for the kernels that
 keep their rows in registers -- three pairs that send macro-steps down both square-root branches of csrc/dtw_spot_sweep.h (the
 wave-wide gate `d2 >= 2^-96 and d2 < inf` on every squared distance of a macro-step, dead cells included).  What the kernels do

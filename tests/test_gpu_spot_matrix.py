@@ -1,5 +1,6 @@
-"""Every instantiated spotting kernel -- dtw_spot<RT, D> and dtw_spot_record<RT, D> (csrc/dtw_spot.hip, csrc/dtw_spot_path.hip), both
-spot_sweep<RT, D, REC> of csrc/dtw_spot_sweep.h -- against the checkers, with the proof that the NAMED kernel ran.
+"""Every instantiated spotting kernel -- spot_kernel<Kind, RT, D> of csrc/dtw_spot_sweep.h for the kinds SpotSweep ("sweep",
+csrc/dtw_spot.hip) and SpotRecordSweep ("record", csrc/dtw_spot_path.hip), both spot_sweep<RT, D, REC> of that header -- against the
+checkers, with the proof that the NAMED kernel ran.
 
 The matrix is not written here: tests/_kernel_table.py reads kKernelDims and kSpotRegisterRows from csrc/apd_internal.h, and
 tests/_spot_matrix.py builds one case per <RT, D> from them, so a dimension or a register-row class added to the header is a new

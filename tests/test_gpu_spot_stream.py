@@ -1,4 +1,4 @@
-"""GPU tests of the streaming spotting session (apd_spot_stream_*, kernels dtw_spot_stream<RT, D> of csrc/dtw_spot_stream.hip) against
+"""GPU tests of the streaming spotting session (apd_spot_stream_*, kernels spot_kernel<SpotStreamSweep, RT, D> of csrc/dtw_spot_stream.hip) against
 the checkers tests/_spot_reference.py (the whole stream) and tests/_spot_stream_reference.py (chunk by chunk).
 
 The promise under test takes no tolerance: whatever the chunking, the curves of the pushes, one after the other, are the bits of the

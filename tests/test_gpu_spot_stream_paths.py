@@ -1,4 +1,4 @@
-"""GPU tests of the history of a streaming session (apd_spot_stream_keep / _history / _paths; kernels dtw_spot_stream_record<RT, D>,
+"""GPU tests of the history of a streaming session (apd_spot_stream_keep / _history / _paths; kernels spot_kernel<SpotStreamRecordSweep, RT, D>,
 spot_stream_frames_kernel and dtw_spot_stream_trace of csrc/dtw_spot_stream_rec.hip) against the checker tests/_spot_path_reference.py
 on the whole stream, shifted and aged out as tests/_spot_stream_path_reference.expected says (that module's ring session is shown
 equal to it, on the CPU, by tests/test_spot_stream_path_reference.py).

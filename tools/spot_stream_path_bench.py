@@ -4,8 +4,8 @@
   tools/spot_stream_bench.py's workload: 64 templates of 128 frames against 16 channels of 16 384 frames, D = 13, curves on, fed
   in chunks of 1024 columns packed on the device beforehand and pushed back to back through the C ABI.
 
-  off:    the session without a history (the kernels dtw_spot_stream);
-  on:     the same session after apd_spot_stream_keep(H) (dtw_spot_stream_record and the frame-ring copy); its curves and bests are
+  off:    the session without a history (the kernels of the kind SpotStreamSweep);
+  on:     the same session after apd_spot_stream_keep(H) (the kind SpotStreamRecordSweep and the frame-ring copy); its curves and bests are
           compared with `off`'s, bit for bit;
   trace:  after the last push of `on`, apd_spot_stream_paths for one window per pair -- the best-scoring end of the last chunk whose
           start is still kept -- beside apd_spot (curves, (a)) and apd_spot_paths ((b)) for the same 1024 windows on the joined
