@@ -22,6 +22,9 @@ APD_ERR_UNSUPPORTED = -8
 APD_ERR_INCOMPLETE = -9
 APD_ERR_COMM = -10
 APD_COMM_ID_BYTES = 128
+APD_QUANTILES_PER_PAIR, APD_QUANTILES_PER_QUERY, APD_QUANTILES_ALL = 0, 1, 2    # apd_spot_quantiles' groupings
+APD_SPOT_QUANTILES_MAX = 8
+APD_SPOT_QUANTILES_COLUMNS = 256         # columns a workgroup of the select takes per step (tests place stream lengths around it)
 
 
 class AlignConfig(C.Structure):
@@ -182,6 +185,8 @@ SYMBOLS = [
     ("apd_spot_hits", C.c_int, [_f32p, _u32p, C.c_uint64, C.c_uint64, C.c_float, C.POINTER(SpotBest), C.c_uint64, _u64p]),
     ("apd_spot_detect", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, _f32p, C.c_int, C.POINTER(SpotHit), C.c_uint64, _u64p,
                                   _u64p, _u64p]),
+    ("apd_spot_quantiles", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, C.c_uint64, C.c_int, _f32p, C.c_uint32, _f32p,
+                                     C.POINTER(C.c_int32), _u64p, _u64p, _u64p, _u64p]),
     ("apd_spot_path_bound", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
     ("apd_spot_paths", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), C.POINTER(SpotWindow), C.c_uint64, C.POINTER(PathStep), C.c_uint64, _u64p,
                                  _u32p, _u32p, _f32p]),

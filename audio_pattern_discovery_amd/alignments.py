@@ -423,6 +423,56 @@ class AlignmentWorkers:
                 batch.close()
         return hits[:min(int(n_hits.value), int(capacity))].copy(), off[:n_groups.value + 1].copy(), groups
 
+    def score_quantiles(self, pairs, params, perc, by="pair", streams=None, strict=True):
+        """Spot score quantiles (include/apd.h, "spot score quantiles"): numerics::percentile over the scores of groups of spotting
+        curves, on the device.  pairs, params and `streams` as for spot(); perc: a scalar or a sequence of at most 8; by: "pair" (a
+        group per pair), "query" (the pairs of a query pooled, groups in order of first appearance) or "all" (one group).  Returns
+        (values [n_groups, n_perc] float32, group_of [n_pairs], entries [n_groups], nans [n_groups]): apd_spot_quantiles.  A rank
+        beyond a group's non-NaN scores (every perc = 1.0) raises ApdError(APD_ERR_INDEX) with strict=True; with strict=False its value
+        is NaN and the int32 status array [n_groups, n_perc] is returned as a fifth item."""
+        if self._multi is not None or (streams is not None and streams._multi is not None):
+            raise ValueError("score_quantiles() runs on one context: make the AlignmentWorkers without `devices`")
+        grouping = {"pair": _lib.APD_QUANTILES_PER_PAIR, "query": _lib.APD_QUANTILES_PER_QUERY, "all": _lib.APD_QUANTILES_ALL}[by]
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_pairs = len(pr)
+        pc = np.ascontiguousarray(np.atleast_1d(np.asarray(perc, dtype=np.float32)))
+        slots = max(n_pairs, 1)
+        values = np.zeros((slots, len(pc)), dtype=np.float32)
+        status = np.zeros((slots, len(pc)), dtype=np.int32)
+        group_of, entries, nans = (np.zeros(slots, dtype=np.uint64) for _ in range(3))
+        n_groups = C.c_uint64(0)
+        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
+        try:
+            _lib.check(_lib.lib().apd_spot_quantiles(self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs, grouping,
+                                                     pc.ctypes.data_as(f32p), len(pc), values.ctypes.data_as(f32p),
+                                                     status.ctypes.data_as(C.POINTER(C.c_int32)), group_of.ctypes.data_as(u64p),
+                                                     entries.ctypes.data_as(u64p), nans.ctypes.data_as(u64p), C.byref(n_groups)), self.ctx.handle)
+        finally:
+            if streams is not None:
+                batch.close()
+        ng = int(n_groups.value)
+        out = (values[:ng].copy(), group_of[:n_pairs].copy(), entries[:ng].copy(), nans[:ng].copy())
+        if not strict:
+            return out + (status[:ng].copy(),)
+        bad = np.argwhere(status[:ng] != _lib.APD_OK)
+        if len(bad):
+            g, q = (int(v) for v in bad[0])
+            raise _lib.ApdError(int(status[g, q]), "score_quantiles: perc %r of group %d (%d entries, %d NaN) lies beyond its scores"
+                                % (float(pc[q]), g, int(entries[g]), int(nans[g])))
+        return out
+
+    def spot_thresholds(self, pairs, params, rate, by="pair", streams=None, per_query=False):
+        """Detection thresholds from the data: the `rate` quantile of the scores of every pair's group (score_quantiles, strict).
+        Returns one float32 per pair, values[group_of[p], 0] -- what detect(pairs, params, thresholds) takes.  With by="query" and
+        per_query=True: one value per distinct query in order of first appearance -- the vector SpotStream.detect takes when the
+        queries are listed in that order."""
+        if per_query and by != "query":
+            raise ValueError("per_query=True needs by=\"query\"")
+        values, group_of, _, _ = self.score_quantiles(pairs, params, float(rate), by=by, streams=streams)
+        return values[:, 0].copy() if per_query else values[group_of.astype(np.int64), 0]
+
     def spot_paths(self, pairs, windows, params, streams=None):
         """Warping paths of spotted windows (include/apd.h, "warping paths of spotted windows"): window k is columns windows[k]["start"]
         .. windows[k]["end"] of the stream of pairs[k] = (query, stream) -- `windows` a SPOT_BEST array of len(pairs) records, as

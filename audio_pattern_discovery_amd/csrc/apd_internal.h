@@ -391,6 +391,40 @@ hipError_t launch_spot_detect(const SpotDetectLaunch &L, uint32_t m_max, hipStre
 // d_hits[0 .. n_write): the chunk's first n_write hits, group-major
 hipError_t launch_spot_detect_emit(const SpotDetectLaunch &L, apd_spot_hit *d_hits, uint64_t n_write, hipStream_t stream);
 
+// ---- spot score quantiles (dtw_spot_quantile.hip): a radix select over spot_score_key on the curves launch_spot left in the
+// workspace.  A chunk holds whole groups; its pairs are numbered group by group, so a group's curve entries are one stretch.
+constexpr uint32_t kSpotQuantileColumns = 256;      // columns a workgroup of the pass kernel takes per step (its work-items)
+constexpr uint32_t kSpotQuantileBins = 257;         // the 256 digits of a pass, and the NaN scores
+constexpr uint32_t kSpotQuantileWorkgroups = 2048;  // workgroups of a pass the column blocks are chosen to reach (spot_quantile_blocks)
+struct SpotQuantilePair {
+    uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
+    uint32_t m, n;         // frames of the stream and of the query
+    uint32_t group;        // of the chunk
+    uint32_t pad;
+};
+// One (group, quantile) of a chunk between the passes: uploaded with rank = k and zeros.
+struct SpotQuantileState {
+    uint64_t rank;         // the rank left among the keys that match `prefix` under `mask`
+    uint32_t prefix, mask; // the digits found so far, in place
+    int32_t verdict;       // APD_OK, or APD_ERR_INDEX once k proved to lie beyond the non-NaN scores
+    uint32_t pad;
+};
+struct SpotQuantileLaunch {
+    const float *d_cost;
+    const uint32_t *d_start;
+    const SpotQuantilePair *d_pairs;
+    uint32_t n_pairs;
+    uint32_t n_groups, n_perc;
+    SpotQuantileState *d_state;          // [n_groups][n_perc]
+    unsigned long long *d_hist;          // [n_groups][n_perc][kSpotQuantileBins], zeroed by the caller; zero again afterwards
+    float *d_values;                     // [n_groups][n_perc]
+    int32_t *d_status;                   // [n_groups][n_perc]
+    unsigned long long *d_nans;          // [n_groups]
+};
+uint32_t spot_quantile_blocks(uint32_t n_pairs, uint32_t m_max);
+// the four passes; m_max: the longest stream among the pairs
+hipError_t launch_spot_quantiles(const SpotQuantileLaunch &L, uint32_t m_max, hipStream_t stream);
+
 // ---- streaming spotting (dtw_spot_stream.hip): the sweep above entered and left in mid-stream.  A session (apd_spot_stream) keeps,
 // per pair p = channel n_queries + q, the last pushed column of the table and the running best on the device; a push sweeps every
 // channel's chunk from there.  Query rows come from the templates' batch, stream columns from the session's staging buffer.

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <vector>
 
 #pragma GCC visibility push(hidden)   // internal to libapd_hip.so: nothing here joins its exported symbols
 namespace apd {
@@ -50,6 +51,40 @@ struct ClassBuckets {
         for (uint32_t c = 0; c < K; ++c) next[c] = first[c];
     }
     uint64_t slot(uint32_t c) { return next[c]++; }
+};
+
+// The groups of a pair list (apd_spot_detect, apd_spot_quantiles).  number_by_first_appearance: item i of `n` has key keys[i * stride]
+// (< n_keys); group_of[i] = the rank of its key among the distinct keys in order of first appearance; returns their number.
+inline uint64_t number_by_first_appearance(const uint32_t *keys, size_t stride, uint64_t n, uint32_t n_keys, std::vector<uint64_t> &group_of)
+{
+    std::vector<uint64_t> group_of_key(n_keys, ~0ull);
+    uint64_t ng = 0;
+    group_of.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t &g = group_of_key[keys[i * stride]];
+        if (g == ~0ull) g = ng++;
+        group_of[i] = g;
+    }
+    return ng;
+}
+// members[first[g] .. first[g + 1]): the items of group g, ascending (a counting sort of group_of).
+struct GroupMembers {
+    std::vector<uint64_t> first, members;
+    // false, with nothing usable built: some group holds more than max_items items
+    bool build(const std::vector<uint64_t> &group_of, uint64_t n_groups, uint64_t max_items)
+    {
+        first.assign(n_groups + 1, 0);
+        for (uint64_t g : group_of) ++first[g + 1];
+        for (uint64_t g = 0; g < n_groups; ++g) {
+            if (first[g + 1] > max_items) return false;
+            first[g + 1] += first[g];
+        }
+        std::vector<uint64_t> fill(first.begin(), first.end() - 1);
+        members.resize(group_of.size());
+        for (uint64_t i = 0; i < group_of.size(); ++i) members[fill[group_of[i]]++] = i;
+        return true;
+    }
+    uint64_t size(uint64_t g) const { return first[g + 1] - first[g]; }
 };
 
 // Cap of a chunk's device workspace in bytes: the environment variable (APD_PATH_WORKSPACE_BYTES, APD_SPOT_WORKSPACE_BYTES) when it

@@ -144,34 +144,20 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
     for (uint64_t p = 0; p < n_pairs; ++p)
         if ((rc = spot_check_lengths(ctx, "apd_spot_detect", idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1])))) return rc;
     // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
-    std::vector<uint64_t> group_of(n_pairs), member_first, members(n_pairs);
-    uint64_t ng = 0;
-    if (compete == APD_DETECT_PER_PAIR) {
-        ng = n_pairs;
+    std::vector<uint64_t> group_of(n_pairs);
+    uint64_t ng = n_pairs;
+    if (compete == APD_DETECT_PER_PAIR)
         for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
-    } else {
-        std::vector<uint64_t> group_of_stream(n_seq, ~0ull);
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            uint64_t &g = group_of_stream[pairs[2 * p + 1]];
-            if (g == ~0ull) g = ng++;
-            group_of[p] = g;
-        }
+    else
+        ng = number_by_first_appearance(pairs + 1, 2, n_pairs, n_seq, group_of);
+    GroupMembers groups;
+    if (!groups.build(group_of, ng, kMaxPairsPerLaunch)) {
+        ctx->last_error = "apd_spot_detect: a group of more than 2^24 pairs";
+        return APD_ERR_UNSUPPORTED;
     }
-    member_first.assign(ng + 1, 0);
-    for (uint64_t p = 0; p < n_pairs; ++p) ++member_first[group_of[p] + 1];
-    for (uint64_t g = 0; g < ng; ++g) {
-        if (member_first[g + 1] > kMaxPairsPerLaunch) {
-            ctx->last_error = "apd_spot_detect: a group of more than 2^24 pairs";
-            return APD_ERR_UNSUPPORTED;
-        }
-        member_first[g + 1] += member_first[g];
-    }
-    {
-        std::vector<uint64_t> fill(member_first.begin(), member_first.end() - 1);
-        for (uint64_t p = 0; p < n_pairs; ++p) members[fill[group_of[p]]++] = p;
-    }
+    const std::vector<uint64_t> &member_first = groups.first, &members = groups.members;
     auto stream_len = [&](uint64_t g) { return (uint64_t)idx.len(pairs[2 * members[member_first[g]] + 1]); };
-    auto group_pairs = [&](uint64_t g) { return member_first[g + 1] - member_first[g]; };
+    auto group_pairs = [&](uint64_t g) { return groups.size(g); };
     *n_groups = ng;
     HIP_TRY(ctx, bind_device(ctx));
     APD_AFFINITY(ctx, "spot detect launch");
@@ -271,6 +257,135 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
         g0 = g1;
     }
     *n_hits = hit_off[ng];
+    return APD_OK;
+}
+
+// ----------------------------------------------------------------------------------- spot score quantiles
+
+// apd_spot's sweep into the workspace, then the radix select of every (group, quantile) on the device (kernels:
+// dtw_spot_quantile.hip).  A chunk is a run of whole groups; its pairs are numbered group by group.  The rank k of every (group,
+// quantile) is worked out here from the group's entries and uploaded with its state record.
+extern "C" int apd_spot_quantiles(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+                                  int grouping, const float *perc, uint32_t n_perc, float *values, int32_t *status, uint64_t *group_of_out,
+                                  uint64_t *entries_out, uint64_t *nans_out, uint64_t *n_groups)
+{
+    if (!ctx || !batch || !cfg || batch->ctx != ctx || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
+    if (grouping < APD_QUANTILES_PER_PAIR || grouping > APD_QUANTILES_ALL || n_perc == 0 || n_perc > APD_SPOT_QUANTILES_MAX || !perc || !values ||
+        !n_groups)
+        return APD_ERR_INVALID_ARG;
+    const uint32_t n_seq = batch->n_seq;
+    const ResidentIndex idx(batch);
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
+    int rc = check_lengths(batch);
+    if (rc) return rc;
+    if (n_pairs == 0) { *n_groups = 0; return APD_OK; }
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if ((rc = spot_check_lengths(ctx, "apd_spot_quantiles", idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1])))) return rc;
+    // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
+    std::vector<uint64_t> group_of(n_pairs, 0);                           // APD_QUANTILES_ALL: every pair in group 0
+    uint64_t ng = 1;
+    if (grouping == APD_QUANTILES_PER_PAIR) {
+        ng = n_pairs;
+        for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
+    } else if (grouping == APD_QUANTILES_PER_QUERY) {
+        ng = number_by_first_appearance(pairs, 2, n_pairs, n_seq, group_of);
+    }
+    GroupMembers groups;
+    if (!groups.build(group_of, ng, kMaxPairsPerLaunch)) {
+        ctx->last_error = "apd_spot_quantiles: a group of more than 2^24 pairs";
+        return APD_ERR_UNSUPPORTED;
+    }
+    const std::vector<uint64_t> &member_first = groups.first, &members = groups.members;
+    std::vector<uint64_t> group_entries(ng, 0);
+    for (uint64_t p = 0; p < n_pairs; ++p) group_entries[group_of[p]] += idx.len(pairs[2 * p + 1]);
+    auto group_pairs = [&](uint64_t g) { return groups.size(g); };
+    *n_groups = ng;
+    if (group_of_out) std::copy(group_of.begin(), group_of.end(), group_of_out);
+    if (entries_out) std::copy(group_entries.begin(), group_entries.end(), entries_out);
+    HIP_TRY(ctx, bind_device(ctx));
+    APD_AFFINITY(ctx, "spot quantiles launch");
+    ChunkBudget budget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch};
+    constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t);
+    constexpr uint64_t kPairBytes = sizeof(SpotPair) + sizeof(SpotQuantilePair) + sizeof(apd_spot_best);
+    const uint64_t group_bytes = (uint64_t)n_perc * (kSpotQuantileBins * sizeof(unsigned long long) + sizeof(SpotQuantileState) + 8);
+    std::vector<char> upload, results;
+    std::vector<uint64_t> slot_pair;                                      // the caller's pair of every pair of the chunk
+    for (uint64_t g0 = 0; g0 < ng;) {
+        // the chunk of groups [g0, g1): at least one, then as many as keep the curves, the pairs' records and the histograms under the cap
+        uint64_t g1 = g0, entries = 0;
+        budget.reset();
+        while (g1 < ng && budget.admit(group_entries[g1] * kEntryBytes + group_pairs(g1) * kPairBytes + group_bytes, 0, group_pairs(g1))) entries += group_entries[g1++];
+        const uint64_t ngc = g1 - g0, np = budget.items, nq = n_perc;
+        // ws_spot: the curves; what is uploaded -- the sweep's pairs by kernel class, the select's pairs, the states --; the bests; what
+        // is zeroed -- the histograms --; what is read back -- values, statuses, NaN counts
+        Carve ws;
+        const size_t o_cost = ws.take<float>(entries), o_start = ws.take<uint32_t>(entries);
+        const size_t o_desc = ws.take<SpotPair>(np), o_qp = ws.take<SpotQuantilePair>(np), o_state = ws.take<SpotQuantileState>(ngc * nq);
+        const size_t o_best = ws.take<apd_spot_best>(np);
+        const size_t o_hist = ws.take<unsigned long long>(ngc * nq * kSpotQuantileBins);
+        const size_t o_values = ws.take<float>(ngc * nq), o_status = ws.take<int32_t>(ngc * nq), o_nans = ws.take<unsigned long long>(ngc);
+        upload.assign(o_best - o_desc, 0);
+        SpotPair *desc = (SpotPair *)upload.data();
+        SpotQuantilePair *qp = (SpotQuantilePair *)(upload.data() + (o_qp - o_desc));
+        SpotQuantileState *state = (SpotQuantileState *)(upload.data() + (o_state - o_desc));
+        slot_pair.resize(np);
+        SpotClasses classes;
+        uint32_t m_max = 1;
+        uint64_t k = 0, off = 0;
+        for (uint64_t g = g0; g < g1; ++g) {
+            for (uint32_t q = 0; q < n_perc; ++q) state[(g - g0) * nq + q].rank = percentile_index(group_entries[g], perc[q]);
+            for (uint64_t t = member_first[g]; t < member_first[g + 1]; ++t, ++k) {
+                const uint64_t p = members[t];
+                SpotQuantilePair &d = qp[k];
+                d.curve_off = off; d.m = idx.len(pairs[2 * p + 1]); d.n = idx.len(pairs[2 * p]); d.group = (uint32_t)(g - g0);
+                slot_pair[k] = p;
+                off += d.m;
+                m_max = std::max(m_max, d.m);
+                classes.add(batch->dim, d.n);
+            }
+        }
+        classes.close();
+        for (k = 0; k < np; ++k) {
+            const uint64_t p = slot_pair[k];
+            desc[classes.slot(spot_row_class(batch->dim, qp[k].n))] = SpotPair{idx.pos[pairs[2 * p]], idx.pos[pairs[2 * p + 1]], (uint32_t)k, 0, qp[k].curve_off};
+        }
+        rc = reserve_ws(ctx, ctx->ws_spot, ws.size);
+        if (rc) return rc;
+        char *base = ctx->ws_spot.as<char>();
+        SpotLaunch L{};
+        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
+        L.d_cost = (float *)(base + o_cost);
+        L.d_start = (uint32_t *)(base + o_start);
+        const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
+        L.d_best = (apd_spot_best *)(base + o_best);
+        SpotQuantileLaunch Q{};
+        Q.d_cost = L.d_cost; Q.d_start = L.d_start;
+        Q.d_pairs = (const SpotQuantilePair *)(base + o_qp); Q.n_pairs = (uint32_t)np;
+        Q.n_groups = (uint32_t)ngc; Q.n_perc = n_perc;
+        Q.d_state = (SpotQuantileState *)(base + o_state);
+        Q.d_hist = (unsigned long long *)(base + o_hist);
+        Q.d_values = (float *)(base + o_values);
+        Q.d_status = (int32_t *)(base + o_status);
+        Q.d_nans = (unsigned long long *)(base + o_nans);
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(base + o_hist, 0, o_values - o_hist, ctx->stream));
+        if (ctx->timing && g0 == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        for (uint32_t c = 0; c < kSpotClasses; ++c) {
+            L.d_pairs = d_desc + classes.first[c];
+            L.n_pairs = (uint32_t)classes.n[c];
+            HIP_TRY(ctx, launch_spot(L, c, classes.r_max, ctx->stream));
+        }
+        HIP_TRY(ctx, launch_spot_quantiles(Q, m_max, ctx->stream));
+        if (ctx->timing && g1 == ng) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        results.resize(ws.size - o_values);
+        HIP_TRY(ctx, hipMemcpyAsync(results.data(), base + o_values, results.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `upload`)
+        std::memcpy(values + g0 * nq, results.data(), (size_t)(ngc * nq) * sizeof(float));
+        if (status) std::memcpy(status + g0 * nq, results.data() + (o_status - o_values), (size_t)(ngc * nq) * sizeof(int32_t));
+        if (nans_out) std::memcpy(nans_out + g0, results.data() + (o_nans - o_values), (size_t)ngc * sizeof(uint64_t));
+        g0 = g1;
+    }
     return APD_OK;
 }
 

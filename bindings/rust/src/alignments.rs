@@ -201,6 +201,58 @@ pub fn detect(templates: &[NDSequence], streams: &[NDSequence], params: &Discove
     (hits, hit_off)
 }
 
+/// Not in the reference: spot score quantiles, the thresholds of detect() from the data.  Every template against every stream on the
+/// first device of APD_DEVICES (apd_batch_join + apd_spot_quantiles), pair p = t * streams.len() + r as for spot().  grouping:
+/// APD_QUANTILES_PER_PAIR (group g = pair g), APD_QUANTILES_PER_QUERY (group g = template g, its scores pooled over every stream) or
+/// APD_QUANTILES_ALL (one group).  perc: 1 .. APD_SPOT_QUANTILES_MAX values.  Returns (values [groups][perc.len()]: numerics::percentile
+/// of the group's scores, NaN where the index lies beyond its non-NaN scores; status [groups][perc.len()]: 0 or APD_ERR_INDEX there;
+/// entries and NaN scores of every group).
+pub fn score_quantiles(templates: &[NDSequence], streams: &[NDSequence], params: &Discovery, perc: &[f32], grouping: c_int)
+                       -> (Vec<f32>, Vec<i32>, Vec<u64>, Vec<u64>) {
+    let (n1, n2) = (templates.len(), streams.len());
+    if n1 == 0 || n2 == 0 { return (Vec::new(), Vec::new(), Vec::new(), Vec::new()); }
+    assert!(!perc.is_empty() && perc.len() <= APD_SPOT_QUANTILES_MAX, "1 .. APD_SPOT_QUANTILES_MAX quantiles");
+    let cfg = apd_align_config {
+        warping_band_percentage: params.warping_band_percentage, insertion_penalty: params.insertion_penalty,
+        deletion_penalty: params.deletion_penalty, match_penalty: params.match_penalty,
+    };
+    let pack = |set: &[NDSequence]| {
+        let mut offsets = vec![0u64; set.len() + 1];
+        let mut frames: Vec<f32> = Vec::new();
+        for (s, seq) in set.iter().enumerate() {
+            offsets[s + 1] = offsets[s] + seq.len() as u64;
+            frames.extend_from_slice(&seq.frames);
+        }
+        (frames, offsets)
+    };
+    let dim = templates[0].n_bins as u32;
+    let ((fa, oa), (fb, ob)) = (pack(templates), pack(streams));
+    let mut pairs: Vec<u32> = Vec::with_capacity(2 * n1 * n2);
+    for t in 0..n1 { for r in 0..n2 { pairs.push(t as u32); pairs.push((n1 + r) as u32); } }
+    let mut values = vec![0f32; n1 * n2 * perc.len()];
+    let mut status = vec![0i32; n1 * n2 * perc.len()];
+    let (mut entries, mut nans) = (vec![0u64; n1 * n2], vec![0u64; n1 * n2]);
+    let mut n_groups = 0u64;
+    unsafe {
+        let mut ctx = std::ptr::null_mut();
+        check(apd_create(devices()[0], &mut ctx));
+        let (mut a, mut b, mut j) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
+        check(apd_batch_create(ctx, fa.as_ptr(), oa.as_ptr(), n1 as u32, dim, 0, &mut a));
+        check(apd_batch_create(ctx, fb.as_ptr(), ob.as_ptr(), n2 as u32, dim, 0, &mut b));
+        check(apd_batch_join(ctx, a, b, &mut j));
+        let rc = apd_spot_quantiles(ctx, j, &cfg, pairs.as_ptr(), (n1 * n2) as u64, grouping, perc.as_ptr(), perc.len() as u32, values.as_mut_ptr(), status.as_mut_ptr(), std::ptr::null_mut(), entries.as_mut_ptr(), nans.as_mut_ptr(), &mut n_groups);
+        apd_destroy(ctx);                                                 // releases the device side of the three batches
+        for h in [j, b, a] { apd_batch_destroy(h); }
+        check(rc);
+    }
+    let ng = n_groups as usize;
+    values.truncate(ng * perc.len());
+    status.truncate(ng * perc.len());
+    entries.truncate(ng);
+    nans.truncate(ng);
+    (values, status, entries, nans)
+}
+
 /// Not in the reference: a streaming spotting session on the first device of APD_DEVICES (apd_spot_stream_*): every template against
 /// `channels` streams that arrive in chunks.  Pair p = channel * templates.len() + t; the curves of the pushes, one after the other,
 /// are apd_spot's curves of the whole stream, bit for bit, whatever the chunking.  Owns its context and the templates' batch.

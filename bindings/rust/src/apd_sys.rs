@@ -80,6 +80,10 @@ pub struct apd_spot_hit {
 }
 pub const APD_DETECT_PER_PAIR: c_int = 0;
 pub const APD_DETECT_PER_STREAM: c_int = 1;
+pub const APD_QUANTILES_PER_PAIR: c_int = 0;
+pub const APD_QUANTILES_PER_QUERY: c_int = 1;
+pub const APD_QUANTILES_ALL: c_int = 2;
+pub const APD_SPOT_QUANTILES_MAX: usize = 8;
 
 /// A window of stream y matched to query x (apd_spot_paths): end and start as in apd_spot_best.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
@@ -222,6 +226,10 @@ extern "C" {
     pub fn apd_spot_detect(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, pairs: *const u32, n_pairs: u64,
                            thresholds: *const f32, compete: c_int, hits: *mut apd_spot_hit, capacity: u64, hit_off: *mut u64,
                            n_groups: *mut u64, n_hits: *mut u64) -> c_int;
+    // spot score quantiles
+    pub fn apd_spot_quantiles(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, pairs: *const u32, n_pairs: u64,
+                              grouping: c_int, perc: *const f32, n_perc: u32, values: *mut f32, status: *mut i32, group_of: *mut u64,
+                              entries: *mut u64, nans: *mut u64, n_groups: *mut u64) -> c_int;
     // warping paths of spotted windows
     pub fn apd_spot_path_bound(n: u64, end: u64, start: u64) -> u64;
     pub fn apd_spot_paths(ctx: *mut apd_context, batch: *const apd_batch, cfg: *const apd_align_config, windows: *const apd_spot_window,

@@ -513,6 +513,47 @@ int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const apd_align_co
                     const float *thresholds, int compete, apd_spot_hit *hits, uint64_t capacity, uint64_t *hit_off,
                     uint64_t *n_groups, uint64_t *n_hits);
 
+/* ---- spot score quantiles: the thresholds of apd_spot_detect from the data, without the curves leaving the device ---------------
+ * "Each template fires on at most one column in a thousand of this background corpus": the 0.001 quantile of the template's scores
+ * over that corpus, which is numerics::percentile (numerics.rs:125-133) over a group of score curves.
+ * Table, curves, score: exactly apd_spot's -- free start, no band, ALWAYS the literal arithmetic (apd_set_distance_mode is not
+ * read); score(j) = cost / (float)(n + (j - start + 1)), one f32 division.
+ * Groups.  APD_QUANTILES_PER_PAIR: group g is pair g.  APD_QUANTILES_PER_QUERY: group g is the g-th distinct query number x in order
+ * of first appearance in `pairs`, and all pairs of the list with that x belong to it, adjacent in the list or not -- a template's
+ * scores pooled over every stream it is paired with.  APD_QUANTILES_ALL: one group, every pair of the list.
+ * Population of a group: one entry per stream column j = 1 .. m of every pair of the group (a column whose start is 0 included: its
+ * score is +INF or NaN); a repeated pair counts as often as it is listed.  entries[g] = sum of m over the group's pairs.
+ * Value (numerics.rs:125-133 on that population): NaN scores are dropped, nans[g] is their count; the others are ordered ascending
+ * by f32 <, +INF kept; the value is the element at k = (usize)((f32)entries[g] * perc[q]), an f32 product of the UNFILTERED length,
+ * truncated and saturating (a negative or NaN perc gives 0), as apd_percentile computes it.  -0.0 and +0.0 tie and come back as
+ * +0.0; otherwise the value is the bits of an element of the population.  It depends on nothing else -- not on the workspace cap,
+ * not on scheduling.
+ * A rank beyond the population, k >= entries[g] - nans[g] (the reference's numbers[n] panics, numerics.rs:132; every perc = 1.0
+ * ends so): status[g * n_perc + q] = APD_ERR_INDEX and values[g * n_perc + q] = NaN (0x7FC00000) -- a NaN threshold makes
+ * apd_spot_detect find nothing -- and the call still returns APD_OK, as apd_interesting_ranges_batch does for a recording that fails
+ * on its own.  Every other status is APD_OK.
+ * Output: values and status ([n_groups][n_perc]; n_pairs * n_perc slots always suffice; status may be NULL), group_of ([n_pairs]: the
+ * group of every pair; may be NULL), entries and nans ([n_groups], n_pairs slots suffice; either may be NULL), *n_groups.
+ * Errors, each before anything is launched or written: whatever apd_spot refuses, with its code (a pair index >= the batch's sequence
+ * count or a batch of another context APD_ERR_INVALID_ARG, an empty sequence in the batch APD_ERR_EMPTY_SEQUENCE, a query of more than
+ * 16 384 frames or a stream at apd_spot's limit APD_ERR_UNSUPPORTED); grouping other than 0, 1 or 2, n_perc == 0 or above
+ * APD_SPOT_QUANTILES_MAX, perc, values or n_groups NULL: APD_ERR_INVALID_ARG; a group of more than 2^24 pairs: APD_ERR_UNSUPPORTED.
+ * n_pairs == 0: zero groups, APD_OK.
+ * Follows apd_batch_refill.  Blocking.  With apd_set_timing on, apd_last_kernel_ms covers the sweep and the select kernels of the
+ * call (all chunks).
+ * Workspace: per curve entry 8 bytes of curves; per pair 64 bytes; per (group, quantile) a 257-bin 64-bit histogram and 32 bytes.  A
+ * long list is cut into chunks of WHOLE groups that keep this under 1 GiB (APD_SPOT_WORKSPACE_BYTES overrides the cap: tests
+ * only); a chunk holds at least one group even if that group alone exceeds the cap; results identical whatever the cap.
+ * APD_SPOT_QUANTILES_COLUMNS: the columns a workgroup of the select takes per step -- for tests that place stream lengths around it. */
+#define APD_QUANTILES_PER_PAIR  0   /* group g is pair g */
+#define APD_QUANTILES_PER_QUERY 1   /* group g: the g-th distinct query x in order of first appearance; all pairs with that x */
+#define APD_QUANTILES_ALL       2   /* one group: every pair of the list (zero groups if n_pairs == 0) */
+#define APD_SPOT_QUANTILES_MAX  8
+#define APD_SPOT_QUANTILES_COLUMNS 256
+int apd_spot_quantiles(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
+                       int grouping, const float *perc, uint32_t n_perc, float *values, int32_t *status, uint64_t *group_of,
+                       uint64_t *entries, uint64_t *nans, uint64_t *n_groups);
+
 /* ---- warping paths of spotted windows: which query frame was matched to which stream frame inside a window ----------------------
  * Table: exactly apd_spot's T and S -- free start, no band, always the literal arithmetic -- with every cell also remembering the
  * branch alignments.rs:153-159 took: DELETE from (i, j-1), INSERT from (i-1, j), MATCH from (i-1, j-1) otherwise.  Not a table of
