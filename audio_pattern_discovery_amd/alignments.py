@@ -1,6 +1,7 @@
 """Host mirror of src/alignments.rs (+ the NDSequence container of src/spectrogram.rs:13-24,99-101,
 152-154) over the C ABI of include/apd.h.  Names, argument meaning and error behaviour follow the
 Rust items; the compute is the HIP library, never Python."""
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -357,22 +358,32 @@ class AlignmentWorkers:
                                      lens.ctypes.data_as(u32p), scores.ctypes.data_as(C.POINTER(C.c_float))), self.ctx.handle)
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_pairs)], scores
 
+    @contextlib.contextmanager
+    def _pair_call(self, method, pairs, params, streams):
+        """What spot(), detect(), score_quantiles() and spot_paths() begin and end with: one context only; yields (cfg, pairs as
+        an (n, 2) uint32 array, the batch the pair numbers index -- this object's, or the two joined, closed on the way out)."""
+        if self._multi is not None or (streams is not None and streams._multi is not None):
+            raise ValueError("%s() runs on one context: make the AlignmentWorkers without `devices`" % method)
+        cfg = params.align_config()
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
+        try:
+            yield cfg, pr, batch
+        finally:
+            if streams is not None:
+                batch.close()
+
     def spot(self, pairs, params, curves=True, streams=None):
         """Subsequence alignment (include/apd.h, "subsequence alignment"): every (query, stream) pair of `pairs` -- this object's
         sequence numbers, or, with `streams` (an AlignmentWorkers of the same context), numbers of the two joined: below len(self.data)
         this object's, the others `streams`' -- params: Discovery (penalties only: there is no band).  Returns (list of (cost, start)
         arrays in input order, `best` as a SPOT_BEST array); the list is empty with curves=False: apd_spot."""
-        if self._multi is not None or (streams is not None and streams._multi is not None):
-            raise ValueError("spot() runs on one context: make the AlignmentWorkers without `devices`")
-        cfg = params.align_config()
-        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
-        n_pairs = len(pr)
-        L = _lib.lib()
-        off = np.zeros(n_pairs + 1, dtype=np.uint64)
-        best = np.zeros(n_pairs, dtype=SPOT_BEST)
-        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
-        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
-        try:
+        with self._pair_call("spot", pairs, params, streams) as (cfg, pr, batch):
+            n_pairs = len(pr)
+            L = _lib.lib()
+            off = np.zeros(n_pairs + 1, dtype=np.uint64)
+            best = np.zeros(n_pairs, dtype=SPOT_BEST)
+            u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
             head = (self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs)
             tail = (off.ctypes.data_as(u64p), best.ctypes.data_as(C.POINTER(_lib.SpotBest)))
             if not curves:
@@ -382,9 +393,6 @@ class AlignmentWorkers:
             cost = np.zeros(max(int(off[-1]), 1), dtype=np.float32)
             start = np.zeros(len(cost), dtype=np.uint32)
             _lib.check(L.apd_spot(*head, cost.ctypes.data_as(f32p), start.ctypes.data_as(u32p), len(cost), *tail), self.ctx.handle)
-        finally:
-            if streams is not None:
-                batch.close()
         return [(cost[int(off[p]):int(off[p + 1])].copy(), start[int(off[p]):int(off[p + 1])].copy()) for p in range(n_pairs)], best
 
     def detect(self, pairs, params, thresholds, per_stream=False, streams=None, capacity=None):
@@ -394,33 +402,25 @@ class AlignmentWorkers:
         (None: a bound that always suffices).  Returns (hits as a SPOT_HIT array, group-major; hit_off, groups + 1 entries; groups:
         the stream number of every group with per_stream, else its pair index): apd_spot_detect.  With a capacity below the total
         only the first `capacity` hits are returned; hit_off stays exact."""
-        if self._multi is not None or (streams is not None and streams._multi is not None):
-            raise ValueError("detect() runs on one context: make the AlignmentWorkers without `devices`")
-        cfg = params.align_config()
-        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
-        n_pairs = len(pr)
-        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (n_pairs,)))
-        if per_stream:
-            _, first = np.unique(pr[:, 1], return_index=True)
-            groups = pr[np.sort(first), 1].astype(np.uint32)              # distinct streams in order of first appearance
-        else:
-            groups = np.arange(n_pairs, dtype=np.uint32)
-        lens = [len(s.frames) for s in self.data] + ([len(s.frames) for s in streams.data] if streams is not None else [])
-        if capacity is None:
-            known = not n_pairs or int(pr.max()) < len(lens)             # a wrong index is the library's to refuse
-            capacity = int(sum(lens[int(y)] for y in (groups if per_stream else pr[:, 1]))) if known else 0
-        hits = np.zeros(max(int(capacity), 1), dtype=SPOT_HIT)
-        off = np.zeros(n_pairs + 1, dtype=np.uint64)
-        n_groups, n_hits = C.c_uint64(0), C.c_uint64(0)
-        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
-        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
-        try:
+        with self._pair_call("detect", pairs, params, streams) as (cfg, pr, batch):
+            n_pairs = len(pr)
+            thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (n_pairs,)))
+            if per_stream:
+                _, first = np.unique(pr[:, 1], return_index=True)
+                groups = pr[np.sort(first), 1].astype(np.uint32)          # distinct streams in order of first appearance
+            else:
+                groups = np.arange(n_pairs, dtype=np.uint32)
+            lens = [len(s.frames) for s in self.data] + ([len(s.frames) for s in streams.data] if streams is not None else [])
+            if capacity is None:
+                known = not n_pairs or int(pr.max()) < len(lens)         # a wrong index is the library's to refuse
+                capacity = int(sum(lens[int(y)] for y in (groups if per_stream else pr[:, 1]))) if known else 0
+            hits = np.zeros(max(int(capacity), 1), dtype=SPOT_HIT)
+            off = np.zeros(n_pairs + 1, dtype=np.uint64)
+            n_groups, n_hits = C.c_uint64(0), C.c_uint64(0)
+            u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
             _lib.check(_lib.lib().apd_spot_detect(self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs,
                                                   thr.ctypes.data_as(f32p), int(bool(per_stream)), hits.ctypes.data_as(C.POINTER(_lib.SpotHit)),
                                                   int(capacity), off.ctypes.data_as(u64p), C.byref(n_groups), C.byref(n_hits)), self.ctx.handle)
-        finally:
-            if streams is not None:
-                batch.close()
         return hits[:min(int(n_hits.value), int(capacity))].copy(), off[:n_groups.value + 1].copy(), groups
 
     def score_quantiles(self, pairs, params, perc, by="pair", streams=None, strict=True):
@@ -430,28 +430,20 @@ class AlignmentWorkers:
         (values [n_groups, n_perc] float32, group_of [n_pairs], entries [n_groups], nans [n_groups]): apd_spot_quantiles.  A rank
         beyond a group's non-NaN scores (every perc = 1.0) raises ApdError(APD_ERR_INDEX) with strict=True; with strict=False its value
         is NaN and the int32 status array [n_groups, n_perc] is returned as a fifth item."""
-        if self._multi is not None or (streams is not None and streams._multi is not None):
-            raise ValueError("score_quantiles() runs on one context: make the AlignmentWorkers without `devices`")
-        grouping = {"pair": _lib.APD_QUANTILES_PER_PAIR, "query": _lib.APD_QUANTILES_PER_QUERY, "all": _lib.APD_QUANTILES_ALL}[by]
-        cfg = params.align_config()
-        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
-        n_pairs = len(pr)
-        pc = np.ascontiguousarray(np.atleast_1d(np.asarray(perc, dtype=np.float32)))
-        slots = max(n_pairs, 1)
-        values = np.zeros((slots, len(pc)), dtype=np.float32)
-        status = np.zeros((slots, len(pc)), dtype=np.int32)
-        group_of, entries, nans = (np.zeros(slots, dtype=np.uint64) for _ in range(3))
-        n_groups = C.c_uint64(0)
-        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
-        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
-        try:
+        with self._pair_call("score_quantiles", pairs, params, streams) as (cfg, pr, batch):
+            grouping = {"pair": _lib.APD_QUANTILES_PER_PAIR, "query": _lib.APD_QUANTILES_PER_QUERY, "all": _lib.APD_QUANTILES_ALL}[by]
+            n_pairs = len(pr)
+            pc = np.ascontiguousarray(np.atleast_1d(np.asarray(perc, dtype=np.float32)))
+            slots = max(n_pairs, 1)
+            values = np.zeros((slots, len(pc)), dtype=np.float32)
+            status = np.zeros((slots, len(pc)), dtype=np.int32)
+            group_of, entries, nans = (np.zeros(slots, dtype=np.uint64) for _ in range(3))
+            n_groups = C.c_uint64(0)
+            u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
             _lib.check(_lib.lib().apd_spot_quantiles(self.ctx.handle, batch.handle, C.byref(cfg), pr.ctypes.data_as(u32p), n_pairs, grouping,
                                                      pc.ctypes.data_as(f32p), len(pc), values.ctypes.data_as(f32p),
                                                      status.ctypes.data_as(C.POINTER(C.c_int32)), group_of.ctypes.data_as(u64p),
                                                      entries.ctypes.data_as(u64p), nans.ctypes.data_as(u64p), C.byref(n_groups)), self.ctx.handle)
-        finally:
-            if streams is not None:
-                batch.close()
         ng = int(n_groups.value)
         out = (values[:ng].copy(), group_of[:n_pairs].copy(), entries[:ng].copy(), nans[:ng].copy())
         if not strict:
@@ -479,32 +471,24 @@ class AlignmentWorkers:
         spot()'s best or spot_hits() return them (a pair may appear many times, once per hit); numbering and `streams` as for spot().
         Returns (list of PATH_STEP arrays in input order -- empty for a {0, 0} record and for a start that is not the table's --,
         found_start, scores): apd_spot_paths."""
-        if self._multi is not None or (streams is not None and streams._multi is not None):
-            raise ValueError("spot_paths() runs on one context: make the AlignmentWorkers without `devices`")
-        cfg = params.align_config()
-        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
-        n_windows = len(pr)
-        if len(windows) != n_windows:
-            raise ValueError("one window per pair")
-        win = np.zeros(n_windows, dtype=SPOT_WINDOW)
-        win["x"], win["y"] = pr[:, 0], pr[:, 1]
-        win["end"], win["start"] = windows["end"], windows["start"]
-        L = _lib.lib()
-        off = np.zeros(n_windows + 1, dtype=np.uint64)
-        lens = np.zeros(n_windows, dtype=np.uint32)
-        found = np.zeros(n_windows, dtype=np.uint32)
-        scores = np.zeros(n_windows, dtype=np.float32)
-        u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
-        batch = self._batch if streams is None else Batch.join(self._batch, streams._batch)
-        try:
+        with self._pair_call("spot_paths", pairs, params, streams) as (cfg, pr, batch):
+            n_windows = len(pr)
+            if len(windows) != n_windows:
+                raise ValueError("one window per pair")
+            win = np.zeros(n_windows, dtype=SPOT_WINDOW)
+            win["x"], win["y"] = pr[:, 0], pr[:, 1]
+            win["end"], win["start"] = windows["end"], windows["start"]
+            L = _lib.lib()
+            off = np.zeros(n_windows + 1, dtype=np.uint64)
+            lens = np.zeros(n_windows, dtype=np.uint32)
+            found = np.zeros(n_windows, dtype=np.uint32)
+            scores = np.zeros(n_windows, dtype=np.float32)
+            u32p, u64p, f32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
             head = (self.ctx.handle, batch.handle, C.byref(cfg), win.ctypes.data_as(C.POINTER(_lib.SpotWindow)), n_windows)
             _lib.check(L.apd_spot_paths(*head, None, 0, off.ctypes.data_as(u64p), None, None, None), self.ctx.handle)       # sizes
             steps = np.zeros(max(int(off[-1]), 1), dtype=PATH_STEP)
             _lib.check(L.apd_spot_paths(*head, steps.ctypes.data_as(C.POINTER(_lib.PathStep)), len(steps), off.ctypes.data_as(u64p),
                                         lens.ctypes.data_as(u32p), found.ctypes.data_as(u32p), scores.ctypes.data_as(f32p)), self.ctx.handle)
-        finally:
-            if streams is not None:
-                batch.close()
         return [steps[int(off[p]):int(off[p]) + int(lens[p])].copy() for p in range(n_windows)], found, scores
 
     def spot_stream(self, queries, params, channels=1, history=0):

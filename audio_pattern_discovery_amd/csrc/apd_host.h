@@ -1,5 +1,6 @@
 // What the host drivers of the pair-list entry points share (apd_path_api.hip, apd_spot_api.hip, apd_spot_stream_api.hip): the
-// planning arithmetic of apd_plan.h and the few pieces that need the project's types.
+// planning arithmetic of apd_plan.h and the pieces that need the project's types -- among them CurveSweep, the one sweep of a chunk of
+// curves under apd_spot, apd_spot_detect and apd_spot_quantiles.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -44,6 +45,94 @@ struct SpotClasses : ClassBuckets<kSpotClasses> {
         count(c, items);
         if (c == 0) r_max = std::max(r_max, spot_rows_per_lane(n));
         return c;
+    }
+};
+
+// What apd_spot, apd_spot_detect and apd_spot_quantiles check of their list: the pairs name sequences of the batch, and its lengths
+// are sane; then, once the entry has answered what needs no launch, every pair's lengths in the entry's name.
+inline int check_pair_list(const apd_batch *batch, const uint32_t *pairs, uint64_t n_pairs)
+{
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] >= batch->n_seq || pairs[2 * p + 1] >= batch->n_seq) return APD_ERR_INVALID_ARG;
+    return check_lengths(batch);
+}
+inline int spot_check_pairs(apd_context *ctx, const char *entry, const ResidentIndex &idx, const uint32_t *pairs, uint64_t n_pairs)
+{
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (int rc = spot_check_lengths(ctx, entry, idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1]))) return rc;
+    return APD_OK;
+}
+
+// The first stage of apd_spot, apd_spot_detect and apd_spot_quantiles on one chunk of a GroupChunkPlan whose items are the
+// caller's pairs and whose lengths are their streams' frames: launch_spot once per kernel class, the curves of slot k at the plan's
+// offset, its best at L.d_best[k].  Per chunk, after next() has moved the plan to it, in this order:
+//   carve()   opens `ws`, the layout of ws_spot, with the sweep's regions: curves (none: best only), bests, and the descriptors
+//             last -- the records the caller takes next follow them in one host image, uploaded with one copy;
+//   place()   once those are taken: sizes the image up to the end of `ws` and puts the descriptors at its head, by class;
+//             record<T>(off) is where the caller's region at `off` lies in the image;
+//   run()     once the whole workspace is taken: reserves it, uploads the image, zeroes the stretch the caller names, opens the
+//             timing window at the list's first chunk and launches the sweep.  device<T>(off): a region on the device.
+// The caller's own stage follows, then the end of the timing window at the list's last chunk; a synchronisation ends the chunk (the
+// next one reuses the workspace and the image).
+struct CurveSweep {
+    apd_context *ctx;
+    const apd_batch *batch;
+    const apd_align_config *cfg;
+    const ResidentIndex &idx;
+    const uint32_t *pairs;
+    Carve ws{};
+    SpotClasses classes;
+    SpotLaunch L{};                   // d_cost, d_start (null: best only) and d_best: the chunk's, once run() has returned
+    std::vector<char> image;
+    bool curves = true;
+    size_t o_cost = 0, o_start = 0, o_best = 0, o_desc = 0;
+
+    uint32_t query_len(uint64_t p) const { return idx.len(pairs[2 * p]); }
+    uint32_t stream_len(uint64_t p) const { return idx.len(pairs[2 * p + 1]); }
+    // the record a second stage reads the slot's curves by
+    SpotCurve curve(const GroupChunkPlan::Slot &s) const { return {s.off, s.len, query_len(s.item), s.group, (uint32_t)s.item}; }
+    template <class Weight> bool next(GroupChunkPlan &plan, Weight group_bytes) const
+    {
+        return plan.next(group_bytes, [this](uint64_t p) { return stream_len(p); });
+    }
+    void carve(const GroupChunkPlan &plan, bool with_curves = true)
+    {
+        curves = with_curves;
+        ws = Carve();
+        o_cost = ws.take<float>(curves ? plan.entries : 0); o_start = ws.take<uint32_t>(curves ? plan.entries : 0);
+        o_best = ws.take<apd_spot_best>(plan.np()); o_desc = ws.take<SpotPair>(plan.np());
+    }
+    void place(const GroupChunkPlan &plan)
+    {
+        image.assign(ws.size - o_desc, 0);
+        classes = SpotClasses();
+        for (const auto &s : plan.slots) classes.add(batch->dim, query_len(s.item));
+        classes.close();
+        for (uint64_t k = 0; k < plan.np(); ++k) {
+            const auto &s = plan.slots[k];
+            record<SpotPair>(o_desc)[classes.slot(spot_row_class(batch->dim, query_len(s.item)))] =
+                SpotPair{idx.pos[pairs[2 * s.item]], idx.pos[pairs[2 * s.item + 1]], (uint32_t)k, 0, s.off};
+        }
+    }
+    template <class T> T *record(size_t off) { return (T *)(image.data() + (off - o_desc)); }
+    template <class T> T *device(size_t off) const { return (T *)(ctx->ws_spot.as<char>() + off); }
+    int run(const GroupChunkPlan &plan, size_t zero_off = 0, size_t zero_bytes = 0)
+    {
+        if (int rc = reserve_ws(ctx, ctx->ws_spot, ws.size)) return rc;
+        L = SpotLaunch{};
+        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
+        L.d_cost = curves ? device<float>(o_cost) : nullptr;
+        L.d_start = curves ? device<uint32_t>(o_start) : nullptr;
+        L.d_best = device<apd_spot_best>(o_best);
+        HIP_TRY(ctx, hipMemcpyAsync(device<char>(o_desc), image.data(), image.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (zero_bytes) HIP_TRY(ctx, hipMemsetAsync(device<char>(zero_off), 0, zero_bytes, ctx->stream));
+        if (ctx->timing && plan.g0 == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        for (uint32_t c = 0; c < kSpotClasses; ++c) {
+            L.d_pairs = device<SpotPair>(o_desc) + classes.first[c];
+            L.n_pairs = (uint32_t)classes.n[c];
+            HIP_TRY(ctx, launch_spot(L, c, classes.r_max, ctx->stream));
+        }
+        return APD_OK;
     }
 };
 

@@ -355,17 +355,25 @@ void spot_debug_line(const char *kind, int rt, int d, uint32_t n_pairs, uint32_t
 // The pairs of L all have row class `rt`; r_max: the most rows per lane among them (class 0: sizes the LDS).
 hipError_t launch_spot(const SpotLaunch &L, uint32_t rt, uint32_t r_max, hipStream_t stream);
 
-// ---- spot detection (dtw_spot_detect.hip): candidates and greedy non-overlapping picking on the curves launch_spot left in the
-// workspace.  A chunk holds whole groups; its pairs are numbered group by group (a group's pairs adjacent, in the caller's order), so
-// a group's curve entries are one stretch and its candidate list -- one 16-byte slot per entry at most -- lies at the same offset.
-struct SpotDetectPair {
+// ---- the curves of a chunk (apd_spot_detect, apd_spot_quantiles): what launch_spot left in the workspace, read again by a second
+// stage.  A chunk holds whole groups; its pairs are numbered group by group (a group's pairs adjacent, in the caller's order:
+// GroupChunkPlan, apd_plan.h), so a group's curve entries are one stretch.  The column walk over a record: dtw_spot_curves.h.
+struct SpotCurve {
     uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
     uint32_t m, n;         // frames of the stream and of the query
-    float threshold;
     uint32_t group;        // of the chunk
     uint32_t pair;         // the caller's index into `pairs`
+};
+static_assert(sizeof(SpotCurve) == 24, "include/apd.h states the workspace weights of apd_spot_quantiles: 64 bytes per pair");
+
+// ---- spot detection (dtw_spot_detect.hip): candidates and greedy non-overlapping picking on the curves.  A group's candidate list
+// -- one 16-byte slot per entry at most -- lies at the offset of its curve entries.
+struct SpotDetectPair {
+    SpotCurve curve;
+    float threshold;
     uint32_t pad;
 };
+static_assert(sizeof(SpotDetectPair) == 32, "a detection record is the curve record, the threshold and a pad");
 struct SpotDetectGroup {
     uint64_t cand_off;     // first slot of the group's candidate list in d_cand = first curve entry of its first pair
     uint64_t cand_cap;     // its slots: the group's curve entries
@@ -391,17 +399,10 @@ hipError_t launch_spot_detect(const SpotDetectLaunch &L, uint32_t m_max, hipStre
 // d_hits[0 .. n_write): the chunk's first n_write hits, group-major
 hipError_t launch_spot_detect_emit(const SpotDetectLaunch &L, apd_spot_hit *d_hits, uint64_t n_write, hipStream_t stream);
 
-// ---- spot score quantiles (dtw_spot_quantile.hip): a radix select over spot_score_key on the curves launch_spot left in the
-// workspace.  A chunk holds whole groups; its pairs are numbered group by group, so a group's curve entries are one stretch.
+// ---- spot score quantiles (dtw_spot_quantile.hip): a radix select over spot_score_key on the curves; its pairs are SpotCurve records.
 constexpr uint32_t kSpotQuantileColumns = 256;      // columns a workgroup of the pass kernel takes per step (its work-items)
 constexpr uint32_t kSpotQuantileBins = 257;         // the 256 digits of a pass, and the NaN scores
 constexpr uint32_t kSpotQuantileWorkgroups = 2048;  // workgroups of a pass the column blocks are chosen to reach (spot_quantile_blocks)
-struct SpotQuantilePair {
-    uint64_t curve_off;    // first entry of the pair's curves in d_cost / d_start
-    uint32_t m, n;         // frames of the stream and of the query
-    uint32_t group;        // of the chunk
-    uint32_t pad;
-};
 // One (group, quantile) of a chunk between the passes: uploaded with rank = k and zeros.
 struct SpotQuantileState {
     uint64_t rank;         // the rank left among the keys that match `prefix` under `mask`
@@ -412,7 +413,7 @@ struct SpotQuantileState {
 struct SpotQuantileLaunch {
     const float *d_cost;
     const uint32_t *d_start;
-    const SpotQuantilePair *d_pairs;
+    const SpotCurve *d_pairs;
     uint32_t n_pairs;
     uint32_t n_groups, n_perc;
     SpotQuantileState *d_state;          // [n_groups][n_perc]
@@ -769,7 +770,7 @@ struct apd_context {
     apd::DeviceBuf ws_path_dirs;      // apd_align_paths, apd_barycenters: direction words of a chunk of pairs
     apd::DeviceBuf ws_path_steps;     // ... its steps, descriptors and results
     apd::DeviceBuf ws_bary;           // apd_barycenters: the barycenters, their sums and counts, the plan of every chunk
-    apd::DeviceBuf ws_spot;           // apd_spot, apd_spot_detect: curves, descriptors and results of a chunk of pairs
+    apd::DeviceBuf ws_spot;           // CurveSweep (apd_host.h): curves, descriptors and results of a chunk of pairs
     apd::DeviceBuf ws_spot_hits;      // apd_spot_detect: the packed hits of a chunk
     apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
     apd::DeviceBuf ws_spot_steps;     // apd_spot_paths, apd_spot_stream_paths: steps, descriptors and results of a chunk of windows

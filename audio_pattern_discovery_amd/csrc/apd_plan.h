@@ -1,6 +1,7 @@
 // Planning arithmetic of the host drivers (apd_path_api.hip, apd_spot_api.hip, apd_spot_stream_api.hip): where the regions of a
-// workspace lie, where a chunk of a work list ends, where the descriptors of a kernel class go.  Plain C++17 and no project types:
-// tests/cpp/plan_check.cpp checks every piece against its definition on the host.
+// workspace lie, where a chunk of a work list ends, where the descriptors of a kernel class go, how a grouped pair list is cut
+// into chunks of whole groups and numbered inside them.  Plain C++17 and no project types: tests/cpp/plan_check.cpp and
+// tests/cpp/group_check.cpp check every piece against its definition on the host.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -85,6 +86,50 @@ struct GroupMembers {
         return true;
     }
     uint64_t size(uint64_t g) const { return first[g + 1] - first[g]; }
+};
+
+// The cut of a grouped list into chunks of whole groups, and the numbering inside a chunk: what apd_spot, apd_spot_detect and
+// apd_spot_quantiles plan before they sweep (CurveSweep, apd_host.h).  next() moves to the chunk of groups [g0, g1) -- the first
+// group whatever weight(g) bytes it weighs, then every further one that keeps the bytes and the items within the budget -- and
+// numbers its items group by group, members ascending: slot k holds the caller's item, its group of the chunk (g - g0), its length
+// length(item) and its offset, the sum of the lengths before it.  entries: the sum of all; max_len: the longest.
+struct GroupChunkPlan {
+    struct Slot {
+        uint64_t item, off;
+        uint32_t group, len;
+    };
+    const GroupMembers *groups;       // null: n_groups groups of one, group g = item g
+    uint64_t n_groups;
+    ChunkBudget budget;
+    uint64_t g0 = 0, g1 = 0, entries = 0;
+    uint32_t max_len = 0;
+    std::vector<Slot> slots;
+
+    GroupChunkPlan(const GroupMembers &members, ChunkBudget b) : groups(&members), n_groups(members.first.size() - 1), budget(b) {}
+    GroupChunkPlan(uint64_t n_singletons, ChunkBudget b) : groups(nullptr), n_groups(n_singletons), budget(b) {}
+    uint64_t np() const { return slots.size(); }
+    // false: the list is used up
+    template <class Weight, class Length> bool next(Weight weight, Length length)
+    {
+        g0 = g1;
+        if (g0 == n_groups) return false;
+        budget.reset();
+        slots.clear();
+        entries = 0;
+        max_len = 0;
+        while (g1 < n_groups && budget.admit(weight(g1), 0, groups ? groups->size(g1) : 1)) {
+            const uint64_t t0 = groups ? groups->first[g1] : g1, t1 = groups ? groups->first[g1 + 1] : g1 + 1;
+            for (uint64_t t = t0; t < t1; ++t) {
+                const uint64_t item = groups ? groups->members[t] : t;
+                const uint32_t len = length(item);
+                slots.push_back(Slot{item, entries, (uint32_t)(g1 - g0), len});
+                entries += len;
+                max_len = len > max_len ? len : max_len;
+            }
+            ++g1;
+        }
+        return true;
+    }
 };
 
 // Cap of a chunk's device workspace in bytes: the environment variable (APD_PATH_WORKSPACE_BYTES, APD_SPOT_WORKSPACE_BYTES) when it

@@ -1,5 +1,8 @@
-// C ABI of libapd_hip.so (include/apd.h): subsequence alignment over pair lists -- curves and bests, detection, the warping paths
-// of spotted windows.  The host side around dtw_spot.hip, dtw_spot_detect.hip and dtw_spot_path.hip.
+// C ABI of libapd_hip.so (include/apd.h): subsequence alignment over pair lists -- curves and bests, detection, score quantiles, the
+// warping paths of spotted windows.  The host side around dtw_spot.hip, dtw_spot_detect.hip, dtw_spot_quantile.hip and
+// dtw_spot_path.hip.  apd_spot, apd_spot_detect and apd_spot_quantiles are one plan and one sweep -- GroupChunkPlan (apd_plan.h) cuts
+// the list into chunks of whole groups and numbers a chunk's pairs, CurveSweep (apd_host.h) lays out, uploads and launches
+// launch_spot -- and then each its own stage on the curves: the read-back, the detector, the select.
 #include <cstring>
 #include <map>
 #include <new>
@@ -14,69 +17,33 @@ extern "C" int apd_spot(apd_context *ctx, const apd_batch *batch, const apd_alig
 {
     if (!ctx || !batch || !cfg || batch->ctx != ctx || !curve_off || (n_pairs && !pairs)) return APD_ERR_INVALID_ARG;
     if ((cost == nullptr) != (start == nullptr)) return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
     const ResidentIndex idx(batch);
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
+    int rc = check_pair_list(batch, pairs, n_pairs);
     if (rc) return rc;
+    CurveSweep sweep{ctx, batch, cfg, idx, pairs};
     curve_off[0] = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) curve_off[p + 1] = curve_off[p] + idx.len(pairs[2 * p + 1]);
+    for (uint64_t p = 0; p < n_pairs; ++p) curve_off[p + 1] = curve_off[p] + sweep.stream_len(p);
     const bool curves = cost != nullptr;
     if (!curves && !best) return APD_OK;                                  // sizes only
     if (curves && capacity < curve_off[n_pairs]) return APD_ERR_INVALID_ARG;
     if (n_pairs == 0) return APD_OK;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if ((rc = spot_check_lengths(ctx, "apd_spot", idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1])))) return rc;
+    if ((rc = spot_check_pairs(ctx, "apd_spot", idx, pairs, n_pairs))) return rc;
     HIP_TRY(ctx, bind_device(ctx));
     APD_AFFINITY(ctx, "spot launch");
-    ChunkBudget budget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch};
-    std::vector<apd_spot_best> best_sink;
-    if (!best) best_sink.resize(n_pairs);
-    apd_spot_best *h_best = best ? best : best_sink.data();
-    std::vector<SpotPair> desc;
-    for (uint64_t first = 0; first < n_pairs;) {
-        // the chunk [first, last): at least one pair, then as many as keep the curves under the cap (best only: nothing is stored)
-        uint64_t last = first;
-        budget.reset();
-        while (last < n_pairs && budget.admit(curves ? (curve_off[last + 1] - curve_off[last]) * (sizeof(float) + sizeof(uint32_t)) : 0)) ++last;
-        const uint64_t np = last - first;
-        // the chunk's descriptors, grouped by kernel class (one launch each); `out` keeps the input order
-        SpotClasses classes;
-        for (uint64_t p = first; p < last; ++p) classes.add(batch->dim, idx.len(pairs[2 * p]));
-        classes.close();
-        desc.resize(np);
-        for (uint64_t p = first; p < last; ++p)
-            desc[classes.slot(spot_row_class(batch->dim, idx.len(pairs[2 * p])))] =
-                SpotPair{idx.pos[pairs[2 * p]], idx.pos[pairs[2 * p + 1]], (uint32_t)(p - first), 0, curve_off[p] - curve_off[first]};
-        const size_t curve_floats = curves ? (size_t)(curve_off[last] - curve_off[first]) : 0;
-        Carve ws;
-        const size_t o_cost = ws.take<float>(curve_floats), o_start = ws.take<uint32_t>(curve_floats);
-        const size_t o_desc = ws.take<SpotPair>(np), o_best = ws.take<apd_spot_best>(np);
-        rc = reserve_ws(ctx, ctx->ws_spot, ws.size);
-        if (rc) return rc;
-        char *base = ctx->ws_spot.as<char>();
-        SpotLaunch L{};
-        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
-        L.d_cost = curves ? (float *)(base + o_cost) : nullptr;
-        L.d_start = curves ? (uint32_t *)(base + o_start) : nullptr;
-        const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
-        L.d_best = (apd_spot_best *)(base + o_best);
-        HIP_TRY(ctx, hipMemcpyAsync((void *)d_desc, desc.data(), (size_t)np * sizeof(SpotPair), hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->timing && first == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (uint32_t c = 0; c < kSpotClasses; ++c) {
-            L.d_pairs = d_desc + classes.first[c];
-            L.n_pairs = (uint32_t)classes.n[c];
-            HIP_TRY(ctx, launch_spot(L, c, classes.r_max, ctx->stream));
+    // every pair its own group; a chunk: as many as keep the curves under the cap (best only: nothing is stored)
+    constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t);
+    GroupChunkPlan plan(n_pairs, ChunkBudget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch});
+    while (sweep.next(plan, [&](uint64_t p) { return curves ? sweep.stream_len(p) * kEntryBytes : 0; })) {
+        sweep.carve(plan, curves);
+        sweep.place(plan);
+        if ((rc = sweep.run(plan))) return rc;
+        if (ctx->timing && plan.g1 == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        if (curves) {
+            HIP_TRY(ctx, hipMemcpyAsync(cost + curve_off[plan.g0], sweep.L.d_cost, (size_t)plan.entries * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(start + curve_off[plan.g0], sweep.L.d_start, (size_t)plan.entries * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
-        if (ctx->timing && last == n_pairs) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
-        if (curve_floats) {
-            HIP_TRY(ctx, hipMemcpyAsync(cost + curve_off[first], L.d_cost, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(start + curve_off[first], L.d_start, curve_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(h_best + first, L.d_best, (size_t)np * sizeof(apd_spot_best), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `desc`)
-        first = last;
+        if (best) HIP_TRY(ctx, hipMemcpyAsync(best + plan.g0, sweep.L.d_best, plan.np() * sizeof(apd_spot_best), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace
     }
     return APD_OK;
 }
@@ -120,9 +87,8 @@ extern "C" int apd_spot_hits(const float *cost, const uint32_t *start, uint64_t 
 
 // ----------------------------------------------------------------------------------------- spot detection
 
-// apd_spot's sweep into the workspace, then candidates, greedy picking and the packed hits on the device (kernels:
-// dtw_spot_detect.hip).  A chunk is a run of whole groups; its pairs are numbered group by group.  ws_spot_hits: the chunk's packed
-// hits, sized once its hit counts are known.
+// CurveSweep, then candidates, greedy picking and the packed hits on the device (kernels: dtw_spot_detect.hip).  ws_spot_hits: the
+// chunk's packed hits, sized once its hit counts are known.
 extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
                                const float *thresholds, int compete, apd_spot_hit *hits, uint64_t capacity, uint64_t *hit_off,
                                uint64_t *n_groups, uint64_t *n_hits)
@@ -131,111 +97,73 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
     if ((compete != APD_DETECT_PER_PAIR && compete != APD_DETECT_PER_STREAM) || (n_pairs && !thresholds) || !hit_off || !n_groups || !n_hits ||
         (capacity && !hits))
         return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
     const ResidentIndex idx(batch);
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
+    int rc = check_pair_list(batch, pairs, n_pairs);
     if (rc) return rc;
     *n_groups = 0;
     *n_hits = 0;
     hit_off[0] = 0;
     if (n_pairs == 0) return APD_OK;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if ((rc = spot_check_lengths(ctx, "apd_spot_detect", idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1])))) return rc;
-    // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
+    if ((rc = spot_check_pairs(ctx, "apd_spot_detect", idx, pairs, n_pairs))) return rc;
+    // groups in order of first appearance: every pair its own, or the pairs of a stream
     std::vector<uint64_t> group_of(n_pairs);
     uint64_t ng = n_pairs;
     if (compete == APD_DETECT_PER_PAIR)
         for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
     else
-        ng = number_by_first_appearance(pairs + 1, 2, n_pairs, n_seq, group_of);
+        ng = number_by_first_appearance(pairs + 1, 2, n_pairs, batch->n_seq, group_of);
     GroupMembers groups;
     if (!groups.build(group_of, ng, kMaxPairsPerLaunch)) {
         ctx->last_error = "apd_spot_detect: a group of more than 2^24 pairs";
         return APD_ERR_UNSUPPORTED;
     }
-    const std::vector<uint64_t> &member_first = groups.first, &members = groups.members;
-    auto stream_len = [&](uint64_t g) { return (uint64_t)idx.len(pairs[2 * members[member_first[g]] + 1]); };
-    auto group_pairs = [&](uint64_t g) { return groups.size(g); };
     *n_groups = ng;
     HIP_TRY(ctx, bind_device(ctx));
     APD_AFFINITY(ctx, "spot detect launch");
-    ChunkBudget budget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch};
+    CurveSweep sweep{ctx, batch, cfg, idx, pairs};
+    // a group weighs its curves and candidates, and the accepted windows of its stream
     constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t) + sizeof(ulonglong2), kStageBytes = sizeof(uint2);
-    std::vector<char> upload;
+    auto group_bytes = [&](uint64_t g) {
+        const uint64_t m = sweep.stream_len(groups.members[groups.first[g]]);
+        return groups.size(g) * m * kEntryBytes + m * kStageBytes;
+    };
+    GroupChunkPlan plan(groups, ChunkBudget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch});
     std::vector<uint32_t> counts;
-    for (uint64_t g0 = 0; g0 < ng;) {
-        // the chunk of groups [g0, g1): at least one, then as many as keep the curves, the candidates and the windows under the cap
-        uint64_t g1 = g0, entries = 0, stage_slots = 0;
-        budget.reset();
-        while (g1 < ng && budget.admit(group_pairs(g1) * stream_len(g1) * kEntryBytes + stream_len(g1) * kStageBytes, 0, group_pairs(g1))) {
-            entries += group_pairs(g1) * stream_len(g1); stage_slots += stream_len(g1);
-            ++g1;
-        }
-        const uint64_t ngc = g1 - g0, np = budget.items;
-        // ws_spot: the curves, the candidates and the accepted windows; what is uploaded -- the sweep's pairs by kernel class, the
-        // detector's pairs and groups --; the bests; what is zeroed -- candidate and hit counts --; the hit bases
-        Carve ws;
-        const size_t o_cost = ws.take<float>(entries), o_start = ws.take<uint32_t>(entries);
-        const size_t o_cand = ws.take<ulonglong2>(entries), o_stage = ws.take<uint2>(stage_slots);
-        const size_t o_desc = ws.take<SpotPair>(np), o_dp = ws.take<SpotDetectPair>(np), o_grp = ws.take<SpotDetectGroup>(ngc);
-        const size_t o_best = ws.take<apd_spot_best>(np);
+    while (sweep.next(plan, group_bytes)) {
+        const uint64_t g0 = plan.g0, g1 = plan.g1, ngc = g1 - g0, np = plan.np();
+        // ws_spot behind the sweep's regions: what is uploaded with its descriptors -- the detector's pairs and groups --; what is
+        // zeroed -- candidate and hit counts --; the hit bases; the candidates and the accepted windows
+        Carve &ws = sweep.ws;
+        sweep.carve(plan);
+        const size_t o_dp = ws.take<SpotDetectPair>(np), o_grp = ws.take<SpotDetectGroup>(ngc);
+        sweep.place(plan);
         const size_t o_cc = ws.take<unsigned long long>(ngc), o_hc = ws.take<uint32_t>(ngc), o_hb = ws.take<unsigned long long>(ngc + 1);
-        upload.assign(o_best - o_desc, 0);
-        SpotPair *desc = (SpotPair *)upload.data();
-        SpotDetectPair *dp = (SpotDetectPair *)(upload.data() + (o_dp - o_desc));
-        SpotDetectGroup *grp = (SpotDetectGroup *)(upload.data() + (o_grp - o_desc));
-        SpotClasses classes;
-        uint32_t m_max = 1;
-        uint64_t k = 0, off = 0, stage_off = 0;
-        for (uint64_t g = g0; g < g1; ++g) {
-            SpotDetectGroup &G = grp[g - g0];
-            const uint32_t m = (uint32_t)stream_len(g);
-            G.cand_off = off; G.cand_cap = group_pairs(g) * m; G.stage_off = stage_off; G.stage_cap = m;
-            stage_off += m;
-            m_max = std::max(m_max, m);
-            for (uint64_t t = member_first[g]; t < member_first[g + 1]; ++t, ++k) {
-                const uint64_t p = members[t];
-                SpotDetectPair &d = dp[k];
-                d.curve_off = off; d.m = m; d.n = idx.len(pairs[2 * p]); d.threshold = thresholds[p];
-                d.group = (uint32_t)(g - g0); d.pair = (uint32_t)p;
-                off += m;
-                classes.add(batch->dim, d.n);
+        const size_t o_cand = ws.take<ulonglong2>(plan.entries);
+        uint64_t stage_slots = 0;
+        SpotDetectPair *dp = sweep.record<SpotDetectPair>(o_dp);
+        SpotDetectGroup *grp = sweep.record<SpotDetectGroup>(o_grp);
+        for (uint64_t k = 0; k < np; ++k) {
+            const GroupChunkPlan::Slot &s = plan.slots[k];
+            dp[k] = SpotDetectPair{sweep.curve(s), thresholds[s.item], 0};
+            SpotDetectGroup &G = grp[s.group];
+            if (k == 0 || plan.slots[k - 1].group != s.group) {
+                G.cand_off = s.off; G.stage_off = stage_slots; G.stage_cap = s.len;
+                stage_slots += s.len;
             }
+            G.cand_cap += s.len;
         }
-        classes.close();
-        for (k = 0; k < np; ++k) {
-            const uint64_t p = dp[k].pair;
-            desc[classes.slot(spot_row_class(batch->dim, dp[k].n))] = SpotPair{idx.pos[pairs[2 * p]], idx.pos[pairs[2 * p + 1]], (uint32_t)k, 0, dp[k].curve_off};
-        }
-        rc = reserve_ws(ctx, ctx->ws_spot, ws.size);
-        if (rc) return rc;
-        char *base = ctx->ws_spot.as<char>();
-        SpotLaunch L{};
-        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
-        L.d_cost = (float *)(base + o_cost);
-        L.d_start = (uint32_t *)(base + o_start);
-        const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
-        L.d_best = (apd_spot_best *)(base + o_best);
+        const size_t o_stage = ws.take<uint2>(stage_slots);
+        if ((rc = sweep.run(plan, o_cc, o_hb - o_cc))) return rc;
         SpotDetectLaunch D{};
-        D.d_cost = L.d_cost; D.d_start = L.d_start;
-        D.d_pairs = (const SpotDetectPair *)(base + o_dp); D.n_pairs = (uint32_t)np;
-        D.d_groups = (const SpotDetectGroup *)(base + o_grp); D.n_groups = (uint32_t)ngc;
-        D.d_cand = (ulonglong2 *)(base + o_cand);
-        D.d_stage = (uint2 *)(base + o_stage);
-        D.d_cand_count = (unsigned long long *)(base + o_cc);
-        D.d_hit_count = (uint32_t *)(base + o_hc);
-        D.d_hit_base = (unsigned long long *)(base + o_hb);
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(base + o_cc, 0, o_hb - o_cc, ctx->stream));
-        if (ctx->timing && g0 == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (uint32_t c = 0; c < kSpotClasses; ++c) {
-            L.d_pairs = d_desc + classes.first[c];
-            L.n_pairs = (uint32_t)classes.n[c];
-            HIP_TRY(ctx, launch_spot(L, c, classes.r_max, ctx->stream));
-        }
-        HIP_TRY(ctx, launch_spot_detect(D, m_max, ctx->stream));
+        D.d_cost = sweep.L.d_cost; D.d_start = sweep.L.d_start;
+        D.d_pairs = sweep.device<SpotDetectPair>(o_dp); D.n_pairs = (uint32_t)np;
+        D.d_groups = sweep.device<SpotDetectGroup>(o_grp); D.n_groups = (uint32_t)ngc;
+        D.d_cand = sweep.device<ulonglong2>(o_cand);
+        D.d_stage = sweep.device<uint2>(o_stage);
+        D.d_cand_count = sweep.device<unsigned long long>(o_cc);
+        D.d_hit_count = sweep.device<uint32_t>(o_hc);
+        D.d_hit_base = sweep.device<unsigned long long>(o_hb);
+        HIP_TRY(ctx, launch_spot_detect(D, plan.max_len, ctx->stream));
         counts.resize(ngc);
         HIP_TRY(ctx, hipMemcpyAsync(counts.data(), D.d_hit_count, (size_t)ngc * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the packed buffer is sized by the counts
@@ -253,8 +181,7 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
             HIP_TRY(ctx, hipMemcpyAsync(hits + chunk_first, ctx->ws_spot_hits.ptr, (size_t)n_write * sizeof(apd_spot_hit), hipMemcpyDeviceToHost,
                                         ctx->stream));
         }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `upload`)
-        g0 = g1;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace
     }
     *n_hits = hit_off[ng];
     return APD_OK;
@@ -262,9 +189,8 @@ extern "C" int apd_spot_detect(apd_context *ctx, const apd_batch *batch, const a
 
 // ----------------------------------------------------------------------------------- spot score quantiles
 
-// apd_spot's sweep into the workspace, then the radix select of every (group, quantile) on the device (kernels:
-// dtw_spot_quantile.hip).  A chunk is a run of whole groups; its pairs are numbered group by group.  The rank k of every (group,
-// quantile) is worked out here from the group's entries and uploaded with its state record.
+// CurveSweep, then the radix select of every (group, quantile) on the device (kernels: dtw_spot_quantile.hip).  The rank k of every
+// (group, quantile) is worked out here from the group's entries and uploaded with its state record.
 extern "C" int apd_spot_quantiles(apd_context *ctx, const apd_batch *batch, const apd_align_config *cfg, const uint32_t *pairs, uint64_t n_pairs,
                                   int grouping, const float *perc, uint32_t n_perc, float *values, int32_t *status, uint64_t *group_of_out,
                                   uint64_t *entries_out, uint64_t *nans_out, uint64_t *n_groups)
@@ -273,118 +199,73 @@ extern "C" int apd_spot_quantiles(apd_context *ctx, const apd_batch *batch, cons
     if (grouping < APD_QUANTILES_PER_PAIR || grouping > APD_QUANTILES_ALL || n_perc == 0 || n_perc > APD_SPOT_QUANTILES_MAX || !perc || !values ||
         !n_groups)
         return APD_ERR_INVALID_ARG;
-    const uint32_t n_seq = batch->n_seq;
     const ResidentIndex idx(batch);
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] >= n_seq || pairs[2 * p + 1] >= n_seq) return APD_ERR_INVALID_ARG;
-    int rc = check_lengths(batch);
+    int rc = check_pair_list(batch, pairs, n_pairs);
     if (rc) return rc;
     if (n_pairs == 0) { *n_groups = 0; return APD_OK; }
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if ((rc = spot_check_lengths(ctx, "apd_spot_quantiles", idx.len(pairs[2 * p]), idx.len(pairs[2 * p + 1])))) return rc;
-    // groups in order of first appearance; members[member_first[g] .. member_first[g + 1]): the group's pairs, ascending
+    if ((rc = spot_check_pairs(ctx, "apd_spot_quantiles", idx, pairs, n_pairs))) return rc;
+    // groups in order of first appearance: every pair its own, the pairs of a query, or all
     std::vector<uint64_t> group_of(n_pairs, 0);                           // APD_QUANTILES_ALL: every pair in group 0
     uint64_t ng = 1;
     if (grouping == APD_QUANTILES_PER_PAIR) {
         ng = n_pairs;
         for (uint64_t p = 0; p < n_pairs; ++p) group_of[p] = p;
     } else if (grouping == APD_QUANTILES_PER_QUERY) {
-        ng = number_by_first_appearance(pairs, 2, n_pairs, n_seq, group_of);
+        ng = number_by_first_appearance(pairs, 2, n_pairs, batch->n_seq, group_of);
     }
     GroupMembers groups;
     if (!groups.build(group_of, ng, kMaxPairsPerLaunch)) {
         ctx->last_error = "apd_spot_quantiles: a group of more than 2^24 pairs";
         return APD_ERR_UNSUPPORTED;
     }
-    const std::vector<uint64_t> &member_first = groups.first, &members = groups.members;
+    CurveSweep sweep{ctx, batch, cfg, idx, pairs};
     std::vector<uint64_t> group_entries(ng, 0);
-    for (uint64_t p = 0; p < n_pairs; ++p) group_entries[group_of[p]] += idx.len(pairs[2 * p + 1]);
-    auto group_pairs = [&](uint64_t g) { return groups.size(g); };
+    for (uint64_t p = 0; p < n_pairs; ++p) group_entries[group_of[p]] += sweep.stream_len(p);
     *n_groups = ng;
     if (group_of_out) std::copy(group_of.begin(), group_of.end(), group_of_out);
     if (entries_out) std::copy(group_entries.begin(), group_entries.end(), entries_out);
     HIP_TRY(ctx, bind_device(ctx));
     APD_AFFINITY(ctx, "spot quantiles launch");
-    ChunkBudget budget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch};
+    // a group weighs its curves, its pairs' records and the histograms and states of its quantiles
     constexpr uint64_t kEntryBytes = sizeof(float) + sizeof(uint32_t);
-    constexpr uint64_t kPairBytes = sizeof(SpotPair) + sizeof(SpotQuantilePair) + sizeof(apd_spot_best);
-    const uint64_t group_bytes = (uint64_t)n_perc * (kSpotQuantileBins * sizeof(unsigned long long) + sizeof(SpotQuantileState) + 8);
-    std::vector<char> upload, results;
-    std::vector<uint64_t> slot_pair;                                      // the caller's pair of every pair of the chunk
-    for (uint64_t g0 = 0; g0 < ng;) {
-        // the chunk of groups [g0, g1): at least one, then as many as keep the curves, the pairs' records and the histograms under the cap
-        uint64_t g1 = g0, entries = 0;
-        budget.reset();
-        while (g1 < ng && budget.admit(group_entries[g1] * kEntryBytes + group_pairs(g1) * kPairBytes + group_bytes, 0, group_pairs(g1))) entries += group_entries[g1++];
-        const uint64_t ngc = g1 - g0, np = budget.items, nq = n_perc;
-        // ws_spot: the curves; what is uploaded -- the sweep's pairs by kernel class, the select's pairs, the states --; the bests; what
-        // is zeroed -- the histograms --; what is read back -- values, statuses, NaN counts
-        Carve ws;
-        const size_t o_cost = ws.take<float>(entries), o_start = ws.take<uint32_t>(entries);
-        const size_t o_desc = ws.take<SpotPair>(np), o_qp = ws.take<SpotQuantilePair>(np), o_state = ws.take<SpotQuantileState>(ngc * nq);
-        const size_t o_best = ws.take<apd_spot_best>(np);
+    constexpr uint64_t kPairBytes = sizeof(SpotPair) + sizeof(SpotCurve) + sizeof(apd_spot_best);
+    const uint64_t quantile_bytes = (uint64_t)n_perc * (kSpotQuantileBins * sizeof(unsigned long long) + sizeof(SpotQuantileState) + 8);
+    auto group_bytes = [&](uint64_t g) { return group_entries[g] * kEntryBytes + groups.size(g) * kPairBytes + quantile_bytes; };
+    GroupChunkPlan plan(groups, ChunkBudget{workspace_cap("APD_SPOT_WORKSPACE_BYTES"), kMaxPairsPerLaunch});
+    std::vector<char> results;
+    while (sweep.next(plan, group_bytes)) {
+        const uint64_t g0 = plan.g0, ngc = plan.g1 - g0, np = plan.np(), nq = n_perc;
+        // ws_spot behind the sweep's regions: what is uploaded with its descriptors -- the select's pairs, the states --; what is
+        // zeroed -- the histograms --; what is read back -- values, statuses, NaN counts
+        Carve &ws = sweep.ws;
+        sweep.carve(plan);
+        const size_t o_qp = ws.take<SpotCurve>(np), o_state = ws.take<SpotQuantileState>(ngc * nq);
+        sweep.place(plan);
         const size_t o_hist = ws.take<unsigned long long>(ngc * nq * kSpotQuantileBins);
         const size_t o_values = ws.take<float>(ngc * nq), o_status = ws.take<int32_t>(ngc * nq), o_nans = ws.take<unsigned long long>(ngc);
-        upload.assign(o_best - o_desc, 0);
-        SpotPair *desc = (SpotPair *)upload.data();
-        SpotQuantilePair *qp = (SpotQuantilePair *)(upload.data() + (o_qp - o_desc));
-        SpotQuantileState *state = (SpotQuantileState *)(upload.data() + (o_state - o_desc));
-        slot_pair.resize(np);
-        SpotClasses classes;
-        uint32_t m_max = 1;
-        uint64_t k = 0, off = 0;
-        for (uint64_t g = g0; g < g1; ++g) {
+        SpotCurve *qp = sweep.record<SpotCurve>(o_qp);
+        SpotQuantileState *state = sweep.record<SpotQuantileState>(o_state);
+        for (uint64_t k = 0; k < np; ++k) qp[k] = sweep.curve(plan.slots[k]);
+        for (uint64_t g = g0; g < plan.g1; ++g)
             for (uint32_t q = 0; q < n_perc; ++q) state[(g - g0) * nq + q].rank = percentile_index(group_entries[g], perc[q]);
-            for (uint64_t t = member_first[g]; t < member_first[g + 1]; ++t, ++k) {
-                const uint64_t p = members[t];
-                SpotQuantilePair &d = qp[k];
-                d.curve_off = off; d.m = idx.len(pairs[2 * p + 1]); d.n = idx.len(pairs[2 * p]); d.group = (uint32_t)(g - g0);
-                slot_pair[k] = p;
-                off += d.m;
-                m_max = std::max(m_max, d.m);
-                classes.add(batch->dim, d.n);
-            }
-        }
-        classes.close();
-        for (k = 0; k < np; ++k) {
-            const uint64_t p = slot_pair[k];
-            desc[classes.slot(spot_row_class(batch->dim, qp[k].n))] = SpotPair{idx.pos[pairs[2 * p]], idx.pos[pairs[2 * p + 1]], (uint32_t)k, 0, qp[k].curve_off};
-        }
-        rc = reserve_ws(ctx, ctx->ws_spot, ws.size);
-        if (rc) return rc;
-        char *base = ctx->ws_spot.as<char>();
-        SpotLaunch L{};
-        L.src = spot_source(batch, cfg->insertion_penalty, cfg->deletion_penalty, cfg->match_penalty);
-        L.d_cost = (float *)(base + o_cost);
-        L.d_start = (uint32_t *)(base + o_start);
-        const SpotPair *d_desc = (const SpotPair *)(base + o_desc);
-        L.d_best = (apd_spot_best *)(base + o_best);
+        if ((rc = sweep.run(plan, o_hist, o_values - o_hist))) return rc;
         SpotQuantileLaunch Q{};
-        Q.d_cost = L.d_cost; Q.d_start = L.d_start;
-        Q.d_pairs = (const SpotQuantilePair *)(base + o_qp); Q.n_pairs = (uint32_t)np;
+        Q.d_cost = sweep.L.d_cost; Q.d_start = sweep.L.d_start;
+        Q.d_pairs = sweep.device<SpotCurve>(o_qp); Q.n_pairs = (uint32_t)np;
         Q.n_groups = (uint32_t)ngc; Q.n_perc = n_perc;
-        Q.d_state = (SpotQuantileState *)(base + o_state);
-        Q.d_hist = (unsigned long long *)(base + o_hist);
-        Q.d_values = (float *)(base + o_values);
-        Q.d_status = (int32_t *)(base + o_status);
-        Q.d_nans = (unsigned long long *)(base + o_nans);
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, upload.data(), upload.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(base + o_hist, 0, o_values - o_hist, ctx->stream));
-        if (ctx->timing && g0 == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (uint32_t c = 0; c < kSpotClasses; ++c) {
-            L.d_pairs = d_desc + classes.first[c];
-            L.n_pairs = (uint32_t)classes.n[c];
-            HIP_TRY(ctx, launch_spot(L, c, classes.r_max, ctx->stream));
-        }
-        HIP_TRY(ctx, launch_spot_quantiles(Q, m_max, ctx->stream));
-        if (ctx->timing && g1 == ng) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
+        Q.d_state = sweep.device<SpotQuantileState>(o_state);
+        Q.d_hist = sweep.device<unsigned long long>(o_hist);
+        Q.d_values = sweep.device<float>(o_values);
+        Q.d_status = sweep.device<int32_t>(o_status);
+        Q.d_nans = sweep.device<unsigned long long>(o_nans);
+        HIP_TRY(ctx, launch_spot_quantiles(Q, plan.max_len, ctx->stream));
+        if (ctx->timing && plan.g1 == ng) { HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream)); ctx->timed = true; }
         results.resize(ws.size - o_values);
-        HIP_TRY(ctx, hipMemcpyAsync(results.data(), base + o_values, results.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace (and `upload`)
+        HIP_TRY(ctx, hipMemcpyAsync(results.data(), sweep.device<char>(o_values), results.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                  // the next chunk reuses the workspace
         std::memcpy(values + g0 * nq, results.data(), (size_t)(ngc * nq) * sizeof(float));
         if (status) std::memcpy(status + g0 * nq, results.data() + (o_status - o_values), (size_t)(ngc * nq) * sizeof(int32_t));
         if (nans_out) std::memcpy(nans_out + g0, results.data() + (o_nans - o_values), (size_t)ngc * sizeof(uint64_t));
-        g0 = g1;
     }
     return APD_OK;
 }

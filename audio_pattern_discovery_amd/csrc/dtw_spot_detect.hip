@@ -19,7 +19,7 @@
 // map of f32 onto u32 -- after both zeros were made +0.0, so that -0.0 and +0.0 tie as f32 < says they do.  A candidate's score is
 // below its threshold and so below +INF: its key is below 0xFF800000, and hi = 2^64 - 1 is free to mean "dead".  The record's score
 // is computed again from the curves at emit (spot_score again: the same bits, and the sign of a zero survives).
-#include "apd_internal.h"
+#include "dtw_spot_curves.h"
 
 namespace apd {
 
@@ -34,52 +34,31 @@ __device__ __forceinline__ bool key_less(unsigned long long ah, unsigned long lo
     return ah < bh || (ah == bh && al < bl);
 }
 
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// grid: (pairs of the chunk, column blocks); a block walks its pair's columns kMarkThreads at a time, gridDim.y blocks apart
+// grid and walk: spot_curve_walk (dtw_spot_curves.h), kMarkThreads columns a step
 __global__ __launch_bounds__(kMarkThreads) void spot_detect_mark(const SpotDetectLaunch L)
 {
     const uint32_t p = blockIdx.x;
     const SpotDetectPair P = L.d_pairs[p];
-    const float *cost = L.d_cost + P.curve_off;
-    const uint32_t *start = L.d_start + P.curve_off;
-    const SpotDetectGroup G = L.d_groups[P.group];
+    const SpotDetectGroup G = L.d_groups[P.curve.group];
     ulonglong2 *list = L.d_cand + G.cand_off;
-    unsigned long long *counter = L.d_cand_count + P.group;
+    unsigned long long *counter = L.d_cand_count + P.curve.group;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t stride = (uint64_t)gridDim.y * kMarkThreads;
-    // j0: the 0-based column of lane 0 of this wavefront; the trip count is the wavefront's, every lane reaches the ballot
-    for (uint64_t j0 = (uint64_t)blockIdx.y * kMarkThreads + (threadIdx.x - lane); j0 < P.m; j0 += stride) {
-        const uint64_t j = j0 + lane;
-        bool cand = false;
-        uint32_t s = 0;
-        float score = 0.0f;
-        if (j < P.m) {
-            const float c = cost[j];
-            s = start[j];
-            score = spot_score(c, (uint32_t)j + 1u, s, P.n);
-            cand = s != 0u && score < P.threshold;                        // strict; a NaN on either side compares false
-        }
+    spot_curve_walk<kMarkThreads>(P.curve, L.d_cost, L.d_start, [&](uint64_t j, bool live, float, uint32_t s, float score) {
+        const bool cand = live && s != 0u && score < P.threshold;         // strict; a NaN on either side compares false
         const unsigned long long vote = __ballot(cand);
-        if (vote == 0) continue;
+        if (vote == 0) return;
         const int leader = __ffsll((long long)vote) - 1;
         unsigned long long base = 0;
         if ((int)lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(vote));
-        const uint32_t base_lo = (uint32_t)__shfl((int)(uint32_t)base, leader, 64);
-        const uint32_t base_hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), leader, 64);
+        base = shfl_u64(base, leader);
         if (cand) {
-            const uint64_t slot = (((uint64_t)base_hi << 32) | base_lo) + (uint64_t)__popcll(vote & ((1ull << lane) - 1ull));
+            const uint64_t slot = base + (uint64_t)__popcll(vote & ((1ull << lane) - 1ull));
             ulonglong2 k;
             k.x = ((unsigned long long)spot_score_key(score) << 32) | (uint32_t)(j + 1u);
             k.y = ((unsigned long long)p << 32) | s;
             if (slot < G.cand_cap) list[slot] = k;                        // one candidate per entry at most: always true
         }
-    }
+    });
 }
 
 // grid: the chunk's groups
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(64) void spot_detect_emit(const SpotDetectLaunch L,
         const unsigned long long at = base + r;
         if (at >= n_write) break;
         const uint2 w = stage[r];                                         // (pair of the chunk, end)
-        const SpotDetectPair P = L.d_pairs[w.x];
+        const SpotCurve P = L.d_pairs[w.x].curve;
         apd_spot_hit h;
         h.pair = P.pair;
         h.end = w.y;

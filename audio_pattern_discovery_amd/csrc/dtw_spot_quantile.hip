@@ -26,7 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "apd_internal.h"
+#include "dtw_spot_curves.h"
 
 namespace apd {
 
@@ -37,19 +37,12 @@ namespace {
 constexpr uint32_t kBins = kSpotQuantileBins;
 constexpr uint32_t kMaxQ = APD_SPOT_QUANTILES_MAX;
 
-__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, uint32_t delta)
-{
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, delta, 64);
-    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), delta, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// grid: (pairs of the chunk, column blocks); a block walks its pair's columns kSpotQuantileColumns at a time, gridDim.y blocks apart
+// grid and walk: spot_curve_walk (dtw_spot_curves.h), kSpotQuantileColumns columns a step
 __global__ __launch_bounds__(kSpotQuantileColumns) void spot_quantile_pass(const SpotQuantileLaunch L, const int pass)
 {
     __shared__ uint32_t hist[kMaxQ][kBins];
     __shared__ uint32_t s_prefix[kMaxQ], s_mask[kMaxQ], s_rep[kMaxQ];   // s_rep[q]: the quantile whose histogram q reads; kMaxQ: q is settled
-    const SpotQuantilePair P = L.d_pairs[blockIdx.x];
+    const SpotCurve P = L.d_pairs[blockIdx.x];
     const uint32_t nq = L.n_perc, tid = threadIdx.x, lane = tid & 63u;
     const int shift = 24 - 8 * pass;
     for (uint32_t h = tid; h < nq * kBins; h += kSpotQuantileColumns) (&hist[0][0])[h] = 0;
@@ -64,15 +57,7 @@ __global__ __launch_bounds__(kSpotQuantileColumns) void spot_quantile_pass(const
         }
     }
     __syncthreads();
-    const float *cost = L.d_cost + P.curve_off;
-    const uint32_t *start = L.d_start + P.curve_off;
-    const uint64_t stride = (uint64_t)gridDim.y * kSpotQuantileColumns;
-    // j0: the 0-based column of lane 0 of this wavefront; the trip count is the wavefront's, every lane reaches the ballots
-    for (uint64_t j0 = (uint64_t)blockIdx.y * kSpotQuantileColumns + (tid - lane); j0 < P.m; j0 += stride) {
-        const uint64_t j = j0 + lane;
-        const bool live = j < P.m;
-        float score = 0.0f;
-        if (live) score = spot_score(cost[j], (uint32_t)j + 1u, start[j], P.n);
+    spot_curve_walk<kSpotQuantileColumns>(P, L.d_cost, L.d_start, [&](uint64_t, bool live, float, uint32_t, float score) {
         const bool is_nan = score != score;
         const uint32_t key = spot_score_key(score);
         const uint32_t d = is_nan ? 256u : (key >> shift) & 0xFFu;
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(kSpotQuantileColumns) void spot_quantile_pass(const
             if ((int)lane == leader) atomicAdd(&hist[q][ld], (uint32_t)__popcll(same));
             else if (want && d != ld) atomicAdd(&hist[q][d], 1u);
         }
-    }
+    });
     __syncthreads();
     for (uint32_t q = 0; q < nq; ++q) {
         const uint32_t rep = s_rep[q];

@@ -1,5 +1,6 @@
-// The grouping helpers of csrc/apd_plan.h (number_by_first_appearance, GroupMembers) against their definitions, on seeded random
-// inputs.  Plain C++17, no GPU; tests/test_spot_group_plan.py builds it under AddressSanitizer + UBSan and runs it.
+// The grouping helpers of csrc/apd_plan.h (number_by_first_appearance, GroupMembers) and the chunk plan over them (GroupChunkPlan)
+// against their definitions, on seeded random inputs.  Plain C++17, no GPU; tests/test_spot_group_plan.py builds it under
+// AddressSanitizer + UBSan and runs it.
 //   group_check <rounds> <seed>
 #include <cstdio>
 #include <cstdlib>
@@ -53,6 +54,63 @@ int main(int argc, char **argv)
                 if (t > groups.first[g]) REQUIRE(groups.members[t - 1] < groups.members[t]);
             }
         }
+        // the chunk plan over these groups (half the rounds: n groups of one, both forms) under a random weight per group and length
+        // per item.  Caps: below every group, a few groups, everything; in a quarter of the rounds the item limit binds instead.
+        const bool singles = round % 2 == 1;
+        GroupMembers identity;
+        if (singles) {
+            std::vector<uint64_t> own(n);
+            for (uint64_t i = 0; i < n; ++i) own[i] = i;
+            REQUIRE(identity.build(own, n, 1));
+        }
+        const GroupMembers &gm = singles ? identity : groups;
+        const uint64_t n_groups = gm.first.size() - 1;
+        std::vector<uint32_t> len(n);
+        for (auto &v : len) v = 1 + (uint32_t)(rng() % 300);
+        std::vector<uint64_t> weight(n_groups);
+        uint64_t total = 0;
+        for (auto &w : weight) total += w = rng() % 4 == 0 ? 0 : 1 + rng() % 1000;
+        const uint64_t caps[3] = {0, 1 + rng() % 2500, total};
+        const uint64_t cap = caps[rng() % 3];
+        const uint64_t max_items = round % 4 < 2 ? ~0ull : (singles ? 1 : largest) + rng() % 4;
+        const uint64_t cap_used = round % 4 < 2 ? cap : ~0ull >> 1;
+        auto weigh = [&](uint64_t g) { return weight[g]; };
+        auto length = [&](uint64_t i) { return len[i]; };
+        GroupChunkPlan plan(gm, ChunkBudget{cap_used, max_items});
+        GroupChunkPlan ones(n, ChunkBudget{cap_used, max_items});
+        uint64_t expect_g0 = 0;
+        while (plan.next(weigh, length)) {
+            REQUIRE(plan.g0 == expect_g0 && plan.g1 > plan.g0 && plan.g1 <= n_groups);   // in order, never empty
+            // the greedy rule: what the chunk holds beyond its first group fits, and the next group would not
+            uint64_t bytes = 0, items = 0;
+            for (uint64_t g = plan.g0; g < plan.g1; ++g) { bytes += weight[g]; items += gm.size(g); }
+            if (plan.g1 - plan.g0 > 1) REQUIRE(bytes <= cap_used && items <= max_items);
+            if (plan.g1 < n_groups) REQUIRE(bytes + weight[plan.g1] > cap_used || items + gm.size(plan.g1) > max_items);
+            // slots: group by group, members ascending, offsets the prefix sums of the lengths
+            REQUIRE(plan.np() == items && plan.slots.size() == items);
+            uint64_t k = 0, off = 0;
+            uint32_t longest = 0;
+            for (uint64_t g = plan.g0; g < plan.g1; ++g)
+                for (uint64_t t = gm.first[g]; t < gm.first[g + 1]; ++t, ++k) {
+                    const GroupChunkPlan::Slot &s = plan.slots[k];
+                    REQUIRE(s.item == gm.members[t] && s.group == g - plan.g0 && s.len == len[s.item] && s.off == off);
+                    off += s.len;
+                    longest = s.len > longest ? s.len : longest;
+                }
+            REQUIRE(plan.entries == off && plan.max_len == longest);
+            if (singles) {                                                // "n groups of one" is the identity grouping
+                REQUIRE(ones.next(weigh, length) && ones.g0 == plan.g0 && ones.g1 == plan.g1 && ones.np() == plan.np());
+                REQUIRE(ones.entries == plan.entries && ones.max_len == plan.max_len);
+                for (k = 0; k < plan.np(); ++k) {
+                    const GroupChunkPlan::Slot &a = ones.slots[k], &b = plan.slots[k];
+                    REQUIRE(a.item == b.item && a.off == b.off && a.group == b.group && a.len == b.len);
+                }
+            }
+            expect_g0 = plan.g1;
+        }
+        REQUIRE(expect_g0 == n_groups);                                   // the chunks partition the groups
+        REQUIRE(!plan.next(weigh, length) && plan.g0 == n_groups);        // and the end stays the end
+        if (singles) REQUIRE(!ones.next(weigh, length));
     }
     std::printf("groups ok: %ld rounds, no sanitizer report\n", rounds);
     return 0;

@@ -1,6 +1,6 @@
-"""CPU test of the grouping helpers the spot detection and spot quantile host drivers share (csrc/apd_plan.h:
-number_by_first_appearance, GroupMembers): tests/cpp/group_check.cpp checks them against their definitions on seeded random lists,
-built under AddressSanitizer + UBSan as a program of its own."""
+"""CPU test of the grouping helpers and the chunk plan the spot, spot detection and spot quantile host drivers share (csrc/apd_plan.h:
+number_by_first_appearance, GroupMembers, GroupChunkPlan): tests/cpp/group_check.cpp checks them against their definitions on seeded
+random lists, built under AddressSanitizer + UBSan as a program of its own."""
 import os
 import shutil
 import subprocess
