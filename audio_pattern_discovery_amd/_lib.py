@@ -24,6 +24,8 @@ APD_ERR_COMM = -10
 APD_COMM_ID_BYTES = 128
 APD_QUANTILES_PER_PAIR, APD_QUANTILES_PER_QUERY, APD_QUANTILES_ALL = 0, 1, 2    # apd_spot_quantiles' groupings
 APD_SPOT_QUANTILES_MAX = 8
+APD_NEIGHBORS_ROWS, APD_NEIGHBORS_COLUMNS = 0, 1                                # apd_neighbors' axes
+APD_NEIGHBORS_MAX_K = 1024
 APD_SPOT_QUANTILES_COLUMNS = 256         # columns a workgroup of the select takes per step (tests place stream lengths around it)
 
 
@@ -159,6 +161,8 @@ SYMBOLS = [
     ("apd_align_cross", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _f32p, _f32p]),
     ("apd_align_cross_device_async", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _vp, _vp]),
     ("apd_cross_linkage", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("apd_neighbors", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _u32p, C.c_uint32, C.c_uint32, C.c_int,
+                                _vp, _vp, _vp, _vp]),
     ("apd_cluster_medoids", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _u32p, _u32p, C.c_uint32, _vp, _vp]),
     ("apd_barycenters", C.c_int, [_vp, _vp, C.POINTER(AlignConfig), _u32p, _u32p, C.c_uint32, _u32p, C.c_uint32, _vp, C.c_int,
                                   C.c_uint64, _u64p, _f32p, _u32p]),

@@ -558,6 +558,29 @@ class AlignmentWorkers:
             joined.close()
         return fs, sf
 
+    def nearest(self, other, params, k, as_x=True):
+        """For every sequence of this object its k nearest sequences of `other` (an AlignmentWorkers of the same context), params:
+        Discovery.  as_x=True ranks score(x = self q, y = other c) over c -- the rows of cross()'s fs; as_x=False ranks
+        score(x = other c, y = self q) -- the columns of sf.  apd_batch_join + apd_align_cross_device_async + apd_neighbors: the
+        cross matrix is made, ranked and freed in HBM.  Returns what clustering.neighbors returns, indices numbering `other`."""
+        from .clustering import neighbors
+        if self._multi is not None or other._multi is not None:
+            raise ValueError("nearest() runs on one context: make the AlignmentWorkers without `devices`")
+        cfg = params.align_config()
+        n1, n2 = len(self.data), len(other.data)
+        if n1 == 0 or n2 == 0:                                       # an empty set: nothing to align (apd_align_cross writes nothing)
+            return neighbors(np.zeros((n1, n2) if as_x else (n2, n1), np.float32), k, 0 if as_x else 1, ctx=self.ctx)
+        joined = Batch.join(self._batch, other._batch)
+        matrix = self.ctx.alloc(4 * n1 * n2)
+        try:
+            fs, sf = (matrix.at(), None) if as_x else (None, matrix.at())
+            _lib.check(_lib.lib().apd_align_cross_device_async(self.ctx.handle, joined.handle, C.byref(cfg), fs, sf), self.ctx.handle)
+            shape = (matrix.ptr, n1, n2) if as_x else (matrix.ptr, n2, n1)
+            return neighbors(shape, k, 0 if as_x else 1, ctx=self.ctx, on_device=True)
+        finally:
+            joined.close()
+            matrix.free()
+
     def close(self):
         """Releases the GPU side (the reference's Drop of the Arcs)."""
         if self._batch is not None:

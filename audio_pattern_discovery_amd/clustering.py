@@ -107,6 +107,46 @@ def medoids(distances, sets, ctx=None):
     return medoid, cost
 
 
+def neighbors(distances, k, axis=0, skip_self=False, queries=None, ctx=None, on_device=False):
+    """apd_neighbors: the k nearest entries of rows (axis=0: query q ranks distances[q][:]) or columns (axis=1: distances[:][q]) of
+    a 2-D matrix -- the [n][n] one of AlignmentWorkers.align_all, or a cross matrix of cross() -- ascending by (value, index), NaN
+    entries dropped, the query's own number too with skip_self.  queries: row / column numbers in any order, repeats allowed; None:
+    all of them, ascending.  With on_device the matrix is (device pointer, rows, cols) and stays in HBM, as do the results until
+    they are read here.  Returns (index uint32 [Q][k], distance float32 [Q][k], count uint32 [Q], nans uint32 [Q]): count[q]
+    candidates were found (at most k), the slots behind them hold 0xFFFFFFFF and NaN; nans[q] NaN entries were met."""
+    ctx = ctx or _lib.default_context()
+    if on_device:
+        ptr, rows, cols = distances
+        ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+    else:
+        d = np.ascontiguousarray(distances, dtype=np.float32)
+        if d.ndim != 2:
+            raise ValueError("distances must be a 2-D array")
+        (rows, cols), ptr = d.shape, C.c_void_p(d.ctypes.data)
+    q = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32).ravel()
+    n_q = (rows, cols)[int(axis)] if q is None and axis in (0, 1) else (0 if q is None else len(q))
+    k = int(k)
+    shape = (n_q, max(k, 0))
+    index, distance = np.zeros(shape, np.uint32), np.zeros(shape, np.float32)
+    count, nans = np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint32)
+    q_ptr = None if q is None else q.ctypes.data_as(C.POINTER(C.c_uint32))
+    head = (ctx.handle, ptr, int(bool(on_device)), int(rows), int(cols), int(axis), q_ptr, 0 if q is None else len(q), k, int(bool(skip_self)))
+    outs = (index, distance, count, nans)
+    if not on_device:
+        _lib.check(_lib.lib().apd_neighbors(*head, *[C.c_void_p(a.ctypes.data) for a in outs]), ctx.handle)
+        return outs
+    bufs = [ctx.alloc(max(a.nbytes, 16)) for a in outs]
+    try:
+        _lib.check(_lib.lib().apd_neighbors(*head, *[b.at() for b in bufs]), ctx.handle)
+        for a, b in zip(outs, bufs):
+            if a.size:
+                a[...] = b.to_numpy(a.dtype, a.size).reshape(a.shape)     # the copy waits for the context's stream
+    finally:
+        for b in bufs:
+            b.free()
+    return outs
+
+
 def percentile(x, perc, ctx=None):
     """numerics.rs:125-133 on the GPU (apd_percentile)."""
     ctx = ctx or _lib.default_context()

@@ -774,6 +774,7 @@ struct apd_context {
     apd::DeviceBuf ws_spot_hits;      // apd_spot_detect: the packed hits of a chunk
     apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
     apd::DeviceBuf ws_spot_steps;     // apd_spot_paths, apd_spot_stream_paths: steps, descriptors and results of a chunk of windows
+    apd::DeviceBuf ws_neighbors;      // apd_neighbors, column form: the [panel][rows] gather of the queried columns (bounded)
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

@@ -84,6 +84,9 @@ pub const APD_QUANTILES_PER_PAIR: c_int = 0;
 pub const APD_QUANTILES_PER_QUERY: c_int = 1;
 pub const APD_QUANTILES_ALL: c_int = 2;
 pub const APD_SPOT_QUANTILES_MAX: usize = 8;
+pub const APD_NEIGHBORS_ROWS: c_int = 0;
+pub const APD_NEIGHBORS_COLUMNS: c_int = 1;
+pub const APD_NEIGHBORS_MAX_K: usize = 1024;
 
 /// A window of stream y matched to query x (apd_spot_paths): end and start as in apd_spot_best.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
@@ -265,6 +268,10 @@ extern "C" {
     pub fn apd_cross_linkage(ctx: *mut apd_context, fs: *const f32, sf: *const f32, on_device: c_int, n_first: u32, n_second: u32,
                              members: *const u32, set_off: *const u32, n_sets: u32, link_fs: *mut f32, link_sf: *mut f32,
                              nearest: *mut u32, nearest_linkage: *mut f32) -> c_int;
+    // nearest neighbours (axis: APD_NEIGHBORS_ROWS / APD_NEIGHBORS_COLUMNS)
+    pub fn apd_neighbors(ctx: *mut apd_context, distances: *const f32, on_device: c_int, rows: u32, cols: u32, axis: c_int,
+                         queries: *const u32, n_queries: u32, k: u32, skip_self: c_int, index: *mut u32, distance: *mut f32,
+                         count: *mut u32, nans: *mut u32) -> c_int;
     // cluster prototypes
     pub fn apd_cluster_medoids(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, members: *const u32,
                                set_off: *const u32, n_sets: u32, medoid: *mut u32, cost: *mut f32) -> c_int;

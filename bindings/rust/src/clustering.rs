@@ -104,6 +104,22 @@ impl AgglomerativeClustering {
         (0..sets.len()).map(|k| (if medoid[k] == u32::MAX { None } else { Some(medoid[k] as usize) }, cost[k])).collect()
     }
 
+    /// Not in the reference: the k nearest entries of every row (`by_columns` false: query q ranks distances[q][..]) or column
+    /// (true: distances[..][q]) of a rows x cols matrix of align_all or align_cross (apd_neighbors), ascending by (value, index),
+    /// NaN entries dropped and, with `skip_self`, entry q itself.  Per query the (index, distance) pairs found: at most k.
+    pub fn neighbors(distances: &[f32], rows: usize, cols: usize, k: usize, by_columns: bool, skip_self: bool) -> Vec<Vec<(usize, f32)>> {
+        let n_queries = if by_columns { cols } else { rows };
+        let mut index = vec![0u32; (n_queries * k).max(1)];
+        let mut distance = vec![0f32; (n_queries * k).max(1)];
+        let mut count = vec![0u32; n_queries.max(1)];
+        with_context(|ctx| unsafe {
+            check(apd_neighbors(ctx, distances.as_ptr(), 0, rows as u32, cols as u32, if by_columns { APD_NEIGHBORS_COLUMNS } else { APD_NEIGHBORS_ROWS },
+                                std::ptr::null(), 0, k as u32, skip_self as i32, index.as_mut_ptr(), distance.as_mut_ptr(), count.as_mut_ptr(),
+                                std::ptr::null_mut()));
+        });
+        (0..n_queries).map(|q| (0..count[q] as usize).map(|s| (index[q * k + s] as usize, distance[q * k + s])).collect()).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

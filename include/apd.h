@@ -787,6 +787,38 @@ int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on
                       const uint32_t *members, const uint32_t *set_off, uint32_t n_sets,
                       float *link_fs, float *link_sf, uint32_t *nearest, float *nearest_linkage);
 
+/* ---- nearest neighbours: the k smallest entries of rows or columns of a distance matrix ---------------------------------------
+ * distances: row-major [rows][cols], square or not: the matrix of apd_align_all, or a cross matrix of apd_align_cross.  Query q
+ * ranks the entries d[q][j], j < cols (APD_NEIGHBORS_ROWS) or d[j][q], j < rows (APD_NEIGHBORS_COLUMNS); the matrices are not
+ * symmetric (the band is [-w, w-1]), so the two are different questions.
+ * queries: HOST array of n_queries row (ROWS) or column (COLUMNS) numbers, in any order, repeats allowed, each answered on its own;
+ * NULL: every row / column ascending, n_queries is not read.  Q is the number of queries.
+ * The candidates of query q are its entries (j, v) with v not NaN and, if skip_self, j != q (a plain comparison of numbers, for
+ * rectangular matrices too: pass 0 for cross matrices).  They are ordered ascending by (v, j): v under IEEE `<` -- -0.0 and +0.0
+ * tie, +INF is a candidate behind every finite value -- and equal values by the smaller j.  Then
+ *   count[q] = min(k, candidates); index[q][s], distance[q][s] for s < count[q]: j and the matrix's own bits of v (a -0.0 comes
+ *   back as -0.0); the slots behind them hold 0xFFFFFFFF and a quiet NaN (0x7FC00000); nans[q] (nans may be NULL) = NaN entries of
+ *   the row / column, not counting a skipped self entry.
+ * A function of the matrix alone, bit for bit: no workgroup size, schedule or workspace size enters it.
+ * index, distance: [Q][k]; count, nans: [Q]; host, or all device pointers if on_device (the matrix and the results stay in HBM; the
+ * call waits once for the upload of the query list -- not at all without one -- and the kernels are only enqueued on the context's
+ * stream, as apd_cross_linkage does).  Otherwise the call blocks.
+ * APD_ERR_INVALID_ARG, before anything is launched or written: k == 0, k > APD_NEIGHBORS_MAX_K, another axis, a query >= rows (ROWS)
+ * or >= cols (COLUMNS).  Q == 0: APD_OK, nothing written; rows == 0 or cols == 0 with Q > 0: counts of 0 and padding.  k larger
+ * than a row is fine: the tail is padding.
+ * Rows of up to 32768 entries are read from HBM once and kept in LDS; longer ones are re-read per digit pass.  COLUMNS gathers the
+ * queried columns into a [panel][rows] workspace of the context (256 MiB) and ranks its rows, in as many panels as it takes.
+ * Environment (tests only; read at every call; results are bit-identical whatever they say): APD_NEIGHBORS_LDS_COLUMNS=<entries>
+ * lowers the LDS residency limit, APD_NEIGHBORS_WORKSPACE_BYTES=<bytes> sets the panel workspace (at least one column is taken),
+ * APD_NEIGHBORS_WORKGROUP=<64 .. 1024, a multiple of 64> sets the work-items of a select workgroup (default 256 for rows of up to
+ * 8192 entries, 512 or 1024 beyond). */
+#define APD_NEIGHBORS_ROWS    0
+#define APD_NEIGHBORS_COLUMNS 1
+#define APD_NEIGHBORS_MAX_K   1024
+int apd_neighbors(apd_context *ctx, const float *distances, int on_device, uint32_t rows, uint32_t cols, int axis,
+                  const uint32_t *queries, uint32_t n_queries, uint32_t k, int skip_self,
+                  uint32_t *index, float *distance, uint32_t *count, uint32_t *nans);
+
 /* ---- cluster prototypes: which member stands for a cluster, and the cluster's average shape ---------------------------------
  * The medoid of every set: the member closest to all the others, from the [n][n] matrix of apd_align_all.  For set k with its
  * members sorted ascending j1 < j2 < ..., whatever order `members` lists them in, the cost of member i is
