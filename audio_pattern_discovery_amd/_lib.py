@@ -211,6 +211,9 @@ SYMBOLS = [
                                  _u32p, _f32p]),
     ("apd_cluster_sets", C.c_int, [C.POINTER(ClusterOp), C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _u32p,
                                    _u32p]),
+    ("apd_dendrogram_cut", C.c_int, [C.POINTER(ClusterOp), C.c_uint32, C.c_float, _u32p]),
+    ("apd_cut_labels", C.c_int, [C.POINTER(ClusterOp), C.c_uint32, C.c_uint32, _u32p]),
+    ("apd_silhouette", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, _u32p, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("apd_encoder_create", C.c_int, [_vp, _f32p, _f32p, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     ("apd_encoder_destroy", C.c_int, [_vp]),
     ("apd_encode_async", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp]),

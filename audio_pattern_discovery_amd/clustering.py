@@ -62,6 +62,117 @@ class AgglomerativeClustering:
                                                set_off.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n_sets)))
         return [members[set_off[s]:set_off[s + 1]].tolist() for s in range(n_sets.value)]
 
+    @staticmethod
+    def cut(operations, threshold):
+        """apd_dendrogram_cut: the prefix of `operations` a run at `threshold` performs -- the loop condition of clustering.rs:104-108
+        replayed, so the operation that reaches the threshold is kept; a NaN threshold or one <= 0 keeps nothing."""
+        n_kept = C.c_uint32(0)
+        _lib.check(_lib.lib().apd_dendrogram_cut(_c_ops(operations), len(operations), float(threshold), C.byref(n_kept)))
+        return list(operations[:n_kept.value])
+
+    @staticmethod
+    def assignment(operations, n_instances):
+        """clustering.rs:115-128 after the merges of `operations` (apd_cut_labels): uint32[n], every instance's root -- its own
+        number for an instance never merged.  A list that is not a dendrogram over n_instances raises ApdError(APD_ERR_INVALID_ARG)."""
+        labels = np.zeros(n_instances, dtype=np.uint32)
+        keep = np.zeros(max(n_instances, 1), dtype=np.uint32)                  # (a pointer that is never NULL)
+        _lib.check(_lib.lib().apd_cut_labels(_c_ops(operations), len(operations), n_instances, keep.ctypes.data_as(C.POINTER(C.c_uint32))))
+        labels[:] = keep[:n_instances]
+        return labels
+
+    @staticmethod
+    def sweep(distances, n_instances, percs, axis=0, ctx=None, return_operations=False):
+        """One UPGMA run, every percentile of `percs` as a cut of its dendrogram, the silhouette of all cuts in one apd_silhouette:
+        the matrix is uploaded once, apd_clustering runs at max(percs), each threshold is apd_percentile on the resident matrix.
+        Returns per percentile, in the order given, (perc, threshold, n_ops, n_clusters, score, nans); the first n_ops operations
+        of the run are what clustering() returns at that percentile.  With return_operations: (rows, the run's operations)."""
+        ctx = ctx or _lib.default_context()
+        d = np.ascontiguousarray(distances, dtype=np.float32).ravel()
+        n = int(n_instances)
+        if d.size != n * n:
+            raise ValueError("distances must hold n_instances^2 values")
+        percs = [float(p) for p in percs]
+        if not percs:
+            return ([], []) if return_operations else []
+        L = _lib.lib()
+        buf = ctx.upload(d) if d.size else ctx.alloc(16)
+        try:
+            ops = (_lib.ClusterOp * max(n, 1))()
+            roots = np.zeros(max(n, 1), dtype=np.uint32)
+            n_ops, n_roots, thr = C.c_uint32(0), C.c_uint32(0), C.c_float(0)
+            _lib.check(L.apd_clustering(ctx.handle, buf.at(), 1, n, max(percs), ops, C.byref(n_ops), roots.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        C.byref(n_roots), C.byref(thr)), ctx.handle)
+            operations = [ClusteringOperation(o.merge_i, o.merge_j, o.into, o.distance, Merge(o.operation)) for o in ops[:n_ops.value]]
+            thresholds, kept = [], []
+            labels = np.zeros((len(percs), n), dtype=np.uint32)
+            for c, p in enumerate(percs):
+                v = C.c_float(0)
+                _lib.check(L.apd_percentile(ctx.handle, buf.at(), d.size, p, 1, C.byref(v)), ctx.handle)
+                thresholds.append(float(v.value))
+                kept.append(len(AgglomerativeClustering.cut(operations, v.value)))
+                labels[c] = AgglomerativeClustering.assignment(operations[:kept[c]], n)
+            score, clusters, nans = silhouette((buf.at(), n), labels, axis=axis, ctx=ctx, on_device=True)
+        finally:
+            buf.free()
+        rows = [(percs[c], thresholds[c], kept[c], int(clusters[c]), float(score[c]), int(nans[c])) for c in range(len(percs))]
+        return (rows, operations) if return_operations else rows
+
+
+def _c_ops(operations):
+    ops = (_lib.ClusterOp * max(len(operations), 1))()
+    for t, o in enumerate(operations):
+        ops[t] = _lib.ClusterOp(o.merge_i, o.merge_j, o.into, o.distance, int(o.operation))
+    return ops
+
+
+def silhouette(distances, labels, axis=0, samples=False, ctx=None, on_device=False):
+    """apd_silhouette: the silhouette of cluster assignments over the [n][n] matrix of AlignmentWorkers.align_all.  labels: [n], or
+    [L][n] for L assignments scored in one pass over the matrix; arbitrary uint32 values.  axis=0: dist(i, y) = distances[i][y],
+    axis=1: distances[y][i] (the matrix is directed).  Per assignment a(i) is the mean distance to the other members of i's cluster
+    (ascending f32 chain, the diagonal skipped), b(i) the smallest such mean over the other clusters (the smaller label among equals,
+    NaN never), s(i) = (b - a) / max(a, b), 0 for a singleton, NaN where the arithmetic gives one; score is the sequential mean of
+    the non-NaN s(i).  With on_device the matrix is (device pointer, n) and stays in HBM, as do the results until they are read here.
+    Returns (score float32, clusters uint32, nans uint32) -- scalars for an [n] labels, [L] arrays otherwise -- and with samples also
+    (s, a, b, nearest): float32 / uint32 [n] or [L][n]; nearest[i] is the label b(i) came from, 0xFFFFFFFF if none."""
+    ctx = ctx or _lib.default_context()
+    lab = np.ascontiguousarray(labels, dtype=np.uint32)
+    single = lab.ndim == 1
+    lab = lab.reshape(1, -1) if single else lab
+    if lab.ndim != 2:
+        raise ValueError("labels must be [n] or [L][n]")
+    if on_device:
+        ptr, n = distances
+        ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+    else:
+        d = np.ascontiguousarray(distances, dtype=np.float32)
+        n = int(round(d.size ** 0.5))
+        if d.size != n * n:
+            raise ValueError("distances must hold n^2 values")
+        ptr = C.c_void_p(d.ctypes.data)
+    if lab.shape[1] != n:
+        raise ValueError("labels must hold n values per assignment")
+    cuts = lab.shape[0]
+    per_cut = [np.zeros(cuts, np.float32), np.zeros(cuts, np.uint32), np.zeros(cuts, np.uint32)]
+    per_sample = [np.zeros((cuts, n), t) for t in (np.float32, np.float32, np.float32, np.uint32)] if samples else []
+    outs = per_cut + per_sample
+    head = (ctx.handle, ptr, int(bool(on_device)), n, int(axis), lab.ctypes.data_as(C.POINTER(C.c_uint32)), cuts)
+    none = [None] * (4 - len(per_sample))
+    if not on_device:
+        _lib.check(_lib.lib().apd_silhouette(*head, *[C.c_void_p(o.ctypes.data) for o in outs], *none), ctx.handle)
+    else:
+        bufs = [ctx.alloc(max(o.nbytes, 16)) for o in outs]
+        try:
+            _lib.check(_lib.lib().apd_silhouette(*head, *[b.at() for b in bufs], *none), ctx.handle)
+            for o, b in zip(outs, bufs):
+                if o.size:
+                    o[...] = b.to_numpy(o.dtype, o.size).reshape(o.shape)     # the copy waits for the context's stream
+        finally:
+            for b in bufs:
+                b.free()
+    if single:
+        outs = [o[0] for o in outs]
+    return (tuple(outs[:3]), tuple(outs[3:])) if samples else tuple(outs)
+
 
 def cross_linkage(fs, sf, sets, ctx=None):
     """apd_cross_linkage: the reference's average linkage (clustering.rs:153-170) between every first-set sequence q and every

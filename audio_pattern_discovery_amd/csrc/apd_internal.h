@@ -627,6 +627,11 @@ hipError_t launch_cross_linkage(const float *d_fs, const float *d_sf, uint32_t n
 // clustering.hip: the two kernels of apd_cluster_medoids.  d_members: sorted ascending per set; d_keys: [n_sets] workspace.
 hipError_t launch_cluster_medoids(const float *d_dist, uint32_t n, const uint32_t *d_members, const uint32_t *d_set_off, uint32_t n_sets,
                                   uint32_t n_members, unsigned long long *d_keys, uint32_t *d_medoid, float *d_cost, hipStream_t stream);
+// neighbors.hip: panel[s][y] = d[y][column of slot q_first + s] for s < n_slots, y < rows (d: [rows][cols]; d_queries null: slot s is
+// column s), 64 x 64 tiles through LDS; `stride` floats from a panel row to the next.  The column forms of apd_neighbors and
+// apd_silhouette.  n_slots, rows > 0.
+hipError_t launch_column_gather(const float *d, uint32_t rows, uint32_t cols, const uint32_t *d_queries, uint32_t q_first, uint32_t n_slots,
+                                float *panel, uint64_t stride, hipStream_t stream);
 hipError_t launch_sqrt_sweep(uint32_t first, uint64_t count, unsigned long long *d_out, hipStream_t stream);
 // The feature range of the fast kernels: a batch is theirs when every feature is 0 or has kFeatureFloor <= |v| < kFeatureBound;
 // any other value (NaN and the infinities included) raises the batch's flag, and the literal kernel aligns every pair.
@@ -774,7 +779,7 @@ struct apd_context {
     apd::DeviceBuf ws_spot_hits;      // apd_spot_detect: the packed hits of a chunk
     apd::DeviceBuf ws_spot_dirs;      // apd_spot_paths: direction words of the intervals of a chunk of windows
     apd::DeviceBuf ws_spot_steps;     // apd_spot_paths, apd_spot_stream_paths: steps, descriptors and results of a chunk of windows
-    apd::DeviceBuf ws_neighbors;      // apd_neighbors, column form: the [panel][rows] gather of the queried columns (bounded)
+    apd::DeviceBuf ws_neighbors;      // apd_neighbors, apd_silhouette, column form: the [panel][rows] gather of the queried columns (bounded)
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

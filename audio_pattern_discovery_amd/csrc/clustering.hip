@@ -1745,3 +1745,35 @@ extern "C" int apd_cluster_sets(const apd_cluster_op *ops, uint32_t n_ops, const
     *n_sets = ns;
     return APD_OK;
 }
+
+// The loop condition of clustering.rs:104-108 replayed over a recorded merge list: how many of its first operations a run at
+// `threshold` performs.  The operation that reaches the threshold is kept, as the reference keeps it.
+extern "C" int apd_dendrogram_cut(const apd_cluster_op *ops, uint32_t n_ops, float threshold, uint32_t *n_kept)
+{
+    if ((n_ops && !ops) || !n_kept) return APD_ERR_INVALID_ARG;
+    uint32_t kept = 0;
+    float distance = 0.0f;
+    while (kept < n_ops && distance < threshold) { distance = ops[kept].distance; ++kept; }   // a NaN threshold keeps nothing
+    *n_kept = kept;
+    return APD_OK;
+}
+
+// assignment() (clustering.rs:115-128) after the first n_kept merges (merge_clusters, clustering.rs:134-141): every instance's root.
+extern "C" int apd_cut_labels(const apd_cluster_op *ops, uint32_t n_kept, uint32_t n, uint32_t *labels)
+{
+    if ((n_kept && !ops) || (n && !labels)) return APD_ERR_INVALID_ARG;
+    const uint64_t ids = (uint64_t)n + n_kept;
+    if (ids > 0xFFFFFFFFull) return APD_ERR_INVALID_ARG;
+    std::vector<uint32_t> parents(ids);
+    for (uint64_t p = 0; p < ids; ++p) parents[p] = (uint32_t)p;
+    for (uint32_t t = 0; t < n_kept; ++t) {
+        const uint32_t p = ops[t].merge_i, q = ops[t].merge_j, k = n + t;
+        // a current root: an instance or an earlier node, not merged since
+        if (ops[t].into != k || p == q || p >= k || q >= k || parents[p] != p || parents[q] != q) return APD_ERR_INVALID_ARG;
+        parents[p] = k;                                                                            // :136-137
+        parents[q] = k;
+    }
+    for (uint64_t p = ids; p-- > 0;) parents[p] = parents[parents[p]];   // a parent's number is larger: roots first, then everyone's root
+    for (uint32_t i = 0; i < n; ++i) labels[i] = parents[i];
+    return APD_OK;
+}

@@ -277,6 +277,16 @@ int launch_select(apd_context *ctx, SelectParams S, uint32_t n_q, uint32_t resid
 
 }  // namespace
 
+// The gather's launch, shared with the column form of apd_silhouette (silhouette.hip).  n_slots, rows > 0.
+hipError_t apd::launch_column_gather(const float *d, uint32_t rows, uint32_t cols, const uint32_t *d_queries, uint32_t q_first,
+                                     uint32_t n_slots, float *panel, uint64_t stride, hipStream_t stream)
+{
+    const uint64_t tiles = (uint64_t)((rows + 63) / 64) * ((n_slots + 63) / 64);
+    hipLaunchKernelGGL(neighbors_gather_kernel, dim3((unsigned)std::min<uint64_t>(tiles, 65536)), dim3(256), 0, stream, d, rows, cols, d_queries,
+                       q_first, n_slots, panel, stride);
+    return hipGetLastError();
+}
+
 // Workspaces, both owned by the context so that the device form only enqueues: ws_misc [query list | host form: matrix | index |
 // distance | count | nans], ws_neighbors the column form's panel.
 extern "C" int apd_neighbors(apd_context *ctx, const float *distances, int on_device, uint32_t rows, uint32_t cols, int axis,
@@ -333,12 +343,7 @@ extern "C" int apd_neighbors(apd_context *ctx, const float *distances, int on_de
         S.src = panel; S.stride = panel_stride; S.from_panel = 1;
         for (uint64_t at = 0; at < n_q; at += panel_cols) {                           // the stream orders a panel's select before its refill
             const uint32_t first = (uint32_t)at, part = std::min(panel_cols, n_q - first);
-            if (n) {
-                const uint64_t tiles = (uint64_t)((n + 63) / 64) * ((part + 63) / 64);
-                hipLaunchKernelGGL(neighbors_gather_kernel, dim3((unsigned)std::min<uint64_t>(tiles, 65536)), dim3(256), 0, ctx->stream, d_mat, rows,
-                                   cols, d_queries, first, part, panel, panel_stride);
-                HIP_TRY(ctx, hipGetLastError());
-            }
+            if (n) HIP_TRY(ctx, launch_column_gather(d_mat, rows, cols, d_queries, first, part, panel, panel_stride, ctx->stream));
             S.q_first = first;
             if (const int rc = launch_select(ctx, S, part, resident_columns)) return rc;
         }

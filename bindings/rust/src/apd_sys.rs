@@ -272,6 +272,12 @@ extern "C" {
     pub fn apd_neighbors(ctx: *mut apd_context, distances: *const f32, on_device: c_int, rows: u32, cols: u32, axis: c_int,
                          queries: *const u32, n_queries: u32, k: u32, skip_self: c_int, index: *mut u32, distance: *mut f32,
                          count: *mut u32, nans: *mut u32) -> c_int;
+    // cuts of a dendrogram (host only) and their silhouette (axis as for apd_neighbors; labels: host [n_cuts][n])
+    pub fn apd_dendrogram_cut(ops: *const apd_cluster_op, n_ops: u32, threshold: f32, n_kept: *mut u32) -> c_int;
+    pub fn apd_cut_labels(ops: *const apd_cluster_op, n_kept: u32, n: u32, labels: *mut u32) -> c_int;
+    pub fn apd_silhouette(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, axis: c_int, labels: *const u32,
+                          n_cuts: u32, score: *mut f32, clusters: *mut u32, nans: *mut u32, s: *mut f32, a: *mut f32, b: *mut f32,
+                          nearest: *mut u32) -> c_int;
     // cluster prototypes
     pub fn apd_cluster_medoids(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, members: *const u32,
                                set_off: *const u32, n_sets: u32, medoid: *mut u32, cost: *mut f32) -> c_int;

@@ -120,6 +120,41 @@ impl AgglomerativeClustering {
         (0..n_queries).map(|q| (0..count[q] as usize).map(|s| (index[q * k + s] as usize, distance[q * k + s])).collect()).collect()
     }
 
+    /// Not in the reference: the prefix of `operations` a run at `threshold` performs (apd_dendrogram_cut: the loop condition of
+    /// clustering.rs:104-108 replayed; the operation that reaches the threshold is kept).
+    pub fn dendrogram_cut(operations: &[ClusteringOperation], threshold: f32) -> &[ClusteringOperation] {
+        let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();
+        let mut n_kept = 0u32;
+        unsafe { check(apd_dendrogram_cut(ops.as_ptr(), ops.len() as u32, threshold, &mut n_kept)); }
+        &operations[..n_kept as usize]
+    }
+
+    /// clustering.rs:115-128 (private there) after the merges of `operations`: every instance's root, singletons their own number
+    /// (apd_cut_labels).  Panics on a list that is not a dendrogram over n_instances.
+    pub fn assignment(operations: &[ClusteringOperation], n_instances: usize) -> Vec<usize> {
+        let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();
+        let mut labels = vec![0u32; n_instances.max(1)];
+        unsafe { check(apd_cut_labels(ops.as_ptr(), ops.len() as u32, n_instances as u32, labels.as_mut_ptr())); }
+        labels[..n_instances].iter().map(|l| *l as usize).collect()
+    }
+
+    /// Not in the reference: the silhouette of every assignment in `labels` (n_instances labels each, as `assignment` returns them)
+    /// over the n x n matrix of align_all (apd_silhouette); `by_columns` false: dist(i, y) = distances[i][y], true: distances[y][i].
+    /// Per assignment (score, distinct labels, instances whose silhouette is NaN).
+    pub fn silhouette(distances: &[f32], n_instances: usize, labels: &[Vec<usize>], by_columns: bool) -> Vec<(f32, usize, usize)> {
+        let flat: Vec<u32> = labels.iter().flat_map(|l| l.iter().map(|v| *v as u32)).collect();
+        let cuts = labels.len();
+        let mut score = vec![0f32; cuts.max(1)];
+        let mut clusters = vec![0u32; cuts.max(1)];
+        let mut nans = vec![0u32; cuts.max(1)];
+        with_context(|ctx| unsafe {
+            check(apd_silhouette(ctx, distances.as_ptr(), 0, n_instances as u32, if by_columns { APD_NEIGHBORS_COLUMNS } else { APD_NEIGHBORS_ROWS },
+                                 flat.as_ptr(), cuts as u32, score.as_mut_ptr(), clusters.as_mut_ptr(), nans.as_mut_ptr(),
+                                 std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()));
+        });
+        (0..cuts).map(|c| (score[c], clusters[c] as usize, nans[c] as usize)).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

@@ -769,6 +769,17 @@ int apd_clustering(apd_context *ctx, const float *distances, int distances_on_de
  * members capacity >= n + n_ops + 2, set_off capacity >= n_roots+1. */
 int apd_cluster_sets(const apd_cluster_op *ops, uint32_t n_ops, const uint32_t *roots, uint32_t n_roots,
                      uint32_t n, uint32_t *members, uint32_t *set_off, uint32_t *n_sets);
+/* Cuts of a dendrogram; host-only bookkeeping.  The merge sequence does not depend on the threshold, so a run of apd_clustering at a
+ * lower threshold is a prefix of a run at a higher one.  apd_dendrogram_cut replays the loop condition of clustering.rs:104-108:
+ *   kept = 0; distance = 0.0f; while (kept < n_ops && distance < threshold) { distance = ops[kept].distance; ++kept; }
+ * so the operation that reaches the threshold is kept, as the reference keeps it, and a NaN threshold or one <= 0 keeps nothing.  If
+ * ops came from apd_clustering at threshold T, then for t <= T the first *n_kept of them are exactly what apd_clustering returns at t.
+ * apd_cut_labels is assignment() (clustering.rs:115-128) after the first n_kept merges: labels[i] = i for an instance never merged,
+ * otherwise the `into` of the last kept operation whose subtree holds i -- singletons keep a label, which apd_cluster_sets cannot
+ * give.  labels: [n].  APD_ERR_INVALID_ARG, with nothing written, unless for every operation t < n_kept: into == n + t, and merge_i
+ * and merge_j are distinct and each a current root (an instance < n or an earlier `into`, not merged since). */
+int apd_dendrogram_cut(const apd_cluster_op *ops, uint32_t n_ops, float threshold, uint32_t *n_kept);
+int apd_cut_labels(const apd_cluster_op *ops, uint32_t n_kept, uint32_t n, uint32_t *labels);
 
 /* Average linkage of every first-set sequence to clusters of the second set, from the two cross matrices of apd_align_cross:
  * clustering.rs:153-170 with each first-set sequence q as a cluster of its own and set k of the second set as the other:
@@ -818,6 +829,40 @@ int apd_cross_linkage(apd_context *ctx, const float *fs, const float *sf, int on
 int apd_neighbors(apd_context *ctx, const float *distances, int on_device, uint32_t rows, uint32_t cols, int axis,
                   const uint32_t *queries, uint32_t n_queries, uint32_t k, int skip_self,
                   uint32_t *index, float *distance, uint32_t *count, uint32_t *nans);
+
+/* ---- silhouette: how well n_cuts cluster assignments ("cuts") fit the distance matrix, in one pass over it ---------------------
+ * distances: the [n][n] matrix of apd_align_all.  labels: HOST [n_cuts][n], arbitrary uint32 values per cut (they need not be dense;
+ * apd_cut_labels gives them for cuts of a dendrogram).  The matrix is directed, so axis chooses as for apd_neighbors:
+ * APD_NEIGHBORS_ROWS: dist(i, y) = d[i][y] ({i} is the x cluster of clustering.rs:153-170); APD_NEIGHBORS_COLUMNS: dist(i, y) = d[y][i].
+ * Bit for bit, for cut c and instance i, with C(y) the label of y in that cut:
+ *   sum(i, L) = ((0.0f + dist(i, y1)) + dist(i, y2)) + ... over the y with C(y) == L and y != i, ascending: f32, one rounded add per
+ *     term; the diagonal entry is skipped, not added.  cnt(i, L): the number of terms.
+ *   a(i) = sum(i, C(i)) / (float)cnt(i, C(i)); a singleton (cnt(i, C(i)) == 0) has a(i) = 0.0f and s(i) = 0.0f.
+ *   b(i), nearest(i): scan the labels L != C(i) in ascending label value, mean = sum(i, L) / (float)cnt(i, L); keep a mean only if it is
+ *     strictly below the best so far under IEEE `<`, starting from +INF -- the smaller label wins ties, -0.0 and +0.0 tie, NaN is
+ *     never kept.  nearest(i) is the kept label; nothing kept: b = +INF, nearest = 0xFFFFFFFF.
+ *   a non-singleton: m = (a < b) ? b : a; s(i) = (b - a) / m, one subtraction and one division.  NaN falls out of the arithmetic
+ *     and is not patched (a single cluster, a = b = 0, a NaN in the row); which NaN an operation makes (sign, payload) is the
+ *     hardware's choice, not this contract's.
+ *   clusters[c]: the distinct labels of the cut; nans[c]: the i with NaN s(i);
+ *   score[c] = (((0.0f + s(i1)) + s(i2)) + ...) / (float)kept over the non-NaN s(i), i ascending; kept == 0: a quiet NaN (0x7FC00000).
+ * For L != C(i) and ROWS, mean(i, L) is the bits of apd_cross_linkage's link_fs[i][L] with fs = the matrix.
+ * A function of the matrix and the labels alone: no workgroup size, schedule, LDS limit, panel cut or number of cuts per call enters
+ * it; a call with L cuts equals L calls with one cut.
+ * score, clusters, nans: [n_cuts]; s, a, b, nearest: [n_cuts][n], each may be NULL.  distances and the outputs: host, or all device
+ * pointers if on_device (the call waits once for the upload of the label tables -- once per 1024 cuts -- and the kernels are only
+ * enqueued on the context's stream, as apd_cross_linkage does).  Otherwise the call blocks.
+ * APD_ERR_INVALID_ARG, before anything is launched or written: another axis, n_cuts == 0, a NULL labels, score, clusters or nans.
+ * n == 0: APD_OK with NaN scores and zero counts.  A workspace that does not fit: APD_ERR_OOM.  Workspace: 8 n bytes per cut and 16
+ * bytes per (cut, cluster), n floats per cut more when s is NULL; the host form also holds the matrix and the results.
+ * Rows of up to 32768 entries are staged in LDS once; longer ones are read from HBM.  COLUMNS gathers the columns into a [panel][n]
+ * workspace of the context (256 MiB, shared with apd_neighbors) and walks its rows, in as many panels as it takes.
+ * Environment (tests only; read at every call; results are bit-identical whatever they say): APD_SILHOUETTE_WORKGROUP=<64 .. 1024, a
+ * multiple of 64> sets the work-items of a row's workgroup, APD_SILHOUETTE_LDS_COLUMNS=<entries> lowers the LDS residency limit,
+ * APD_SILHOUETTE_WORKSPACE_BYTES=<bytes> sets the panel workspace (at least one column is taken). */
+int apd_silhouette(apd_context *ctx, const float *distances, int on_device, uint32_t n, int axis,
+                   const uint32_t *labels, uint32_t n_cuts, float *score, uint32_t *clusters, uint32_t *nans,
+                   float *s, float *a, float *b, uint32_t *nearest);
 
 /* ---- cluster prototypes: which member stands for a cluster, and the cluster's average shape ---------------------------------
  * The medoid of every set: the member closest to all the others, from the [n][n] matrix of apd_align_all.  For set k with its
