@@ -26,6 +26,9 @@ APD_QUANTILES_PER_PAIR, APD_QUANTILES_PER_QUERY, APD_QUANTILES_ALL = 0, 1, 2    
 APD_SPOT_QUANTILES_MAX = 8
 APD_NEIGHBORS_ROWS, APD_NEIGHBORS_COLUMNS = 0, 1                                # apd_neighbors' axes
 APD_NEIGHBORS_MAX_K = 1024
+APD_DENSITY_EITHER, APD_DENSITY_BOTH = 0, 1                                      # apd_density_clusters' links
+APD_DENSITY_MAX_SETTINGS = 8
+APD_DENSITY_NOISE, APD_DENSITY_BORDER, APD_DENSITY_CORE = 0, 1, 2                # ... and its kinds
 APD_SPOT_QUANTILES_COLUMNS = 256         # columns a workgroup of the select takes per step (tests place stream lengths around it)
 
 
@@ -214,6 +217,8 @@ SYMBOLS = [
     ("apd_dendrogram_cut", C.c_int, [C.POINTER(ClusterOp), C.c_uint32, C.c_float, _u32p]),
     ("apd_cut_labels", C.c_int, [C.POINTER(ClusterOp), C.c_uint32, C.c_uint32, _u32p]),
     ("apd_silhouette", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, _u32p, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("apd_density_clusters", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, _f32p, _u32p, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    ("apd_density_last_profile", C.c_int, [_vp, _f32p, _u32p]),
     ("apd_encoder_create", C.c_int, [_vp, _f32p, _f32p, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     ("apd_encoder_destroy", C.c_int, [_vp]),
     ("apd_encode_async", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp]),

@@ -174,6 +174,79 @@ def silhouette(distances, labels, axis=0, samples=False, ctx=None, on_device=Fal
     return (tuple(outs[:3]), tuple(outs[3:])) if samples else tuple(outs)
 
 
+def density(distances, eps, min_pts, link="either", ctx=None, on_device=False, details=False):
+    """apd_density_clusters: DBSCAN over the [n][n] matrix of AlignmentWorkers.align_all.  near(i, j) is distances[i][j] <= eps (a NaN
+    is never near); the matrix is directed, so link="either" joins i and j when one direction is near, "both" when both are.  A point
+    with at least min_pts - 1 such neighbours is a core point (it counts itself, scikit-learn's convention: the k-th distance of
+    neighbors(..., k, skip_self=True) as eps with min_pts = k + 1 makes the point core); clusters are the connected components of the
+    core points, labelled by their smallest member; a non-core neighbour of core points is a border point and takes the smallest
+    label among them; everything else is noise and keeps its own number, so the labels go straight into silhouette().
+    eps, min_pts: scalars, or sequences of S settings (a scalar beside a sequence is repeated) answered from one pass over the matrix.
+    With on_device the matrix is (device pointer, n) and stays in HBM.  Returns (labels uint32, counts uint32): [n] and [4] for
+    scalars, [S][n] and [S][4] otherwise; counts = clusters, core, border, noise points.  With details also (kind uint8, degree
+    uint32, nans int): kind 0 noise, 1 border, 2 core; nans the NaN entries off the diagonal."""
+    ctx = ctx or _lib.default_context()
+    single = np.ndim(eps) == 0 and np.ndim(min_pts) == 0
+    e = np.atleast_1d(np.asarray(eps, dtype=np.float32)).ravel()
+    m = np.atleast_1d(np.asarray(min_pts, dtype=np.int64)).ravel()
+    if len(e) != len(m):
+        if 1 not in (len(e), len(m)):
+            raise ValueError("eps and min_pts must hold the same number of settings")
+        e, m = np.repeat(e, len(m)) if len(e) == 1 else e, np.repeat(m, len(e)) if len(m) == 1 else m
+    if len(e) == 0 or (m < 0).any() or (m > 0xFFFFFFFF).any():
+        raise ValueError("at least one setting, and min_pts within 32 bits")
+    e, m = np.ascontiguousarray(e), np.ascontiguousarray(m.astype(np.uint32))
+    link = {"either": _lib.APD_DENSITY_EITHER, "both": _lib.APD_DENSITY_BOTH}.get(link, link)
+    if on_device:
+        ptr, n = distances
+        ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+    else:
+        d = np.ascontiguousarray(distances, dtype=np.float32)
+        n = int(round(d.size ** 0.5))
+        if d.size != n * n:
+            raise ValueError("distances must hold n^2 values")
+        ptr = C.c_void_p(d.ctypes.data)
+    S = len(e)
+    labels, counts = np.zeros((S, n), np.uint32), np.zeros((S, 4), np.uint32)
+    kind, degree, nans = np.zeros((S, n), np.uint8), np.zeros((S, n), np.uint32), np.zeros(1, np.uint64)
+    L, f32p, u32p = _lib.lib(), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    for s0 in range(0, S, _lib.APD_DENSITY_MAX_SETTINGS):                     # a call with S settings equals S calls with one
+        s1 = min(s0 + _lib.APD_DENSITY_MAX_SETTINGS, S)
+        head = (ctx.handle, ptr, int(bool(on_device)), n, int(link), e[s0:s1].ctypes.data_as(f32p), m[s0:s1].ctypes.data_as(u32p), s1 - s0)
+        outs = [labels[s0:s1], kind[s0:s1] if details else None, degree[s0:s1] if details else None, counts[s0:s1], nans if details else None]
+        if not on_device:
+            _lib.check(L.apd_density_clusters(*head, *[None if o is None else C.c_void_p(o.ctypes.data) for o in outs]), ctx.handle)
+            continue
+        bufs = [None if o is None else ctx.alloc(max(o.nbytes, 16)) for o in outs]
+        try:
+            _lib.check(L.apd_density_clusters(*head, *[None if b is None else b.at() for b in bufs]), ctx.handle)
+            for o, b in zip(outs, bufs):
+                if o is not None and o.size:
+                    o[...] = b.to_numpy(o.dtype, o.size).reshape(o.shape)
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+    if single:
+        labels, counts, kind, degree = labels[0], counts[0], kind[0], degree[0]
+    return ((labels, counts), (kind, degree, int(nans[0]))) if details else (labels, counts)
+
+
+def density_sets(labels, kind):
+    """The clusters of one density() assignment in apd_cluster_sets' layout, for medoids, barycenters and cross_linkage: (members,
+    set_off) with set k = members[set_off[k]:set_off[k + 1]].  Host only.  Noise is left out; the sets ascend by label and the
+    members inside a set ascend."""
+    lab, kd = np.asarray(labels, dtype=np.uint32).ravel(), np.asarray(kind, dtype=np.uint8).ravel()
+    if lab.shape != kd.shape:
+        raise ValueError("labels and kind must hold one value per instance")
+    kept = np.flatnonzero(kd != _lib.APD_DENSITY_NOISE)
+    order = kept[np.argsort(lab[kept], kind="stable")]                        # by (label, index)
+    sizes = np.unique(lab[kept], return_counts=True)[1]
+    set_off = np.zeros(len(sizes) + 1, np.uint32)
+    set_off[1:] = np.cumsum(sizes)
+    return order.astype(np.uint32), set_off
+
+
 def cross_linkage(fs, sf, sets, ctx=None):
     """apd_cross_linkage: the reference's average linkage (clustering.rs:153-170) between every first-set sequence q and every
     set of second-set sequence numbers in `sets` (as cluster_sets returns them; any order inside a set), from the cross matrices

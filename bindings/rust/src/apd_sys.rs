@@ -87,6 +87,12 @@ pub const APD_SPOT_QUANTILES_MAX: usize = 8;
 pub const APD_NEIGHBORS_ROWS: c_int = 0;
 pub const APD_NEIGHBORS_COLUMNS: c_int = 1;
 pub const APD_NEIGHBORS_MAX_K: usize = 1024;
+pub const APD_DENSITY_EITHER: c_int = 0;
+pub const APD_DENSITY_BOTH: c_int = 1;
+pub const APD_DENSITY_MAX_SETTINGS: usize = 8;
+pub const APD_DENSITY_NOISE: u8 = 0;
+pub const APD_DENSITY_BORDER: u8 = 1;
+pub const APD_DENSITY_CORE: u8 = 2;
 
 /// A window of stream y matched to query x (apd_spot_paths): end and start as in apd_spot_best.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
@@ -278,6 +284,11 @@ extern "C" {
     pub fn apd_silhouette(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, axis: c_int, labels: *const u32,
                           n_cuts: u32, score: *mut f32, clusters: *mut u32, nans: *mut u32, s: *mut f32, a: *mut f32, b: *mut f32,
                           nearest: *mut u32) -> c_int;
+    // density clustering (link: APD_DENSITY_EITHER / APD_DENSITY_BOTH; eps, min_pts: host [n_settings]; blocking in both forms)
+    pub fn apd_density_clusters(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, link: c_int, eps: *const f32,
+                                min_pts: *const u32, n_settings: u32, labels: *mut u32, kind: *mut u8, degree: *mut u32,
+                                counts: *mut u32, nans: *mut u64) -> c_int;
+    pub fn apd_density_last_profile(ctx: *mut apd_context, phase_ms: *mut f32, rounds: *mut u32) -> c_int;
     // cluster prototypes
     pub fn apd_cluster_medoids(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, members: *const u32,
                                set_off: *const u32, n_sets: u32, medoid: *mut u32, cost: *mut f32) -> c_int;

@@ -155,6 +155,28 @@ impl AgglomerativeClustering {
         (0..cuts).map(|c| (score[c], clusters[c] as usize, nans[c] as usize)).collect()
     }
 
+    /// Not in the reference: DBSCAN over the n x n matrix of align_all for every (eps, min_pts) of `settings`, at most
+    /// APD_DENSITY_MAX_SETTINGS of them, in one pass over the matrix (apd_density_clusters).  `both` false: i and j are neighbours when
+    /// distances[i][j] <= eps or distances[j][i] <= eps, true: when both are.  Per setting (labels, kind, [clusters, core, border,
+    /// noise]): a core point's label is the smallest core point of its component, a border point's the smallest label among its core
+    /// neighbours, a noise point's its own number -- what `silhouette` takes; kind is APD_DENSITY_NOISE, _BORDER or _CORE.
+    pub fn density(distances: &[f32], n_instances: usize, settings: &[(f32, usize)], both: bool) -> Vec<(Vec<usize>, Vec<u8>, [usize; 4])> {
+        let eps: Vec<f32> = settings.iter().map(|s| s.0).collect();
+        let min_pts: Vec<u32> = settings.iter().map(|s| s.1 as u32).collect();
+        let count = settings.len();
+        let mut labels = vec![0u32; (count * n_instances).max(1)];
+        let mut kind = vec![0u8; (count * n_instances).max(1)];
+        let mut counts = vec![0u32; (count * 4).max(1)];
+        with_context(|ctx| unsafe {
+            check(apd_density_clusters(ctx, distances.as_ptr(), 0, n_instances as u32, if both { APD_DENSITY_BOTH } else { APD_DENSITY_EITHER },
+                                       eps.as_ptr(), min_pts.as_ptr(), count as u32, labels.as_mut_ptr(), kind.as_mut_ptr(), std::ptr::null_mut(),
+                                       counts.as_mut_ptr(), std::ptr::null_mut()));
+        });
+        (0..count).map(|s| (labels[s * n_instances..(s + 1) * n_instances].iter().map(|l| *l as usize).collect(),
+                            kind[s * n_instances..(s + 1) * n_instances].to_vec(),
+                            [counts[4 * s] as usize, counts[4 * s + 1] as usize, counts[4 * s + 2] as usize, counts[4 * s + 3] as usize])).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

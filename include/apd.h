@@ -864,6 +864,53 @@ int apd_silhouette(apd_context *ctx, const float *distances, int on_device, uint
                    const uint32_t *labels, uint32_t n_cuts, float *score, uint32_t *clusters, uint32_t *nans,
                    float *s, float *a, float *b, uint32_t *nearest);
 
+/* ---- density clustering: which instances recur at least min_pts times within eps, and which are alone (DBSCAN) -----------------
+ * distances: the [n][n] matrix of apd_align_all.  eps, min_pts: HOST arrays of n_settings (<= APD_DENSITY_MAX_SETTINGS) settings, all
+ * answered from one pass over the matrix.  The matrix is directed and components need a symmetric relation, so for setting s:
+ *   near(i, j) := d[i][j] <= eps[s] under IEEE comparison: a NaN entry or a NaN eps is never near, -0.0 and +0.0 are equal, eps = +INF
+ *     makes every non-NaN entry near, +INF included.
+ *   for i != j: adj(i, j) := near(i, j) || near(j, i) (APD_DENSITY_EITHER), near(i, j) && near(j, i) (APD_DENSITY_BOTH).  The value on
+ *     the diagonal enters nothing.
+ *   degree[i] = the number of j != i with adj(i, j).  i is a core point iff (uint64)degree[i] + 1 >= min_pts[s]: the point counts
+ *     itself and the comparison is <=, scikit-learn's DBSCAN convention -- the k-th neighbour distance of i from apd_neighbors
+ *     (skip_self) as eps with min_pts = k + 1 makes i core.
+ *   labels: clusters are the connected components of adj restricted to core points; a core point's label is the smallest core point
+ *     of its component.  A non-core point with at least one core neighbour is a border point, its label the smallest label among its
+ *     core neighbours (a fixed rule where the textbook algorithm depends on the visiting order).  Every other point is noise with
+ *     labels[i] = i, apd_cut_labels' idiom for an instance never merged; it cannot collide with a cluster, whose label is a core
+ *     point's number.  So labels[s] is always a valid assignment for apd_silhouette, noise as singletons.
+ *   kind[i]: APD_DENSITY_NOISE, _BORDER or _CORE.  counts[s] = {distinct cluster labels, core, border, noise points}; the last three
+ *     sum to n.  nans: the NaN entries off the diagonal.
+ * Every bit of the result is decided by one comparison per entry; everything behind it is integer (ballots, popcounts, minima of
+ * numbers).  A function of the matrix and the settings alone: no workgroup size, schedule, round count, workspace size or number of
+ * settings per call enters it; a call with S settings equals S calls with one.
+ * labels, degree: [n_settings][n] uint32, kind: [n_settings][n] bytes, counts: [n_settings][4], nans: one value; kind, degree and nans
+ * may be NULL.  distances and the outputs: host, or all device pointers if on_device.  BLOCKING IN BOTH FORMS, unlike apd_neighbors
+ * (whose kernels are only enqueued): the component search converges on the device -- minimum-label propagation with hooking and
+ * pointer jumping, with no bound on its rounds other than n -- and the host reads a "changed" word between batches of rounds.  With
+ * apd_set_timing on, apd_last_kernel_ms covers the call's kernels and apd_density_last_profile splits them: phase_ms[4] = adjacency,
+ * degree, propagation, border (summed over the groups below), rounds = propagation rounds enqueued.
+ * APD_ERR_INVALID_ARG, before anything is launched or written: another link, n_settings == 0 or above the maximum, a min_pts[s] == 0,
+ * a NULL eps, min_pts, labels or counts.  n == 0: APD_OK with zero counts.  A workspace that does not fit: APD_ERR_OOM.  More than
+ * 2^21 instances: APD_ERR_UNSUPPORTED.
+ * Workspace: a bit matrix of n * ceil(n / 64) * 8 bytes per setting (32 MiB at n = 16384), bounded by 256 MiB; when the planes of all
+ * settings do not fit, the settings are processed in groups and every group reads the matrix again -- the only case in which it is
+ * read more than once.  The host form also holds the matrix and the results.
+ * Environment (tests only; read at every call; results are bit-identical whatever they say): APD_DENSITY_WORKSPACE_BYTES=<bytes> sets
+ * the bound on the planes (at least one setting's plane is taken), APD_DENSITY_ROUNDS_PER_SYNC=<r> the rounds enqueued between two
+ * reads of the changed words (default 4), APD_DENSITY_WORKGROUP=<64 .. 1024, a multiple of 64> the work-items of a workgroup of the
+ * propagation and border kernels (default 256). */
+#define APD_DENSITY_EITHER 0
+#define APD_DENSITY_BOTH   1
+#define APD_DENSITY_MAX_SETTINGS 8
+#define APD_DENSITY_NOISE  0
+#define APD_DENSITY_BORDER 1
+#define APD_DENSITY_CORE   2
+int apd_density_clusters(apd_context *ctx, const float *distances, int on_device, uint32_t n, int link,
+                         const float *eps, const uint32_t *min_pts, uint32_t n_settings,
+                         uint32_t *labels, uint8_t *kind, uint32_t *degree, uint32_t *counts, uint64_t *nans);
+int apd_density_last_profile(apd_context *ctx, float *phase_ms, uint32_t *rounds);
+
 /* ---- cluster prototypes: which member stands for a cluster, and the cluster's average shape ---------------------------------
  * The medoid of every set: the member closest to all the others, from the [n][n] matrix of apd_align_all.  For set k with its
  * members sorted ascending j1 < j2 < ..., whatever order `members` lists them in, the cost of member i is
