@@ -219,6 +219,10 @@ SYMBOLS = [
     ("apd_silhouette", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, _u32p, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("apd_density_clusters", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, _f32p, _u32p, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     ("apd_density_last_profile", C.c_int, [_vp, _f32p, _u32p]),
+    ("apd_density_tree", C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp, _u32p, C.POINTER(C.c_uint64)]),
+    ("apd_density_tree_last_profile", C.c_int, [_vp, _f32p, _u32p]),
+    ("apd_density_tree_cut", C.c_int, [C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
+    ("apd_density_tree_operations", C.c_int, [C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(ClusterOp)]),
     ("apd_encoder_create", C.c_int, [_vp, _f32p, _f32p, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     ("apd_encoder_destroy", C.c_int, [_vp]),
     ("apd_encode_async", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp]),

@@ -247,6 +247,122 @@ def density_sets(labels, kind):
     return order.astype(np.uint32), set_off
 
 
+def density_tree(distances, min_pts, link="either", ctx=None, on_device=False):
+    """apd_density_tree: the density hierarchy of the [n][n] matrix of AlignmentWorkers.align_all at one min_pts -- every eps of
+    density() at once.  Values are ordered with NaN as missing and last, -0.0 equal to +0.0; sym(i, j) is the smaller ("either") or
+    larger ("both") of distances[i][j] and distances[j][i]; core[i] the (min_pts - 1)-th smallest sym(i, j) over j != i (-INF for
+    min_pts = 1, NaN when there are not that many or the entry is missing), so core[i] <= eps exactly when density(eps, min_pts) calls
+    i core; the tree is the minimum spanning forest of the mutual reachability max(core[i], core[j], sym(i, j)), its edges ordered
+    by (weight, i, j).  With min_pts = 1 it is the single-linkage dendrogram.  With on_device the matrix is (device pointer, n) and
+    stays in HBM.  Returns (core float32 [n], edge_i uint32, edge_j uint32, weight float32, nans int): the edge arrays trimmed to
+    the edges found (at most n - 1), edge_i < edge_j, ascending; nans the NaN entries off the diagonal."""
+    ctx = ctx or _lib.default_context()
+    link = {"either": _lib.APD_DENSITY_EITHER, "both": _lib.APD_DENSITY_BOTH}.get(link, link)
+    m = int(min_pts)
+    if not 0 <= m <= 0xFFFFFFFF:
+        raise ValueError("min_pts within 32 bits")
+    if on_device:
+        ptr, n = distances
+        ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+    else:
+        d = np.ascontiguousarray(distances, dtype=np.float32)
+        n = int(round(d.size ** 0.5))
+        if d.size != n * n:
+            raise ValueError("distances must hold n^2 values")
+        ptr = C.c_void_p(d.ctypes.data)
+    slots = max(n - 1, 0)
+    outs = [np.zeros(n, np.float32), np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.float32)]
+    n_edges, nans = C.c_uint32(0), C.c_uint64(0)
+    head = (ctx.handle, ptr, int(bool(on_device)), n, int(link), m)
+    if not on_device:
+        keep = [o if o.size else np.zeros(1, o.dtype) for o in outs]              # (pointers that are never NULL)
+        _lib.check(_lib.lib().apd_density_tree(*head, *[C.c_void_p(o.ctypes.data) for o in keep], C.byref(n_edges), C.byref(nans)), ctx.handle)
+    else:
+        bufs = [ctx.alloc(max(o.nbytes, 16)) for o in outs]
+        try:
+            _lib.check(_lib.lib().apd_density_tree(*head, *[b.at() for b in bufs], C.byref(n_edges), C.byref(nans)), ctx.handle)
+            for o, b in zip(outs, bufs):
+                if o.size:
+                    o[...] = b.to_numpy(o.dtype, o.size)
+        finally:
+            for b in bufs:
+                b.free()
+    core, edge_i, edge_j, weight = outs
+    e = n_edges.value
+    return core, edge_i[:e].copy(), edge_j[:e].copy(), weight[:e].copy(), int(nans.value)
+
+
+_NOTHING = np.zeros(2, np.uint64)
+
+
+def _ptr(array):
+    """The array's address; an empty array gives a pointer that is not NULL and is never read."""
+    return C.c_void_p(array.ctypes.data if array.size else _NOTHING.ctypes.data)
+
+
+def _tree_arrays(tree):
+    core, edge_i, edge_j, weight = (np.ascontiguousarray(a, dtype=t).ravel()
+                                    for a, t in zip(tree[:4], (np.float32, np.uint32, np.uint32, np.float32)))
+    if not len(edge_i) == len(edge_j) == len(weight):
+        raise ValueError("edge_i, edge_j and weight must hold one value per edge")
+    return core, edge_i, edge_j, weight
+
+
+def density_cut(tree, eps, details=False):
+    """apd_density_tree_cut: density clustering at eps read off a density_tree() result, on the host.  Edges with weight <= eps are
+    joined; a point with core <= eps is core and takes the smallest number of its component, every other point is noise and keeps its
+    own number (DBSCAN*: no border points).  On the core points the labels are density()'s at the same eps, min_pts and link.  eps: a
+    scalar or a sequence of any length; NaN is refused.  Returns (labels uint32, counts uint32): [n] and [4] for a scalar, [S][n] and
+    [S][4] otherwise; counts = clusters, core, 0, noise points.  With details also kind (uint8: 0 noise, 2 core)."""
+    core, edge_i, edge_j, weight = _tree_arrays(tree)
+    single = np.ndim(eps) == 0
+    e = np.ascontiguousarray(np.atleast_1d(np.asarray(eps, dtype=np.float32)).ravel())
+    n, S = len(core), len(e)
+    labels, kind, counts = np.zeros((S, n), np.uint32), np.zeros((S, n), np.uint8), np.zeros((S, 4), np.uint32)
+    _lib.check(_lib.lib().apd_density_tree_cut(n, _ptr(core), _ptr(edge_i), _ptr(edge_j), _ptr(weight), len(edge_i), _ptr(e), S, _ptr(labels),
+                                               _ptr(kind), _ptr(counts)))
+    if single:
+        labels, kind, counts = labels[0], kind[0], counts[0]
+    return (labels, counts, kind) if details else (labels, counts)
+
+
+def density_operations(tree):
+    """apd_density_tree_operations: the edges of a density_tree() result as a merge list in ClusteringOperation form -- edge t merges
+    the current roots of its endpoints into n + t at distance weight[t] -- for AgglomerativeClustering.assignment / cluster_sets and
+    dendrograms().  With min_pts = 1 this is the single-linkage dendrogram."""
+    core, edge_i, edge_j, weight = _tree_arrays(tree)
+    ops = (_lib.ClusterOp * max(len(edge_i), 1))()
+    _lib.check(_lib.lib().apd_density_tree_operations(len(core), _ptr(edge_i), _ptr(edge_j), _ptr(weight), len(edge_i), ops))
+    return [ClusteringOperation(o.merge_i, o.merge_j, o.into, o.distance, Merge(o.operation)) for o in ops[:len(edge_i)]]
+
+
+def density_sweep(distances, min_pts, eps=None, link="either", axis=0, ctx=None):
+    """One density_tree(), every eps as a cut of it, the silhouette of all cuts in one apd_silhouette: the matrix is uploaded once and
+    read by the tree's rounds and by the silhouette only.  eps: the values to try; None: the distinct edge weights, thinned to at
+    most 64 evenly by rank.  Returns per eps, in the order given, (eps, clusters, core, noise, score, nans): the counts of
+    density_cut and the silhouette of its labels, noise as singletons.  AgglomerativeClustering.sweep's counterpart."""
+    ctx = ctx or _lib.default_context()
+    d = np.ascontiguousarray(distances, dtype=np.float32)
+    n = int(round(d.size ** 0.5))
+    if d.size != n * n:
+        raise ValueError("distances must hold n^2 values")
+    buf = ctx.upload(d.ravel()) if d.size else ctx.alloc(16)
+    try:
+        tree = density_tree((buf.at(), n), min_pts, link=link, ctx=ctx, on_device=True)
+        if eps is None:
+            eps = np.unique(tree[3])
+            if len(eps) > 64:
+                eps = eps[np.round(np.linspace(0, len(eps) - 1, 64)).astype(np.int64)]
+        eps = np.atleast_1d(np.asarray(eps, dtype=np.float32)).ravel()
+        if len(eps) == 0:
+            return []
+        labels, counts = density_cut(tree, eps)
+        score, _, nans = silhouette((buf.at(), n), labels, axis=axis, ctx=ctx, on_device=True)
+    finally:
+        buf.free()
+    return [(float(eps[c]), int(counts[c][0]), int(counts[c][1]), int(counts[c][3]), float(score[c]), int(nans[c])) for c in range(len(eps))]
+
+
 def cross_linkage(fs, sf, sets, ctx=None):
     """apd_cross_linkage: the reference's average linkage (clustering.rs:153-170) between every first-set sequence q and every
     set of second-set sequence numbers in `sets` (as cluster_sets returns them; any order inside a set), from the cross matrices

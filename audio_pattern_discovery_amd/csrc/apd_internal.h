@@ -783,6 +783,9 @@ struct apd_context {
     apd::DeviceBuf ws_density;        // apd_density_clusters: the bit planes of a group of settings, their core masks, the changed words (bounded)
     float density_phase_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // ... with timing on: adjacency, degree, propagation, border of the last call
     uint32_t density_rounds = 0;      // ... propagation rounds it enqueued, summed over its groups of settings
+    apd::DeviceBuf ws_density_tree;   // apd_density_tree: core keys, components, the words of a round, the edges being sorted (O(n))
+    float density_tree_phase_ms[3] = {0.0f, 0.0f, 0.0f};    // ... with timing on: core distances, rounds, final ordering of the last call
+    uint32_t density_tree_rounds = 0; // ... Boruvka rounds it ran
     uint32_t *d_status = nullptr;     // sticky device word: bit 0 = an unpack met an unwritten (poisoned) pair score
     uint32_t drop_tiles = 0;          // fault injection (apd_set_fault_injection)
     apd_batch *pair_batch = nullptr;  // apd_align_pair: the last pair's two-sequence batch, refilled while (n, m, dim) repeat

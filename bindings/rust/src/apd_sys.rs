@@ -289,6 +289,16 @@ extern "C" {
                                 min_pts: *const u32, n_settings: u32, labels: *mut u32, kind: *mut u8, degree: *mut u32,
                                 counts: *mut u32, nans: *mut u64) -> c_int;
     pub fn apd_density_last_profile(ctx: *mut apd_context, phase_ms: *mut f32, rounds: *mut u32) -> c_int;
+    // density hierarchy (core: [n]; edge_i, edge_j, weight: [n - 1]; n_edges, nans: host words; blocking in both forms) and its
+    // host-only readers
+    pub fn apd_density_tree(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, link: c_int, min_pts: u32,
+                            core: *mut f32, edge_i: *mut u32, edge_j: *mut u32, weight: *mut f32, n_edges: *mut u32,
+                            nans: *mut u64) -> c_int;
+    pub fn apd_density_tree_last_profile(ctx: *mut apd_context, phase_ms: *mut f32, rounds: *mut u32) -> c_int;
+    pub fn apd_density_tree_cut(n: u32, core: *const f32, edge_i: *const u32, edge_j: *const u32, weight: *const f32, n_edges: u32,
+                                eps: *const f32, n_eps: u32, labels: *mut u32, kind: *mut u8, counts: *mut u32) -> c_int;
+    pub fn apd_density_tree_operations(n: u32, edge_i: *const u32, edge_j: *const u32, weight: *const f32, n_edges: u32,
+                                       ops: *mut apd_cluster_op) -> c_int;
     // cluster prototypes
     pub fn apd_cluster_medoids(ctx: *mut apd_context, distances: *const f32, on_device: c_int, n: u32, members: *const u32,
                                set_off: *const u32, n_sets: u32, medoid: *mut u32, cost: *mut f32) -> c_int;

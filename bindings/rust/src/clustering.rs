@@ -177,6 +177,43 @@ impl AgglomerativeClustering {
                             [counts[4 * s] as usize, counts[4 * s + 1] as usize, counts[4 * s + 2] as usize, counts[4 * s + 3] as usize])).collect()
     }
 
+    /// Not in the reference: the density hierarchy of the n x n matrix of align_all at one min_pts (apd_density_tree): every eps of
+    /// `density` at once.  (core, edges): core[i] is the (min_pts - 1)-th smallest symmetrised distance of i (-INF for min_pts = 1,
+    /// NaN when missing), so core[i] <= eps exactly when `density` calls i core; edges are the (i, j, weight) of the minimum
+    /// spanning forest of the mutual reachability, i < j, ascending by (weight, i, j).  With min_pts = 1: single linkage.
+    /// Like the rest of this module it has not been compiled (no rustc where it was written).
+    pub fn density_tree(distances: &[f32], n_instances: usize, min_pts: usize, both: bool) -> (Vec<f32>, Vec<(usize, usize, f32)>) {
+        let slots = n_instances.saturating_sub(1).max(1);
+        let mut core = vec![0f32; n_instances.max(1)];
+        let (mut edge_i, mut edge_j, mut weight) = (vec![0u32; slots], vec![0u32; slots], vec![0f32; slots]);
+        let (mut n_edges, mut nans) = (0u32, 0u64);
+        with_context(|ctx| unsafe {
+            check(apd_density_tree(ctx, distances.as_ptr(), 0, n_instances as u32, if both { APD_DENSITY_BOTH } else { APD_DENSITY_EITHER },
+                                   min_pts as u32, core.as_mut_ptr(), edge_i.as_mut_ptr(), edge_j.as_mut_ptr(), weight.as_mut_ptr(), &mut n_edges,
+                                   &mut nans));
+        });
+        core.truncate(n_instances);
+        (core, (0..n_edges as usize).map(|t| (edge_i[t] as usize, edge_j[t] as usize, weight[t])).collect())
+    }
+
+    /// Not in the reference: `density` at every eps of `eps`, read off a `density_tree` on the host (apd_density_tree_cut).  Per eps
+    /// (labels, [clusters, core, 0, noise]): a core point's label is the smallest point of its component, every other point keeps
+    /// its own number (no border points).  Panics on a NaN eps or an edge list that is not a forest.
+    pub fn density_cut(core: &[f32], edges: &[(usize, usize, f32)], eps: &[f32]) -> Vec<(Vec<usize>, [usize; 4])> {
+        let n = core.len();
+        let edge_i: Vec<u32> = edges.iter().map(|e| e.0 as u32).collect();
+        let edge_j: Vec<u32> = edges.iter().map(|e| e.1 as u32).collect();
+        let weight: Vec<f32> = edges.iter().map(|e| e.2).collect();
+        let mut labels = vec![0u32; (eps.len() * n).max(1)];
+        let mut counts = vec![0u32; (eps.len() * 4).max(1)];
+        unsafe {
+            check(apd_density_tree_cut(n as u32, core.as_ptr(), edge_i.as_ptr(), edge_j.as_ptr(), weight.as_ptr(), edges.len() as u32, eps.as_ptr(),
+                                       eps.len() as u32, labels.as_mut_ptr(), std::ptr::null_mut(), counts.as_mut_ptr()));
+        }
+        (0..eps.len()).map(|s| (labels[s * n..(s + 1) * n].iter().map(|l| *l as usize).collect(),
+                                [counts[4 * s] as usize, counts[4 * s + 1] as usize, counts[4 * s + 2] as usize, counts[4 * s + 3] as usize])).collect()
+    }
+
     /// clustering.rs:40-76: leaf lists per root; roots that were never merged are skipped ("Cluster not found").
     pub fn cluster_sets(operations: &[ClusteringOperation], cluster_ids: &HashSet<usize>, n_instances: usize) -> Vec<Vec<usize>> {
         let ops: Vec<apd_cluster_op> = operations.iter().map(|o| o.to_c()).collect();

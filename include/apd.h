@@ -911,6 +911,58 @@ int apd_density_clusters(apd_context *ctx, const float *distances, int on_device
                          uint32_t *labels, uint8_t *kind, uint32_t *degree, uint32_t *counts, uint64_t *nans);
 int apd_density_last_profile(apd_context *ctx, float *phase_ms, uint32_t *rounds);
 
+/* ---- density hierarchy: every eps of apd_density_clusters at one min_pts, from one tree (HDBSCAN's hierarchy) ------------------
+ * distances: the [n][n] matrix of apd_align_all.  A function of the matrix, link and min_pts alone, bit for bit.
+ * Order.  Every value is compared through a key: NaN is MISSING and ranks behind everything, +INF included; -0.0 and +0.0 are equal;
+ *   everything else follows IEEE order -- negative values and +-INF are ordinary values.  Values come back in canonical form: either
+ *   zero as +0.0, missing as the quiet NaN 0x7FC00000, so nothing depends on which of two equal entries was "chosen".
+ * Symmetrised distance, i != j (the diagonal enters nothing): sym(i, j) = the smaller of d[i][j] and d[j][i] under the order
+ *   (APD_DENSITY_EITHER: a NaN loses to any number, two NaNs give missing), the larger (APD_DENSITY_BOTH: a NaN wins).  For every
+ *   non-NaN eps, sym(i, j) <= eps is exactly apd_density_clusters' adj(i, j).
+ * Core distance.  min_pts = 1: core[i] = -INF.  min_pts = m >= 2: the (m - 1)-th smallest sym(i, j) over j != i under the order;
+ *   missing when m - 1 > n - 1 or when that entry is missing.  Only the one value is selected, so there is no cap on min_pts such as
+ *   APD_NEIGHBORS_MAX_K.  core[i] <= eps holds exactly when i is a core point of apd_density_clusters(eps, m, link).
+ * Mutual reachability: mr(i, j) = the largest of core[i], core[j] and sym(i, j) under the order.
+ * Tree: the minimum spanning forest of the graph on n vertices whose edges are the pairs i < j with non-missing mr(i, j), the edges
+ *   ordered by the strict total order (key(mr), i, j) -- under which the forest is unique.  *n_edges <= n - 1 edges come back with
+ *   edge_i[t] < edge_j[t] and weight[t] = mr, t ascending in that order; the slots behind them hold 0xFFFFFFFF, 0xFFFFFFFF and the
+ *   quiet NaN.  *nans: the NaN entries off the diagonal, as apd_density_clusters counts them.
+ * core: [n] floats; edge_i, edge_j, weight: [n - 1] (none for n <= 1, and then they may be NULL); host, or all device pointers if
+ * on_device.  n_edges and nans are HOST words in both forms.  BLOCKING IN BOTH FORMS, like apd_density_clusters: the forest is built in
+ * Boruvka rounds on the device (every component takes its smallest edge that leaves it; a round is one pass over the matrix) and the
+ * host reads the number of edges between rounds.  At most ceil(log2 n) + 1 rounds; more is an internal error (APD_ERR_HIP), not a
+ * longer loop.  With apd_set_timing on, apd_last_kernel_ms covers the call's kernels and apd_density_tree_last_profile splits them:
+ * phase_ms[3] = core distances, rounds, final ordering; rounds = the rounds run.
+ * APD_ERR_INVALID_ARG, before anything is launched or written: another link, min_pts == 0, a NULL n_edges, nans, core (n >= 1) or
+ * edge array (n >= 2).  n == 0: APD_OK with no edges; n == 1: core[0] and no edges.  More than 2^21 instances: APD_ERR_UNSUPPORTED.
+ * A workspace that does not fit: APD_ERR_OOM.
+ * Workspace: at most 56 bytes per instance, and for min_pts in 2 .. n the [panel][n] gather of mirror columns shared with apd_neighbors (256
+ * MiB at most); no n^2 workspace -- every round reads the matrix.  The host form also holds the matrix and the results.
+ * Environment (tests only; read at every call; results are bit-identical whatever they say): APD_DENSITY_TREE_WORKSPACE_BYTES=<bytes>
+ * sets the bound on the panel (at least one column is taken), APD_DENSITY_TREE_WORKGROUP=<64 .. 1024, a multiple of 64> the work-items
+ * of a workgroup of the core-distance select and of the per-instance kernels (default 256).
+ *
+ * apd_density_tree_cut: host only, no context.  For each of n_eps values of eps (any number of them): join the endpoints of every
+ *   edge with weight <= eps; a vertex with core[i] <= eps is core (kind APD_DENSITY_CORE) and its label is the smallest vertex of its
+ *   component -- such a component holds core points only, because mr >= core; every other vertex is noise (APD_DENSITY_NOISE) with
+ *   labels[i] = i.  counts[s] = {clusters, core, 0, noise}.  This is DBSCAN* (no border points: assigning them needs the adjacency and
+ *   stays with apd_density_clusters): the core mask equals kind == CORE of apd_density_clusters(eps, min_pts, link) and the labels
+ *   agree on those points, for every non-NaN eps.  labels: [n_eps][n], kind: [n_eps][n] bytes or NULL, counts: [n_eps][4].
+ *   APD_ERR_INVALID_ARG with nothing written: a NaN eps (the one setting where the two calls cannot agree: with min_pts = 1
+ *   apd_density_clusters calls every point core under a NaN eps), a NULL core, eps, labels or counts, or an edge list that is not a
+ *   forest over n (a vertex >= n, edge_i >= edge_j, or a cycle).
+ * apd_density_tree_operations: host only.  The single-linkage merge list (min_pts = 1; for larger min_pts the same over mr) in
+ *   apd_cluster_op format: edge t merges the current roots of its endpoints, merge_i the root on edge_i's side, merge_j the root on
+ *   edge_j's side, into = n + t, distance = weight[t], operation by the rule of clustering.rs:193-201.  ops: [n_edges].
+ *   apd_cut_labels, apd_cluster_sets and apd_dendrograms take the list as they take apd_clustering's.  The same refusals. */
+int apd_density_tree(apd_context *ctx, const float *distances, int on_device, uint32_t n, int link, uint32_t min_pts,
+                     float *core, uint32_t *edge_i, uint32_t *edge_j, float *weight, uint32_t *n_edges, uint64_t *nans);
+int apd_density_tree_last_profile(apd_context *ctx, float *phase_ms, uint32_t *rounds);
+int apd_density_tree_cut(uint32_t n, const float *core, const uint32_t *edge_i, const uint32_t *edge_j, const float *weight,
+                         uint32_t n_edges, const float *eps, uint32_t n_eps, uint32_t *labels, uint8_t *kind, uint32_t *counts);
+int apd_density_tree_operations(uint32_t n, const uint32_t *edge_i, const uint32_t *edge_j, const float *weight, uint32_t n_edges,
+                                apd_cluster_op *ops);
+
 /* ---- cluster prototypes: which member stands for a cluster, and the cluster's average shape ---------------------------------
  * The medoid of every set: the member closest to all the others, from the [n][n] matrix of apd_align_all.  For set k with its
  * members sorted ascending j1 < j2 < ..., whatever order `members` lists them in, the cost of member i is
